@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline metric on MI355X: assembly Mbp/s polished + Gk-mers/s counted, k=37.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: starts its own ranks, or runs under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One STEP = one pass of the whole hot path over one batch of synthetic input that is already resident in HBM:
     new table -> count canonical 37-mers of the read shard (K1+K2) -> [N>1: the counts brought together by key owner
     over RCCL, the table kept key-sharded over the GPUs: --count] -> histogram (K3) -> threshold (src/jellyfish.py) -> P fixing passes + 1 QV pass over this rank's
     chunk records (K4-K6) -> polished text (left in HBM, like the inputs) + fix records and QV counters on the host.
-After the timed region the same polish call is repeated with host buffers in and out (`polish_host_io_ms`, the
-PCIe-inclusive figure) and its text is compared with the HBM-resident result.
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR, see dump_outputs)
+and prints the result line.  Everything else runs only with --full: after the timed region the same polish call is repeated
+with host buffers in and out (`polish_host_io_ms`, the PCIe-inclusive figure) and its text is compared with the HBM-resident
+result; the CPU baseline and the untimed files-in / files-out legs of the drop-in CLI (below).
 Workload at N=1 = BASELINE.json configs[1]: "human chr21"-sized synthetic genome (47 Mb) + 30x 150-bp reads, k=37,
 2 passes, chunked as `jasper.sh -t 16` would (BATCH_SIZE = int(47e6/16*.9)).  For N>1 the genome, the reads and
 the assembly grow with N (weak scaling): every rank counts 1/N of the reads of the N x 47 Mb genome and polishes
@@ -19,9 +21,9 @@ region lists grouped by key owner and deduplicated, one all_to_all delivers them
 polishing kernels then read each key from its owner's HBM (their own, or a peer's over xGMI).
 
 Prints ONE JSON line (rank 0). `value` = assembly bases polished per second of whole-job wall time (Mbp/s);
-the counting rate, the polishing-only rate, the roofline of the dominant kernels (the counting pipeline, HIP-event timed
-on the table's own stream; `roofline_polish`) and a CPU baseline (the C restatement, multi-threaded, on the WHOLE workload of
-a step with its results compared with the GPU's; rank 0 at N=1 only) ride along.
+the counting rate, the polishing-only rate and the roofline of the dominant kernels (the counting pipeline, HIP-event timed
+on the table's own stream; `roofline_polish`) ride along; with --full also a CPU baseline (the C restatement, multi-threaded,
+on the WHOLE workload of a step with its results compared with the GPU's; rank 0 at N=1 only).
 """
 import argparse
 import json
@@ -133,12 +135,60 @@ def one_step(torch, dev_index, local, reads, d_chunks, world, timers, shard=None
     info = table.info()
     timers.append(dict(count=t1 - t0, clear=t0b - t0, merge=t2 - t1, histo=t3 - t2, polish=t4 - t3, kernel_ms=kms, launches=launches, stages=stages, part_launches=part_launches, path=path,
                        exchange=xinfo,
-                       polish_dev=res.seconds, thr=thr, qv=res.qv, nfix=res.n_records, merged=merged,
+                       polish_dev=res.seconds, thr=thr, rows=rows, qv=res.qv, nfix=res.n_records, merged=merged,
                        distinct=info["distinct"], occurrences=info["occurrences"], slots=info["slots"], lookups=res.lookups,
                        segments=res.segments, respeculated=res.respeculated,
                        shard_distinct=shard.info()["distinct"] if shard is not None else None,
                        shard_slots=shard.info()["slots"] if shard is not None else None))
     return res
+
+
+DUMP_TEXT_SAMPLE = 4_000_000     # polished bases sampled into polished_text_sample.npy (float32: 16 MB at N = 1)
+DUMP_BLOCK = 4096                # bases per entry of polished_block_sums.npy
+DUMP_SEED = 12345
+
+
+def dump_outputs(d, res, T, n_chunks, rank, world):
+    """What the caller of the timed path received from the LAST timed step, as .npy files in d (float64 unless said otherwise;
+    N > 1: one set per rank, names ending in _rank<r>):
+      histogram             (multiplicity, k-mers) rows of the histogram
+      threshold             the solid threshold the histogram gave
+      count_totals          distinct k-mers, k-mer occurrences in the table
+      qv_counters           (bad0, total0, badP, totalP)
+      fix_records           one row per fix record (chunk, pass, seqno, kind, index, newc, oldc, rep), sorted by (chunk, pass, seqno)
+      fix_patches           float32: the bytes of the 'x' records' patch + original text, in the order of fix_records
+      polished_lengths      length of every polished chunk record
+      polished_text_sample  float32: the polished bytes (chunks back to back) at DUMP_TEXT_SAMPLE / N positions drawn with a fixed
+                            seed (all of them when the text is no longer)
+      polished_block_sums   sum of byte x (1 + offset in block) over every DUMP_BLOCK bytes of that text (a digest of all of it)
+    Under 20 MB in all at N = 1."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    out = {}
+    out["histogram"] = np.array(T["rows"], dtype=np.float64).reshape(-1, 2)
+    out["threshold"] = np.array([T["thr"]], dtype=np.float64)
+    out["count_totals"] = np.array([T["distinct"], T["occurrences"]], dtype=np.float64)
+    out["qv_counters"] = np.array(res.qv, dtype=np.float64)
+    raw = res._raw
+    order = np.lexsort((raw["seqno"], raw["pass_"], raw["chunk"]))
+    raw = raw[order]
+    cols = ("chunk", "pass_", "seqno", "kind", "index", "newc", "oldc", "rep")
+    out["fix_records"] = np.stack([raw[c].astype(np.float64) for c in cols], axis=1) if len(raw) else np.zeros((0, len(cols)))
+    patches = [res.aux[int(e["chunk"])][int(e["aux_off"]):int(e["aux_off"]) + int(e["aux_len"]) + int(e["rep"])]
+               for e in raw if e["kind"] == ord("x")]
+    out["fix_patches"] = np.frombuffer(b"".join(patches), dtype=np.uint8).astype(np.float32)
+    text = [bytes(res.seq_view(i)) for i in range(n_chunks)]
+    out["polished_lengths"] = np.array([len(t) for t in text], dtype=np.float64)
+    text = np.frombuffer(b"".join(text), dtype=np.uint8)
+    m = DUMP_TEXT_SAMPLE // world
+    pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, len(text), size=m)) if len(text) > m else slice(None)
+    out["polished_text_sample"] = text[pos].astype(np.float32)
+    w = np.arange(1, DUMP_BLOCK + 1, dtype=np.int64)
+    out["polished_block_sums"] = np.array([np.dot(text[i:i + DUMP_BLOCK].astype(np.int64), w[:len(text[i:i + DUMP_BLOCK])])
+                                           for i in range(0, len(text), DUMP_BLOCK)], dtype=np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), arr)
 
 
 def host_cpu():
@@ -348,14 +398,18 @@ def e2e_cli_big(fixture="fullsize_cfg3", need_gb=40):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=4)      # (a table polishes in three lanes from its second call on; the lanes' buffers are settled two calls later)
     ap.add_argument("--genome-mb", type=float, default=47.0, help="assembly size per GPU in Mb (47 = chr21-sized, BASELINE configs[1])")
     ap.add_argument("--seed", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the untimed legs: host-buffer polish calls compared with the timed result, the CPU baseline, the "
+                         "files-in / files-out runs of the drop-in CLI")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-selftest", action="store_true", help="N > 1: skip the transport self-test in throw-away processes")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the untimed files-in / files-out run of the drop-in CLI (e2e_cli)")
-    ap.add_argument("--no-e2e-cfg3", action="store_true", help="skip the second untimed leg (configs[2]-sized files through the CLI)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the untimed files-in / files-out run of the drop-in CLI (e2e_cli)")
+    ap.add_argument("--no-e2e-cfg3", action="store_true", help="--full without the second untimed leg (configs[2]-sized files through the CLI)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--one-gpu", action="store_true", help="rehearsal: all ranks share GPU 0")
     ap.add_argument("--count", choices=("auto", "exchange", "local"), default="auto",
@@ -366,6 +420,8 @@ def main():
                     help="N>1: keep the merged table key-sharded over the GPUs (lookups read the owner's HBM over xGMI) or replicate "
                          "it on every GPU; auto = sharded, replicated only if the peers' memory cannot be mapped")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if os.environ.get("JASPER_BENCH_WATCHDOG"):      # debugging aid: where is every thread, every N seconds
         import faulthandler
@@ -390,7 +446,7 @@ def main():
     #  per GB, and an allocation that gets such memory waits for it -- the configs[2] run allocates ~100 GB and took 3.1 s instead
     #  of 1.3 s right behind the four configs[1] runs, all of it in its first allocations; docs/experiments.md)
     e2e3 = e2e4 = None
-    if a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.genome_mb == 47.0 and not a.no_e2e and not a.no_e2e_cfg3:
+    if a.full and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.genome_mb == 47.0 and not a.no_e2e and not a.no_e2e_cfg3:
         try:        # one rank's share of configs[3] (24 GB of FASTQ, a 2^32-slot table): the largest case, on the untouched GPU
             e2e4 = e2e_cli_big("fullsize_cfg4_share", need_gb=70)
         except Exception as e:
@@ -402,7 +458,7 @@ def main():
             e2e3 = {"seconds": None, "failed": "%r" % (e,)}
         time.sleep(6.0)
     e2e = None
-    if a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.genome_mb == 47.0 and not a.no_e2e:
+    if a.full and a.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.genome_mb == 47.0 and not a.no_e2e:
         try:
             e2e = e2e_cli()
         except Exception as e:      # a report, like the CPU baseline: never a reason to lose the measurement
@@ -533,16 +589,19 @@ def main():
         res = step()
     barrier()
     dt = time.perf_counter() - t0
-    # untimed: the same batch with host buffers in and out (PCIe-inclusive), and a check that both give the same text
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, timers[-1], len(seqs), rank, world)
+    # untimed (--full): the same batch with host buffers in and out (PCIe-inclusive), and a check that both give the same text
     host_ms = []
-    for _ in range(3):
+    for _ in range(3 if a.full else 0):
         th = time.perf_counter()
         res_h = (shard if shard is not None else loc["table"]).polish_batch(seqs, timers[-1]["thr"], PASSES, fix=True)
         host_ms.append((time.perf_counter() - th) * 1e3)
-    same_text = all(bytes(res.seq_view(i)) == bytes(res_h.seq_view(i)) for i in range(len(seqs)))
-    if not same_text or res.qv != res_h.qv or res.n_records != res_h.n_records:
-        raise RuntimeError("HBM-resident and host-buffer polish calls disagree")
-    del res_h
+    if host_ms:
+        same_text = all(bytes(res.seq_view(i)) == bytes(res_h.seq_view(i)) for i in range(len(seqs)))
+        if not same_text or res.qv != res_h.qv or res.n_records != res_h.n_records:
+            raise RuntimeError("HBM-resident and host-buffer polish calls disagree")
+        del res_h
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -616,10 +675,8 @@ def main():
         "count_exchange": T["exchange"],      # N>1: rounds, bytes this rank put on the wire per step, list geometry (null: tables per GPU, summed by owner)
         "polish_device_ms": round(mean("polish_dev") * 1e3, 2),
         "polish_first_call": first_call,       # one lane, buffers not yet allocated (the drop-in CLI's case); the timed steps: lanes settled
-        "polish_calls_in_process": a.warmup + a.steps + 3,      # (tools/summarize_prof.py divides the polishing kernels' counters by this)
+        "polish_calls_in_process": a.warmup + a.steps + len(host_ms),      # (tools/summarize_prof.py divides the polishing kernels' counters by this)
         "io": "reads and chunk records resident in HBM; polished text left in HBM; fix records, histogram and QV counters on the host",
-        "polish_host_io_ms": round(min(host_ms), 2),
-        "value_pcie_inclusive_polish": round(asm_total / 1e6 / (dt / steps + (min(host_ms) * 1e-3 - mean("polish"))), 3),
         "qv_counters": list(T["qv"]), "fix_records": T["nfix"], "polish_lookups": T["lookups"],
         "polish_segments": T["segments"], "polish_chunks_redone_unsegmented": T["respeculated"],
         "roofline": {"bound": "hbm",
@@ -645,8 +702,11 @@ def main():
                               "algorithmic_bytes_per_step": int(polish_bytes), "device_ms": round(pol_s * 1e3, 3),
                               "lookups_per_base_and_scan": round(T["lookups"] / max(asm_len * (PASSES + 1), 1), 4), "traffic": pol_traffic,
                               "traffic_source": pol_traffic_src}
+    if host_ms:
+        out["polish_host_io_ms"] = round(min(host_ms), 2)
+        out["value_pcie_inclusive_polish"] = round(asm_total / 1e6 / (dt / steps + (min(host_ms) * 1e-3 - mean("polish"))), 3)
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # the last step's fix records as the rows jasper.py would write (per pass, chunk order), like polisher.polish_batch
             per_pass = [[] for _ in range(PASSES)]
             for r in res.records:

@@ -132,7 +132,7 @@ def test_bench_three_ranks_rehearsed_on_one_gpu(hip):
     import json
     import subprocess
     env = dict(os.environ, PYTHONPATH=ROOT)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1", "--genome-mb", "2", "--backend", "gloo", "--one-gpu"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1", "--genome-mb", "2", "--backend", "gloo", "--one-gpu", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -176,7 +176,7 @@ def test_bench_two_gpus_self_launch(hip, count):
     """`python bench.py --gpus 2` starts its own ranks and prints ONE line that says which world it saw; with --count exchange
     the region lists travel over RCCL instead of the entries of per-GPU tables"""
     env = dict(os.environ, PYTHONPATH=ROOT)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-mb", "4", "--count", count],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-mb", "4", "--count", count, "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
