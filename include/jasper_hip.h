@@ -102,6 +102,13 @@ int jasper_count_reads_file_ranges(jasper_table *t, const char *const *paths, co
 /* of the last jasper_count_reads_files call: text bytes parsed by the GPU kernels / by the host state machine (the
  * fallback for multi-line records, DOS line ends, malformed input and stream tails) */
 int jasper_last_ingest(jasper_table *t, uint64_t *gpu_bytes, uint64_t *host_bytes);
+/* of the last jasper_count_reads_files* or feed call: the gzip input, summed over its files --
+ *   stats[0] decoders launched by the device inflater, [1] chunks it accepted into the text, [2] text bytes inflated on the device,
+ *   [3] text bytes inflated on the host (zlib or the many-thread reader: files not selected for the device, spans it gave back),
+ *   [4] slabs, [5] gzip members checked by the device inflater.
+ * A regular gzip file read from byte 0 goes to the device inflater when it has at least JASPER_INGEST_GZ_DEVICE_MIN_MB compressed
+ * MiB (JASPER_INGEST_GZ=auto, the default; with that variable unset, never), always (=device) or never (=host). */
+int jasper_last_inflate(jasper_table *t, uint64_t stats[6]);
 int jasper_histogram(jasper_table *t, uint64_t *out10002);
 /* the same over the keys of ONE owner partition (as in jasper_table_export_packed): after a multi-GPU merge every rank
  * bins the range it owns and the 10002 bins are summed over ranks, instead of every rank scanning the whole table */
@@ -315,6 +322,10 @@ int jasper_table_release_retired(jasper_table *t);
  * bytes per unit of work (0: default 4 MiB).  *n_out = inflated bytes; *parallel = 1 when the many-thread reader handled the
  * file, 0 when it declined (small file, not a regular gzip file) and zlib's reader was used. */
 int jasper_inflate_file(const char *path, int threads, uint64_t chunk_bytes, const char *out_path, uint64_t *n_out, int *parallel);
+/* The same on GPU `device` (jasper_amd/csrc/inflate_gpu.hpp): the deflate data is decoded by kernels, the host does the
+ * bookkeeping and inflates with zlib only what the device gives back.  Same text and same failures as jasper_inflate_file.
+ * chunk_bytes = compressed bytes per decoder (0: default 32 KiB); out_path may be NULL; stats as for jasper_last_inflate. */
+int jasper_inflate_file_device(int device, const char *path, uint64_t chunk_bytes, const char *out_path, uint64_t *n_out, uint64_t stats[6]);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ SYMBOLS = {
     "jasper_table_write_jf": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_char_p), C.c_int]),
     "jasper_debug_mix": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "jasper_last_ingest": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jasper_last_inflate": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "jasper_histogram_part": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "jasper_histogram_is_fused": (C.c_int, [_P]),
     "jasper_histogram": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -79,6 +80,7 @@ SYMBOLS = {
     "jasper_ipc_probe": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32]),
     "jasper_table_release_retired": (C.c_int, [_P]),
     "jasper_inflate_file": (C.c_int, [C.c_char_p, C.c_int, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "jasper_inflate_file_device": (C.c_int, [C.c_int, C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jasper_owner_of": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "jasper_polish_batch": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "jasper_result_num_chunks": (C.c_int, [_P]),

@@ -4,6 +4,7 @@
 #include "polish_host.hpp"
 #include "table.hpp"
 #include "pgunzip.hpp"
+#include "inflate_gpu.hpp"
 #include "asmio.hpp"
 #include <zlib.h>
 #include <algorithm>
@@ -201,6 +202,7 @@ int jasper_count_reads_files(jasper_table *t, const char *const *paths, int n_pa
     t->t.reset_timing();
     Table *T = &t->t;
     T->ingest_gpu_bytes = T->ingest_host_bytes = 0;
+    for (uint64_t &v : T->inflate_stats) v = 0;
     if (!getenv("JASPER_INGEST_HOST")) {       // text parsed on the GPU; the host state machine takes over whatever is not plain 4-line FASTQ / FASTA
         const int rc = T->count_files_gpu(paths, n_paths, &T->ingest_gpu_bytes, &T->ingest_host_bytes, g_err);
         return rc < -1 ? rc : (rc ? JASPER_ERR : JASPER_OK);
@@ -215,6 +217,12 @@ int jasper_count_reads_files(jasper_table *t, const char *const *paths, int n_pa
 int jasper_last_ingest(jasper_table *t, uint64_t *gpu_bytes, uint64_t *host_bytes) {
     if (gpu_bytes) *gpu_bytes = t->t.ingest_gpu_bytes;
     if (host_bytes) *host_bytes = t->t.ingest_host_bytes;
+    return JASPER_OK;
+}
+
+int jasper_last_inflate(jasper_table *t, uint64_t stats[6]) {
+    if (!t || !stats) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < GZS_N; ++i) stats[i] = t->t.inflate_stats[i];
     return JASPER_OK;
 }
 
@@ -384,6 +392,70 @@ int jasper_inflate_file(const char *path, int threads, uint64_t chunk_bytes, con
     if (f) fclose(f);
     if (n_out) *n_out = total;
     if (parallel) *parallel = par;
+    return rc;
+}
+
+int jasper_inflate_file_device(int device, const char *path, uint64_t chunk_bytes, const char *out_path, uint64_t *n_out, uint64_t stats[6]) {
+    if (!path) { g_err = "bad arguments"; return JASPER_ERR; }
+    uint64_t st[GZS_N] = {};
+    uint64_t total = 0;
+    int rc = JASPER_OK;
+    FILE *f = nullptr;
+    if (out_path) { f = fopen(out_path, "wb"); if (!f) { g_err = std::string("cannot write ") + out_path; return JASPER_ERR; } }
+    hipStream_t s = nullptr;
+    std::vector<void *> bufs;
+    char *h_buf = nullptr;
+    const size_t BUF = 64u << 20;
+    GzdConfig cfg = GzdConfig::from_env();
+    if (chunk_bytes) cfg.chunk = std::max<size_t>(4096, (size_t)chunk_bytes);
+    cfg.slab = std::max(cfg.slab, 4 * cfg.chunk);
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+        if (f) fclose(f);
+        g_err = "no device";
+        return JASPER_ERR;
+    }
+    {
+        DeviceGunzip dg(path, device, s, cfg, st);
+        auto alloc = [&bufs](int, size_t bytes) -> void * {
+            void *p = nullptr;
+            if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            bufs.push_back(p);
+            return p;
+        };
+        if (dg.open(alloc) && hipHostMalloc((void **)&h_buf, BUF, hipHostMallocDefault) == hipSuccess) {
+            for (;;) {
+                const long r = dg.read(h_buf, BUF);
+                if (r < 0) { g_err = dg.err; rc = JASPER_ERR; break; }
+                if (r == 0) break;
+                total += (uint64_t)r;
+                if (f && fwrite(h_buf, 1, (size_t)r, f) != (size_t)r) { g_err = "write error"; rc = JASPER_ERR; break; }
+            }
+        } else {
+            // not for the device inflater (not a regular gzip file with a valid header, no device memory): zlib's reader, as
+            // jasper_inflate_file reads such a file
+            gzFile g = gzopen(path, "rb");
+            if (!g) { g_err = std::string("cannot open ") + path; rc = JASPER_ERR; }
+            else {
+                std::vector<char> buf(4u << 20);
+                for (;;) {
+                    const int r = gzread(g, buf.data(), (unsigned)buf.size());
+                    if (r < 0) { g_err = std::string("read error in ") + path; rc = JASPER_ERR; break; }
+                    if (r == 0) break;
+                    total += (uint64_t)r;
+                    st[GZS_HOST_BYTES] += (uint64_t)r;
+                    if (f && fwrite(buf.data(), 1, (size_t)r, f) != (size_t)r) { g_err = "write error"; rc = JASPER_ERR; break; }
+                }
+                gzclose(g);
+            }
+        }
+    }
+    (void)hipStreamSynchronize(s);
+    for (void *p : bufs) (void)hipFree(p);
+    if (h_buf) (void)hipHostFree(h_buf);
+    (void)hipStreamDestroy(s);
+    if (f) fclose(f);
+    if (n_out) *n_out = total;
+    if (stats) for (int i = 0; i < GZS_N; ++i) stats[i] = st[i];
     return rc;
 }
 

@@ -14,6 +14,7 @@
 // DOS line ends and malformed input, and which then keeps the rest of the stream.  FASTA needs no such assumption: a line
 // is a header iff it starts with '>'.
 #include "ingest.hpp"
+#include "inflate_gpu.hpp"
 #include "pgunzip.hpp"
 #include "table.hpp"
 #include <cstdio>
@@ -284,6 +285,14 @@ struct Reader {           // the concatenation of all input files as one byte st
     std::vector<std::unique_ptr<GzAhead>> ahead;   // per path: the inflating thread of a gzip file (started for all of them at once)
     bool ahead_started = false;
     GzAhead *ga = nullptr;                         // the current file's, when it is a gzip file
+    // A large regular gzip file read from byte 0 is inflated on the GPU instead (inflate_gpu.hpp), one file at a time in file order
+    // (one fills the GPU); its device buffers come from the table's workspace, allocated by start_ahead on the calling thread.
+    // JASPER_INGEST_GZ=auto (default): files of at least JASPER_INGEST_GZ_DEVICE_MIN_MB compressed MiB (unset: none); =device: every
+    // regular gzip file; =host: none.
+    Table *T = nullptr;
+    std::vector<char> gz_dev;                      // per path: 1 = the device inflater
+    GzdConfig gz_cfg;
+    std::unique_ptr<DeviceGunzip> dg;              // the current file's, when it is inflated on the device
     gzFile g = nullptr;   // pipes and other non-regular files are read through zlib's pass-through ...
     int fd = -1;          // ... anything else is read as it is (what `zcat -f` does): pread by a few threads, because one
     off_t off = 0, size = 0;   // thread copies out of the page cache at only ~7 GB/s
@@ -330,7 +339,7 @@ struct Reader {           // the concatenation of all input files as one byte st
         size_t got = 0;
         if (!ahead_started) start_ahead();
         while (got < want) {
-            if (!g && fd < 0 && !ga) {
+            if (!g && fd < 0 && !ga && !dg) {
                 if (cur >= n_paths) break;
                 fd = open(paths[cur], O_RDONLY);
                 if (fd < 0) { err = std::string("cannot open ") + paths[cur]; return -1; }
@@ -348,8 +357,16 @@ struct Reader {           // the concatenation of all input files as one byte st
                 if (m == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
                     close(fd);
                     fd = -1;
-                    if (!ahead[cur]) ahead[cur].reset(new GzAhead(paths[cur], ahead_cap, gz_threads));
-                    ga = ahead[cur].get();
+                    if (!gz_dev.empty() && gz_dev[cur]) {
+                        Table *t_ = T;
+                        dg.reset(new DeviceGunzip(paths[cur], T->device, T->gz_stream, gz_cfg, T->inflate_stats));
+                        std::string e_;
+                        if (!dg->open([t_, &e_](int slot, size_t bytes) { return t_->workspace(Table::WS_GZ + slot, bytes, e_); })) dg.reset();
+                    }
+                    if (!dg) {                                   // (not for the device inflater after all: the host's readers)
+                        if (!ahead[cur]) ahead[cur].reset(new GzAhead(paths[cur], ahead_cap, gz_threads));
+                        ga = ahead[cur].get();
+                    }
                 } else if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {       // pipes etc.: sequential reads through zlib's pass-through
                     // (on the descriptor already open: closing a FIFO's only reader would break the writer's pipe)
                     g = gzdopen(fd, "rb");
@@ -375,9 +392,13 @@ struct Reader {           // the concatenation of all input files as one byte st
                 }
             }
             long r = 0;
-            if (ga) {
+            if (dg) {
+                r = dg->read(buf + got, want - got);
+                if (r < 0) { err = dg->err; return -1; }
+            } else if (ga) {
                 r = ga->read(buf + got, want - got);
                 if (r < 0) { err = ga->err; return -1; }
+                if (T) T->inflate_stats[GZS_HOST_BYTES] += (uint64_t)r;
             } else if (g) {
                 r = gzread(g, buf + got, (unsigned)std::min<size_t>(want - got, 1u << 30));
                 if (r < 0) { err = std::string("read error in ") + paths[cur]; return -1; }
@@ -407,7 +428,8 @@ struct Reader {           // the concatenation of all input files as one byte st
                 }
             }
             if (r == 0) {
-                if (ga) { ga = nullptr; ahead[cur].reset(); }
+                if (dg) dg.reset();
+                else if (ga) { ga = nullptr; ahead[cur].reset(); }
                 else if (g) { gzclose(g); g = nullptr; }
                 else { unmap(); close(fd); fd = -1; }
                 ++cur;
@@ -437,6 +459,7 @@ struct Reader {           // the concatenation of all input files as one byte st
             close(f);
             if (m == 2 && magic[0] == 0x1f && magic[1] == 0x8b) gz.push_back(i);
         }
+        select_device(gz);
         if (gz.empty()) return;
         size_t budget = 16ull << 30;
         const long pages = sysconf(_SC_PHYS_PAGES), psz = sysconf(_SC_PAGE_SIZE);
@@ -459,7 +482,39 @@ struct Reader {           // the concatenation of all input files as one byte st
         ahead_cap = std::max<size_t>(ahead_cap, (size_t)gz_threads * (96u << 20));
         for (size_t j = 0; j < gz.size() && j < max_threads; ++j) ahead[(size_t)gz[j]].reset(new GzAhead(paths[gz[j]], ahead_cap, gz_threads));
     }
-    ~Reader() { unmap(); if (g) gzclose(g); if (fd >= 0) close(fd); }
+    // the files of `gz` (regular gzip files read from byte 0) that go to the device inflater leave the list; their buffers are allocated
+    // here, for the largest of them (a failed allocation is not an error: the files stay with the host's readers, and the counters say so)
+    void select_device(std::vector<int> &gz) {
+        gz_dev.assign((size_t)n_paths, 0);
+        if (!T || gz.empty()) return;
+        const char *mode = getenv("JASPER_INGEST_GZ");
+        const bool force = mode && !strcmp(mode, "device");
+        if (mode && !strcmp(mode, "host")) return;
+        // (no crossover: on the MI355X box the device inflater is slower than the 16-thread host reader at every size measured,
+        //  DESIGN.md 6 -- so auto picks it only when JASPER_INGEST_GZ_DEVICE_MIN_MB is given)
+        size_t min_bytes = SIZE_MAX;
+        if (const char *e = getenv("JASPER_INGEST_GZ_DEVICE_MIN_MB")) min_bytes = (size_t)strtoull(e, nullptr, 10) << 20;
+        gz_cfg = GzdConfig::from_env();
+        size_t largest = 0;
+        std::vector<int> host;
+        for (int i : gz) {
+            struct stat st;
+            if (stat(paths[i], &st) == 0 && (force || (size_t)st.st_size >= min_bytes)) { gz_dev[(size_t)i] = 1; largest = std::max(largest, (size_t)st.st_size); }
+            else host.push_back(i);
+        }
+        if (host.size() == gz.size()) return;
+        bool ok = T->gz_stream || hipStreamCreateWithFlags(&T->gz_stream, hipStreamNonBlocking) == hipSuccess;
+        std::string e;
+        for (int s = 0; ok && s < DeviceGunzip::N_SLOTS; ++s) ok = T->workspace(Table::WS_GZ + s, DeviceGunzip::bytes_needed(s, largest, gz_cfg), e) != nullptr;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (getenv("JASPER_COUNT_DEBUG")) fprintf(stderr, "[ingest] no device buffers for the gzip inflater (%s): host readers\n", e.c_str());
+            gz_dev.assign((size_t)n_paths, 0);
+            return;
+        }
+        gz.swap(host);
+    }
+    ~Reader() { dg.reset(); unmap(); if (g) gzclose(g); if (fd >= 0) close(fd); }
 };
 
 }  // namespace
@@ -523,6 +578,9 @@ int Table::count_files_gpu(const char *const *paths, int n_paths, uint64_t *gpu_
     rd.n_paths = n_paths;
     rd.begins = ingest_begin;
     rd.ends = ingest_end;
+    rd.T = this;
+    for (uint64_t &v : inflate_stats) v = 0;
+    rd.start_ahead();                                     // (the device inflater's buffers: on this thread, before any read-ahead thread)
     if (!h_ingest || ingest_chunk < CHUNK) {              // kept with the table between calls
         if (h_ingest) (void)hipHostFree(h_ingest);
         h_ingest = nullptr;

@@ -663,6 +663,7 @@ void Table::wait_streams() {
     if (jf_stream) (void)jk_stream_wait(jf_stream);
     if (ingest_stream) (void)jk_stream_wait(ingest_stream);
     if (ingest_copy_stream) (void)jk_stream_wait(ingest_copy_stream);
+    if (gz_stream) (void)jk_stream_wait(gz_stream);
 }
 
 void *Table::workspace(int id, size_t bytes, std::string &err) {
@@ -719,6 +720,7 @@ void Table::destroy() {
     if (ingest_stream) { (void)jk_stream_wait(ingest_stream); (void)hipStreamDestroy(ingest_stream); ingest_stream = nullptr; }
     if (ingest_copy_stream) { (void)jk_stream_wait(ingest_copy_stream); (void)hipStreamDestroy(ingest_copy_stream); ingest_copy_stream = nullptr; }
     for (hipEvent_t &e : ingest_copy_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    if (gz_stream) { (void)jk_stream_wait(gz_stream); (void)hipStreamDestroy(gz_stream); gz_stream = nullptr; }
     for (WsBuf &b : ws) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
     for (WsBuf &b : pin) { if (b.p) (void)hipHostFree(b.p); b.p = nullptr; b.bytes = 0; }
     for (int i = 0; i < 2; ++i) {

@@ -341,7 +341,8 @@ struct Table {
     // polish_stream[l] and the slots from WS_LANE0 + (l - 1) * WS_POLISH_MAX on.
     static constexpr int POLISH_LANES_MAX = 4;
     static constexpr int WS_POLISH_MAX = 40, WS_COUNT = 40, WS_INGEST = 44, WS_XCHG = 51, WS_HOSTBASES = 55, WS_LANE0 = 56,
-                         WS_SLOTS = WS_LANE0 + (POLISH_LANES_MAX - 1) * WS_POLISH_MAX;
+                         WS_GZ = WS_LANE0 + (POLISH_LANES_MAX - 1) * WS_POLISH_MAX,      // the device inflater's buffers (inflate_gpu.hpp)
+                         WS_SLOTS = WS_GZ + 5;
     WsBuf ws[WS_SLOTS];   // 0..WS_POLISH_MAX-1: polisher (polish_host.hip, in allocation order); WS_COUNT..+3: partitioned counting
     hipStream_t polish_stream[POLISH_LANES_MAX] = {nullptr, nullptr, nullptr, nullptr};      // [0] unused (= stream); created on first use
     hipEvent_t polish_ev = nullptr;
@@ -382,6 +383,10 @@ struct Table {
     // (ingest_gpu.hip); reports how many text bytes each parser handled
     int count_files_gpu(const char *const *paths, int n_paths, uint64_t *gpu_bytes, uint64_t *host_bytes, std::string &err);
     uint64_t ingest_gpu_bytes = 0, ingest_host_bytes = 0;
+    // gzip input of the last count_files_gpu call (jasper_last_inflate): decoders, chunks accepted, text bytes inflated on the
+    // device / on the host, slabs, members (inflate_gpu.hpp GZS_*)
+    uint64_t inflate_stats[6] = {};
+    hipStream_t gz_stream = nullptr;        // the device inflater's copies and kernels
     const int64_t *ingest_begin = nullptr, *ingest_end = nullptr;   // per-file byte ranges of the next count_files_gpu call (or null)
     // The read files as a FEED of base batches in HBM instead of counts in this table (ingest_gpu.hip, "feed"): a thread runs
     // count_files_gpu with `bases_sink` set, every batch it would have counted is handed to the caller of feed_next and the

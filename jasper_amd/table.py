@@ -201,6 +201,15 @@ class KmerTable:
         check(self._L.jasper_last_ingest(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    INFLATE_KEYS = ("decoders", "accepted", "device_bytes", "host_bytes", "slabs", "members")
+
+    def last_inflate(self):
+        """the gzip input of the last count_files / feed call, summed over its files: decoders the device inflater launched, chunks it
+        accepted, text bytes inflated on the device and on the host, slabs, members (include/jasper_hip.h jasper_last_inflate)"""
+        st = (C.c_uint64 * 6)()
+        check(self._L.jasper_last_inflate(self._h, st))
+        return dict(zip(self.INFLATE_KEYS, (int(v) for v in st)))
+
     def count_text(self, text):
         if isinstance(text, str):
             text = text.encode()
