@@ -33,10 +33,14 @@ def _tty():
 _T0 = [None]
 
 
+def _timing_on():
+    return bool(os.environ.get("JASPER_AMD_TIMING"))
+
+
 def _timing(label):
     """JASPER_AMD_TIMING=1: seconds since the previous mark, on stderr (not part of the reference's output)"""
     import time
-    if not os.environ.get("JASPER_AMD_TIMING"):
+    if not _timing_on():
         return
     now = time.perf_counter()
     if _T0[0] is not None:
@@ -403,31 +407,71 @@ def _write_histo(path, rows):
     os.replace(path + ".tmp", path)
 
 
-def _run_multi(o, rank, world, dev, batch_size, passes, kmer, job=None):
-    """the stages of run() below with the work of one node's GPUs divided as SURVEY.md 8e says: every rank counts its byte
-    ranges of the read files (or its record range of an existing database) into a local table, dist.shard_tables sums the
-    counts by key owner, and every rank polishes its share of the batch files with lookups served from the owners' HBM.
-    Rank 0 alone splits, joins, writes the histogram / threshold / sentinels and talks; the stage decisions (which
-    sentinels exist) are taken by rank 0 and shared, so that no rank sees a file another one is just creating.
-    mer_counts$K.jf is written by all GPUs together (dist.write_jf_sharded); an existing one, or -j, is read in record ranges."""
-    import torch
-    import torch.distributed as tdist
-    from . import dist as jdist
-    is0 = rank == 0
-    last_it = passes - 1
-    qfn = o.query_fn
+def _nonempty(path):
+    """bash's `[ -s path ]`"""
+    return os.path.isfile(path) and os.path.getsize(path) > 0
 
-    def bar():
-        torch.cuda.synchronize(dev)
-        tdist.barrier()
 
-    def decide(cond):
-        return bool(jdist.all_reduce_ints([1 if (is0 and cond()) else 0], device=dev)[0])
+def _touch(sentinel):
+    open(sentinel, "w").close()
 
-    def together(work, msg):
+
+def _drop(sentinel):
+    if os.path.exists(sentinel):
+        os.remove(sentinel)
+
+
+SPLIT_FAILED = "Splitting files failed, do you have enough disk space?"      # :158
+
+
+def _jf_failed(path):                                                   # :182-184
+    return "Computing mer counts histogram from %s failed, please make sure that %s is a valid Jellyfish mer counts file" % (path, path)
+
+
+class _Ranks:
+    """How the processes of a run agree.  Several ranks (one process per GPU): rank 0 alone splits, joins, writes the histogram /
+    threshold / sentinels and talks; the stage decisions (which sentinels exist) are taken by rank 0 and shared, so that no rank
+    sees a file another one is just creating.  One process: the same interface without a single collective call (and without
+    torch: interpreter start-up is most of a small run)."""
+
+    def __init__(self, rank=0, world=1, dev=None):
+        self.rank, self.world, self.dev, self.is0 = rank, world, dev, rank == 0
+
+    def total(self, values, op="sum"):
+        """a short list of ints summed (or "min") over the ranks"""
+        from . import dist as jdist
+        return jdist.all_reduce_ints(values, device=self.dev, op=op)
+
+    def bar(self):
+        if self.world > 1:
+            import torch
+            import torch.distributed as tdist
+            if self.dev is not None and self.dev.type == "cuda":
+                torch.cuda.synchronize(self.dev)
+            tdist.barrier()
+
+    def decide(self, cond):
+        """rank 0 evaluates cond(), everybody gets the answer"""
+        if self.world == 1:
+            return bool(cond())
+        return bool(self.total([1 if (self.is0 and cond()) else 0])[0])
+
+    def agree(self, flag):
+        """true when it is on every rank"""
+        if self.world == 1:
+            return bool(flag)
+        return bool(self.total([1 if flag else 0], op="min")[0])
+
+    def together(self, work, msg, catch=()):
         """a stage that every rank runs on its own share: a rank that fails (an exception, or the reference's own sys.exit(1))
         must not leave the others waiting in the next collective -- the outcome is agreed, and either all ranks go on or all
-        leave with the message jasper.sh prints for that stage (only rank 0 talks)"""
+        leave with the message jasper.sh prints for that stage (only rank 0 talks).
+        One process: only `catch` ends with the message -- what that stage has caught so far, which differs from stage to stage."""
+        if self.world == 1:
+            try:
+                return work()
+            except catch:
+                error_exit(msg)
         failed, why, out = 0, "", None
         try:
             out = work()
@@ -436,312 +480,10 @@ def _run_multi(o, rank, world, dev, batch_size, passes, kmer, job=None):
         except BaseException as e:                      # noqa: BLE001 -- whatever it was, the others must hear of it
             failed, why = 1, "%s: %s" % (type(e).__name__, e)
         if why:
-            sys.stderr.write("jasper_amd: rank %d: %s\n" % (rank, why))
-        if jdist.all_reduce_ints([failed], device=dev)[0]:
+            sys.stderr.write("jasper_amd: rank %d: %s\n" % (self.rank, why))
+        if self.total([failed])[0]:
             error_exit(msg)
         return out
-
-    keep_fixed = bool(os.environ.get("JASPER_AMD_KEEP_INTERMEDIATES"))
-    job_split = job_polished = False
-    file_owner = None
-    pinner = None
-
-    def split_done():
-        """the job's batch files are complete on every rank (or "Splitting files failed" on all): jasper.split.success"""
-        if job_split and decide(lambda: not os.path.exists("jasper.split.success")):
-            together(job.split_wait, "Splitting files failed, do you have enough disk space?")
-            bar()
-            if is0:
-                if os.path.exists("jasper.correct.success"):
-                    os.remove("jasper.correct.success")
-                open("jasper.split.success", "w").close()
-
-    if decide(lambda: not os.path.exists("jasper.split.success")):      # :152-159
-        log("Splitting query into batches for parallel execution")
-        # every rank holds the assembly in a job of its own (the same records and batch files everywhere: the plan is a function of
-        # the file and the batch size); a rank writes the batch files it will polish, on a thread, while the reads are counted --
-        # nobody splits alone behind a barrier.  Any rank without a job (not an ordinary FASTA): rank 0 splits in Python, as before.
-        use_job = bool(jdist.all_reduce_ints([1 if (job is not None and batch_size > 0 and job.n_contigs) else 0], device=dev, op="min")[0])
-        if is0:
-            for p in glob.glob("%s.batch.*.fa" % glob.escape(qfn)):
-                os.remove(p)
-        bar()
-        if use_job:
-            def plan_and_write():
-                nonlocal file_owner
-                job.split(batch_size, qfn, write_files=False)
-                order = sorted(range(job.n_files), key=job.batch_file_name)                    # `ls` order, as the polishing stage lists them
-                own = jdist.assign_chunks([job.file_bytes[f] for f in order], world)
-                file_owner = {f: ow for f, ow in zip(order, own)}
-                job.split(batch_size, qfn, write_files=True, only_files=[f for f in order if file_owner[f] == rank])
-            together(plan_and_write, "Splitting files failed, do you have enough disk space?")
-            job_split = True
-            pinner = _in_thread(lambda: job.pin(o.device))
-        else:
-            if is0:
-                try:
-                    split_batches(read_assembly(o.query), batch_size, qfn)
-                except OSError:
-                    error_exit("Splitting files failed, do you have enough disk space?")
-                if os.path.exists("jasper.correct.success"):
-                    os.remove("jasper.correct.success")
-                open("jasper.split.success", "w").close()
-            bar()
-
-    histo_file = "jfhisto%d.csv" % kmer
-    counted = False
-    if o.jf_db is None:                                                 # :162-185
-        reads = o.reads.split()
-        for fn in reads:
-            if not (os.path.isfile(fn) and os.path.getsize(fn) > 0):
-                error_exit("The reads file  %s does not exist. Please supply a series of valid reads files separated by space and wrapped in one pair of quotation marks." % fn)
-        jf_file = "mer_counts%d.jf" % kmer
-        if decide(lambda: os.path.isfile(jf_file) and os.path.getsize(jf_file) > 0):     # :171-173
-            log("Using existing jellyfish database %s" % jf_file)
-            if is0 and os.path.exists("jasper.no_cat.success"):
-                os.remove("jasper.no_cat.success")
-            local = together(lambda: KmerTable.from_jf_part(jf_file, rank, world, device=o.device),
-                             "Computing mer counts histogram from %s failed, please make sure that %s is a valid Jellyfish mer counts file" % (jf_file, jf_file))
-        else:
-            _timing("split")
-            log("Creating jellyfish database mer_counts%d.jf" % kmer)
-            fail_msg = "Computing mer counts histogram from mer_counts%d.jf failed, please make sure that mer_counts%d.jf is a valid Jellyfish mer counts file" % (kmer, kmer)
-            my_ranges = jdist.plan_read_shards(reads, world)[rank]
-            # No table per GPU when the key owners' table has a geometry for it (dist.count_sharded): the file reader feeds batches
-            # of bases, every batch is partitioned into region lists by key owner, ONE all_to_all moves the lists, the owners insert.
-            sharded = None
-            how = os.environ.get("JASPER_AMD_COUNT", "auto")
-            if how != "local":
-                # (sized like the reference's `-s $JF_SIZE` hash, for the keys one owner will hold; JASPER_AMD_SHARD_SLOTS overrides)
-                shard_slots = int(os.environ.get("JASPER_AMD_SHARD_SLOTS", max(1 << 21, int(1.25 * o.jf_size / world))))
-                sharded = together(lambda: KmerTable(kmer, min_slots=shard_slots, device=o.device), fail_msg)
-                plan = sharded.exchange_plan(1 << 26, world)
-                take = plan is not None
-                if take and how == "auto":   # bytes per link decide (dist.prefer_exchange): FASTQ is ~2.1 bytes per base; -s is the expected number of distinct k-mers
-                    occ = sum((e if e >= 0 else os.path.getsize(p)) - b for p, b, e in my_ranges) / 2.1
-                    dedup = plan["p2"] >= 1 and jdist.dedupe_pays(world)
-                    take = jdist.prefer_exchange(world, occ, o.jf_size, deduplicated=dedup)
-                if not jdist.all_reduce_ints([1 if take else 0], device=dev, op="min")[0]:
-                    sharded.close()
-                    sharded = None
-            if sharded is not None:
-                feeder = KmerTable(kmer, min_slots=1 << 10, device=o.device)      # lends its device buffers to the reader
-                together(lambda: feeder.feed_start(my_ranges), fail_msg)
-                try:
-                    info = jdist.count_sharded(sharded, 0, 0, dev, feeder=feeder)
-                except jdist.ShardAttachError as e:         # (raised on every rank together, after all lists were inserted)
-                    sharded._attach_failed = str(e)
-                    info = dict(rounds=-1)
-                except jdist.CollectiveCountError as e:     # (raised on every rank together: e.g. shards sized from a hint that was far too small;
-                                                            #  anything else is this rank's own failure and ends it -- no fallback the peers do not take)
-                    if is0:
-                        sys.stderr.write("jasper_amd: %s -- counting into a table per GPU instead\n" % e)
-                    info = None
-                finally:
-                    feeder.close()
-                if info is None:                            # start over the round-1 way (the read files are read again)
-                    sharded.detach()
-                    bar()
-                    sharded.close()
-                    sharded = None
-                else:
-                    local = None
-                    _timing("count reads (file ranges -> region lists -> owners' shards, %d rounds)" % info["rounds"])
-            if sharded is None:
-                def count_my_ranges():
-                    t = KmerTable(kmer, min_slots=max(1 << 20, int(1.25 * o.jf_size / world)), device=o.device)
-                    t.count_file_ranges(my_ranges)
-                    return t
-                local = together(count_my_ranges, fail_msg)
-                _timing("count reads (file ranges -> local table)")
-            counted = True
-    else:
-        local = together(lambda: KmerTable.from_jf_part(o.jf_db, rank, world, device=o.device),
-                         "Computing mer counts histogram from %s failed, please make sure that %s is a valid Jellyfish mer counts file" % (o.jf_db, o.jf_db))
-    # key-wise sum over the GPUs; the result stays sharded by key owner unless the peers' HBM cannot be mapped
-    write_db = counted and os.environ.get("JASPER_AMD_NO_JF", "") not in ("1", "true", "yes")
-    db_cmdline = ["count", "-C", "-t", str(o.num_threads), "-s", str(o.jf_size), "-m", str(kmer), "-o", "mer_counts%d.jf" % kmer] + (o.reads.split() if counted else [])
-    # sharded by owner, or a copy of the whole table on every GPU?  dist.prefer_replicated: it must fit and the gather must cost less than
-    # the remote lookups it saves -- with one polish call per counted table it does not (JASPER_AMD_TABLE=replicated|sharded overrides)
-    how_table = os.environ.get("JASPER_AMD_TABLE", "auto")
-    replicate = how_table == "replicated"
-    if how_table == "auto":
-        try:
-            import ctypes as C
-            from . import _lib
-            free_b, total_b = C.c_uint64(0), C.c_uint64(0)
-            _lib.check(_lib.lib().jasper_device_mem_info(int(o.device), C.byref(free_b), C.byref(total_b)))
-            asm_bases = job.n_bases if job is not None else os.path.getsize(o.query)
-            replicate = jdist.prefer_replicated(world, max(o.jf_size, 1), asm_bases / world, passes + 1, free_b.value)
-        except Exception:           # noqa: BLE001 -- no answer: the default
-            replicate = False
-    replicate = bool(jdist.all_reduce_ints([1 if replicate else 0], device=dev, op="min")[0])
-    try:
-        if replicate:
-            raise jdist.ShardAttachError("a copy of the whole table on every GPU was asked for (or is expected to pay)")
-        if local is None:       # counted straight into the owners' shards
-            table = sharded
-            local = table       # (what the fallback below merges: the shards are disjoint, their key-wise sum is the whole table)
-            if getattr(table, "_attach_failed", None):
-                raise jdist.ShardAttachError(table._attach_failed)
-        else:
-            table = KmerTable(local.k, min_slots=1 << 21, device=o.device)
-            jdist.shard_tables(local, table, dev)
-            local.close()
-        if write_db:       # :177 `... | tee $JF_DB | ...`: every GPU sorts and writes one consecutive piece of the file
-            jdist.write_jf_sharded(table, "mer_counts%d.jf" % kmer, db_cmdline, dev)
-            _timing("write mer_counts.jf")
-        h = jdist.histogram_sharded(table, dev)
-    except jdist.ShardAttachError as e:
-        if is0:
-            sys.stderr.write("jasper_amd: %s -- replicating the merged table on every GPU instead\n" % e)
-        if replicate:
-            table = local if local is not None else sharded
-            local = table
-        table.detach()          # (whatever was mapped is unmapped on every rank before anybody frees its slot array)
-        bar()
-        if table is not local:
-            table.close()
-        table = local
-        jdist.merge_tables(table, dev)
-        if write_db:
-            if is0:
-                table.write_jf("mer_counts%d.jf.tmp" % kmer, db_cmdline)
-                os.replace("mer_counts%d.jf.tmp" % kmer, "mer_counts%d.jf" % kmer)
-            bar()
-        h = jdist.histogram_merged(table, dev)
-    rows = [(m, h[m]) for m in range(1, 10002) if h[m]]
-    _timing("sum counts over the GPUs + histogram")
-    if counted and is0:
-        _write_histo(histo_file, rows)
-        open("jasper.no_cat.success", "w").close()
-        open("jasper.histo.success", "w").close()
-        if os.path.exists("jasper.correct.success"):
-            os.remove("jasper.correct.success")
-    bar()
-
-    split_done()
-    if decide(lambda: not os.path.exists("jasper.histo.success") or not (os.path.isfile(histo_file) and os.path.getsize(histo_file) > 0)):   # :187-193
-        log("Computing K-mer histogram")
-        if is0:
-            _write_histo(histo_file, rows)
-            if os.path.exists("jasper.correct.success"):
-                os.remove("jasper.correct.success")
-            open("jasper.histo.success", "w").close()
-        bar()
-
-    if decide(lambda: not os.path.exists("jasper.correct.success")):    # :195-216
-        log("Polishing")
-        if is0:
-            txt, status = polisher.threshold_from_histo_file(histo_file)
-            if status == 0:
-                with open("threshold.txt.tmp", "w") as f:
-                    f.write(txt)
-                os.replace("threshold.txt.tmp", "threshold.txt")
-        bar()
-        if not (os.path.isfile("threshold.txt") and os.path.getsize("threshold.txt") > 0):
-            error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable for polishing.")
-        thresh = int(open("threshold.txt").read().split()[0])
-        log("Lower threshold for unreliable kmers is %d" % thresh)
-        group, group_bytes = [], 0
-        if job_split:
-            # (as in run(): record text from the job's arena, polished text back into the job, no `_iter*.fixed.fa` unless asked for,
-            #  and jasper.correct.success only once the join below has made the polished FASTA)
-            def flush_group():
-                if group:
-                    polisher.main_many_job(job, list(group), kmer, True, True, table, thresh, passes, keep_fixed=keep_fixed)
-                    if keep_fixed:
-                        for f in group:
-                            bf = job.batch_file_name(f)
-                            os.replace("_iter%d_%s.fixed.fa.tmp" % (last_it, bf), "_iter%d_%s.fixed.fa" % (last_it, bf))
-                    del group[:]
-            def polish_my_batches():
-                nonlocal group_bytes
-                if pinner is not None:
-                    pinner.join()
-                for f in sorted(range(job.n_files), key=job.batch_file_name):
-                    if file_owner[f] != rank:
-                        continue
-                    group.append(f)
-                    group_bytes += job.file_bytes[f]
-                    if group_bytes > (1 << 30):
-                        flush_group()
-                        group_bytes = 0
-                flush_group()
-            together(polish_my_batches, "Polishing failed")                          # :215
-            job_polished = True
-            bar()
-            if is0 and os.path.exists("jasper.join.success"):
-                os.remove("jasper.join.success")
-            bar()
-        else:
-            batch_files = sorted(glob.glob("%s.batch.*.fa" % glob.escape(qfn)))   # `ls` order
-            owner = jdist.assign_chunks([os.path.getsize(bf) for bf in batch_files], world)
-
-            def flush_group():
-                if group:
-                    polisher.main_many(group, kmer, True, True, table, thresh, passes)
-                    for bf in group:
-                        os.replace("_iter%d_%s.fixed.fa.tmp" % (last_it, bf), "_iter%d_%s.fixed.fa" % (last_it, bf))
-                    del group[:]
-            def polish_my_batches():
-                nonlocal group_bytes
-                for bf, ow in zip(batch_files, owner):
-                    if ow != rank:
-                        continue
-                    group.append(bf)
-                    group_bytes += os.path.getsize(bf)
-                    if group_bytes > (1 << 30):
-                        flush_group()
-                        group_bytes = 0
-                flush_group()
-            together(polish_my_batches, "Polishing failed")                          # :215
-            bar()
-            if is0:
-                if os.path.exists("jasper.join.success"):
-                    os.remove("jasper.join.success")
-                open("jasper.correct.success", "w").close()
-            bar()
-
-    if decide(lambda: not os.path.exists("jasper.join.success")):       # :218-232
-        _timing("polish batches")
-        log("Joining")
-        if job_polished:
-            # every rank writes the records it polished straight into their places of ONE file: a record's place follows from the
-            # polished lengths of the records before it (a sum over ranks of a short vector), so no text moves between ranks and
-            # nobody reads the assembly or the fixed files again (src/jasper.sh:220)
-            lens, have = job.polished_lens()
-            all_lens = jdist.all_reduce_ints([int(v) for v in lens], device=dev)
-            held = jdist.all_reduce_ints([int(v) for v in have], device=dev)
-            tmp = qfn + ".fixed.fasta.tmp"
-
-            def create():
-                if min(held, default=1) != 1 or max(held, default=1) != 1:
-                    raise RuntimeError("a chunk record was polished by no rank, or by two")
-                if is0:
-                    job.join(tmp, all_lens=all_lens, mode=1)
-            together(create, "Joining failed")
-            bar()
-            together(lambda: job.join(tmp, all_lens=all_lens, mode=2), "Joining failed")
-            bar()
-            if is0:
-                os.replace(tmp, qfn + ".polished.fasta")
-                open("jasper.correct.success", "w").close()
-                _join_and_merge(o, qfn, batch_size, last_it, None, fasta_done=True)
-        elif is0:
-            _join_and_merge(o, qfn, batch_size, last_it, read_assembly(o.query))
-        bar()
-    if is0:
-        _qv_block(passes, kmer)
-    _timing("join + QV")
-    log("Polished sequence is in %s.polished.fasta" % qfn)
-    bar()                       # nobody unmaps or frees a shard that a peer may still be reading ...
-    table.detach()              # ... every rank lets go of its peers' memory ...
-    bar()                       # ... and only then is any of it freed
-    table.close()
-    bar()
-    tdist.destroy_process_group()
-    return 0
 
 
 def _stop_thread(th, leftover=None):
@@ -762,107 +504,158 @@ def _stop_thread(th, leftover=None):
                 pass
 
 
-class _EarlyTable:
-    """KmerTable(k, min_slots) created -- and the read files counted into it -- by a thread (the library calls release the GIL)
-    while the caller splits the assembly; get() hands the table over, or raises what the thread raised"""
+class _Background:
+    """fn() on a daemon thread (the library calls release the GIL); result() waits and returns what fn returned, or raises what
+    it raised -- drop_errors: optional work, what it raises is dropped.
+    at_exit: an exit taken while the thread is still inside the GPU driver (the split stage that runs beside the counting calls
+    error_exit -> sys.exit on an unreadable assembly or a full disk) must wait for it: tearing the interpreter down under a
+    thread that initialises HIP can hang or crash instead of giving the reference's clean exit code for that stage.
+    `leftover`, the thread's unfinished file, goes then."""
 
-    def __init__(self, k, min_slots, device, reads=None):
+    def __init__(self, fn, drop_errors=False, at_exit=False, leftover=None):
         import threading
         self.out, self.err = None, None
 
         def work():
             try:
-                import time
-                t0 = time.perf_counter()
-                t = KmerTable(k, min_slots=min_slots, device=device)
-                t1 = time.perf_counter()
-                if reads:
-                    t.count_files(reads)
-                if os.environ.get("JASPER_AMD_TIMING"):
-                    sys.stderr.write("[timing-thread] library + GPU runtime + table %.3f s, files -> table %.3f s\n" % (t1 - t0, time.perf_counter() - t1))
-                self.out = t
-            except BaseException as e:          # noqa: BLE001 -- handed to the caller of get()
-                self.err = e
+                self.out = fn()
+            except BaseException as e:          # noqa: BLE001 -- handed to the caller of result()
+                if not drop_errors:
+                    self.err = e
 
         self.th = threading.Thread(target=work, daemon=True)
         self.th.start()
-        # an exit taken while the thread is still inside the GPU driver (the split stage that runs beside it calls error_exit ->
-        # sys.exit on an unreadable assembly or a full disk) must wait for it: tearing the interpreter down under a thread that
-        # initialises HIP can hang or crash instead of giving the reference's clean "Splitting files failed" exit code
-        import atexit
-        atexit.register(_stop_thread, self.th)
+        if at_exit:
+            import atexit
+            atexit.register(_stop_thread, self.th, leftover)
 
-    def get(self):
+    def result(self):
         self.th.join()
         if self.err is not None:
             raise self.err
         return self.out
 
 
-def _in_thread(fn):
-    """fn() on a daemon thread; what it raises is dropped (optional work: pinning buffers)"""
-    import threading
-
-    def work():
-        try:
-            fn()
-        except BaseException:           # noqa: BLE001
-            pass
-    th = threading.Thread(target=work, daemon=True)
-    th.start()
-    return th
+def _early_table(k, min_slots, device, reads):
+    """KmerTable(k, min_slots) created, and the read files counted into it: the work of a thread while the caller splits the assembly"""
+    import time
+    t0 = time.perf_counter()
+    t = KmerTable(k, min_slots=min_slots, device=device)
+    t1 = time.perf_counter()
+    t.count_files(reads)
+    if _timing_on():
+        sys.stderr.write("[timing-thread] library + GPU runtime + table %.3f s, files -> table %.3f s\n" % (t1 - t0, time.perf_counter() - t1))
+    return t
 
 
-class _JobJoin:
-    """job.join(tmp) by a thread (src/jasper.sh:220 from the job's memory; the library call releases the GIL); finish() waits and
-    raises what the thread raised"""
-
-    def __init__(self, job, tmp):
-        import threading
-        self.err = None
-
-        def work():
-            try:
-                job.join(tmp)
-            except BaseException as e:          # noqa: BLE001 -- handed to the caller of finish()
-                self.err = e
-
-        self.th = threading.Thread(target=work, daemon=True)
-        self.th.start()
-
-    def finish(self):
-        self.th.join()
-        if self.err is not None:
-            raise self.err
+def _groups(items, size_of, limit=1 << 30):
+    """the reference starts one jasper.py process per batch file (:207-212); chunk records are independent, so all files go
+    through the GPU in groups of about `limit` bytes of text per call: a group is cut once its sum exceeds the limit (the last
+    one may be small, none is empty)"""
+    groups, group, total = [], [], 0
+    for it in items:
+        group.append(it)
+        total += size_of(it)
+        if total > limit:
+            groups.append(group)
+            group, total = [], 0
+    if group:
+        groups.append(group)
+    return groups
 
 
-class _JfWriter:
-    """table.write_jf(tmp) + rename to `final`, by a thread, while the caller goes on to the histogram and the polishing (the
-    database file is `tee`'s by-product in the reference, src/jasper.sh:177: nothing in the same run reads it, and writing 14 bytes
-    per distinct k-mer takes longer than all the polishing).  finish() waits and raises what the thread raised; the file gets its
-    name only when it is complete."""
+def _split(ranks, o, job, batch_size):
+    """src/jasper.sh:152-159.  Returns (file_owner, pinner, contigs): file_owner[f] = the rank that wrote, and will polish, the
+    job's batch file f -- None when the batch files are not the job's; the thread that pins the job's arena; the contigs when
+    the assembly was split in Python."""
+    qfn = o.query_fn
+    file_owner = pinner = contigs = None
+    if ranks.decide(lambda: not os.path.exists("jasper.split.success")):
+        log("Splitting query into batches for parallel execution")
+        # every rank holds the assembly in a job of its own (the same records and batch files everywhere: the plan is a function of
+        # the file and the batch size); a rank writes the batch files it will polish, on a thread of the job, while the reads are
+        # counted -- nobody splits alone behind a barrier -- and jasper.split.success appears when they are complete (_split_done,
+        # before "Polishing").  Any rank without a job (not an ordinary FASTA): rank 0 splits in Python.
+        use_job = ranks.agree(job is not None and batch_size > 0 and job.n_contigs)
+        if ranks.is0:
+            for p in glob.glob("%s.batch.*.fa" % glob.escape(qfn)):
+                os.remove(p)
+        ranks.bar()
+        if use_job:
+            def plan_and_write():
+                if ranks.world == 1:            # every file is rank 0's: perl #1 + perl #2 on the arena in one call
+                    job.split(batch_size, qfn, write_files=True)
+                    return dict.fromkeys(range(job.n_files), 0)
+                from . import dist as jdist
+                job.split(batch_size, qfn, write_files=False)
+                order = sorted(range(job.n_files), key=job.batch_file_name)                    # `ls` order, as the polishing stage lists them
+                owner = dict(zip(order, jdist.assign_chunks([job.file_bytes[f] for f in order], ranks.world)))
+                job.split(batch_size, qfn, write_files=True, only_files=[f for f in order if owner[f] == ranks.rank])
+                return owner
+            file_owner = ranks.together(plan_and_write, SPLIT_FAILED, catch=Exception)   # (a full disk, a directory that went away)
+            pinner = _Background(lambda: job.pin(o.device), drop_errors=True)      # (waits for the GPU runtime, pins the arena: beside the counting)
+        else:
+            if ranks.is0:
+                try:
+                    contigs = read_assembly(o.query)
+                    split_batches(contigs, batch_size, qfn)
+                except OSError:
+                    error_exit(SPLIT_FAILED)
+                _drop("jasper.correct.success")
+                _touch("jasper.split.success")
+            ranks.bar()
+    return file_owner, pinner, contigs
 
-    def __init__(self, table, tmp, final, cmdline):
-        import threading
-        self.err = None
-        self.cmdline = cmdline
 
-        def work():
-            try:
-                table.write_jf(tmp, cmdline)
-                os.replace(tmp, final)
-            except BaseException as e:          # noqa: BLE001 -- handed to the caller of finish()
-                self.err = e
+def _split_done(ranks, job, file_owner):
+    """the job's batch files are complete on every rank (or SPLIT_FAILED on all): jasper.split.success"""
+    if file_owner is not None and ranks.decide(lambda: not os.path.exists("jasper.split.success")):
+        ranks.together(job.split_wait, SPLIT_FAILED, catch=Exception)
+        ranks.bar()
+        if ranks.is0:
+            _drop("jasper.correct.success")
+            _touch("jasper.split.success")
 
-        self.th = threading.Thread(target=work, daemon=True)
-        self.th.start()
-        import atexit
-        atexit.register(_stop_thread, self.th, tmp)   # (an exit taken meanwhile waits for the thread, as for _EarlyTable; its unfinished file goes)
 
-    def finish(self):
-        self.th.join()
-        if self.err is not None:
-            raise self.err
+def _reads(o):
+    reads = o.reads.split()
+    for fn in reads:
+        if not _nonempty(fn):
+            error_exit("The reads file  %s does not exist. Please supply a series of valid reads files separated by space and wrapped in one pair of quotation marks." % fn)
+    return reads
+
+
+def _existing_db(ranks, jf_file):
+    """src/jasper.sh:171-173: is there a database to read instead of counting?"""
+    if not ranks.decide(lambda: _nonempty(jf_file)):
+        return False
+    log("Using existing jellyfish database %s" % jf_file)
+    if ranks.is0:
+        _drop("jasper.no_cat.success")
+    return True
+
+
+def _jf_wanted():
+    return os.environ.get("JASPER_AMD_NO_JF", "") not in ("1", "true", "yes")
+
+
+def _jf_cmdline(o, kmer):
+    """the `jellyfish count` of src/jasper.sh:177, for the header of the database file"""
+    return ["count", "-C", "-t", str(o.num_threads), "-s", str(o.jf_size), "-m", str(kmer), "-o", "mer_counts%d.jf" % kmer] + o.reads.split()
+
+
+def _write_jf(table, o, kmer):
+    """the file gets its name only when it is complete"""
+    jf_file = "mer_counts%d.jf" % kmer
+    table.write_jf(jf_file + ".tmp", _jf_cmdline(o, kmer))
+    os.replace(jf_file + ".tmp", jf_file)
+
+
+def _counted():
+    """the sentinels of a database counted from the reads, its histogram file written (:185)"""
+    _touch("jasper.no_cat.success")
+    _touch("jasper.histo.success")
+    _drop("jasper.correct.success")
 
 
 def _jf_write_fits_beside_polishing(table, device, qfn, text_bytes=None):
@@ -884,6 +677,275 @@ def _jf_write_fits_beside_polishing(table, device, qfn, text_bytes=None):
     return need < free.value
 
 
+def _count_one(ranks, o, kmer, early, job, file_owner, histo_file):
+    """src/jasper.sh:162-185 in one process: the table `early` has counted beside the split (or one counted here), or an existing
+    database read into HBM.  Returns (table, the thread that writes mer_counts$K.jf beside the later stages -- or None)."""
+    jf_writer = None
+    if o.jf_db is not None:
+        # -j: an existing Jellyfish database; its header decides k (JF::swig/mer_file.i:23 -- the DB wins over -k)
+        try:
+            return KmerTable.from_jf(o.jf_db, device=o.device), None
+        except Exception as e:      # (several ranks give the message without the reason)
+            error_exit(_jf_failed(o.jf_db) + " (%s)" % e)
+    reads = _reads(o)
+    jf_file = "mer_counts%d.jf" % kmer
+    if _existing_db(ranks, jf_file):
+        return KmerTable.from_jf(jf_file, device=o.device), None
+    _timing("split")
+    log("Creating jellyfish database mer_counts%d.jf" % kmer)
+    if early is not None:
+        try:                                    # (what the later stages import, while this thread only waits)
+            import numpy                        # noqa: F401 -- 0.1 s that histo_rows / the fix records would otherwise spend
+            import csv, io                      # noqa: F401,E401
+        except ImportError:
+            pass
+        table = early.result()                  # (counted while the assembly was split)
+    else:
+        table = KmerTable(kmer, min_slots=max(1 << 20, int(1.25 * o.jf_size)), device=o.device)
+        table.count_files(reads)
+    _timing("count reads (files -> table)")
+    # (the histogram first, on this thread: whatever a lazily cleared table still owes its slots is settled before a
+    #  second thread looks at them.  Several ranks write it from the reduced histogram, after the database file.)
+    _write_histo(histo_file, table.histo_rows())
+    if _jf_wanted():
+        # :177 `... | tee $JF_DB | ...`: leave the database behind for reruns and for other Jellyfish tools.  Written by a
+        # thread beside the polishing when the device has room for both (the writer holds ~48 bytes per distinct k-mer plus
+        # its sort's workspace, the polisher several times its batch's text); otherwise first the file, then the polishing,
+        # as the reference orders them.  The database file is `tee`'s by-product: nothing in the same run reads it, and writing
+        # 14 bytes per distinct k-mer takes longer than all the polishing.
+        if _jf_write_fits_beside_polishing(table, o.device, o.query_fn, sum(job.file_bytes) if file_owner is not None else None):      # (the job's files may still be being written)
+            jf_writer = _Background(lambda: _write_jf(table, o, kmer), at_exit=True, leftover=jf_file + ".tmp")
+        else:
+            try:
+                _write_jf(table, o, kmer)
+            except Exception as e:             # noqa: BLE001 -- what `set -o pipefail` makes of a failing tee (src/jasper.sh:177-181)
+                error_exit("Creating jellyfish database mer_counts%d.jf failed (%s)" % (kmer, e))
+            _timing("write mer_counts.jf (before the polishing: not enough device memory for both at once)")
+    _counted()
+    return table, jf_writer
+
+
+def _jf_written(jf_writer, table, o, kmer):
+    """the end of _count_one's writer thread"""
+    try:
+        try:
+            jf_writer.result()
+        except Exception as e1:            # noqa: BLE001 -- e.g. a device allocation that failed beside the polisher's: once more, alone
+            if "alloc" not in str(e1).lower() and "memory" not in str(e1).lower():
+                raise
+            _write_jf(table, o, kmer)
+    except Exception as e:                 # noqa: BLE001 -- what `set -o pipefail` makes of a failing tee (src/jasper.sh:177-181)
+        error_exit("Creating jellyfish database mer_counts%d.jf failed (%s)" % (kmer, e))
+    _timing("mer_counts.jf complete (written beside the stages above)")
+
+
+def _count_ranks(ranks, o, kmer, passes, job, histo_file):
+    """src/jasper.sh:162-185 with the work of one node's GPUs divided as SURVEY.md 8e says: every rank counts its byte ranges of
+    the read files (or its record range of an existing database, or of -j) into a local table -- or straight into the key
+    owners' shards -- and dist.shard_tables sums the counts by key owner; the polisher's lookups are then served from the
+    owners' HBM.  mer_counts$K.jf is written by all GPUs together (dist.write_jf_sharded).
+    Returns (table, the rows of the histogram summed over the GPUs)."""
+    from . import dist as jdist
+    rank, world, dev, is0 = ranks.rank, ranks.world, ranks.dev, ranks.is0
+    counted = False
+    sharded = None
+    if o.jf_db is not None:
+        local = ranks.together(lambda: KmerTable.from_jf_part(o.jf_db, rank, world, device=o.device), _jf_failed(o.jf_db))
+    else:
+        reads = _reads(o)
+        jf_file = "mer_counts%d.jf" % kmer
+        if _existing_db(ranks, jf_file):
+            local = ranks.together(lambda: KmerTable.from_jf_part(jf_file, rank, world, device=o.device), _jf_failed(jf_file))
+        else:
+            _timing("split")
+            log("Creating jellyfish database mer_counts%d.jf" % kmer)
+            fail_msg = _jf_failed(jf_file)
+            my_ranges = jdist.plan_read_shards(reads, world)[rank]
+            # No table per GPU when the key owners' table has a geometry for it (dist.count_sharded): the file reader feeds batches
+            # of bases, every batch is partitioned into region lists by key owner, ONE all_to_all moves the lists, the owners insert.
+            how = os.environ.get("JASPER_AMD_COUNT", "auto")
+            if how != "local":
+                # (sized like the reference's `-s $JF_SIZE` hash, for the keys one owner will hold; JASPER_AMD_SHARD_SLOTS overrides)
+                shard_slots = int(os.environ.get("JASPER_AMD_SHARD_SLOTS", max(1 << 21, int(1.25 * o.jf_size / world))))
+                sharded = ranks.together(lambda: KmerTable(kmer, min_slots=shard_slots, device=o.device), fail_msg)
+                plan = sharded.exchange_plan(1 << 26, world)
+                take = plan is not None
+                if take and how == "auto":   # bytes per link decide (dist.prefer_exchange): FASTQ is ~2.1 bytes per base; -s is the expected number of distinct k-mers
+                    occ = sum((e if e >= 0 else os.path.getsize(p)) - b for p, b, e in my_ranges) / 2.1
+                    dedup = plan["p2"] >= 1 and jdist.dedupe_pays(world)
+                    take = jdist.prefer_exchange(world, occ, o.jf_size, deduplicated=dedup)
+                if not ranks.agree(take):
+                    sharded.close()
+                    sharded = None
+            if sharded is not None:
+                feeder = KmerTable(kmer, min_slots=1 << 10, device=o.device)      # lends its device buffers to the reader
+                ranks.together(lambda: feeder.feed_start(my_ranges), fail_msg)
+                try:
+                    info = jdist.count_sharded(sharded, 0, 0, dev, feeder=feeder)
+                except jdist.ShardAttachError as e:         # (raised on every rank together, after all lists were inserted)
+                    sharded._attach_failed = str(e)
+                    info = dict(rounds=-1)
+                except jdist.CollectiveCountError as e:     # (raised on every rank together: e.g. shards sized from a hint that was far too small;
+                                                            #  anything else is this rank's own failure and ends it -- no fallback the peers do not take)
+                    if is0:
+                        sys.stderr.write("jasper_amd: %s -- counting into a table per GPU instead\n" % e)
+                    info = None
+                finally:
+                    feeder.close()
+                if info is None:                            # start over the round-1 way (the read files are read again)
+                    sharded.detach()
+                    ranks.bar()
+                    sharded.close()
+                    sharded = None
+                else:
+                    local = None
+                    _timing("count reads (file ranges -> region lists -> owners' shards, %d rounds)" % info["rounds"])
+            if sharded is None:
+                def count_my_ranges():
+                    t = KmerTable(kmer, min_slots=max(1 << 20, int(1.25 * o.jf_size / world)), device=o.device)
+                    t.count_file_ranges(my_ranges)
+                    return t
+                local = ranks.together(count_my_ranges, fail_msg)
+                _timing("count reads (file ranges -> local table)")
+            counted = True
+    # key-wise sum over the GPUs; the result stays sharded by key owner unless the peers' HBM cannot be mapped
+    write_db = counted and _jf_wanted()
+    # sharded by owner, or a copy of the whole table on every GPU?  dist.prefer_replicated: it must fit and the gather must cost less than
+    # the remote lookups it saves -- with one polish call per counted table it does not (JASPER_AMD_TABLE=replicated|sharded overrides)
+    how_table = os.environ.get("JASPER_AMD_TABLE", "auto")
+    replicate = how_table == "replicated"
+    if how_table == "auto":
+        try:
+            import ctypes as C
+            from . import _lib
+            free_b, total_b = C.c_uint64(0), C.c_uint64(0)
+            _lib.check(_lib.lib().jasper_device_mem_info(int(o.device), C.byref(free_b), C.byref(total_b)))
+            asm_bases = job.n_bases if job is not None else os.path.getsize(o.query)
+            replicate = jdist.prefer_replicated(world, max(o.jf_size, 1), asm_bases / world, passes + 1, free_b.value)
+        except Exception:           # noqa: BLE001 -- no answer: the default
+            replicate = False
+    replicate = ranks.agree(replicate)
+    try:
+        if replicate:
+            raise jdist.ShardAttachError("a copy of the whole table on every GPU was asked for (or is expected to pay)")
+        if local is None:       # counted straight into the owners' shards
+            table = sharded
+            local = table       # (what the fallback below merges: the shards are disjoint, their key-wise sum is the whole table)
+            if getattr(table, "_attach_failed", None):
+                raise jdist.ShardAttachError(table._attach_failed)
+        else:
+            table = KmerTable(local.k, min_slots=1 << 21, device=o.device)
+            jdist.shard_tables(local, table, dev)
+            local.close()
+        if write_db:       # :177 `... | tee $JF_DB | ...`: every GPU sorts and writes one consecutive piece of the file
+            jdist.write_jf_sharded(table, "mer_counts%d.jf" % kmer, _jf_cmdline(o, kmer), dev)
+            _timing("write mer_counts.jf")
+        h = jdist.histogram_sharded(table, dev)
+    except jdist.ShardAttachError as e:
+        if is0:
+            sys.stderr.write("jasper_amd: %s -- replicating the merged table on every GPU instead\n" % e)
+        if replicate:
+            table = local if local is not None else sharded
+            local = table
+        table.detach()          # (whatever was mapped is unmapped on every rank before anybody frees its slot array)
+        ranks.bar()
+        if table is not local:
+            table.close()
+        table = local
+        jdist.merge_tables(table, dev)
+        if write_db:
+            if is0:
+                _write_jf(table, o, kmer)
+            ranks.bar()
+        h = jdist.histogram_merged(table, dev)
+    rows = [(m, h[m]) for m in range(1, 10002) if h[m]]
+    _timing("sum counts over the GPUs + histogram")
+    if counted and is0:         # (one process writes the file before its database file, from the table)
+        _write_histo(histo_file, rows)
+        _counted()
+    ranks.bar()
+    return table, rows
+
+
+def _histogram(ranks, histo_file, rows):
+    """src/jasper.sh:187-193; rows() gives the histogram's rows"""
+    if ranks.decide(lambda: not os.path.exists("jasper.histo.success") or not _nonempty(histo_file)):
+        log("Computing K-mer histogram")
+        if ranks.is0:
+            _write_histo(histo_file, rows())
+            _drop("jasper.correct.success")
+            _touch("jasper.histo.success")
+        ranks.bar()
+
+
+def _threshold(ranks, histo_file):
+    """src/jasper.sh:195-206"""
+    if ranks.is0:
+        txt, status = polisher.threshold_from_histo_file(histo_file)
+        if status == 0:
+            with open("threshold.txt.tmp", "w") as f:
+                f.write(txt)
+            os.replace("threshold.txt.tmp", "threshold.txt")
+    ranks.bar()
+    if not _nonempty("threshold.txt"):
+        error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable for polishing.")
+    thresh = int(open("threshold.txt").read().split()[0])
+    log("Lower threshold for unreliable kmers is %d" % thresh)
+    return thresh
+
+
+def _polish(ranks, o, job, file_owner, pinner, table, kmer, thresh, passes):
+    """src/jasper.sh:207-216: this rank's batch files through the GPU, in `ls` order, leaving the reference's per-file artefacts.
+    Returns (the polished records are in the job's memory, the thread that writes the polished FASTA from them or None)."""
+    qfn, last_it = o.query_fn, passes - 1
+    keep_fixed = bool(os.environ.get("JASPER_AMD_KEEP_INTERMEDIATES"))
+    in_job = file_owner is not None
+    join_writer = []
+    if in_job:
+        # the job's own batch files; record text goes from the arena to the GPU and the polished text back into the job.  The
+        # `_iter*.fixed.fa` files have one reader, the join, which then works from memory: they are not written
+        # (JASPER_AMD_KEEP_INTERMEDIATES=1 writes them), and so jasper.correct.success -- "the fixed files are complete" --
+        # appears only once the join has made the polished FASTA from them (a run that dies in between starts the polishing
+        # over instead of joining files that are not there).
+        mine = [f for f in sorted(range(job.n_files), key=job.batch_file_name) if file_owner[f] == ranks.rank]
+        groups = _groups(mine, lambda f: job.file_bytes[f])
+        if ranks.world == 1:
+            _drop("jasper.join.success")        # (a difference: one process removes it before the polishing here, everything else after it)
+    else:
+        from . import dist as jdist
+        batch_files = sorted(glob.glob("%s.batch.*.fa" % glob.escape(qfn)))
+        owner = jdist.assign_chunks([os.path.getsize(bf) for bf in batch_files], ranks.world)
+        groups = _groups([bf for bf, ow in zip(batch_files, owner) if ow == ranks.rank], os.path.getsize)
+
+    def start_join():
+        join_writer.append(_Background(lambda: job.join(qfn + ".fixed.fasta.tmp")))
+
+    def polish_my_batches():
+        if pinner is not None:
+            pinner.result()
+        for g in groups:
+            if in_job:
+                # (one process: the moment the last group's polished text is in the job, a thread starts writing the polished
+                #  FASTA from it, src/jasper.sh:220, while this one still turns fix records into CSV rows; several ranks join
+                #  together, in _join)
+                polisher.main_many_job(job, g, kmer, True, True, table, thresh, passes, keep_fixed=keep_fixed,
+                                       on_taken=start_join if ranks.world == 1 and g is groups[-1] else None)
+                written = [job.batch_file_name(f) for f in g] if keep_fixed else []
+            else:
+                polisher.main_many(g, kmer, True, True, table, thresh, passes)
+                written = g
+            for bf in written:
+                os.replace("_iter%d_%s.fixed.fa.tmp" % (last_it, bf), "_iter%d_%s.fixed.fa" % (last_it, bf))
+    ranks.together(polish_my_batches, "Polishing failed")      # :215 (one process does not catch what the polisher raises: the traceback ends the run)
+    ranks.bar()
+    if ranks.is0:
+        _drop("jasper.join.success")
+        if not in_job:
+            _touch("jasper.correct.success")
+    ranks.bar()
+    return in_job, (join_writer[0] if join_writer else None)
+
+
 def _join_and_merge(o, qfn, batch_size, last_it, contigs, fasta_done=False):
     """src/jasper.sh:218-232 (fasta_done: the polished FASTA is already in place, written from an AssemblyJob)"""
     if not fasta_done:
@@ -897,11 +959,44 @@ def _join_and_merge(o, qfn, batch_size, last_it, contigs, fasta_done=False):
     csvs = sorted(glob.glob("_iter*_%s.batch.*.fa.fix.csv" % glob.escape(qfn)))
     write_merged_fix_csvs(csvs, qfn + ".fixes.csv.tmp")
     os.replace(qfn + ".fixes.csv.tmp", qfn + ".fixes.csv")
-    open("jasper.join.success", "w").close()
+    _touch("jasper.join.success")
     if not o.debug:
         for p in csvs + glob.glob("%s.batch.*.fa" % glob.escape(qfn)):
-            if os.path.exists(p):
-                os.remove(p)
+            _drop(p)
+
+
+def _join(ranks, o, job, in_job, join_writer, batch_size, last_it, contigs):
+    """src/jasper.sh:218-232; in_job: the polished records are in the job's memory"""
+    qfn = o.query_fn
+    tmp = qfn + ".fixed.fasta.tmp"
+    if in_job and ranks.world == 1:
+        ranks.together(join_writer.result if join_writer is not None else (lambda: job.join(tmp)), "Joining failed", catch=Exception)
+    elif in_job:
+        # every rank writes the records it polished straight into their places of ONE file: a record's place follows from the
+        # polished lengths of the records before it (a sum over ranks of a short vector), so no text moves between ranks and
+        # nobody reads the assembly or the fixed files again (src/jasper.sh:220)
+        lens, have = job.polished_lens()
+        all_lens = ranks.total([int(v) for v in lens])
+        held = ranks.total([int(v) for v in have])
+
+        def create():
+            if min(held, default=1) != 1 or max(held, default=1) != 1:
+                raise RuntimeError("a chunk record was polished by no rank, or by two")
+            if ranks.is0:
+                job.join(tmp, all_lens=all_lens, mode=1)
+        ranks.together(create, "Joining failed")
+        ranks.bar()
+        ranks.together(lambda: job.join(tmp, all_lens=all_lens, mode=2), "Joining failed")
+        ranks.bar()
+    if in_job and ranks.is0:
+        os.replace(tmp, qfn + ".polished.fasta")
+        _touch("jasper.correct.success")
+        if ranks.world == 1:
+            _timing("  polished FASTA complete")
+        _join_and_merge(o, qfn, batch_size, last_it, None, fasta_done=True)
+    elif ranks.is0:
+        _join_and_merge(o, qfn, batch_size, last_it, contigs if contigs is not None else read_assembly(o.query))
+    ranks.bar()
 
 
 def _qv_block(passes, kmer):
@@ -919,7 +1014,7 @@ def _qv_block(passes, kmer):
         b1, t1 = colsum("%dqValCalcHelper.csv" % passes)
         log("Before Polishing: Q value = %s" % qv.q_value(b0, t0, kmer))
         log("After Polishing: Q value = %s" % qv.q_value(b1, t1, kmer))
-        if os.environ.get("JASPER_AMD_TIMING"):       # (the column sums themselves: the reference removes the files it takes them from, :258)
+        if _timing_on():       # (the column sums themselves: the reference removes the files it takes them from, :258)
             sys.stderr.write("[qv] before %d %d after %d %d\n" % (b0, t0, b1, t1))
         for p in glob.glob("*qValCalcHelper.csv"):
             os.remove(p)
@@ -950,13 +1045,13 @@ def _init_multi(o):
 
 
 def run(argv):
-    if os.environ.get("JASPER_AMD_TIMING"):
+    """the stages of src/jasper.sh, for one process and for one process per GPU (_Ranks; the counting stage is _count_one or _count_ranks)"""
+    if _timing_on():
         import time
         sys.stderr.write("[timing-abs] run() entered at %.6f\n" % time.time())
     o = parse_args(argv)
-    rank, world, dev = _init_multi(o)
-    multi = world > 1
-    if not (os.path.isfile(o.query) and os.path.getsize(o.query) > 0):
+    ranks = _Ranks(*_init_multi(o))
+    if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
     # but the database file -- is the work of a thread that starts NOW, before this one even sizes the batches: the two do not
@@ -969,10 +1064,10 @@ def run(argv):
                     and float(o.num_threads) > 0)
         except ValueError:
             return False
-    if (not multi and _flags_ok()
-            and o.jf_db is None and not (os.path.isfile("mer_counts%d.jf" % int(o.kmer)) and os.path.getsize("mer_counts%d.jf" % int(o.kmer)) > 0)
-            and not os.environ.get("JASPER_AMD_NO_EARLY_TABLE") and o.reads.split() and all(os.path.isfile(fn) and os.path.getsize(fn) > 0 for fn in o.reads.split())):
-        early = _EarlyTable(int(o.kmer), max(1 << 20, int(1.25 * o.jf_size)), o.device, reads=o.reads.split())
+    if (ranks.world == 1 and _flags_ok()
+            and o.jf_db is None and not _nonempty("mer_counts%d.jf" % int(o.kmer))
+            and not os.environ.get("JASPER_AMD_NO_EARLY_TABLE") and o.reads.split() and all(_nonempty(fn) for fn in o.reads.split())):
+        early = _Background(lambda: _early_table(int(o.kmer), max(1 << 20, int(1.25 * o.jf_size)), o.device, o.reads.split()), at_exit=True)
     batch_size = o.batch_size
     if not re.match(r"^[0-9]+$", str(batch_size)):
         log("BATCH SIZE supplied is not a positive integer. Calculating BATCH SIZE from QUERY SIZE")
@@ -980,7 +1075,7 @@ def run(argv):
     batch_size = int(batch_size)
     # The assembly is read ONCE, natively and by several threads, into a host arena that the split, the polisher and the join all
     # work from (assembly.AssemblyJob); a file that is not an ordinary FASTA -- '\r', blanks in sequence lines, non-ASCII bytes,
-    # text before the first '>', a name that occurs twice -- gives None and takes the line-by-line rules below, in Python.
+    # text before the first '>', a name that occurs twice -- gives None and takes the line-by-line rules above, in Python.
     job = None
     if not os.environ.get("JASPER_AMD_NO_NATIVE_ASM"):
         try:
@@ -1004,238 +1099,48 @@ def run(argv):
     if not re.match(r"^-?[0-9]+$", str(o.kmer)) or int(o.kmer) - 1 < 0:
         error_exit("The k-mer size supplied by -k must be a positive integer")
     passes, kmer = int(o.passes), int(o.kmer)
-    last_it = passes - 1
-    qfn = o.query_fn
-    contigs = None
-    if multi:
-        return _run_multi(o, rank, world, dev, batch_size, passes, kmer, job)
-
-    jf_writer = None
-    keep_fixed = bool(os.environ.get("JASPER_AMD_KEEP_INTERMEDIATES"))
-    job_split = False          # the batch files are the job's (being written by its thread until _split_done())
-    job_polished = False       # the polished records are in the job's memory
-    join_writer = []           # [_JobJoin]: the polished FASTA being written from them
-    pinner = None              # thread: job.pin()
-
-    def _split_done():
-        nonlocal job_split
-        if job_split and not os.path.exists("jasper.split.success"):
-            try:
-                job.split_wait()
-            except Exception:           # noqa: BLE001 -- a full disk, a directory that went away
-                error_exit("Splitting files failed, do you have enough disk space?")
-            if os.path.exists("jasper.correct.success"):
-                os.remove("jasper.correct.success")
-            open("jasper.split.success", "w").close()
-
-    if not os.path.exists("jasper.split.success"):                      # :152-159
-        log("Splitting query into batches for parallel execution")
-        for p in glob.glob("%s.batch.*.fa" % glob.escape(qfn)):
-            os.remove(p)
-        if job is not None and batch_size > 0 and job.n_contigs:
-            # perl #1 + perl #2 on the arena; the files are written by a thread of the job while the reads are counted, and
-            # jasper.split.success appears when they are complete (_split_done, before "Polishing")
-            try:
-                job.split(batch_size, qfn, write_files=True)
-            except Exception:           # noqa: BLE001
-                error_exit("Splitting files failed, do you have enough disk space?")
-            job_split = True
-            pinner = _in_thread(lambda: job.pin(o.device))      # (waits for the GPU runtime, pins the arena: beside the counting)
-        else:
-            try:
-                contigs = read_assembly(o.query)
-                split_batches(contigs, batch_size, qfn)
-            except OSError:
-                error_exit("Splitting files failed, do you have enough disk space?")
-            if os.path.exists("jasper.correct.success"):
-                os.remove("jasper.correct.success")
-            open("jasper.split.success", "w").close()
-
-    table = None
+    one = ranks.world == 1
     histo_file = "jfhisto%d.csv" % kmer
-    if o.jf_db is None:                                                 # :162-185
-        reads = o.reads.split()
-        for fn in reads:
-            if not (os.path.isfile(fn) and os.path.getsize(fn) > 0):
-                error_exit("The reads file  %s does not exist. Please supply a series of valid reads files separated by space and wrapped in one pair of quotation marks." % fn)
-        jf_file = "mer_counts%d.jf" % kmer
-        if os.path.isfile(jf_file) and os.path.getsize(jf_file) > 0:     # :171-173
-            log("Using existing jellyfish database %s" % jf_file)
-            if os.path.exists("jasper.no_cat.success"):
-                os.remove("jasper.no_cat.success")
-            table = KmerTable.from_jf(jf_file, device=o.device)
-        else:
-            _timing("split")
-            log("Creating jellyfish database mer_counts%d.jf" % kmer)
-            if early is not None:
-                try:                                    # (what the later stages import, while this thread only waits)
-                    import numpy                        # noqa: F401 -- 0.1 s that histo_rows / the fix records would otherwise spend
-                    import csv, io                      # noqa: F401,E401
-                except ImportError:
-                    pass
-                table = early.get()                     # (counted while the assembly was split)
-                early = None
-            else:
-                table = KmerTable(kmer, min_slots=max(1 << 20, int(1.25 * o.jf_size)), device=o.device)
-                table.count_files(reads)
-            _timing("count reads (files -> table)")
-            # (the histogram first, on this thread: whatever a lazily cleared table still owes its slots is settled before a
-            #  second thread looks at them)
-            with open(histo_file + ".tmp", "w") as f:
-                for m, n in table.histo_rows():
-                    f.write("%d %d\n" % (m, n))
-            os.replace(histo_file + ".tmp", histo_file)
-            if os.environ.get("JASPER_AMD_NO_JF", "") not in ("1", "true", "yes"):
-                # :177 `... | tee $JF_DB | ...`: leave the database behind for reruns and for other Jellyfish tools.  Written by a
-                # thread beside the polishing when the device has room for both (the writer holds ~48 bytes per distinct k-mer plus
-                # its sort's workspace, the polisher several times its batch's text); otherwise first the file, then the polishing,
-                # as the reference orders them.
-                jf_cmdline = ["count", "-C", "-t", str(o.num_threads), "-s", str(o.jf_size), "-m", str(kmer), "-o", jf_file] + reads
-                if _jf_write_fits_beside_polishing(table, o.device, qfn, sum(job.file_bytes) if job_split else None):      # (the job's files may still be being written)
-                    jf_writer = _JfWriter(table, jf_file + ".tmp", jf_file, jf_cmdline)
-                else:
-                    try:
-                        table.write_jf(jf_file + ".tmp", jf_cmdline)
-                        os.replace(jf_file + ".tmp", jf_file)
-                    except Exception as e:             # noqa: BLE001 -- what `set -o pipefail` makes of a failing tee (src/jasper.sh:177-181)
-                        error_exit("Creating jellyfish database mer_counts%d.jf failed (%s)" % (kmer, e))
-                    _timing("write mer_counts.jf (before the polishing: not enough device memory for both at once)")
-            open("jasper.no_cat.success", "w").close()
-            open("jasper.histo.success", "w").close()
-            if os.path.exists("jasper.correct.success"):
-                os.remove("jasper.correct.success")
+
+    file_owner, pinner, contigs = _split(ranks, o, job, batch_size)                     # :152-159
+    if not one:
+        contigs = None          # (a difference: only one process hands the split's contigs to the join; rank 0 reads the assembly again)
+    jf_writer = None
+    if one:                                                                             # :162-185
+        table, jf_writer = _count_one(ranks, o, kmer, early, job, file_owner, histo_file)
+        rows = table.histo_rows
     else:
-        # -j: an existing Jellyfish database; its header decides k (JF::swig/mer_file.i:23 -- the DB wins over -k)
-        try:
-            table = KmerTable.from_jf(o.jf_db, device=o.device)
-        except Exception as e:
-            error_exit("Computing mer counts histogram from %s failed, please make sure that %s is a valid Jellyfish mer counts file (%s)"
-                       % (o.jf_db, o.jf_db, e))
-
-    _split_done()
-    if not os.path.exists("jasper.histo.success") or not (os.path.isfile(histo_file) and os.path.getsize(histo_file) > 0):   # :187-193
-        log("Computing K-mer histogram")
-        with open(histo_file + ".tmp", "w") as f:
-            for m, n in table.histo_rows():
-                f.write("%d %d\n" % (m, n))
-        os.replace(histo_file + ".tmp", histo_file)
-        if os.path.exists("jasper.correct.success"):
-            os.remove("jasper.correct.success")
-        open("jasper.histo.success", "w").close()
-
-    if not os.path.exists("jasper.correct.success"):                    # :195-216
-        _timing("histogram")
+        table, summed = _count_ranks(ranks, o, kmer, passes, job, histo_file)
+        rows = lambda: summed
+    _split_done(ranks, job, file_owner)
+    _histogram(ranks, histo_file, rows)                                                 # :187-193
+    in_job, join_writer = False, None
+    if ranks.decide(lambda: not os.path.exists("jasper.correct.success")):              # :195-216
+        if one:
+            _timing("histogram")
         log("Polishing")
-        txt, status = polisher.threshold_from_histo_file(histo_file)
-        if status == 0:
-            with open("threshold.txt.tmp", "w") as f:
-                f.write(txt)
-            os.replace("threshold.txt.tmp", "threshold.txt")
-        if not (os.path.isfile("threshold.txt") and os.path.getsize("threshold.txt") > 0):
-            error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable for polishing.")
-        thresh = int(open("threshold.txt").read().split()[0])
-        log("Lower threshold for unreliable kmers is %d" % thresh)
-        # the reference starts one jasper.py process per batch file (:207-212); chunk records are independent, so all
-        # files go through the GPU in groups (<= ~1 Gbase of text per call) and leave the same per-file artefacts
-        group, group_bytes = [], 0
-        if job_split:
-            # the job's own batch files, in `ls` order; record text goes from the arena to the GPU and the polished text back into
-            # the job.  The `_iter*.fixed.fa` files have one reader, the join below, which then works from memory: they are not
-            # written (JASPER_AMD_KEEP_INTERMEDIATES=1 writes them), and so jasper.correct.success -- "the fixed files are
-            # complete" -- appears only once the join has made the polished FASTA from them (a run that dies in between starts the
-            # polishing over instead of joining files that are not there).
-            if pinner is not None:
-                pinner.join()
-            groups = [[]]
-            for f in sorted(range(job.n_files), key=job.batch_file_name):
-                groups[-1].append(f)
-                group_bytes += job.file_bytes[f]
-                if group_bytes > (1 << 30):
-                    groups.append([])
-                    group_bytes = 0
-            groups = [g for g in groups if g]
-            if os.path.exists("jasper.join.success"):
-                os.remove("jasper.join.success")
-            for gi, g in enumerate(groups):
-                # (the moment the last group's polished text is in the job, a thread starts writing the polished FASTA from it,
-                #  src/jasper.sh:220, while this one still turns fix records into CSV rows)
-                last = gi == len(groups) - 1
-                polisher.main_many_job(job, g, kmer, True, True, table, thresh, passes, keep_fixed=keep_fixed,
-                                       on_taken=(lambda: join_writer.append(_JobJoin(job, qfn + ".fixed.fasta.tmp"))) if last else None)
-                if keep_fixed:
-                    for f in g:
-                        bf = job.batch_file_name(f)
-                        os.replace("_iter%d_%s.fixed.fa.tmp" % (last_it, bf), "_iter%d_%s.fixed.fa" % (last_it, bf))
-            job_polished = True
-        else:
-            batch_files = sorted(glob.glob("%s.batch.*.fa" % glob.escape(qfn)))   # `ls` order
-            def flush_group():
-                if group:
-                    polisher.main_many(group, kmer, True, True, table, thresh, passes)
-                    for bf in group:
-                        os.replace("_iter%d_%s.fixed.fa.tmp" % (last_it, bf), "_iter%d_%s.fixed.fa" % (last_it, bf))
-                    del group[:]
-            for bf in batch_files:
-                group.append(bf)
-                group_bytes += os.path.getsize(bf)
-                if group_bytes > (1 << 30):
-                    flush_group()
-                    group_bytes = 0
-            flush_group()
-            if os.path.exists("jasper.join.success"):
-                os.remove("jasper.join.success")
-            open("jasper.correct.success", "w").close()
-
-    if not os.path.exists("jasper.join.success"):                       # :218-232
+        thresh = _threshold(ranks, histo_file)
+        in_job, join_writer = _polish(ranks, o, job, file_owner, pinner, table, kmer, thresh, passes)
+    if ranks.decide(lambda: not os.path.exists("jasper.join.success")):                 # :218-232
         _timing("polish batches")
         log("Joining")
-        if job_polished:
-            try:
-                if join_writer:
-                    join_writer[0].finish()
-                else:
-                    job.join(qfn + ".fixed.fasta.tmp")
-            except Exception:           # noqa: BLE001
-                error_exit("Joining failed")
-            os.replace(qfn + ".fixed.fasta.tmp", qfn + ".polished.fasta")
-            open("jasper.correct.success", "w").close()
-            _timing("  polished FASTA complete")
-        else:
-            if contigs is None:
-                contigs = read_assembly(o.query)
-            fixed_files = sorted(glob.glob("_iter%d_%s.batch.*.fa.fixed.fa" % (last_it, glob.escape(qfn))))
-            text = join_polished(fixed_files, batch_size, [c[0] for c in contigs])
-            with open(qfn + ".fixed.fasta.tmp", "w") as f:
-                f.write(text)
-            os.replace(qfn + ".fixed.fasta.tmp", qfn + ".polished.fasta")
-        for p in glob.glob("_iter*_%s.batch.*.fa.fixed.fa" % glob.escape(qfn)) + glob.glob("_iter*_%s.batch.*.fa.fixed.fa.tmp" % glob.escape(qfn)):
-            os.remove(p)
-        csvs = sorted(glob.glob("_iter*_%s.batch.*.fa.fix.csv" % glob.escape(qfn)))
-        write_merged_fix_csvs(csvs, qfn + ".fixes.csv.tmp")
-        os.replace(qfn + ".fixes.csv.tmp", qfn + ".fixes.csv")
-        open("jasper.join.success", "w").close()
-        if not o.debug:
-            for p in csvs + glob.glob("%s.batch.*.fa" % glob.escape(qfn)):
-                if os.path.exists(p):
-                    os.remove(p)
-
-    _qv_block(passes, kmer)      # (:235-257)
+        _join(ranks, o, job, in_job, join_writer, batch_size, passes - 1, contigs)
+    if ranks.is0:
+        _qv_block(passes, kmer)                                                         # :235-257
     _timing("join + QV")
     if jf_writer is not None:
-        try:
-            try:
-                jf_writer.finish()
-            except Exception as e1:            # noqa: BLE001 -- e.g. a device allocation that failed beside the polisher's: once more, alone
-                if "alloc" not in str(e1).lower() and "memory" not in str(e1).lower():
-                    raise
-                table.write_jf("mer_counts%d.jf.tmp" % kmer, jf_writer.cmdline)
-                os.replace("mer_counts%d.jf.tmp" % kmer, "mer_counts%d.jf" % kmer)
-        except Exception as e:                 # noqa: BLE001 -- what `set -o pipefail` makes of a failing tee (src/jasper.sh:177-181)
-            error_exit("Creating jellyfish database mer_counts%d.jf failed (%s)" % (kmer, e))
-        _timing("mer_counts.jf complete (written beside the stages above)")
-    log("Polished sequence is in %s.polished.fasta" % qfn)
-    if table is not None:
+        _jf_written(jf_writer, table, o, kmer)
+    log("Polished sequence is in %s.polished.fasta" % o.query_fn)
+    if one:
         table.close()
+        return 0
+    import torch.distributed as tdist
+    ranks.bar()                 # nobody unmaps or frees a shard that a peer may still be reading ...
+    table.detach()              # ... every rank lets go of its peers' memory ...
+    ranks.bar()                 # ... and only then is any of it freed
+    table.close()
+    ranks.bar()
+    tdist.destroy_process_group()
     return 0
 
 
@@ -1337,7 +1242,7 @@ def main():
                                       "--master-addr", "127.0.0.1", "--master-port", port, "-m", "jasper_amd.cli"] + argv))
     done_fd = _front_process()
     rc = run(argv)
-    if os.environ.get("JASPER_AMD_TIMING"):
+    if _timing_on():
         import time
         sys.stderr.write("[timing-abs] run() returned at %.6f\n" % time.time())
     if done_fd is not None and not rc:

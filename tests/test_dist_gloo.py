@@ -409,3 +409,73 @@ def test_count_sharded_failures_are_collective():
     assert all(isinstance(x, str) and x.startswith("raised") for r in range(2) for x in res[r])
     res = _run_count("fail_plan")
     assert all(isinstance(x, str) and x.startswith("raised") for r in range(2) for x in res[r])
+
+
+# ---- cli._Ranks: how the ranks of a run agree on a stage's outcome and on rank 0's decisions ----------------------------
+def _ranks_worker(rank, world, port, q, case, tmp):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    import torch.distributed as dist
+    from jasper_amd import cli
+    sys.stderr = open(os.path.join(tmp, "stderr.%d" % rank), "w", buffering=1)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    cli._QUIET[0] = rank != 0                   # (as cli._init_multi: only rank 0 talks)
+    ranks = cli._Ranks(rank, world, None)       # (no GPU: host tensors, no device to wait for)
+    try:
+        def work():
+            if rank == 1 and case == "raise":
+                raise RuntimeError("no space left on rank 1")
+            if rank == 1 and case == "exit":
+                sys.exit(1)
+            return "share of rank %d" % rank
+        out = ranks.together(work, "Stage failed on some rank")
+        ranks.bar()
+        asked = []
+
+        def only_rank0_looks(name):
+            asked.append(name)
+            return os.path.exists(os.path.join(tmp, name))
+        yes = ranks.decide(lambda: only_rank0_looks("there"))
+        no = ranks.decide(lambda: only_rank0_looks("not there"))
+        q.put((rank, (out, yes, no, asked, ranks.agree(True), ranks.agree(rank == 0))))
+    finally:
+        dist.destroy_process_group()
+
+
+def _run_ranks(case, tmp):
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    open(os.path.join(tmp, "there"), "w").close()
+    ps = [ctx.Process(target=_ranks_worker, args=(r, 2, port, q, case, tmp)) for r in range(2)]
+    for p in ps:
+        p.start()
+    res = dict(q.get(timeout=180) for _ in ps) if case == "ok" else None
+    for p in ps:
+        p.join(timeout=180)
+    said = [open(os.path.join(tmp, "stderr.%d" % r)).read() for r in range(2)]
+    return [p.exitcode for p in ps], res, said, q
+
+
+@pytest.mark.parametrize("case", ["raise", "exit"])
+def test_a_failing_rank_ends_every_rank(case, tmp_path):
+    """rank 1's share of a stage raises, or leaves like the reference's sys.exit(1): BOTH ranks leave through error_exit (status 1)
+    instead of rank 0 waiting in the next collective; only rank 0 prints the stage's message, rank 1's own reason is on its stderr"""
+    codes, _, said, q = _run_ranks(case, str(tmp_path))
+    assert codes == [1, 1]
+    assert q.empty()                                             # nobody went on past the stage
+    assert "Stage failed on some rank" in said[0] and "Stage failed on some rank" not in said[1]
+    assert "rank 1" not in said[0]
+    if case == "raise":
+        assert "jasper_amd: rank 1: RuntimeError: no space left on rank 1" in said[1]
+
+
+def test_success_is_shared_and_rank0_decides(tmp_path):
+    """nobody fails: every rank gets what its own work returned and goes on; a following decide() is answered by rank 0 alone
+    (rank 1 never evaluates the condition) and is the same on both; agree() is true only when it is on every rank"""
+    codes, res, said, _ = _run_ranks("ok", str(tmp_path))
+    assert codes == [0, 0]
+    assert res[0] == ("share of rank 0", True, False, ["there", "not there"], True, False)
+    assert res[1] == ("share of rank 1", True, False, [], True, False)
+    assert "Stage failed" not in said[0] + said[1]

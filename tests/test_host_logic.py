@@ -367,3 +367,19 @@ def test_rows_straight_from_the_record_array_equal_rows_from_record():
     for r in sorted(res.records, key=lambda r: (r["chunk"], r["pass_"], r["seqno"])):
         want.setdefault((r["pass_"], r["chunk"]), []).extend(polisher.rows_from_record("ctg%d:0" % r["chunk"], r))
     assert got == want and sum(len(v) for v in got.values()) >= n
+
+
+def test_groups_of_batch_files_for_one_polish_call():
+    """cli._groups: items are appended in order and a group is cut when its running sum first EXCEEDS the limit -- reaching it
+    exactly does not cut --, a single item above the limit is a group of its own, the last group may be small, none is empty"""
+    size = {"a": 40, "b": 60, "c": 1, "d": 99, "e": 2, "f": 5}
+    assert cli._groups("abcdef", size.get, limit=100) == [["a", "b", "c"], ["d", "e"], ["f"]]        # 100 is not a cut, 101 is
+    assert cli._groups("ab", size.get, limit=100) == [["a", "b"]]
+    assert cli._groups("abc", size.get, limit=100) == [["a", "b", "c"]]                               # the cut falls on the last item: no empty group after it
+    big = {"x": 10, "huge": 1000, "y": 10}
+    assert cli._groups(["x", "huge", "y"], big.get, limit=100) == [["x", "huge"], ["y"]]
+    assert cli._groups(["huge", "x"], big.get, limit=100) == [["huge"], ["x"]]
+    assert cli._groups(["huge"], big.get, limit=100) == [["huge"]]
+    assert cli._groups([], big.get) == []
+    assert cli._groups([1, 2, 3], lambda i: 1 << 29) == [[1, 2, 3]]                                   # the default: about 1 GiB of text (3 * 2^29 > 2^30 only at the third)
+    assert cli._groups([1, 2, 3, 4], lambda i: 1 << 29) == [[1, 2, 3], [4]]
