@@ -249,6 +249,41 @@ int jasper_result_segments(const jasper_result *r, uint64_t *n_segments, uint64_
 int jasper_result_retried(const jasper_result *r);
 void jasper_result_free(jasper_result *r);
 
+/* Dense k-mer report: per-sequence counters and the maximal runs of unreliable k-mers, computed on the GPU from the resident
+ * table (whole or attached owner-sharded, any k <= 64).
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  Its QV pass (src/jasper.py:50-111) walks the
+ * chunk records with a stride and prints two numbers for the whole assembly (src/jasper.sh:239-242); that stays what it is
+ * (jasper_result_qv).  What it is: the windows of src/jasper.py:55-71 taken DENSELY over whole sequences, to be turned into a QV
+ * per sequence by the formula of src/jasper.sh:239-242.  For a sequence of n bytes and the table's k:
+ *   window i (0 <= i <= n-k)  valid       iff all its k bytes are ACGTacgt (case folded)
+ *                             count       the table's count of its canonical k-mer, clamped to 2^32-1 as jasper_lookup does
+ *                             unreliable  valid and count < thre        (thre == 0: none)
+ *                             absent      valid and count == 0          (counted whether or not it is unreliable too)
+ *   run                       a maximal range of consecutive unreliable windows of one sequence (an invalid or reliable window,
+ *                             or the sequence's end, ends it): first window, windows, absent windows among them, smallest count
+ * Sequences shorter than k (empty ones too) are legal and give zeros.  Runs are ordered by (seq, start).  The table is not
+ * modified.  The library sizes its buffers by itself and repeats the scan when there are more runs than it had room for
+ * (jasper_report_retried), so a call succeeds whatever the input is.  The kernel works in tiles of
+ * jasper_report_tile_windows() = 4096 windows of one sequence; runs are stitched across tiles.
+ *   jasper_kmer_report         sequences in host memory
+ *   jasper_kmer_report_device  sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the table's device; offsets is a host
+ *                              array of n_seqs+1 entries
+ *   jasper_report_counts       out4 = windows, valid, unreliable, absent of one sequence
+ *   jasper_report_runs         the run list (owned by the report)
+ *   jasper_report_seconds      device time of the report's kernels (HIP events) */
+typedef struct jasper_report jasper_report;
+typedef struct jasper_kmer_run { int64_t start; uint64_t n_kmers; uint64_t n_absent; uint32_t seq; uint32_t min_count; } jasper_kmer_run;
+int jasper_kmer_report(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_report **out);
+int jasper_kmer_report_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_report **out);
+int jasper_report_tile_windows(void);
+int jasper_report_num_seqs(const jasper_report *r);
+int jasper_report_counts(const jasper_report *r, int seq, uint64_t out4[4]);   /* windows, valid, unreliable, absent */
+int jasper_report_runs(const jasper_report *r, const jasper_kmer_run **runs, uint64_t *n);
+double jasper_report_seconds(const jasper_report *r);                           /* device time, HIP events */
+int jasper_report_retried(const jasper_report *r);
+void jasper_report_free(jasper_report *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

@@ -24,6 +24,13 @@ class FixRec(C.Structure):
 
 assert C.sizeof(FixRec) == 32
 
+
+class KmerRun(C.Structure):
+    _fields_ = [("start", C.c_int64), ("n_kmers", C.c_uint64), ("n_absent", C.c_uint64), ("seq", C.c_uint32), ("min_count", C.c_uint32)]
+
+
+assert C.sizeof(KmerRun) == 32
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -97,6 +104,15 @@ SYMBOLS = {
     "jasper_result_segments": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jasper_result_retried": (C.c_int, [_P]),
     "jasper_result_free": (None, [_P]),
+    "jasper_kmer_report": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
+    "jasper_kmer_report_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
+    "jasper_report_tile_windows": (C.c_int, []),
+    "jasper_report_num_seqs": (C.c_int, [_P]),
+    "jasper_report_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_report_runs": (C.c_int, [_P, C.POINTER(C.POINTER(KmerRun)), C.POINTER(C.c_uint64)]),
+    "jasper_report_seconds": (C.c_double, [_P]),
+    "jasper_report_retried": (C.c_int, [_P]),
+    "jasper_report_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

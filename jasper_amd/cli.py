@@ -2,7 +2,7 @@
 sentinel files and log lines; the Jellyfish + per-batch python processes are replaced by the HBM table and the GPU
 polisher.  Lines are cited as src/jasper.sh:N.
 
-    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N]
+    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -98,6 +98,7 @@ class Options:
         self.jf_db = None
         self.verbose = False
         self.device = 0
+        self.report = False
 
 
 def parse_args(argv):
@@ -140,6 +141,8 @@ def parse_args(argv):
             o.device = int(nxt); i += 1
         elif key == "--gpus":                                          # extension: handled by main() (one process per GPU)
             i += 1
+        elif key == "--report":                                        # extension: per-contig k-mer QV and unreliable-k-mer tracks (_report)
+            o.report = True
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1020,6 +1023,33 @@ def _qv_block(passes, kmer):
             os.remove(p)
 
 
+def scan_contigs(table, contigs, thre):
+    """the dense k-mer report of whole contigs [(name token, sequence)] -> (names, lengths, KmerReport)"""
+    from . import report
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.kmer_report([s for _, s in contigs], thre)
+
+
+def _report(o, table):
+    """--report (an extension, no counterpart in src/jasper.sh): two dense scans through the table while it is still in HBM -- the
+    input assembly's contigs and the polished contigs, WHOLE contigs read back from the two FASTA files, so the windows that span
+    two chunk records are there -- into `$QUERY_FN.kmer_qv.tsv` and `$QUERY_FN.unreliable.{before,after}.bed` (jasper_amd/report.py).
+    The threshold is the one the polisher used (threshold.txt); k is the table's (a -j database decides it)."""
+    from . import report
+    qfn, k = o.query_fn, table.k
+    thresh = int(open("threshold.txt").read().split()[0])
+    names, len0, rep0 = scan_contigs(table, read_assembly(o.query), thresh)
+    names1, len1, rep1 = scan_contigs(table, read_assembly(qfn + ".polished.fasta"), thresh)
+    len1a, cnt1a = report.align(names, names1, len1, rep1.counts)
+    report.write_atomic(qfn + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("before", len0, rep0.counts), ("after", len1a, cnt1a)]))
+    report.write_atomic(qfn + ".unreliable.before.bed", report.bed_text(k, names, rep0.runs))
+    report.write_atomic(qfn + ".unreliable.after.bed", report.bed_text(k, names1, rep1.runs))
+    for stage, counts in (("Before", rep0.counts), ("After", cnt1a)):
+        _, v, u, a = report.totals(counts)
+        log("%s Polishing: dense k-mer QV = %s (unreliable k-mers), %s (absent k-mers)" % (stage, report.qv_text(u, v, k), report.qv_text(a, v, k)))
+    if _timing_on():
+        sys.stderr.write("[report] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1127,6 +1157,11 @@ def run(argv):
         _join(ranks, o, job, in_job, join_writer, batch_size, passes - 1, contigs)
     if ranks.is0:
         _qv_block(passes, kmer)                                                         # :235-257
+    if o.report:
+        # rank 0 alone scans, through the attached owner-sharded table; the other ranks wait for its outcome here and at the barrier
+        # that precedes detach (unmeasured over RCCL, like everything multi-GPU here)
+        ranks.together((lambda: _report(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
+        _timing("k-mer report")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

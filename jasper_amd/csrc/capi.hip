@@ -6,9 +6,11 @@
 #include "pgunzip.hpp"
 #include "inflate_gpu.hpp"
 #include "asmio.hpp"
+#include "report.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -40,6 +42,13 @@ struct jasper_result {
 };
 
 static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record layouts must match");
+
+struct jasper_report {
+    ReportOut r;
+};
+static_assert(sizeof(jasper_kmer_run) == sizeof(KmerRun) && offsetof(jasper_kmer_run, n_absent) == offsetof(KmerRun, n_absent) &&
+                  offsetof(jasper_kmer_run, seq) == offsetof(KmerRun, seq) && offsetof(jasper_kmer_run, min_count) == offsetof(KmerRun, min_count),
+              "public and device run layouts must match");
 
 // copy a device-resident result's text to the host (before its workspace is reused, or when the caller asks for it)
 static int result_fetch(jasper_result *r) {
@@ -719,5 +728,42 @@ void jasper_result_free(jasper_result *r) {
     if (r && r->owner && r->owner->pending == r) r->owner->pending = nullptr;
     delete r;
 }
+
+// ---- dense k-mer report (report.hip) ----
+static int report_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
+                       jasper_report **out) {
+    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_report *r = new jasper_report();
+    const int rc = d_text || offsets ? kmer_report_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r->r, g_err)
+                                     : kmer_report_host(t->t, n_seqs, seqs, lens, thre, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_kmer_report(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_report **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return report_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, out);
+}
+int jasper_kmer_report_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_report **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return report_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, out);
+}
+int jasper_report_tile_windows(void) { return RP_TILE; }
+int jasper_report_num_seqs(const jasper_report *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
+int jasper_report_counts(const jasper_report *r, int seq, uint64_t out4[4]) {
+    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_report_runs(const jasper_report *r, const jasper_kmer_run **runs, uint64_t *n) {
+    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *runs = reinterpret_cast<const jasper_kmer_run *>(r->r.runs.data());
+    *n = r->r.runs.size();
+    return JASPER_OK;
+}
+double jasper_report_seconds(const jasper_report *r) { return r ? r->r.seconds : 0.0; }
+int jasper_report_retried(const jasper_report *r) { return r ? r->r.retried : 0; }
+void jasper_report_free(jasper_report *r) { delete r; }
 
 }  // extern "C"

@@ -611,7 +611,7 @@ static int grid_for(uint64_t work_items, int per_block) {
 int Table::min_log2_slots(int k) {
     // the tag holds 63 - OFFBITS remainder bits, the ext word of a wide table (kmer.hpp: wide_rem) 64 more: B - s <= 117
     int need = 2 * k - (63 - OFFBITS) - 64;
-    return std::max(need, 10);
+    return std::max(need, std::min(10, 2 * k));      // (k < 5: there are fewer than 2^10 keys, and never more slots than keys)
 }
 
 int Table::init(int k_, uint64_t min_slots, int device_, std::string &err) {

@@ -1,0 +1,85 @@
+"""Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
+
+    python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D]
+
+An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
+decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
+histogram unless --threshold gives one, and writes
+
+    PREFIX.kmer_qv.tsv       per contig one row of stage `asm`, then contig `*` with the sums   (jasper_amd/report.py)
+    PREFIX.unreliable.bed    one line per maximal run of unreliable k-mers
+
+PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
+"""
+import os
+import sys
+
+from . import cli, polisher, report
+from .table import KmerTable
+
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D]"
+
+
+def parse_args(argv):
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0)
+    keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
+            "--threshold": "threshold", "-o": "prefix", "--device": "device"}
+    i = 0
+    while i < len(argv):
+        key = argv[i]
+        if key in ("-h", "--help"):
+            print(USAGE)
+            sys.exit(0)
+        if key not in keys or i + 1 >= len(argv):
+            print("Unknown option %s" % key)
+            sys.exit(1)
+        o[keys[key]] = argv[i + 1]
+        i += 2
+    return o
+
+
+def run(argv):
+    a = parse_args(argv)
+    if not a["asm"] or not cli._nonempty(a["asm"]):
+        cli.error_exit("The query file does not exist. Please supply a valid fasta file with -a option.")
+    if (a["reads"] is None) == (a["jf"] is None):
+        cli.error_exit("Exactly one of -r (reads) and -j (Jellyfish database) must be given")
+    try:
+        k, device = int(a["k"]), int(a["device"])
+        given = None if a["threshold"] is None else int(a["threshold"])
+        if k < 1 or (given is not None and given < 0):
+            raise ValueError
+    except ValueError:
+        cli.error_exit("-k, --threshold and --device take non-negative integers (k at least 1)")
+    if a["jf"] is not None:
+        try:
+            table = KmerTable.from_jf(a["jf"], device=device)
+        except Exception as e:      # noqa: BLE001
+            cli.error_exit(cli._jf_failed(a["jf"]) + " (%s)" % e)
+    else:
+        o = cli.Options()
+        o.reads = a["reads"]
+        reads = cli._reads(o)
+        size = sum(os.stat(f).st_size for f in reads) // 10                        # (the `-s` of src/jasper.sh:82)
+        table = KmerTable(k, min_slots=max(1 << 20, int(1.25 * size)), device=device)
+        table.count_files(reads)
+    k = table.k
+    if given is None:
+        txt, status = polisher.threshold_from_histo_rows(table.histo_rows())    # src/jellyfish.py, as cli._threshold applies it
+        if status != 0 or not txt.split():
+            cli.error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable; give --threshold.")
+        given = int(txt.split()[0])
+    cli.log("Lower threshold for unreliable kmers is %d" % given)
+    names, lengths, rep = cli.scan_contigs(table, cli.read_assembly(a["asm"]), given)
+    table.close()
+    prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
+    report.write_atomic(prefix + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("asm", lengths, rep.counts)]))
+    report.write_atomic(prefix + ".unreliable.bed", report.bed_text(k, names, rep.runs))
+    _, v, u, ab = report.totals(rep.counts)
+    cli.log("Dense k-mer QV = %s (unreliable k-mers), %s (absent k-mers); %d runs in %s.unreliable.bed" %
+            (report.qv_text(u, v, k), report.qv_text(ab, v, k), len(rep.runs), prefix))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(run(sys.argv[1:]))

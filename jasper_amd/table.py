@@ -101,6 +101,28 @@ class PolishResult:
         return self._records
 
 
+KMERRUN_DTYPE = [("start", "<i8"), ("n_kmers", "<u8"), ("n_absent", "<u8"), ("seq", "<u4"), ("min_count", "<u4")]
+
+
+class KmerReport:
+    """dense k-mer report of a set of sequences (include/jasper_hip.h: jasper_kmer_report): `counts[i]` = (windows, valid,
+    unreliable, absent) of sequence i, `runs` = numpy structured array (KMERRUN_DTYPE) of the maximal runs of unreliable
+    k-mers ordered by (seq, start), `seconds` = device time of the kernels."""
+
+    def __init__(self, counts, runs, seconds, retried):
+        self.counts = counts
+        self.runs = runs
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, KmerReport) and self.counts == other.counts and self.runs.tobytes() == other.runs.tobytes()
+
+    def run_tuples(self):
+        """[(seq, start, n_kmers, n_absent, min_count)]"""
+        return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["n_absent"]), int(r["min_count"])) for r in self.runs]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -455,6 +477,53 @@ class KmerTable:
         res = C.c_void_p()
         rc = self._L.jasper_polish_batch_device(self._h, n, C.c_void_p(ptr), offs, int(solid_thre), int(passes), 1 if fix else 0, C.byref(res))
         return self._wrap_result(rc, res, n, False)
+
+    # ---- dense k-mer report (an extension: no counterpart in the reference) ------------------------------
+    def kmer_report(self, seqs, thre):
+        """per-sequence counters and runs of unreliable k-mers (count < thre) of `seqs` (str or bytes) -> KmerReport"""
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = self._L.jasper_kmer_report(self._h, n, cs, lens, int(thre), C.byref(res))
+        return self._wrap_report(rc, res)
+
+    def kmer_report_device(self, d_text, offsets, thre):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_kmer_report_device(self._h, n, C.c_void_p(ptr), offs, int(thre), C.byref(res))
+        return self._wrap_report(rc, res)
+
+    @staticmethod
+    def report_tile_windows():
+        """windows per tile of the report's scan kernel (runs are stitched across tiles; tests aim at the seams)"""
+        return int(_lib.lib().jasper_report_tile_windows())
+
+    def _wrap_report(self, rc, res):
+        try:
+            check(rc)
+            import numpy as np
+            counts = []
+            c4 = (C.c_uint64 * 4)()
+            for i in range(self._L.jasper_report_num_seqs(res)):
+                check(self._L.jasper_report_counts(res, i, c4))
+                counts.append(tuple(int(v) for v in c4))
+            rp = C.POINTER(_lib.KmerRun)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_report_runs(res, C.byref(rp), C.byref(rn)))
+            if rn.value:
+                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.KmerRun)), dtype=KMERRUN_DTYPE).copy()
+            else:
+                runs = np.zeros(0, dtype=KMERRUN_DTYPE)
+            return KmerReport(counts, runs, self._L.jasper_report_seconds(res), bool(self._L.jasper_report_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_report_free(res)
 
     def _wrap_result(self, rc, res, n, want_str):
         try:
