@@ -284,6 +284,27 @@ double jasper_report_seconds(const jasper_report *r);                           
 int jasper_report_retried(const jasper_report *r);
 void jasper_report_free(jasper_report *r);
 
+/* Copy-number k-mer spectrum: two resident tables of the same k on the same device -- `reads` (R) and `assembly` (A, the assembly's
+ * contigs counted into a table of its own with the usual counting calls: case folded, every non-ACGT byte a separator) -- joined on
+ * the GPU.  No key crosses to the host.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart (it is the spectra-cn / completeness half of a
+ * k-mer evaluation; jasper_kmer_report is the other half).  The spectrum is a matrix S[6][10002] of unsigned 64-bit cells, row-major:
+ *   row m     = min(count in A, 5): 0 = not in the assembly, 5 = five copies or more          (jasper_spectrum_rows() = 6)
+ *   column c  = min(min(count in R, 2^32-1), 10001), the binning of jasper_histogram: 0 = not in the reads
+ *   S[m][c], c >= 1   distinct keys of R with that (m, c)
+ *   S[m][0], m >= 1   distinct keys of A that R does not have: the assembly-only k-mers by copy number
+ *   S[0][0]           0
+ * A slot whose count is 0 is no key, in either table (as for jasper_histogram).  So the sum over m of S[m][c] is R's histogram bin c
+ * for every c >= 1, and the sum over all c of S[m][c] is A's histogram bin m for m = 1..4, bins 5.. together for m = 5.  From it,
+ * for a threshold t >= 1 (jasper_amd/spectra.py): solid = sum over c >= t and all m, found = the same over m >= 1, completeness =
+ * found / solid, asm_distinct = sum over m >= 1 and all c, asm_only = sum over m >= 1 of S[m][0].
+ * Either table may be narrow or wide.  R may be an attached owner-sharded table (every owner's shard is swept); A must be a whole
+ * table.  Neither table is modified.  A different k, different devices, an attached A, or the same handle twice is JASPER_ERR.
+ * out_cells: 6 * 10002 words in host memory; device_seconds (may be NULL): device time of the two sweeps, HIP events. */
+int jasper_spectrum_rows(void);
+int jasper_table_spectrum(jasper_table *reads, jasper_table *assembly, uint64_t *out_cells /* 6 * 10002, row-major */, double *device_seconds);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

@@ -113,6 +113,8 @@ SYMBOLS = {
     "jasper_report_seconds": (C.c_double, [_P]),
     "jasper_report_retried": (C.c_int, [_P]),
     "jasper_report_free": (None, [_P]),
+    "jasper_spectrum_rows": (C.c_int, []),
+    "jasper_table_spectrum": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -2,7 +2,7 @@
 sentinel files and log lines; the Jellyfish + per-batch python processes are replaced by the HBM table and the GPU
 polisher.  Lines are cited as src/jasper.sh:N.
 
-    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report]
+    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -99,6 +99,7 @@ class Options:
         self.verbose = False
         self.device = 0
         self.report = False
+        self.spectra = False
 
 
 def parse_args(argv):
@@ -143,6 +144,8 @@ def parse_args(argv):
             i += 1
         elif key == "--report":                                        # extension: per-contig k-mer QV and unreliable-k-mer tracks (_report)
             o.report = True
+        elif key == "--spectra":                                       # extension: copy-number k-mer spectrum and completeness (_spectra)
+            o.spectra = True
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1050,6 +1053,39 @@ def _report(o, table):
         sys.stderr.write("[report] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
 
 
+def assembly_spectrum(table, contigs):
+    """the contigs [(name token, sequence)] counted into a second table of their own (sized from their length; the sequences
+    joined by a separator byte, so no k-mer spans two contigs), joined on the GPU with `table`, the reads' -> KmerSpectrum"""
+    from .table import KmerTable
+    seqs = [s for _, s in contigs]
+    asm = KmerTable(table.k, min_slots=max(1 << 16, int(1.25 * sum(len(s) for s in seqs))), device=table.device)
+    try:
+        asm.count_bases("N".join(seqs))
+        return table.spectrum(asm)
+    finally:
+        asm.close()
+
+
+def _spectra(o, table):
+    """--spectra (an extension, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each counted into a
+    second table and joined with the read table while that is still in HBM, into `$QUERY_FN.spectra_cn.{before,after}.tsv` and
+    `$QUERY_FN.completeness.tsv` (jasper_amd/spectra.py).  The threshold for solid k-mers is the polisher's (threshold.txt)."""
+    from . import spectra
+    qfn, k = o.query_fn, table.k
+    thresh = int(open("threshold.txt").read().split()[0])
+    rows, secs = [], []
+    for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta")):
+        spec = assembly_spectrum(table, read_assembly(path))
+        spectra.write_atomic("%s.spectra_cn.%s.tsv" % (qfn, stage), spectra.spectra_cn_text(spec))
+        rows.append(spectra.completeness_row(stage, spec, thresh))
+        secs.append(spec.seconds)
+    spectra.write_atomic(qfn + ".completeness.tsv", spectra.completeness_text(k, rows))
+    for stage, row in zip(("Before", "After"), rows):
+        log("%s Polishing: %s" % (stage, spectra.log_text(row)))
+    if _timing_on():
+        sys.stderr.write("[spectra] device seconds: before %.6f after %.6f\n" % tuple(secs))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1162,6 +1198,10 @@ def run(argv):
         # that precedes detach (unmeasured over RCCL, like everything multi-GPU here)
         ranks.together((lambda: _report(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
         _timing("k-mer report")
+    if o.spectra:
+        # as for --report: rank 0 alone, its sweeps go over every owner's shard of the attached table
+        ranks.together((lambda: _spectra(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer spectrum failed")
+        _timing("k-mer spectrum")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

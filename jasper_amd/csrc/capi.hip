@@ -7,6 +7,7 @@
 #include "inflate_gpu.hpp"
 #include "asmio.hpp"
 #include "report.hpp"
+#include "spectra.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -765,5 +766,12 @@ int jasper_report_runs(const jasper_report *r, const jasper_kmer_run **runs, uin
 double jasper_report_seconds(const jasper_report *r) { return r ? r->r.seconds : 0.0; }
 int jasper_report_retried(const jasper_report *r) { return r ? r->r.retried : 0; }
 void jasper_report_free(jasper_report *r) { delete r; }
+
+// ---- copy-number k-mer spectrum (spectra.hip) ----
+int jasper_spectrum_rows(void) { return SP_ROWS; }
+int jasper_table_spectrum(jasper_table *reads, jasper_table *assembly, uint64_t *out_cells, double *device_seconds) {
+    if (!reads || !assembly || !out_cells) { g_err = "bad argument"; return JASPER_ERR; }
+    return table_spectrum(reads->t, assembly->t, out_cells, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
 
 }  // extern "C"

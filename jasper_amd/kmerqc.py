@@ -1,6 +1,6 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
-    python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D]
+    python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -9,19 +9,25 @@ histogram unless --threshold gives one, and writes
     PREFIX.kmer_qv.tsv       per contig one row of stage `asm`, then contig `*` with the sums   (jasper_amd/report.py)
     PREFIX.unreliable.bed    one line per maximal run of unreliable k-mers
 
+With --spectra the assembly's contigs are also counted into a second table and joined with the first on the GPU
+(KmerTable.spectrum), and two more files are written (jasper_amd/spectra.py):
+
+    PREFIX.spectra_cn.tsv    distinct k-mers by copies in the assembly and count in the reads
+    PREFIX.completeness.tsv  one row of stage `asm`: the share of the reads' solid k-mers the assembly holds, assembly-only k-mers
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 """
 import os
 import sys
 
-from . import cli, polisher, report
+from . import cli, polisher, report, spectra
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device"}
     i = 0
@@ -30,6 +36,10 @@ def parse_args(argv):
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
+        if key == "--spectra":
+            o["spectra"] = True
+            i += 1
+            continue
         if key not in keys or i + 1 >= len(argv):
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -70,7 +80,9 @@ def run(argv):
             cli.error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable; give --threshold.")
         given = int(txt.split()[0])
     cli.log("Lower threshold for unreliable kmers is %d" % given)
-    names, lengths, rep = cli.scan_contigs(table, cli.read_assembly(a["asm"]), given)
+    contigs = cli.read_assembly(a["asm"])
+    names, lengths, rep = cli.scan_contigs(table, contigs, given)
+    spec = cli.assembly_spectrum(table, contigs) if a["spectra"] else None
     table.close()
     prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
     report.write_atomic(prefix + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("asm", lengths, rep.counts)]))
@@ -78,6 +90,11 @@ def run(argv):
     _, v, u, ab = report.totals(rep.counts)
     cli.log("Dense k-mer QV = %s (unreliable k-mers), %s (absent k-mers); %d runs in %s.unreliable.bed" %
             (report.qv_text(u, v, k), report.qv_text(ab, v, k), len(rep.runs), prefix))
+    if spec is not None:
+        row = spectra.completeness_row("asm", spec, given)
+        spectra.write_atomic(prefix + ".spectra_cn.tsv", spectra.spectra_cn_text(spec))
+        spectra.write_atomic(prefix + ".completeness.tsv", spectra.completeness_text(k, [row]))
+        cli.log("Assembly: %s" % spectra.log_text(row))
     return 0
 
 

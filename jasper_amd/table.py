@@ -123,6 +123,20 @@ class KmerReport:
         return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["n_absent"]), int(r["min_count"])) for r in self.runs]
 
 
+class KmerSpectrum:
+    """copy-number k-mer spectrum of a read table and an assembly table (include/jasper_hip.h: jasper_table_spectrum): `cells` =
+    numpy uint64 array (6, 10002), cells[m][c] = distinct k-mers with min(copies in the assembly, 5) = m and min(count in the
+    reads, 10001) = c (column 0: only in the assembly), `seconds` = device time of the two sweeps.  The numbers derived from it
+    and the files: jasper_amd/spectra.py."""
+
+    def __init__(self, cells, seconds):
+        self.cells = cells
+        self.seconds = seconds
+
+    def __eq__(self, other):
+        return isinstance(other, KmerSpectrum) and self.cells.shape == other.cells.shape and bool((self.cells == other.cells).all())
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -503,6 +517,18 @@ class KmerTable:
     def report_tile_windows():
         """windows per tile of the report's scan kernel (runs are stitched across tiles; tests aim at the seams)"""
         return int(_lib.lib().jasper_report_tile_windows())
+
+    # ---- copy-number k-mer spectrum (an extension: no counterpart in the reference) ------------------------
+    def spectrum(self, assembly_table):
+        """this table as the reads' counts joined on the GPU with `assembly_table` (a whole KmerTable of the same k on the same
+        device, the assembly counted into it) -> KmerSpectrum; neither table is modified"""
+        import numpy as np
+        if not isinstance(assembly_table, KmerTable) or not assembly_table._h:
+            raise TypeError("spectrum: the assembly must be an open KmerTable")
+        cells = np.zeros((int(self._L.jasper_spectrum_rows()), 10002), dtype=np.uint64)
+        secs = C.c_double(0)
+        check(self._L.jasper_table_spectrum(self._h, assembly_table._h, cells.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(secs)))
+        return KmerSpectrum(cells, secs.value)
 
     def _wrap_report(self, rc, res):
         try:
