@@ -847,13 +847,16 @@ int Table::resize(int new_s, std::string &err) {
 
 // after a batch of insertions: re-insert spilled k-mers into a bigger table, grow when past the load limit
 int Table::after_batch(std::string &err) {
-    for (int round = 0; round < 8; ++round) {
+    // up to eight rounds of growth; the state after the last one is looked at as well (a re-insertion that settled in the
+    // eighth round is a success, not "did not settle")
+    for (int round = 0; round <= 8; ++round) {
         if (read_stats(err)) return -1;
         if (h_stats[ST_FATAL]) { err = "k-mer table overflow (spill buffer exhausted): pass a larger size hint"; return -2; }
         const uint64_t spilled = h_stats[ST_SPILL];
         if (getenv("JASPER_COUNT_DEBUG") && spilled) fprintf(stderr, "[count] after_batch: %llu spilled insertions\n", (unsigned long long)spilled);
         const bool too_full = (double)h_stats[ST_DISTINCT] > grow_at * (double)nslots && d.s < d.B;
         if (!spilled && !too_full) return 0;
+        if (round == 8) break;
         std::vector<unsigned long long> sp;
         if (spilled) {
             sp.resize(3 * spilled);
@@ -1284,6 +1287,15 @@ int Table::ensure_narrow(std::string &err) {
     if (need > 34) { err = WIDE_NO_EXCHANGE; return -1; }
     return resize(std::max(need, d.s), err);
 }
+// An export met a count that the packing has no bits for (packed_entry_of / owner_entry_of set the mark): the export is refused,
+// the table is as it was -- the mark is taken back, or every later insertion would read it as a table overflow (after_batch)
+int Table::packed_count_refused(std::string &err) {
+    HIPCHK(hipMemsetAsync(d.stats + ST_FATAL, 0, sizeof(unsigned long long), stream));
+    HIPCHK(jk_stream_wait(stream));
+    h_stats[ST_FATAL] = 0;
+    err = "a count does not fit the packed exchange format";
+    return -2;
+}
 int Table::export_packed(void *d_dst, uint64_t cap, uint64_t *n_out, uint32_t part, uint32_t nparts, std::string &err) {
     if (d.B > 96) { err = WIDE_NO_EXCHANGE; return -1; }
     HIPCHK(hipSetDevice(device));
@@ -1302,7 +1314,7 @@ int Table::export_packed(void *d_dst, uint64_t cap, uint64_t *n_out, uint32_t pa
     HIPCHK(hipMemcpyAsync(&got, d_counts + EXP_BLOCKS, sizeof got, hipMemcpyDeviceToHost, stream));
     HIPCHK(jk_stream_wait(stream));
     if (read_stats(err)) return -1;
-    if (h_stats[ST_FATAL] == 2) { err = "a count does not fit the packed exchange format"; return -2; }
+    if (h_stats[ST_FATAL] == 2) return packed_count_refused(err);
     *n_out = got;   // may exceed cap: the caller sizes its buffer with a first call (cap = 0) or from info()
     return 0;
 }
@@ -1323,7 +1335,7 @@ int Table::export_owner(void *d_dst, uint64_t cap, uint32_t nown, int sort_r, ui
     HIPCHK(hipMemcpy2DAsync(got, 8, d_counts + EXP_BLOCKS, (size_t)EXP_STRIDE * 8, 8, nown, hipMemcpyDeviceToHost, stream));
     HIPCHK(jk_stream_wait(stream));
     if (read_stats(err)) return -1;
-    if (h_stats[ST_FATAL] == 2) { err = "a count does not fit the packed exchange format"; return -2; }
+    if (h_stats[ST_FATAL] == 2) return packed_count_refused(err);
     for (uint32_t o = 0; o < nown; ++o) counts_out[o] = got[o];
     return 0;
 }

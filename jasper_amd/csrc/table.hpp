@@ -412,6 +412,7 @@ struct Table {
     // falls into partition `part` of `nparts` equal slot ranges; mode 0 = add counts, 1 = set counts
     int export_packed(void *d_dst, uint64_t cap, uint64_t *n_out, uint32_t part, uint32_t nparts, std::string &err);
     int import_packed(const void *d_src, uint64_t n, int mode, std::string &err);
+    int packed_count_refused(std::string &err);      // the error return of an export that met a count too large for the packing
     int import_packed_multi(const void *const *d_srcs, const uint64_t *counts, uint32_t n_src, std::string &err);   // add, all lists in one sweep
     int reserve(uint64_t min_slots, std::string &err);
     // Owner-sharded table (table.hip, "shards"): all entries of this table in ONE pass, grouped by owner_of(hash, nown)
