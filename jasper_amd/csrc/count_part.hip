@@ -23,6 +23,11 @@
 // The table layout, tags and probe order are exactly those of the direct path, so lookups, histogram, export, growth
 // and the polisher do not know which path filled the table.  HBM traffic per k-mer: 1 B base + 8 B x 2 (part1 list)
 // + 8 B x 2 (part2 list) + the table once in, once out -- all of it streaming.
+//
+// Host side: Table::partition_geometry sizes the lists (PartGeom, table.hpp), Table::launch_count_partitioned puts a piece's
+// passes on the stream, the xchg_* entry points do the same for the exchange between GPUs (each begins with xchg_begin).  Every
+// pass has one place that picks the kernel instance -- launch_part1, launch_part2, launch_region_insert -- and every instance
+// is launched through launch_big_lds, which raises its dynamic-LDS limit the first time.
 #include "table.hpp"
 #include <algorithm>
 #include <cmath>
@@ -54,14 +59,7 @@ constexpr int PT_HALO = 4;
 constexpr int PT_MAXBUCKETS = 2048;              // p1, p2 <= 11
 constexpr int RG_MAXBITS = 12;                   // region = 4096 slots: 48 KB of LDS in region_insert_kernel, three workgroups per CU (8192 for the largest tables)
 
-struct PartGeom {
-    int p1, p2, rbits;       // p1 + p2 + rbits == s
-    int recbits;             // 2k - p1  (<= 64): bits kept in a record
-    uint32_t nblk1;          // slices per level-1 list: the part1 blocks b, b + nblk1, b + 2 nblk1, ... append to slice b % nblk1 of every list
-    uint32_t grid1;          // part1 blocks
-    uint32_t nblk2;          // part2 blocks per level-1 bucket: every one owns a slice of each of the bucket's region lists
-    uint32_t cap1, cap2;     // slice capacities (records)
-};
+// (PartGeom, the geometry of the two list levels: table.hpp)
 // level-1 list of bucket b = slices  out1[(b * nblk1 + g) * cap1 ...], filled counts cnt1[g * 2^p1 + b]  (slice-major: a wave's 64
 // fill-count atomics in part1 -- lane = bucket -- are then 256 contiguous bytes, four requests to the memory side instead of 8 x nblk1)
 // region list of region r  = slices  out2[(r * nblk2 + x) * cap2 ...],   filled counts cnt2[r * nblk2 + x]
@@ -722,42 +720,56 @@ __global__ __launch_bounds__(256) void transpose_counts_kernel(const unsigned in
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < nb1 * nblk1) out[(i % nb1) * nblk1 + i / nb1] = in[i];
 }
+// ---- host side: what the launch sites below share ----------------------------------------------------------------
+// The list kernels keep their stages in dynamic LDS beyond the default limit: every instance has the limit raised once per
+// process, the first time it is launched (an instance that missed its own line failed only at run time, on the shape that
+// reached it).
+constexpr int BIG_LDS = 160 * 1024;    // the whole LDS of a CU
+template <auto KERNEL, typename... Args>
+static hipError_t launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
+    if (raised != hipSuccess) return raised;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+// the deferred list in a buffer: a 64-byte header (word 0 = number of entries) followed by cap entries of 3 words (hash.hi, hash.lo, count)
+struct DeferList { unsigned long long *n, *e; uint64_t cap; };
+static DeferList defer_list(void *buf, uint64_t cap) { unsigned long long *w = (unsigned long long *)buf; return DeferList{w, w + 8, cap}; }
+// ... and emptied (every pass that starts a list; xchg_partition goes on with the one its scan began)
+static hipError_t defer_list_begin(void *buf, uint64_t cap, hipStream_t stream, DeferList &D) {
+    D = defer_list(buf, cap);
+    return hipMemsetAsync(D.n, 0, 64, stream);
+}
+
+// the stage boundaries of a piece, whichever entry point records them
+static hipError_t ensure_stage_events(Table &t) {
+    for (hipEvent_t &e : t.ev_stage_t) {
+        if (e) continue;
+        const hipError_t r = hipEventCreate(&e);
+        if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+}
+
 // one launch site for the three word counts: k <= 16, 17..32, 33..37
 static hipError_t launch_part1(hipStream_t stream, int k, const uint8_t *d_piece, uint64_t len, uint64_t ntiles, uint64_t emit_from, const TableDev &d, const PartGeom &G,
-                               uint64_t *out1, unsigned int *cnt1, unsigned long long *defer_e, unsigned long long *defer_n, uint64_t deferred_cap) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1_kernel<3, 37>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-        attr_set = true;
-    }
+                               uint64_t *out1, unsigned int *cnt1, const DeferList &D) {
     P1Args P;
     P.k = k; P.p1 = G.p1; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.cap1 = G.cap1; P.stats = d.stats;
     const uint32_t n_cnt1 = (1u << G.p1) * G.nblk1;
-    {
-        hipError_t e = hipMemsetAsync(cnt1, 0, (size_t)n_cnt1 * 4, stream);
-        if (e != hipSuccess) return e;
-    }
-#define JK_P1_LAUNCH(...) hipLaunchKernelGGL((part1_kernel<__VA_ARGS__>), dim3(G.grid1), dim3(P1_TH), P1_LDS, stream, d_piece, len, ntiles, emit_from, P, out1, cnt1, defer_e, defer_n, deferred_cap)
-    if (k == 37 && G.p1 == 10 && G.recbits == 64 && !getenv("JASPER_EXPERIMENT_NO_KFIX")) JK_P1_LAUNCH(3, 37);
-    else if (G.recbits > 64) {                // 16-byte records (k >= 38)
-        static bool attrw_set = false;
-        if (!attrw_set) {
-            hipError_t e;
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1w_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(part1w_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            attrw_set = true;
-        }
-        if (k <= 48) hipLaunchKernelGGL((part1w_kernel<3>), dim3(G.grid1), dim3(P1_TH), P1W_LDS, stream, d_piece, len, ntiles, emit_from, P, reinterpret_cast<Rec16 *>(out1), cnt1, defer_e, defer_n, deferred_cap);
-        else hipLaunchKernelGGL((part1w_kernel<4>), dim3(G.grid1), dim3(P1_TH), P1W_LDS, stream, d_piece, len, ntiles, emit_from, P, reinterpret_cast<Rec16 *>(out1), cnt1, defer_e, defer_n, deferred_cap);
-    }
-    else if (k <= 16) JK_P1_LAUNCH(1);
-    else if (k <= 32) JK_P1_LAUNCH(2);
-    else JK_P1_LAUNCH(3);                     // (k <= 37: 8-byte records while 2k - 64 <= p1 <= 10)
+    hipError_t e = hipMemsetAsync(cnt1, 0, (size_t)n_cnt1 * 4, stream);
+    if (e != hipSuccess) return e;
+#define JK_P1_LAUNCH(...) launch_big_lds<part1_kernel<__VA_ARGS__>>(dim3(G.grid1), dim3(P1_TH), P1_LDS, stream, d_piece, len, ntiles, emit_from, P, out1, cnt1, D.e, D.n, D.cap)
+#define JK_P1W_LAUNCH(NW) launch_big_lds<part1w_kernel<NW>>(dim3(G.grid1), dim3(P1_TH), P1W_LDS, stream, d_piece, len, ntiles, emit_from, P, reinterpret_cast<Rec16 *>(out1), cnt1, D.e, D.n, D.cap)
+    if (k == 37 && G.p1 == 10 && G.recbits == 64 && !getenv("JASPER_EXPERIMENT_NO_KFIX")) e = JK_P1_LAUNCH(3, 37);
+    else if (G.recbits > 64) e = k <= 48 ? JK_P1W_LAUNCH(3) : JK_P1W_LAUNCH(4);      // 16-byte records (k >= 38)
+    else if (k <= 16) e = JK_P1_LAUNCH(1);
+    else if (k <= 32) e = JK_P1_LAUNCH(2);
+    else e = JK_P1_LAUNCH(3);                 // (k <= 37: 8-byte records while 2k - 64 <= p1 <= 10)
 #undef JK_P1_LAUNCH
+#undef JK_P1W_LAUNCH
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(clamp_counts_kernel, dim3((n_cnt1 + 255) / 256), dim3(256), 0, stream, cnt1, n_cnt1, G.cap1);
     return hipGetLastError();
 }
@@ -1692,8 +1704,7 @@ __global__ __launch_bounds__(256) void import3h_kernel(const unsigned long long 
 static uint32_t list_cap(double avg) { return (uint32_t)std::min<double>(4.0e9, avg * 1.25 + 8.0 * std::sqrt(avg) + 64.0); }
 
 // can this piece take the partitioned path, and with which geometry?
-bool Table::partition_geometry(uint64_t piece_bases, void *geom_out) const {
-    PartGeom &G = *reinterpret_cast<PartGeom *>(geom_out);
+bool Table::partition_geometry(uint64_t piece_bases, PartGeom &G) const {
     if (getenv("JASPER_COUNT_DIRECT")) return false;
     if (piece_bases < (8u << 20)) return false;          // small pieces: the direct kernel is already latency-hidden
     const int B = d.B, s = d.s;
@@ -1748,84 +1759,98 @@ bool Table::partition_geometry(uint64_t piece_bases, void *geom_out) const {
     return true;
 }
 
-int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const void *geom, std::string &err) {
-    const PartGeom G = *reinterpret_cast<const PartGeom *>(geom);
+// second pass, one place for one GPU and for a sender of the exchange: every level-1 bucket -> nown x 2^p2 lists (nown = 1: one
+// GPU; by_owner: laid out owner-major, part2_kernel).  The whole-line kernel takes what it can: at most 512 lists per bucket
+// and slices of whole lines; 16-byte records have no other.
+template <int MAXB, int ROWS, bool OWN, typename REC>
+static hipError_t launch_part2f(hipStream_t stream, dim3 grid, P2Args P, const uint64_t *out1, const unsigned int *cnt1, uint64_t *out2, unsigned int *cnt2, const DeferList &D) {
+    using F = P2F<MAXB, ROWS, (int)sizeof(REC)>;
+    P.vper = (P.cap1 + (uint32_t)F::PIECE - 1u) / (uint32_t)F::PIECE;
+    return launch_big_lds<part2f_kernel<MAXB, ROWS, OWN, REC>>(grid, dim3(PT_THREADS), F::LDS, stream, reinterpret_cast<const REC *>(out1), cnt1, P, reinterpret_cast<REC *>(out2), cnt2,
+                                                               D.e, D.n, D.cap);
+}
+static int launch_part2(hipStream_t stream, const TableDev &d, const PartGeom &G, uint32_t nown, bool by_owner, const uint64_t *out1, const unsigned int *cnt1, uint64_t *out2,
+                        unsigned int *cnt2, const DeferList &D, std::string &err) {
+    const dim3 grid(G.nblk2, std::min<uint32_t>(1u << G.p1, 2048));
+    const uint64_t nlists = (uint64_t)nown << G.p2;            // per bucket
+    const bool rec16 = G.recbits > 64;
+    const bool lines = nlists <= 512 && G.cap2 % P2F_LINE == 0;
+    if (rec16 && !lines) { err = "count: no list geometry for 16-byte records"; return -1; }
+    P2Args P;
+    P.p1 = G.p1; P.p2 = G.p2; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.nblk2 = G.nblk2; P.cap1 = G.cap1; P.cap2 = G.cap2; P.stats = d.stats; P.nown = nown;
+    P.vper = 0;                                                // (launch_part2f: from the instance's piece)
+    if (rec16) HIPCHK((launch_part2f<512, 4, false, Rec16>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
+    else if (lines && !getenv("JASPER_EXPERIMENT_OLDP2")) {
+        // (the sender's split in whole lines, like the single-GPU pass)
+        if (by_owner) HIPCHK((launch_part2f<512, 10, true, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
+        else if (nlists <= 128) HIPCHK((launch_part2f<128, 12, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
+        else HIPCHK((launch_part2f<512, 10, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
+    }
+    else if (by_owner) HIPCHK(launch_big_lds<part2_kernel<true>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, nown, 0));
+    else HIPCHK(launch_big_lds<part2_kernel<false>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, 1u, 0));
+    return 0;
+}
+
+// final pass, one place for one GPU and for an owner of the exchange: one launch over all regions (region_insert_kernel: a
+// probe that leaves its region takes the direct path afterwards).  fresh: the table is logically empty and is not read -- on one
+// GPU also: the piece is below 2^32 bases, so that the image counts in 32 bits.  xchg: the lists are what nsrc senders laid out
+// (cbits, fbits: region_insert_kernel).
+static hipError_t launch_region_insert(hipStream_t stream, const TableDev &d, const PartGeom &G, uint32_t nregions, const void *lists, const unsigned int *lcnt, uint32_t lcap,
+                                       uint32_t nsl, const DeferList &D, unsigned long long *histo, bool fresh, bool xchg, uint32_t nsrc, int cbits, int fbits) {
+    const size_t R = (size_t)1 << G.rbits;
+    const bool rec16 = G.recbits > 64;
+    // (a wide table's image: tag, second word and count per slot, no histogram bins)
+    const size_t lds = xchg ? R * 16 + LDS_HBINS * 4 + (LI_MAXSL + 1) * 4 : d.ext ? R * (fresh ? 20 : 24) : R * (fresh ? 12 : 16) + (histo ? LDS_HBINS * 4 : 0);
+    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, BIG_LDS / lds));
+    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>(nregions, 256 * per_cu * 4));
+#define JK_RI_LAUNCH(REC, KERNEL, ...) \
+    launch_big_lds<KERNEL>(dim3(nblk), dim3(RI_TH), lds, stream, reinterpret_cast<const REC *>(lists), lcnt, lcap, nsl, d, G, nregions, D.e, D.n, D.cap, ##__VA_ARGS__)
+    if (xchg) return fresh ? JK_RI_LAUNCH(uint64_t, (region_insert_kernel<true, true>), histo, nsrc, cbits, fbits)
+                           : JK_RI_LAUNCH(uint64_t, (region_insert_kernel<false, true>), histo, nsrc, cbits, fbits);
+    if (d.ext) return fresh ? JK_RI_LAUNCH(Rec16, region_insertw_kernel<true>) : JK_RI_LAUNCH(Rec16, region_insertw_kernel<false>);
+    if (rec16) return fresh ? JK_RI_LAUNCH(Rec16, (region_insert_kernel<true, false, Rec16>), histo, 1u, 0, 0)
+                            : JK_RI_LAUNCH(Rec16, (region_insert_kernel<false, false, Rec16>), histo, 1u, 0, 0);
+    if (fresh && G.rbits == 12 && !getenv("JASPER_EXPERIMENT_NO_AHEAD"))               // (the instance that runs a batch of records ahead)
+        return JK_RI_LAUNCH(uint64_t, (region_insert_kernel<true, false, uint64_t, true>), histo, 1u, 0, 0);
+    return fresh ? JK_RI_LAUNCH(uint64_t, region_insert_kernel<true>, histo, 1u, 0, 0) : JK_RI_LAUNCH(uint64_t, region_insert_kernel<false>, histo, 1u, 0, 0);
+#undef JK_RI_LAUNCH
+}
+
+int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const PartGeom &G, std::string &err) {
     const uint32_t nb1 = 1u << G.p1, nregions = 1u << (G.p1 + G.p2);
     const uint64_t deferred_cap = std::max<uint64_t>(1u << 16, len / 48);      // (24 bytes each; a piece that needs more abandons itself: part_decide_kernel)
     const size_t n_cnt1 = (size_t)nb1 * G.nblk1, n_cnt2 = G.p2 ? (size_t)nregions * G.nblk2 : n_cnt1;      // (one level: the counts once more, bucket-major)
-    const bool rec16 = G.recbits > 64;
-    const size_t RB = rec16 ? 16 : 8;
+    const size_t RB = G.recbits > 64 ? 16 : 8;
     uint64_t *out1 = (uint64_t *)workspace(WS_COUNT + 0, n_cnt1 * G.cap1 * RB, err);
     uint64_t *out2 = G.p2 ? (uint64_t *)workspace(WS_COUNT + 1, n_cnt2 * G.cap2 * RB, err) : nullptr;
     unsigned int *cur = (unsigned int *)workspace(WS_COUNT + 2, (n_cnt1 + n_cnt2 + 4) * 4, err);
     unsigned long long *defer = (unsigned long long *)workspace(WS_COUNT + 3, deferred_cap * 24 + 64, err);
     if (!out1 || (G.p2 && !out2) || !cur || !defer) return -2;
     unsigned int *cnt1 = cur, *cnt2 = cur + n_cnt1;
-    unsigned long long *defer_n = defer;                    // first 8 bytes: counter; entries start 64 bytes in
-    unsigned long long *defer_e = defer + 8;
-    HIPCHK(hipMemsetAsync(defer_n, 0, 64, stream));
+    DeferList D;
+    HIPCHK(defer_list_begin(defer, deferred_cap, stream, D));
     const uint64_t ntiles = (len + (uint64_t)PT_TILE - 1) / (uint64_t)PT_TILE;
-    for (int i = 0; i < 6; ++i) if (!ev_stage_t[i]) HIPCHK(hipEventCreate(&ev_stage_t[i]));
+    HIPCHK(ensure_stage_events(*this));
     part_stage_n = 4;
     count_path = 1;
     HIPCHK(hipEventRecord(ev_k0, stream));
     HIPCHK(hipEventRecord(ev_stage_t[0], stream));
-    HIPCHK(launch_part1(stream, k, d_piece, len, ntiles, emit_from, d, G, out1, cnt1, defer_e, defer_n, deferred_cap));
+    HIPCHK(launch_part1(stream, k, d_piece, len, ntiles, emit_from, d, G, out1, cnt1, D));
     HIPCHK(hipEventRecord(ev_stage_t[1], stream));
     const uint64_t *lists = out1;
     const unsigned int *lcnt = cnt1;
     uint32_t lcap = G.cap1, nsl = G.nblk1;
     if (G.p2) {
-        dim3 grid(G.nblk2, std::min<uint32_t>(nb1, 2048));
-        static bool attr2_set = false;
-        if (!attr2_set) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr2_set = true;
-        }
-        if (rec16) {
-            static bool attr2w_set = false;
-            if (!attr2w_set) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2f_kernel<512, 4, false, Rec16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr2w_set = true;
-            }
-            if ((1 << G.p2) > 512 || G.cap2 % P2F_LINE) { err = "count: no list geometry for 16-byte records"; return -1; }
-            P2Args P;
-            P.p1 = G.p1; P.p2 = G.p2; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.nblk2 = G.nblk2; P.cap1 = G.cap1; P.cap2 = G.cap2; P.stats = d.stats; P.nown = 1;
-            constexpr uint32_t piece = (uint32_t)P2F<512, 4, 16>::PIECE;
-            P.vper = (G.cap1 + piece - 1u) / piece;
-            constexpr size_t lds2 = P2F<512, 4, 16>::LDS;
-            hipLaunchKernelGGL((part2f_kernel<512, 4, false, Rec16>), grid, dim3(PT_THREADS), lds2, stream, reinterpret_cast<const Rec16 *>(out1), cnt1, P, reinterpret_cast<Rec16 *>(out2), cnt2, defer_e, defer_n,
-                               deferred_cap);
-        } else if ((1 << G.p2) <= 512 && G.cap2 % P2F_LINE == 0 && !getenv("JASPER_EXPERIMENT_OLDP2")) {
-            static bool attr2f_set = false;
-            if (!attr2f_set) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2f_kernel<512, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2f_kernel<128, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr2f_set = true;
-            }
-            P2Args P;
-            P.p1 = G.p1; P.p2 = G.p2; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.nblk2 = G.nblk2; P.cap1 = G.cap1; P.cap2 = G.cap2; P.stats = d.stats; P.nown = 1;
-            if ((1 << G.p2) <= 128) {
-                P.vper = (G.cap1 + (uint32_t)P2F<128, 12>::PIECE - 1u) / (uint32_t)P2F<128, 12>::PIECE;
-                constexpr size_t lds2 = P2F<128, 12>::LDS;
-                hipLaunchKernelGGL((part2f_kernel<128, 12>), grid, dim3(PT_THREADS), lds2, stream, out1, cnt1, P, out2, cnt2, defer_e, defer_n, deferred_cap);
-            } else {
-                P.vper = (G.cap1 + (uint32_t)P2F<512, 10>::PIECE - 1u) / (uint32_t)P2F<512, 10>::PIECE;
-                constexpr size_t lds2 = P2F<512, 10>::LDS;
-                hipLaunchKernelGGL((part2f_kernel<512, 10>), grid, dim3(PT_THREADS), lds2, stream, out1, cnt1, P, out2, cnt2, defer_e, defer_n, deferred_cap);
-            }
-        } else
-            hipLaunchKernelGGL(part2_kernel<false>, grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, defer_e, defer_n, deferred_cap, 1u);
-        HIPCHK(hipGetLastError());
+        if (const int rc = launch_part2(stream, d, G, 1, false, out1, cnt1, out2, cnt2, D, err)) return rc;
         lists = out2; lcnt = cnt2; lcap = G.cap2; nsl = G.nblk2;
     } else {
         hipLaunchKernelGGL(transpose_counts_kernel, dim3((uint32_t)((n_cnt1 + 255) / 256)), dim3(256), 0, stream, cnt1, cnt2, nb1, G.nblk1);
         HIPCHK(hipGetLastError());
         lcnt = cnt2;
     }
-    hipLaunchKernelGGL(part_decide_kernel, dim3(1), dim3(1), 0, stream, defer_n, deferred_cap, d.stats);
+    hipLaunchKernelGGL(part_decide_kernel, dim3(1), dim3(1), 0, stream, D.n, D.cap, d.stats);
     HIPCHK(hipGetLastError());
-    part_defer_header = defer_n;
+    part_defer_header = D.n;
     part_slots_dirty_before = slots_dirty;
     HIPCHK(hipEventRecord(ev_stage_t[2], stream));
     // fused histogram: asked for by count_device when this piece is the whole input going into an empty table
@@ -1837,51 +1862,11 @@ int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64
     const bool empty_tbl = slots_dirty || histo != nullptr;
     const bool fresh32 = empty_tbl && len < (1ull << 32);
     if (slots_dirty && !fresh32) { if (materialize(err)) return -1; }
-    const uint32_t R = 1u << G.rbits;
-    const size_t lds = (size_t)R * (fresh32 ? 12 : 16) + (histo ? LDS_HBINS * 4 : 0);
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<true, false, uint64_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    {
-        const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / std::max<size_t>(lds, 1)));
-        const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>(nregions, 256 * per_cu * 4));
-        if (d.ext) {
-            static bool attrww_set = false;
-            if (!attrww_set) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insertw_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insertw_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attrww_set = true;
-            }
-            const size_t ldsw = (size_t)R * (fresh32 ? 20 : 24);
-            const uint32_t per_cuw = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / ldsw));
-            const uint32_t nblkw = std::max<uint32_t>(1, std::min<uint32_t>(nregions, 256 * per_cuw * 4));
-            const Rec16 *lw = reinterpret_cast<const Rec16 *>(lists);
-            if (fresh32) hipLaunchKernelGGL(region_insertw_kernel<true>, dim3(nblkw), dim3(RI_TH), ldsw, stream, lw, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap);
-            else hipLaunchKernelGGL(region_insertw_kernel<false>, dim3(nblkw), dim3(RI_TH), ldsw, stream, lw, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap);
-        } else if (rec16) {
-            static bool attrw_set = false;
-            if (!attrw_set) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<true, false, Rec16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<false, false, Rec16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attrw_set = true;
-            }
-            const Rec16 *lw = reinterpret_cast<const Rec16 *>(lists);
-            if (fresh32) hipLaunchKernelGGL((region_insert_kernel<true, false, Rec16>), dim3(nblk), dim3(RI_TH), lds, stream, lw, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap, histo, 1u, 0, 0);
-            else hipLaunchKernelGGL((region_insert_kernel<false, false, Rec16>), dim3(nblk), dim3(RI_TH), lds, stream, lw, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap, histo, 1u, 0, 0);
-        } else if (fresh32 && G.rbits == 12 && !getenv("JASPER_EXPERIMENT_NO_AHEAD"))      // (the instance that runs a batch of records ahead)
-            hipLaunchKernelGGL((region_insert_kernel<true, false, uint64_t, true>), dim3(nblk), dim3(RI_TH), lds, stream, lists, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap, histo, 1u, 0, 0);
-        else if (fresh32) hipLaunchKernelGGL(region_insert_kernel<true>, dim3(nblk), dim3(RI_TH), lds, stream, lists, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap, histo);
-        else hipLaunchKernelGGL(region_insert_kernel<false>, dim3(nblk), dim3(RI_TH), lds, stream, lists, lcnt, lcap, nsl, d, G, nregions, defer_e, defer_n, deferred_cap, histo);
-        HIPCHK(hipGetLastError());
-    }
+    HIPCHK(launch_region_insert(stream, d, G, nregions, lists, lcnt, lcap, nsl, D, histo, fresh32, false, 1u, 0, 0));
     HIPCHK(hipEventRecord(ev_stage_t[3], stream));
     slots_dirty = false;   // every region has been written by the launch above
-    if (d.ext) hipLaunchKernelGGL(import3w_kernel, dim3(256), dim3(256), 0, stream, defer_e, defer_n, deferred_cap, d);
-    else hipLaunchKernelGGL(import3h_kernel, dim3(256), dim3(256), 0, stream, defer_e, defer_n, deferred_cap, d, histo);
+    if (d.ext) hipLaunchKernelGGL(import3w_kernel, dim3(256), dim3(256), 0, stream, D.e, D.n, D.cap, d);
+    else hipLaunchKernelGGL(import3h_kernel, dim3(256), dim3(256), 0, stream, D.e, D.n, D.cap, d, histo);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev_k1, stream));
     HIPCHK(hipEventRecord(ev_stage_t[4], stream));
@@ -1889,7 +1874,7 @@ int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64
     if (getenv("JASPER_COUNT_DEBUG") && atoi(getenv("JASPER_COUNT_DEBUG")) >= 2) {
         HIPCHK(jk_stream_wait(stream));
         unsigned long long dn = 0;
-        HIPCHK(hipMemcpy(&dn, defer_n, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&dn, D.n, 8, hipMemcpyDeviceToHost));
         std::vector<unsigned int> hc(n_cnt1 + n_cnt2);
         HIPCHK(hipMemcpy(hc.data(), cur, hc.size() * 4, hipMemcpyDeviceToHost));
         unsigned int mx1 = 0, mx2 = 0;
@@ -1921,14 +1906,13 @@ static uint32_t xchg_cap(double avg, double mult) { return (uint32_t)std::min<do
 // owner -- a bucket can be split 2048 ways in one pass, and the senders also split by owner, so for very large shards (2^32
 // slots on 8 GPUs) the owner runs one more split pass over what it received (part2_kernel<false, MIN>) before its insert.
 static int xchg_max_lists() { const char *e = getenv("JASPER_XCHG_TEST_MAXLISTS"); return e ? std::max(2, atoi(e)) : PT_MAXBUCKETS; }   // (tests: force the extra pass on small tables)
-static bool xchg_geometry(const Table &t, uint64_t piece_max, uint64_t records_max, uint32_t nown, PartGeom &G, int &p2b) {
-    if (nown < 2 || nown > MAX_SHARDS) return false;
-    alignas(16) char raw[64];
+// (returns p2b, or -1: no geometry)
+static int xchg_geometry(const Table &t, uint64_t piece_max, uint64_t records_max, uint32_t nown, PartGeom &G) {
+    if (nown < 2 || nown > MAX_SHARDS) return -1;
     // (a feed's last batch may be small: the lists are then laid out as for the smallest piece the passes are tuned for)
     piece_max = std::max<uint64_t>(piece_max, 8u << 20);
-    if (!t.partition_geometry(piece_max, raw)) return false;
-    G = *reinterpret_cast<const PartGeom *>(raw);
-    if (G.recbits > 64) return false;                     // (keys of more than 74 bits: per-GPU tables and the entry exchange instead)
+    if (!t.partition_geometry(piece_max, G)) return -1;
+    if (G.recbits > 64) return -1;                        // (keys of more than 74 bits: per-GPU tables and the entry exchange instead)
     // the senders split by (owner, second-level bits): more than 512 lists per bucket would leave the whole-line kernel, so the
     // owners take regions of 8192 slots instead of 4096 where that is what it takes -- for up to four owners, whose lists travel
     // deduplicated (dist.dedupe_pays).  Beyond that the lists travel as they are, and an owner inserting 10^9 raw records into
@@ -1937,13 +1921,13 @@ static bool xchg_geometry(const Table &t, uint64_t piece_max, uint64_t records_m
     // of kernels per rank).  JASPER_EXPERIMENT_XCHG_RB12 / _RB13 force one or the other.
     const bool rb13 = getenv("JASPER_EXPERIMENT_XCHG_RB13") ? true : getenv("JASPER_EXPERIMENT_XCHG_RB12") ? false : nown <= 4;
     if (((uint64_t)nown << G.p2) > 512 && ((uint64_t)nown << (G.p2 - 1)) <= 512 && G.p2 > 0 && G.rbits == RG_MAXBITS && rb13) { --G.p2; ++G.rbits; }
-    p2b = 0;
+    int p2b = 0;
     while (((uint64_t)nown << (G.p2 - p2b)) > (uint64_t)xchg_max_lists() && p2b < G.p2) ++p2b;
-    if (((uint64_t)nown << (G.p2 - p2b)) > (uint64_t)PT_MAXBUCKETS) return false;
+    if (((uint64_t)nown << (G.p2 - p2b)) > (uint64_t)PT_MAXBUCKETS) return -1;
     G.p2 -= p2b;
     const uint32_t nb1 = 1u << G.p1;
     G.nblk2 = nb1 >= 256 ? 1u : std::min<uint32_t>(G.nblk1, 8u);
-    if (nown * G.nblk2 > (uint32_t)LI_MAXSL) return false;
+    if (nown * G.nblk2 > (uint32_t)LI_MAXSL) return -1;
     const double lists = (double)nb1 * (double)((uint64_t)nown << G.p2) * (double)G.nblk2;
     if (records_max) {
         const double rec = (double)std::min(records_max, piece_max);
@@ -1951,14 +1935,26 @@ static bool xchg_geometry(const Table &t, uint64_t piece_max, uint64_t records_m
         G.cap2 = xchg_cap(rec / lists, rec / keys);
     } else G.cap2 = list_cap((double)piece_max / lists);
     G.cap2 = (G.cap2 + 15u) & ~15u;                       // whole 128-byte lines (part2f_kernel<., ., OWN>)
-    return true;
+    return p2b;
+}
+// how the entry points below begin: this table's device, the geometry all ranks agree on and -- lists1: for the sender's passes --
+// the level-1 lists in the workspace (the scan fills them, the partition reads them: same sizes, nothing is reallocated)
+struct XchgCall { PartGeom G; int p2b; size_t n_cnt1; uint64_t *out1; unsigned int *cnt1; };
+static int xchg_begin(Table &t, uint64_t piece_max, uint64_t records_max, uint32_t nown, bool lists1, XchgCall &X, std::string &err) {
+    HIPCHK(hipSetDevice(t.device));
+    X.p2b = xchg_geometry(t, piece_max, records_max, nown, X.G);
+    if (X.p2b < 0) { err = "count exchange: no geometry for this table / piece size"; return -1; }
+    X.n_cnt1 = ((size_t)1 << X.G.p1) * X.G.nblk1;
+    X.out1 = lists1 ? (uint64_t *)t.workspace(Table::WS_COUNT + 0, X.n_cnt1 * X.G.cap1 * 8, err) : nullptr;
+    X.cnt1 = lists1 ? (unsigned int *)t.workspace(Table::WS_COUNT + 2, (X.n_cnt1 + 4) * 4, err) : nullptr;
+    return lists1 && (!X.out1 || !X.cnt1) ? -2 : 0;
 }
 
 int Table::xchg_plan(uint64_t piece_max, uint64_t records_max, uint32_t nown, uint64_t out[8], std::string &err) {
     (void)err;
     PartGeom G;
-    int p2b = 0;
-    if (!xchg_geometry(*this, piece_max, records_max, nown, G, p2b)) return 1;
+    const int p2b = xchg_geometry(*this, piece_max, records_max, nown, G);
+    if (p2b < 0) return 1;
     const uint64_t lists_per_owner = (uint64_t)1 << (G.p1 + G.p2);
     out[0] = lists_per_owner * G.nblk2 * G.cap2;               // records (8 B) per owner block
     out[1] = lists_per_owner * G.nblk2;                        // slice counts (4 B) per owner block
@@ -1970,27 +1966,20 @@ int Table::xchg_plan(uint64_t piece_max, uint64_t records_max, uint32_t nown, ui
 // d_defer: 64-byte header (word 0 = number of entries) + defer_cap entries of 3 words (hash.hi, hash.lo, 1)
 int Table::xchg_scan(const uint8_t *d_bases, uint64_t n, uint64_t pos, uint64_t end, uint64_t piece_max, uint32_t nown, void *d_defer, uint64_t defer_cap,
                      uint64_t *records, std::string &err) {
-    HIPCHK(hipSetDevice(device));
-    PartGeom G;
-    int p2b = 0;
-    if (!xchg_geometry(*this, piece_max, 0, nown, G, p2b)) { err = "count exchange: no geometry for this table / piece size"; return -1; }
+    XchgCall X;
+    if (const int rc = xchg_begin(*this, piece_max, 0, nown, true, X, err)) return rc;
     if (end > n) end = n;
-    const uint32_t nb1 = 1u << G.p1;
-    unsigned long long *defer_n = (unsigned long long *)d_defer, *defer_e = defer_n + 8;
-    HIPCHK(hipMemsetAsync(defer_n, 0, 64, stream));
-    for (int i = 0; i <= N_STAGES; ++i) if (!ev_stage_t[i]) HIPCHK(hipEventCreate(&ev_stage_t[i]));
+    DeferList D;
+    HIPCHK(defer_list_begin(d_defer, defer_cap, stream, D));
+    HIPCHK(ensure_stage_events(*this));
     count_path = 3;
     part_stage_n = 5;
     if (read_stats(err)) return -1;
     const uint64_t occ_before = h_stats[ST_OCCURRENCES];
     HIPCHK(hipEventRecord(ev_stage_t[0], stream));
     xchg_partitioned = true;
-    const size_t n_cnt1 = (size_t)nb1 * G.nblk1;
-    uint64_t *out1 = (uint64_t *)workspace(WS_COUNT + 0, n_cnt1 * G.cap1 * 8, err);
-    unsigned int *cnt1 = (unsigned int *)workspace(WS_COUNT + 2, (n_cnt1 + 4) * 4, err);
-    if (!out1 || !cnt1) return -2;
     if (pos >= end) {                                          // nothing of mine in this round: empty lists
-        HIPCHK(hipMemsetAsync(cnt1, 0, n_cnt1 * 4, stream));
+        HIPCHK(hipMemsetAsync(X.cnt1, 0, X.n_cnt1 * 4, stream));
         HIPCHK(hipEventRecord(ev_stage_t[1], stream));
         if (records) *records = 0;
         return 0;
@@ -2003,7 +1992,7 @@ int Table::xchg_scan(const uint8_t *d_bases, uint64_t n, uint64_t pos, uint64_t 
     start = start >= a ? start - a : 0;
     const uint64_t len = end - start, emit_from = pos - start;
     const uint64_t ntiles = (len + (uint64_t)PT_TILE - 1) / (uint64_t)PT_TILE;
-    HIPCHK(launch_part1(stream, k, d_bases + start, len, ntiles, emit_from, d, G, out1, cnt1, defer_e, defer_n, defer_cap));
+    HIPCHK(launch_part1(stream, k, d_bases + start, len, ntiles, emit_from, d, X.G, X.out1, X.cnt1, D));
     HIPCHK(hipEventRecord(ev_stage_t[1], stream));
     if (read_stats(err)) return -1;                            // (waits for the kernel)
     if (records) *records = h_stats[ST_OCCURRENCES] - occ_before;
@@ -2011,39 +2000,10 @@ int Table::xchg_scan(const uint8_t *d_bases, uint64_t n, uint64_t pos, uint64_t 
 }
 
 int Table::xchg_partition(uint64_t piece_max, uint64_t records_max, uint32_t nown, void *d_send, void *d_send_cnt, void *d_defer, uint64_t defer_cap, std::string &err) {
-    HIPCHK(hipSetDevice(device));
-    PartGeom G;
-    int p2b = 0;
-    if (!xchg_geometry(*this, piece_max, records_max, nown, G, p2b)) { err = "count exchange: no geometry for this table / piece size"; return -1; }
+    XchgCall X;
+    if (const int rc = xchg_begin(*this, piece_max, records_max, nown, true, X, err)) return rc;
     if (!xchg_partitioned) { err = "count exchange: partition without a scan before it"; return -1; }
-    const uint32_t nb1 = 1u << G.p1;
-    unsigned long long *defer_n = (unsigned long long *)d_defer, *defer_e = defer_n + 8;
-    const size_t n_cnt1 = (size_t)nb1 * G.nblk1;
-    uint64_t *out1 = (uint64_t *)workspace(WS_COUNT + 0, n_cnt1 * G.cap1 * 8, err);       // (what the scan filled: same sizes, nothing is reallocated)
-    unsigned int *cnt1 = (unsigned int *)workspace(WS_COUNT + 2, (n_cnt1 + 4) * 4, err);
-    if (!out1 || !cnt1) return -2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    if (((uint64_t)nown << G.p2) <= 512 && G.cap2 % P2F_LINE == 0 && !getenv("JASPER_EXPERIMENT_OLDP2")) {
-        // the sender's split in whole lines, like the single-GPU pass
-        static bool attrf_set = false;
-        if (!attrf_set) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2f_kernel<512, 10, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attrf_set = true;
-        }
-        P2Args P;
-        P.p1 = G.p1; P.p2 = G.p2; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.nblk2 = G.nblk2; P.cap1 = G.cap1; P.cap2 = G.cap2; P.stats = d.stats; P.nown = nown;
-        P.vper = (G.cap1 + (uint32_t)P2F<512, 10>::PIECE - 1u) / (uint32_t)P2F<512, 10>::PIECE;
-        constexpr size_t lds2 = P2F<512, 10>::LDS;
-        hipLaunchKernelGGL((part2f_kernel<512, 10, true>), dim3(G.nblk2, std::min<uint32_t>(nb1, 2048)), dim3(PT_THREADS), lds2, stream, out1, cnt1, P, (uint64_t *)d_send,
-                           (unsigned int *)d_send_cnt, defer_e, defer_n, defer_cap);
-    } else
-    hipLaunchKernelGGL(part2_kernel<true>, dim3(G.nblk2, std::min<uint32_t>(nb1, 2048)), dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, (uint64_t *)d_send,
-                       (unsigned int *)d_send_cnt, defer_e, defer_n, defer_cap, nown);
-    HIPCHK(hipGetLastError());
+    if (const int rc = launch_part2(stream, d, X.G, nown, true, X.out1, X.cnt1, (uint64_t *)d_send, (unsigned int *)d_send_cnt, defer_list(d_defer, defer_cap), err)) return rc;
     HIPCHK(hipEventRecord(ev_stage_t[2], stream));
     return 0;
 }
@@ -2142,10 +2102,9 @@ __global__ __launch_bounds__(DD_TH) void list_dedupe_kernel(uint64_t *__restrict
 
 // 0 done (*max_fill = records in the fullest list now), 1 this geometry has no bits to hold the counts (nothing done)
 int Table::xchg_dedupe(uint64_t piece_max, uint64_t records_max, uint32_t nown, void *d_send, void *d_send_cnt, uint32_t *max_fill, int *cbits_out, std::string &err) {
-    HIPCHK(hipSetDevice(device));
-    PartGeom G;
-    int p2b = 0;
-    if (!xchg_geometry(*this, piece_max, records_max, nown, G, p2b)) { err = "count exchange: no geometry for this table / piece size"; return -1; }
+    XchgCall X;
+    if (const int rc = xchg_begin(*this, piece_max, records_max, nown, false, X, err)) return rc;
+    const PartGeom &G = X.G;
     if (G.p2 < 1) return 1;                                    // (G.p2: the second-level bits the senders resolve)
     const int cbits = std::min(G.p2, 16);
     const uint64_t nlists = ((uint64_t)nown << (G.p1 + G.p2)) * G.nblk2;
@@ -2185,10 +2144,10 @@ __global__ __launch_bounds__(256) void import3_owned_kernel(const unsigned long 
 // everything that goes into this (empty) shard -> the multiplicity histogram is taken on the way out.
 int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piece_max, uint64_t records_max, uint32_t nown, uint32_t self, const void *d_defer_all,
                        uint64_t n_defer_all, int whole_input, uint32_t slice_cap, int cbits, std::string &err) {
-    HIPCHK(hipSetDevice(device));
-    PartGeom G;
-    int p2b = 0;
-    if (!xchg_geometry(*this, piece_max, records_max, nown, G, p2b)) { err = "count exchange: no geometry for this table / piece size"; return -1; }
+    XchgCall X;
+    if (const int rc = xchg_begin(*this, piece_max, records_max, nown, false, X, err)) return rc;
+    PartGeom G = X.G;
+    const int p2b = X.p2b;
     if (read_stats(err)) return -1;
     const uint32_t nregions = 1u << (G.p1 + G.p2 + p2b);
     const bool empty = h_stats[ST_DISTINCT] == 0;
@@ -2197,20 +2156,13 @@ int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piec
     if (histo) HIPCHK(hipMemsetAsync(histo, 0, HISTO_WORDS * sizeof(unsigned long long), stream));
     // (a table that is logically empty is not read: the images start from zeros and every slot is written)
     const bool fresh = slots_dirty || histo != nullptr;
-    const size_t lds = (size_t)(1u << G.rbits) * 16 + LDS_HBINS * 4 + (LI_MAXSL + 1) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(region_insert_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
     // this rank's own deferred list lives in the caller's buffer; the kernel's own overflow (probe beyond the halo) goes to a list of its own
     const uint64_t own_cap = std::max<uint64_t>(1u << 16, piece_max / 16);
     unsigned long long *defer = (unsigned long long *)workspace(WS_COUNT + 3, own_cap * 24 + 64, err);
     if (!defer) return -2;
-    unsigned long long *defer_n = defer, *defer_e = defer + 8;
-    HIPCHK(hipMemsetAsync(defer_n, 0, 64, stream));
-    for (int i = 0; i <= N_STAGES; ++i) if (!ev_stage_t[i]) HIPCHK(hipEventCreate(&ev_stage_t[i]));
+    DeferList D;
+    HIPCHK(defer_list_begin(defer, own_cap, stream, D));
+    HIPCHK(ensure_stage_events(*this));
     count_path = 3;
     part_stage_n = 5;
     HIPCHK(hipEventRecord(ev_stage_t[3], stream));
@@ -2231,31 +2183,15 @@ int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piec
         uint64_t *out2 = (uint64_t *)workspace(WS_XCHG + 1, (size_t)nregions * G2.cap2 * 8, err);
         unsigned int *cnt2 = (unsigned int *)workspace(WS_XCHG + 2, ((size_t)nregions + 4) * 4, err);
         if (!out2 || !cnt2) return -2;
-        static bool attr2_set = false;
-        if (!attr2_set) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(part2_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr2_set = true;
-        }
-        hipLaunchKernelGGL((part2_kernel<false, true>), dim3(1, std::min<uint32_t>(1u << G2.p1, 2048)), dim3(PT_THREADS), P2_LDS, stream, (const uint64_t *)d_recv,
-                           (const unsigned int *)d_recv_cnt, d, G2, out2, cnt2, defer_e, defer_n, own_cap, nown, cbits);
-        HIPCHK(hipGetLastError());
+        HIPCHK((launch_big_lds<part2_kernel<false, true>>(dim3(1, std::min<uint32_t>(1u << G2.p1, 2048)), dim3(PT_THREADS), P2_LDS, stream, (const uint64_t *)d_recv,
+                                                          (const unsigned int *)d_recv_cnt, d, G2, out2, cnt2, D.e, D.n, D.cap, nown, cbits)));
         lists = out2; lcnt = cnt2; lcap = G2.cap2; nsl = 1;
     }
-    {
-        // one launch over all regions (region_insert_kernel: a probe that leaves its region takes the direct path afterwards)
-        const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-        const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>(nregions, 256 * per_cu * 4));
-        const uint32_t nsrc = p2b ? 1u : nown;
-        if (fresh) hipLaunchKernelGGL((region_insert_kernel<true, true>), dim3(nblk), dim3(RI_TH), lds, stream, (const uint64_t *)lists, lcnt, lcap, nsl, d, GI, nregions, defer_e, defer_n,
-                                      own_cap, histo, nsrc, cbits, G.p2);
-        else hipLaunchKernelGGL((region_insert_kernel<false, true>), dim3(nblk), dim3(RI_TH), lds, stream, (const uint64_t *)lists, lcnt, lcap, nsl, d, GI, nregions, defer_e, defer_n,
-                                own_cap, histo, nsrc, cbits, G.p2);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev_stage_t[4], stream));
-        HIPCHK(hipEventRecord(ev_stage_t[5], stream));
-    }
+    HIPCHK(launch_region_insert(stream, d, GI, nregions, lists, lcnt, lcap, nsl, D, histo, fresh, true, p2b ? 1u : nown, cbits, G.p2));
+    HIPCHK(hipEventRecord(ev_stage_t[4], stream));
+    HIPCHK(hipEventRecord(ev_stage_t[5], stream));
     slots_dirty = false;      // every region has been written by the launch above
-    hipLaunchKernelGGL(import3h_kernel, dim3(256), dim3(256), 0, stream, defer_e, defer_n, own_cap, d, histo);      // (keeps the fused histogram exact)
+    hipLaunchKernelGGL(import3h_kernel, dim3(256), dim3(256), 0, stream, D.e, D.n, D.cap, d, histo);      // (keeps the fused histogram exact)
     HIPCHK(hipGetLastError());
     if (n_defer_all) {
         hipLaunchKernelGGL(import3_owned_kernel, dim3(256), dim3(256), 0, stream, (const unsigned long long *)d_defer_all, n_defer_all, d, nown, self, histo ? histo + 10002 : nullptr);

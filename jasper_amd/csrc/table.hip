@@ -891,7 +891,7 @@ int Table::ensure_capacity(uint64_t upcoming_kmers, std::string &err) {
 }
 
 int Table::launch_count(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, std::string &err) {
-    alignas(16) char geom[64];
+    PartGeom geom;
     // the partitioned path streams the whole table once per piece: worth it only for pieces that are large relative
     // to the table (host-staged 64 MiB pieces stay on the direct kernel and are PCIe-bound anyway)
     // break-even measured on MI355X: direct ~18 Gk-mers/s; partitioned ~55 Gk-mers/s for the two list passes plus one

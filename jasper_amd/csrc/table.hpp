@@ -288,6 +288,16 @@ __device__ __forceinline__ u128 encode_padded(int k, long n, Get get) {
     return m;
 }
 
+// geometry of the two list levels of the partitioned counting path (count_part.hip); its kernels take it by value
+struct PartGeom {
+    int p1, p2, rbits;       // p1 + p2 + rbits == s
+    int recbits;             // 2k - p1  (<= 64): bits kept in a record
+    uint32_t nblk1;          // slices per level-1 list: the part1 blocks b, b + nblk1, b + 2 nblk1, ... append to slice b % nblk1 of every list
+    uint32_t grid1;          // part1 blocks
+    uint32_t nblk2;          // part2 blocks per level-1 bucket: every one owns a slice of each of the bucket's region lists
+    uint32_t cap1, cap2;     // slice capacities (records)
+};
+
 // ---- host side ----------------------------------------------------------------------------------
 struct Table {
     int device = 0;
@@ -308,9 +318,9 @@ struct Table {
     uint64_t count_launches = 0;
     void reset_timing() { count_kernel_ms = 0; count_launches = 0; count_partitioned_launches = 0; for (double &m : part_stage_ms) m = 0; }
     int launch_count(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, std::string &err);
-    // partitioned (atomic-free) path, count_part.hip; `geom` is an opaque PartGeom
-    bool partition_geometry(uint64_t piece_bases, void *geom_out) const;
-    int launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const void *geom, std::string &err);
+    // partitioned (atomic-free) path, count_part.hip
+    bool partition_geometry(uint64_t piece_bases, PartGeom &G) const;
+    int launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const PartGeom &G, std::string &err);
     uint64_t count_partitioned_launches = 0;
     static constexpr int N_STAGES = 8;
     hipEvent_t ev_stage_t[N_STAGES + 1] = {};   // stage boundaries of the last partitioned piece
