@@ -305,6 +305,50 @@ void jasper_report_free(jasper_report *r);
 int jasper_spectrum_rows(void);
 int jasper_table_spectrum(jasper_table *reads, jasper_table *assembly, uint64_t *out_cells /* 6 * 10002, row-major */, double *device_seconds);
 
+/* Copy-number scan: WHERE on the sequences the reads support another number of copies than the assembly holds.  Two resident tables of
+ * the same k on the same device -- `reads` (R, whole or attached owner-sharded) and `assembly` (A, a whole table, a different handle from
+ * R; otherwise JASPER_ERR as for jasper_table_spectrum) -- and a set of sequences, scanned densely on the GPU as jasper_kmer_report
+ * scans them, every window looked up in both tables.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  jasper_table_spectrum counts the distinct k-mers
+ * that are collapsed or duplicated; this locates them.  `peak` (>= 1, else JASPER_ERR) is the read count of a k-mer present once in the
+ * genome.  For a sequence of n bytes and the tables' k:
+ *   window i (0 <= i <= n-k)  valid    iff all its k bytes are ACGTacgt (case folded)
+ *                             c        R's count of its canonical k-mer, clamped to 2^32-1
+ *                             a        A's count of it, clamped to 2^32-1 (0 is possible: A need not be counted from this text)
+ *                             e        (2 c + peak) div (2 peak) in 64-bit arithmetic: the copies the reads support, rounded half up
+ *                             excess   (class 1) valid, c >= thre and e > a: the reads support more copies than A holds -- collapsed
+ *                             deficit  (class 2) valid, c >= thre and e < a: A holds more copies than the reads support -- duplicated
+ *                                      or thinly supported
+ *                             class 0  otherwise.  Windows with c < thre are jasper_kmer_report's business; with thre == 0 a valid
+ *                                      window with c == 0 and a >= 1 is `deficit`
+ *   per sequence              six counters: windows, valid, excess, deficit, sum_reads, sum_asm (the sums of c and of a over its valid
+ *                             windows)
+ *   run                       a maximal range of consecutive windows of one sequence with the same non-zero class (a window of another
+ *                             class, an invalid window or the sequence's end ends it; an excess window directly followed by a deficit
+ *                             window gives two runs that touch): first window, windows, sums of c and of a over them, sequence, class
+ * Sequences shorter than k (empty ones too) are legal and give zeros.  Runs are ordered by (seq, start).  Neither table is modified and
+ * the result is the same on every call.  The library sizes its run buffer by itself and repeats the scan once when there were more runs
+ * than it had room for (jasper_copyrep_retried).  Tiles are those of the report (jasper_report_tile_windows()).
+ *   jasper_copy_report         sequences in host memory
+ *   jasper_copy_report_device  sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the tables' device; offsets is a host array of
+ *                              n_seqs+1 entries
+ *   jasper_copyrep_counts      out6 = windows, valid, excess, deficit, sum_reads, sum_asm of one sequence
+ *   jasper_copyrep_runs        the run list (owned by the result)
+ *   jasper_copyrep_seconds     device time of the scan's kernels (HIP events) */
+typedef struct jasper_copyrep jasper_copyrep;
+typedef struct jasper_copy_run { int64_t start; uint64_t n_kmers; uint64_t sum_reads; uint64_t sum_asm; uint32_t seq; uint32_t kind; } jasper_copy_run;
+int jasper_copy_report(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak,
+                       jasper_copyrep **out);
+int jasper_copy_report_device(jasper_table *reads, jasper_table *assembly, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, uint32_t peak,
+                              jasper_copyrep **out);
+int jasper_copyrep_num_seqs(const jasper_copyrep *r);
+int jasper_copyrep_counts(const jasper_copyrep *r, int seq, uint64_t out6[6]);   /* windows, valid, excess, deficit, sum_reads, sum_asm */
+int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, uint64_t *n);
+double jasper_copyrep_seconds(const jasper_copyrep *r);                          /* device time, HIP events */
+int jasper_copyrep_retried(const jasper_copyrep *r);
+void jasper_copyrep_free(jasper_copyrep *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

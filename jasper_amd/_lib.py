@@ -31,6 +31,13 @@ class KmerRun(C.Structure):
 
 assert C.sizeof(KmerRun) == 32
 
+
+class CopyRun(C.Structure):
+    _fields_ = [("start", C.c_int64), ("n_kmers", C.c_uint64), ("sum_reads", C.c_uint64), ("sum_asm", C.c_uint64), ("seq", C.c_uint32), ("kind", C.c_uint32)]
+
+
+assert C.sizeof(CopyRun) == 40
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -115,6 +122,14 @@ SYMBOLS = {
     "jasper_report_free": (None, [_P]),
     "jasper_spectrum_rows": (C.c_int, []),
     "jasper_table_spectrum": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_copy_report": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "jasper_copy_report_device": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "jasper_copyrep_num_seqs": (C.c_int, [_P]),
+    "jasper_copyrep_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_copyrep_runs": (C.c_int, [_P, C.POINTER(C.POINTER(CopyRun)), C.POINTER(C.c_uint64)]),
+    "jasper_copyrep_seconds": (C.c_double, [_P]),
+    "jasper_copyrep_retried": (C.c_int, [_P]),
+    "jasper_copyrep_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

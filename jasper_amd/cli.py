@@ -2,7 +2,7 @@
 sentinel files and log lines; the Jellyfish + per-batch python processes are replaced by the HBM table and the GPU
 polisher.  Lines are cited as src/jasper.sh:N.
 
-    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra]
+    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -100,6 +100,9 @@ class Options:
         self.device = 0
         self.report = False
         self.spectra = False
+        self.copies = False
+        self.peak = None             # --peak: the read count of a single-copy k-mer (default: from the histogram)
+        self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
 
 
 def parse_args(argv):
@@ -144,8 +147,14 @@ def parse_args(argv):
             i += 1
         elif key == "--report":                                        # extension: per-contig k-mer QV and unreliable-k-mer tracks (_report)
             o.report = True
-        elif key == "--spectra":                                       # extension: copy-number k-mer spectrum and completeness (_spectra)
+        elif key == "--spectra":                                       # extension: copy-number k-mer spectrum and completeness (_spectra_copies)
             o.spectra = True
+        elif key == "--copies":                                        # extension: where the assembly is collapsed or duplicated (_spectra_copies)
+            o.copies = True
+        elif key == "--peak":
+            o.peak = nxt; i += 1
+        elif key == "--copies-min-run":
+            o.copies_min_run = nxt; i += 1
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1053,37 +1062,107 @@ def _report(o, table):
         sys.stderr.write("[report] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
 
 
-def assembly_spectrum(table, contigs):
+def assembly_table(table, contigs):
     """the contigs [(name token, sequence)] counted into a second table of their own (sized from their length; the sequences
-    joined by a separator byte, so no k-mer spans two contigs), joined on the GPU with `table`, the reads' -> KmerSpectrum"""
+    joined by a separator byte, so no k-mer spans two contigs) on `table`'s device -> KmerTable, the caller closes it"""
     from .table import KmerTable
     seqs = [s for _, s in contigs]
     asm = KmerTable(table.k, min_slots=max(1 << 16, int(1.25 * sum(len(s) for s in seqs))), device=table.device)
     try:
         asm.count_bases("N".join(seqs))
+    except BaseException:
+        asm.close()
+        raise
+    return asm
+
+
+def assembly_spectrum(table, contigs, asm=None):
+    """the contigs' table (assembly_table; `asm` when the caller has it already and keeps it) joined on the GPU with `table`, the
+    reads' -> KmerSpectrum"""
+    if asm is not None:
+        return table.spectrum(asm)
+    asm = assembly_table(table, contigs)
+    try:
         return table.spectrum(asm)
     finally:
         asm.close()
 
 
-def _spectra(o, table):
-    """--spectra (an extension, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each counted into a
-    second table and joined with the read table while that is still in HBM, into `$QUERY_FN.spectra_cn.{before,after}.tsv` and
-    `$QUERY_FN.completeness.tsv` (jasper_amd/spectra.py).  The threshold for solid k-mers is the polisher's (threshold.txt)."""
-    from . import spectra
+def copies_flags(peak, min_run):
+    """--peak and --copies-min-run as given (None or text) -> (peak or None, min_run or None); exits on anything but integers >= 1"""
+    try:
+        p = None if peak is None else int(peak)
+        m = None if min_run is None else int(min_run)
+        if (p is not None and not 1 <= p <= 0xFFFFFFFF) or (m is not None and m < 1):
+            raise ValueError
+    except ValueError:
+        error_exit("--peak and --copies-min-run take integers of at least 1")
+    return p, m
+
+
+def copies_peak(given, histo, thresh):
+    """the single-copy read count: --peak, or the histogram's (copies.peak_from_histogram); exits when there is neither"""
+    from . import copies
+    if given is not None:
+        return given
+    peak = copies.peak_from_histogram(histo, thresh)
+    if peak is None:
+        error_exit("The k-mer histogram has no peak at or above the threshold %d. Please give the read count of a single-copy k-mer with --peak." % thresh)
+    return peak
+
+
+def scan_copies(table, asm, contigs, thre, peak):
+    """the copy-number scan of whole contigs [(name token, sequence)] -> (names, lengths, CopyReport)"""
+    from . import report
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.copy_report(asm, [s for _, s in contigs], thre, peak)
+
+
+def _spectra_copies(o, table, histo_file):
+    """--spectra and --copies (extensions, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each counted
+    into a second table -- ONCE per stage, it serves both -- while the read table is still in HBM.
+    --spectra: the two tables joined into `$QUERY_FN.spectra_cn.{before,after}.tsv` and `$QUERY_FN.completeness.tsv`
+    (jasper_amd/spectra.py).  --copies: the contigs scanned densely against both tables into `$QUERY_FN.copies.tsv` and
+    `$QUERY_FN.copies.{before,after}.bed` (jasper_amd/copies.py).  The threshold is the polisher's (threshold.txt)."""
+    from . import copies, report, spectra
     qfn, k = o.query_fn, table.k
     thresh = int(open("threshold.txt").read().split()[0])
-    rows, secs = [], []
+    peak = min_run = None
+    if o.copies:
+        given, min_run = copies_flags(o.peak, o.copies_min_run)
+        with open(histo_file) as f:
+            peak = copies_peak(given, copies.histogram_from_rows(ln.split() for ln in f if ln.split()), thresh)
+        min_run = k if min_run is None else min_run
+    rows, secs, scans = [], [], []
     for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta")):
-        spec = assembly_spectrum(table, read_assembly(path))
-        spectra.write_atomic("%s.spectra_cn.%s.tsv" % (qfn, stage), spectra.spectra_cn_text(spec))
-        rows.append(spectra.completeness_row(stage, spec, thresh))
-        secs.append(spec.seconds)
-    spectra.write_atomic(qfn + ".completeness.tsv", spectra.completeness_text(k, rows))
-    for stage, row in zip(("Before", "After"), rows):
-        log("%s Polishing: %s" % (stage, spectra.log_text(row)))
-    if _timing_on():
-        sys.stderr.write("[spectra] device seconds: before %.6f after %.6f\n" % tuple(secs))
+        contigs = read_assembly(path)
+        asm = assembly_table(table, contigs)
+        try:
+            if o.spectra:
+                spec = assembly_spectrum(table, contigs, asm)
+                spectra.write_atomic("%s.spectra_cn.%s.tsv" % (qfn, stage), spectra.spectra_cn_text(spec))
+                rows.append(spectra.completeness_row(stage, spec, thresh))
+                secs.append(spec.seconds)
+            if o.copies:
+                scans.append(scan_copies(table, asm, contigs, thresh, peak))
+        finally:
+            asm.close()
+    if o.spectra:
+        spectra.write_atomic(qfn + ".completeness.tsv", spectra.completeness_text(k, rows))
+        for stage, row in zip(("Before", "After"), rows):
+            log("%s Polishing: %s" % (stage, spectra.log_text(row)))
+        if _timing_on():
+            sys.stderr.write("[spectra] device seconds: before %.6f after %.6f\n" % tuple(secs))
+    if o.copies:
+        (names, len0, rep0), (names1, len1, rep1) = scans
+        len1a, cnt1a = report.align(names, names1, len1, rep1.counts)
+        copies.write_atomic(qfn + ".copies.tsv", copies.copies_tsv_text(peak, names, [("before", len0, rep0.counts), ("after", len1a, cnt1a)]))
+        copies.write_atomic(qfn + ".copies.before.bed", copies.bed_text(k, peak, names, rep0.runs, min_run))
+        copies.write_atomic(qfn + ".copies.after.bed", copies.bed_text(k, peak, names1, rep1.runs, min_run))
+        log(copies.peak_log_text(peak, o.peak is not None))
+        log("Copy-number scan: before polishing %s; after polishing %s" % (copies.stage_log_text(rep0.counts, len(copies.listed(rep0.runs, min_run))),
+                                                                           copies.stage_log_text(cnt1a, len(copies.listed(rep1.runs, min_run)))))
+        if _timing_on():
+            sys.stderr.write("[copies] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
 
 
 def _init_multi(o):
@@ -1117,6 +1196,8 @@ def run(argv):
         sys.stderr.write("[timing-abs] run() entered at %.6f\n" % time.time())
     o = parse_args(argv)
     ranks = _Ranks(*_init_multi(o))
+    if o.copies:
+        copies_flags(o.peak, o.copies_min_run)      # (a bad value ends the run before it starts, not after the polishing)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
@@ -1198,10 +1279,11 @@ def run(argv):
         # that precedes detach (unmeasured over RCCL, like everything multi-GPU here)
         ranks.together((lambda: _report(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
         _timing("k-mer report")
-    if o.spectra:
-        # as for --report: rank 0 alone, its sweeps go over every owner's shard of the attached table
-        ranks.together((lambda: _spectra(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer spectrum failed")
-        _timing("k-mer spectrum")
+    if o.spectra or o.copies:
+        # as for --report: rank 0 alone, its sweeps and scans go through every owner's shard of the attached table
+        ranks.together((lambda: _spectra_copies(o, table, histo_file)) if ranks.is0 else (lambda: None),
+                       "Writing the k-mer spectrum failed" if not o.copies else "Writing the copy-number scan failed")
+        _timing("k-mer spectrum" if not o.copies else "k-mer spectrum + copy-number scan" if o.spectra else "copy-number scan")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

@@ -8,6 +8,7 @@
 #include "asmio.hpp"
 #include "report.hpp"
 #include "spectra.hpp"
+#include "copies.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -44,6 +45,9 @@ struct jasper_result {
 
 static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record layouts must match");
 
+struct jasper_copyrep {
+    CopyOut r;
+};
 struct jasper_report {
     ReportOut r;
 };
@@ -773,5 +777,44 @@ int jasper_table_spectrum(jasper_table *reads, jasper_table *assembly, uint64_t 
     if (!reads || !assembly || !out_cells) { g_err = "bad argument"; return JASPER_ERR; }
     return table_spectrum(reads->t, assembly->t, out_cells, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
 }
+
+// ---- copy-number scan (copies.hip) ----
+static_assert(sizeof(jasper_copy_run) == sizeof(CopyRun), "jasper_copy_run is CopyRun");
+static int copyrep_call(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets,
+                        uint32_t thre, uint32_t peak, jasper_copyrep **out) {
+    if (!reads || !assembly || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_copyrep *r = new jasper_copyrep();
+    const int rc = d_text || offsets ? copies_report_device(reads->t, assembly->t, n_seqs, (const uint8_t *)d_text, offsets, thre, peak, r->r, g_err)
+                                     : copies_report_host(reads->t, assembly->t, n_seqs, seqs, lens, thre, peak, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_copy_report(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak,
+                       jasper_copyrep **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return copyrep_call(reads, assembly, n_seqs, seqs, lens, nullptr, nullptr, thre, peak, out);
+}
+int jasper_copy_report_device(jasper_table *reads, jasper_table *assembly, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, uint32_t peak,
+                              jasper_copyrep **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return copyrep_call(reads, assembly, n_seqs, nullptr, nullptr, d_text, offsets, thre, peak, out);
+}
+int jasper_copyrep_num_seqs(const jasper_copyrep *r) { return r ? (int)(r->r.counts.size() / 6) : 0; }
+int jasper_copyrep_counts(const jasper_copyrep *r, int seq, uint64_t out6[6]) {
+    if (!r || !out6 || seq < 0 || (size_t)seq >= r->r.counts.size() / 6) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 6; ++i) out6[i] = r->r.counts[6 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, uint64_t *n) {
+    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *runs = reinterpret_cast<const jasper_copy_run *>(r->r.runs.data());
+    *n = r->r.runs.size();
+    return JASPER_OK;
+}
+double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
+int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
+void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
 
 }  // extern "C"

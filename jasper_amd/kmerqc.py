@@ -1,6 +1,7 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
+                                [--copies [--peak N] [--copies-min-run N]]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -15,29 +16,37 @@ With --spectra the assembly's contigs are also counted into a second table and j
     PREFIX.spectra_cn.tsv    distinct k-mers by copies in the assembly and count in the reads
     PREFIX.completeness.tsv  one row of stage `asm`: the share of the reads' solid k-mers the assembly holds, assembly-only k-mers
 
+With --copies the contigs are also scanned against both tables (KmerTable.copy_report; the assembly's table is counted once
+and serves --spectra too), and two more files are written (jasper_amd/copies.py):
+
+    PREFIX.copies.tsv        per contig one row of stage `asm`: excess / deficit windows, the two sums, depth; then contig `*`
+    PREFIX.copies.bed        one line per run of excess or deficit windows of at least --copies-min-run (default k) windows
+
+--peak is the read count of a single-copy k-mer; the default is the highest bin of the histogram at or above the threshold.
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 """
 import os
 import sys
 
-from . import cli, polisher, report, spectra
+from . import cli, copies, polisher, report, spectra
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
-            "--threshold": "threshold", "-o": "prefix", "--device": "device"}
+            "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run"}
     i = 0
     while i < len(argv):
         key = argv[i]
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key == "--spectra":
-            o["spectra"] = True
+        if key in ("--spectra", "--copies"):
+            o[key[2:]] = True
             i += 1
             continue
         if key not in keys or i + 1 >= len(argv):
@@ -61,6 +70,7 @@ def run(argv):
             raise ValueError
     except ValueError:
         cli.error_exit("-k, --threshold and --device take non-negative integers (k at least 1)")
+    peak, min_run = cli.copies_flags(a["peak"], a["min_run"]) if a["copies"] else (None, None)
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
@@ -80,9 +90,19 @@ def run(argv):
             cli.error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable; give --threshold.")
         given = int(txt.split()[0])
     cli.log("Lower threshold for unreliable kmers is %d" % given)
+    if a["copies"]:
+        peak = cli.copies_peak(peak, copies.histogram_from_rows(table.histo_rows()), given)
+        min_run = k if min_run is None else min_run
     contigs = cli.read_assembly(a["asm"])
     names, lengths, rep = cli.scan_contigs(table, contigs, given)
-    spec = cli.assembly_spectrum(table, contigs) if a["spectra"] else None
+    spec = crep = None
+    if a["spectra"] or a["copies"]:
+        asm = cli.assembly_table(table, contigs)          # counted once, it serves both
+        try:
+            spec = cli.assembly_spectrum(table, contigs, asm) if a["spectra"] else None
+            crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
+        finally:
+            asm.close()
     table.close()
     prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
     report.write_atomic(prefix + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("asm", lengths, rep.counts)]))
@@ -95,6 +115,10 @@ def run(argv):
         spectra.write_atomic(prefix + ".spectra_cn.tsv", spectra.spectra_cn_text(spec))
         spectra.write_atomic(prefix + ".completeness.tsv", spectra.completeness_text(k, [row]))
         cli.log("Assembly: %s" % spectra.log_text(row))
+    if crep is not None:
+        copies.write_atomic(prefix + ".copies.tsv", copies.copies_tsv_text(peak, names, [("asm", lengths, crep.counts)]))
+        copies.write_atomic(prefix + ".copies.bed", copies.bed_text(k, peak, names, crep.runs, min_run))
+        cli.log("Copy-number scan: peak %d; %s in %s.copies.bed" % (peak, copies.stage_log_text(crep.counts, len(copies.listed(crep.runs, min_run))), prefix))
     return 0
 
 

@@ -137,8 +137,40 @@ class KmerSpectrum:
         return isinstance(other, KmerSpectrum) and self.cells.shape == other.cells.shape and bool((self.cells == other.cells).all())
 
 
+COPYRUN_DTYPE = [("start", "<i8"), ("n_kmers", "<u8"), ("sum_reads", "<u8"), ("sum_asm", "<u8"), ("seq", "<u4"), ("kind", "<u4")]
+COPY_KINDS = {1: "excess", 2: "deficit"}
+
+
+class CopyReport:
+    """copy-number scan of a set of sequences against the reads' table and the assembly's (include/jasper_hip.h:
+    jasper_copy_report): `counts[i]` = (windows, valid, excess, deficit, sum_reads, sum_asm) of sequence i, `runs` = numpy
+    structured array (COPYRUN_DTYPE) of the maximal runs of one class (kind 1 = excess, 2 = deficit) ordered by (seq, start),
+    `seconds` = device time of the kernels.  The files made from it: jasper_amd/copies.py."""
+
+    def __init__(self, counts, runs, seconds, retried):
+        self.counts = counts
+        self.runs = runs
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, CopyReport) and self.counts == other.counts and self.runs.tobytes() == other.runs.tobytes()
+
+    def run_tuples(self):
+        """[(seq, start, n_kmers, kind, sum_reads, sum_asm)]"""
+        return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"]), int(r["sum_asm"])) for r in self.runs]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
+
+
+def _peak32(peak):
+    """peak as the C-ABI's uint32 (a value outside its range is an error here, not a silent wrap)"""
+    p = int(peak)
+    if p < 0 or p > 0xFFFFFFFF:
+        raise ValueError("peak must be in [1, 2^32-1]")
+    return p
 
 
 class KmerTable:
@@ -529,6 +561,57 @@ class KmerTable:
         secs = C.c_double(0)
         check(self._L.jasper_table_spectrum(self._h, assembly_table._h, cells.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(secs)))
         return KmerSpectrum(cells, secs.value)
+
+    # ---- copy-number scan (an extension: no counterpart in the reference) ---------------------------------
+    def _assembly_handle(self, assembly_table, what):
+        if not isinstance(assembly_table, KmerTable) or not assembly_table._h:
+            raise TypeError("%s: the assembly must be an open KmerTable" % what)
+        return assembly_table._h
+
+    def copy_report(self, assembly_table, seqs, thre, peak):
+        """this table as the reads' counts, `assembly_table` the assembly's (a whole KmerTable of the same k on the same device):
+        per-sequence counters and the runs of windows whose read count supports more (excess) or fewer (deficit) copies than the
+        assembly holds, `peak` = the read count of a single-copy k-mer -> CopyReport; neither table is modified"""
+        ah = self._assembly_handle(assembly_table, "copy_report")
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = self._L.jasper_copy_report(self._h, ah, n, cs, lens, int(thre), _peak32(peak), C.byref(res))
+        return self._wrap_copyrep(rc, res)
+
+    def copy_report_device(self, assembly_table, d_text, offsets, thre, peak):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        ah = self._assembly_handle(assembly_table, "copy_report_device")
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_copy_report_device(self._h, ah, n, C.c_void_p(ptr), offs, int(thre), _peak32(peak), C.byref(res))
+        return self._wrap_copyrep(rc, res)
+
+    def _wrap_copyrep(self, rc, res):
+        try:
+            check(rc)
+            import numpy as np
+            counts = []
+            c6 = (C.c_uint64 * 6)()
+            for i in range(self._L.jasper_copyrep_num_seqs(res)):
+                check(self._L.jasper_copyrep_counts(res, i, c6))
+                counts.append(tuple(int(v) for v in c6))
+            rp = C.POINTER(_lib.CopyRun)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_copyrep_runs(res, C.byref(rp), C.byref(rn)))
+            if rn.value:
+                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.CopyRun)), dtype=COPYRUN_DTYPE).copy()
+            else:
+                runs = np.zeros(0, dtype=COPYRUN_DTYPE)
+            return CopyReport(counts, runs, self._L.jasper_copyrep_seconds(res), bool(self._L.jasper_copyrep_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_copyrep_free(res)
 
     def _wrap_report(self, rc, res):
         try:
