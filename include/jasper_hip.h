@@ -349,6 +349,50 @@ double jasper_copyrep_seconds(const jasper_copyrep *r);                         
 int jasper_copyrep_retried(const jasper_copyrep *r);
 void jasper_copyrep_free(jasper_copyrep *r);
 
+/* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
+ * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
+ * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.
+ *
+ * What it replaces: nothing -- this is an EXTENSION.  The reference meets the situation inside its walk (src/jasper.py: fixdiploid,
+ * fix_k_case_sub), acts on it there and reports nothing.  For a sequence s of n bytes (case folded), the table's k and thre >= 1
+ * (thre == 0 is JASPER_ERR):
+ *   position p  evaluated  iff k-1 <= p <= n-k and all 2k-1 bytes s[p-k+1 .. p+k-1] are ACGTacgt: the k windows that cover p all exist and
+ *                          are valid
+ *   m(p, x)                for a base x: the minimum over those k windows of the table's count of the window's canonical k-mer with byte p
+ *                          replaced by x, counts clamped to 2^32-1 as jasper_lookup clamps them
+ *   ref, ref_min           the folded s[p], m(p, ref)
+ *   record                 for every x != ref with m(p, x) >= thre one {seq, pos = p, ref, alt = x, ref_min, alt_min = m(p, x), kind}:
+ *                          kind het (1) when ref_min >= thre -- both alleles are solid; kind error (2) when ref_min < thre -- only the
+ *                          alternative is solid, a substitution that has not been made
+ *   per sequence           three counters: evaluated positions, het records, error records
+ * Records are ordered by (seq, pos, alt in A < C < G < T order); the key is unique, so the list is identical on every call.  Sequences
+ * shorter than 2k-1 (empty ones too) are legal and give zeros.  The table is not modified.
+ *
+ * Limits: only ISOLATED substitutions are reported.  Two differences less than k apart hide each other, because every window that covers
+ * one of them holds the other allele of the other.  Insertions and deletions are not reported.
+ *
+ * On the device a dense scan probes, per window, the window's last base replaced by each of the other three; a solid one makes the
+ * window's end a candidate (a necessary condition: one of the k terms of m), and a second kernel checks each candidate's k windows.  The
+ * library sizes the candidate list by itself and repeats the scan once when there were more (jasper_varscan_retried).
+ *   jasper_variant_scan         sequences in host memory
+ *   jasper_variant_scan_device  sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the table's device; offsets is a host array of
+ *                               n_seqs+1 entries
+ *   jasper_varscan_counts       out3 = evaluated, het, error of one sequence
+ *   jasper_varscan_records      the record list (owned by the result); ref / alt are the letters 'A', 'C', 'G', 'T'
+ *   jasper_varscan_candidates   what the dense scan handed to the check (>= records)
+ *   jasper_varscan_seconds      device time of the scan's kernels (HIP events) */
+typedef struct jasper_varscan jasper_varscan;
+typedef struct jasper_variant { int64_t pos; uint32_t seq, ref_min, alt_min; uint8_t ref, alt, kind, pad; } jasper_variant; /* 24 B; ref/alt = 'A','C','G','T' */
+int jasper_variant_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_varscan **out);
+int jasper_variant_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_varscan **out);
+int jasper_varscan_num_seqs(const jasper_varscan *r);
+int jasper_varscan_counts(const jasper_varscan *r, int seq, uint64_t out3[3]);   /* evaluated, het, error */
+int jasper_varscan_records(const jasper_varscan *r, const jasper_variant **recs, uint64_t *n);
+int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n);             /* what the dense scan handed to the check */
+double jasper_varscan_seconds(const jasper_varscan *r);                          /* device time, HIP events */
+int jasper_varscan_retried(const jasper_varscan *r);
+void jasper_varscan_free(jasper_varscan *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

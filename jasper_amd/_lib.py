@@ -38,6 +38,14 @@ class CopyRun(C.Structure):
 
 assert C.sizeof(CopyRun) == 40
 
+
+class Variant(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8),
+                ("kind", C.c_uint8), ("pad", C.c_uint8)]
+
+
+assert C.sizeof(Variant) == 24
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -130,6 +138,15 @@ SYMBOLS = {
     "jasper_copyrep_seconds": (C.c_double, [_P]),
     "jasper_copyrep_retried": (C.c_int, [_P]),
     "jasper_copyrep_free": (None, [_P]),
+    "jasper_variant_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
+    "jasper_variant_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
+    "jasper_varscan_num_seqs": (C.c_int, [_P]),
+    "jasper_varscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_varscan_records": (C.c_int, [_P, C.POINTER(C.POINTER(Variant)), C.POINTER(C.c_uint64)]),
+    "jasper_varscan_candidates": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_varscan_seconds": (C.c_double, [_P]),
+    "jasper_varscan_retried": (C.c_int, [_P]),
+    "jasper_varscan_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -2,7 +2,7 @@
 sentinel files and log lines; the Jellyfish + per-batch python processes are replaced by the HBM table and the GPU
 polisher.  Lines are cited as src/jasper.sh:N.
 
-    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]]
+    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -103,6 +103,7 @@ class Options:
         self.copies = False
         self.peak = None             # --peak: the read count of a single-copy k-mer (default: from the histogram)
         self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
+        self.variants = False
 
 
 def parse_args(argv):
@@ -155,6 +156,8 @@ def parse_args(argv):
             o.peak = nxt; i += 1
         elif key == "--copies-min-run":
             o.copies_min_run = nxt; i += 1
+        elif key == "--variants":                                      # extension: heterozygous and unpolished substitution sites (_variants)
+            o.variants = True
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1165,6 +1168,34 @@ def _spectra_copies(o, table, histo_file):
             sys.stderr.write("[copies] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
 
 
+def scan_variants(table, contigs, thre):
+    """the variant scan of whole contigs [(name token, sequence)] -> (names, lengths, VariantScan); exits on a threshold of 0, which
+    would call every alternative solid"""
+    from . import report
+    if thre < 1:
+        error_exit("--variants needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.variant_scan([s for _, s in contigs], thre)
+
+
+def _variants(o, table):
+    """--variants (an extension, no counterpart in src/jasper.sh): the input assembly's contigs and the polished contigs scanned
+    through the read table while it is still in HBM for positions where the reads hold a solid single-base alternative, into
+    `$QUERY_FN.variants.tsv` and `$QUERY_FN.variants.{before,after}.vcf` (jasper_amd/variants.py) -- `before` in the input's
+    coordinates, `after` in the polished FASTA's.  The threshold is the polisher's (threshold.txt)."""
+    from . import report, variants
+    qfn, k = o.query_fn, table.k
+    thresh = int(open("threshold.txt").read().split()[0])
+    names, len0, vs0 = scan_variants(table, read_assembly(o.query), thresh)
+    names1, len1, vs1 = scan_variants(table, read_assembly(qfn + ".polished.fasta"), thresh)
+    len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
+    variants.write_atomic(qfn + ".variants.tsv", variants.variants_tsv_text(names, [("before", len0, vs0.counts), ("after", len1a, cnt1a)]))
+    variants.write_atomic(qfn + ".variants.before.vcf", variants.vcf_text(k, thresh, names, len0, vs0.records))
+    variants.write_atomic(qfn + ".variants.after.vcf", variants.vcf_text(k, thresh, names1, len1, vs1.records))
+    log(variants.log_text(vs0.counts, cnt1a))
+    if _timing_on():
+        sys.stderr.write("[variants] device seconds: before %.6f after %.6f; candidates %d %d\n" % (vs0.seconds, vs1.seconds, vs0.candidates, vs1.candidates))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1284,6 +1315,10 @@ def run(argv):
         ranks.together((lambda: _spectra_copies(o, table, histo_file)) if ranks.is0 else (lambda: None),
                        "Writing the k-mer spectrum failed" if not o.copies else "Writing the copy-number scan failed")
         _timing("k-mer spectrum" if not o.copies else "k-mer spectrum + copy-number scan" if o.spectra else "copy-number scan")
+    if o.variants:
+        # as for --report: rank 0 alone, through every owner's shard of the attached table
+        ranks.together((lambda: _variants(o, table)) if ranks.is0 else (lambda: None), "Writing the variant scan failed")
+        _timing("variant scan")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

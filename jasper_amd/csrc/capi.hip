@@ -9,6 +9,7 @@
 #include "report.hpp"
 #include "spectra.hpp"
 #include "copies.hpp"
+#include "variants.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -47,6 +48,9 @@ static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record
 
 struct jasper_copyrep {
     CopyOut r;
+};
+struct jasper_varscan {
+    VariantOut r;
 };
 struct jasper_report {
     ReportOut r;
@@ -816,5 +820,47 @@ int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, u
 double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
 int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
 void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
+
+// ---- variant scan (variants.hip) ----
+static_assert(sizeof(jasper_variant) == sizeof(Variant), "jasper_variant is Variant");
+static int varscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
+                        jasper_varscan **out) {
+    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_varscan *r = new jasper_varscan();
+    const int rc = d_text || offsets ? variant_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r->r, g_err)
+                                     : variant_scan_host(t->t, n_seqs, seqs, lens, thre, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_variant_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_varscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return varscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, out);
+}
+int jasper_variant_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_varscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return varscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, out);
+}
+int jasper_varscan_num_seqs(const jasper_varscan *r) { return r ? (int)(r->r.counts.size() / 3) : 0; }
+int jasper_varscan_counts(const jasper_varscan *r, int seq, uint64_t out3[3]) {
+    if (!r || !out3 || seq < 0 || (size_t)seq >= r->r.counts.size() / 3) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 3; ++i) out3[i] = r->r.counts[3 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_varscan_records(const jasper_varscan *r, const jasper_variant **recs, uint64_t *n) {
+    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *recs = reinterpret_cast<const jasper_variant *>(r->r.recs.data());
+    *n = r->r.recs.size();
+    return JASPER_OK;
+}
+int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n) {
+    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = r->r.candidates;
+    return JASPER_OK;
+}
+double jasper_varscan_seconds(const jasper_varscan *r) { return r ? r->r.seconds : 0.0; }
+int jasper_varscan_retried(const jasper_varscan *r) { return r ? r->r.retried : 0; }
+void jasper_varscan_free(jasper_varscan *r) { delete r; }
 
 }  // extern "C"

@@ -355,7 +355,8 @@ struct Table {
                          WS_REPORT = WS_GZ + 5,                                          // the dense k-mer report's buffers (report.hip)
                          WS_SPECTRA = WS_REPORT + 8,                                     // the copy-number spectrum's matrix (spectra.hip)
                          WS_COPIES = WS_SPECTRA + 1,                                     // the copy-number scan's buffers (copies.hip)
-                         WS_SLOTS = WS_COPIES + 8;
+                         WS_VARIANTS = WS_COPIES + 8,                                    // the variant scan's buffers (variants.hip)
+                         WS_SLOTS = WS_VARIANTS + 8;
     WsBuf ws[WS_SLOTS];   // 0..WS_POLISH_MAX-1: polisher (polish_host.hip, in allocation order); WS_COUNT..+3: partitioned counting
     hipStream_t polish_stream[POLISH_LANES_MAX] = {nullptr, nullptr, nullptr, nullptr};      // [0] unused (= stream); created on first use
     hipEvent_t polish_ev = nullptr;

@@ -1,7 +1,7 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
-                                [--copies [--peak N] [--copies-min-run N]]
+                                [--copies [--peak N] [--copies-min-run N]] [--variants]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -24,19 +24,25 @@ and serves --spectra too), and two more files are written (jasper_amd/copies.py)
 
 --peak is the read count of a single-copy k-mer; the default is the highest bin of the histogram at or above the threshold.
 
+With --variants the contigs are also scanned for positions where the reads hold a solid single-base alternative
+(KmerTable.variant_scan), and two more files are written (jasper_amd/variants.py); the threshold must be at least 1:
+
+    PREFIX.variants.tsv      per contig one row of stage `asm`: evaluated positions, het and error sites, het per kb; then contig `*`
+    PREFIX.variants.vcf      VCFv4.2, one line per site: KIND=het (both alleles solid) or error (only the alternative is)
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 """
 import os
 import sys
 
-from . import cli, copies, polisher, report, spectra
+from . import cli, copies, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run"}
     i = 0
@@ -45,7 +51,7 @@ def parse_args(argv):
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies"):
+        if key in ("--spectra", "--copies", "--variants"):
             o[key[2:]] = True
             i += 1
             continue
@@ -71,6 +77,8 @@ def run(argv):
     except ValueError:
         cli.error_exit("-k, --threshold and --device take non-negative integers (k at least 1)")
     peak, min_run = cli.copies_flags(a["peak"], a["min_run"]) if a["copies"] else (None, None)
+    if a["variants"] and given is not None and given < 1:
+        cli.error_exit("--variants needs a threshold of at least 1; --threshold %d was given" % given)
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
@@ -103,6 +111,7 @@ def run(argv):
             crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
         finally:
             asm.close()
+    vscan = cli.scan_variants(table, contigs, given)[2] if a["variants"] else None
     table.close()
     prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
     report.write_atomic(prefix + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("asm", lengths, rep.counts)]))
@@ -119,6 +128,10 @@ def run(argv):
         copies.write_atomic(prefix + ".copies.tsv", copies.copies_tsv_text(peak, names, [("asm", lengths, crep.counts)]))
         copies.write_atomic(prefix + ".copies.bed", copies.bed_text(k, peak, names, crep.runs, min_run))
         cli.log("Copy-number scan: peak %d; %s in %s.copies.bed" % (peak, copies.stage_log_text(crep.counts, len(copies.listed(crep.runs, min_run))), prefix))
+    if vscan is not None:
+        variants.write_atomic(prefix + ".variants.tsv", variants.variants_tsv_text(names, [("asm", lengths, vscan.counts)]))
+        variants.write_atomic(prefix + ".variants.vcf", variants.vcf_text(k, given, names, lengths, vscan.records))
+        cli.log("Variant scan: %s in %s.variants.vcf" % (variants.stage_log_text(vscan.counts), prefix))
     return 0
 
 

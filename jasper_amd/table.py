@@ -161,6 +161,32 @@ class CopyReport:
         return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"]), int(r["sum_asm"])) for r in self.runs]
 
 
+VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
+VARIANT_KINDS = {1: "het", 2: "error"}
+
+
+class VariantScan:
+    """variant scan of a set of sequences against the reads' table (include/jasper_hip.h: jasper_variant_scan): `counts[i]` =
+    (evaluated, het, error) of sequence i, `records` = numpy structured array (VARIANT_DTYPE) of the substitution sites (kind 1 =
+    het, 2 = error; ref / alt are the letters' byte values) ordered by (seq, pos, alt), `candidates` = what the dense scan handed
+    to the check, `seconds` = device time of the kernels.  The files made from it: jasper_amd/variants.py."""
+
+    def __init__(self, counts, records, candidates, seconds, retried):
+        self.counts = counts
+        self.records = records
+        self.candidates = candidates
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return (isinstance(other, VariantScan) and self.counts == other.counts and self.candidates == other.candidates
+                and self.records.tobytes() == other.records.tobytes())
+
+    def record_tuples(self):
+        """[(seq, pos, ref, alt, ref_min, alt_min, kind)], ref and alt as one-letter strings"""
+        return [(int(r["seq"]), int(r["pos"]), chr(int(r["ref"])), chr(int(r["alt"])), int(r["ref_min"]), int(r["alt_min"]), int(r["kind"])) for r in self.records]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -612,6 +638,51 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_copyrep_free(res)
+
+    # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
+    def variant_scan(self, seqs, thre):
+        """the positions of the sequences where the reads hold a solid single-base alternative (count of all k covering windows
+        >= thre >= 1) -> VariantScan; the table is not modified"""
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = self._L.jasper_variant_scan(self._h, n, cs, lens, int(thre), C.byref(res))
+        return self._wrap_varscan(rc, res)
+
+    def variant_scan_device(self, d_text, offsets, thre):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_variant_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), C.byref(res))
+        return self._wrap_varscan(rc, res)
+
+    def _wrap_varscan(self, rc, res):
+        try:
+            check(rc)
+            import numpy as np
+            counts = []
+            c3 = (C.c_uint64 * 3)()
+            for i in range(self._L.jasper_varscan_num_seqs(res)):
+                check(self._L.jasper_varscan_counts(res, i, c3))
+                counts.append(tuple(int(v) for v in c3))
+            rp = C.POINTER(_lib.Variant)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_varscan_records(res, C.byref(rp), C.byref(rn)))
+            if rn.value:
+                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Variant)), dtype=VARIANT_DTYPE).copy()
+            else:
+                recs = np.zeros(0, dtype=VARIANT_DTYPE)
+            nc = C.c_uint64(0)
+            check(self._L.jasper_varscan_candidates(res, C.byref(nc)))
+            return VariantScan(counts, recs, int(nc.value), self._L.jasper_varscan_seconds(res), bool(self._L.jasper_varscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_varscan_free(res)
 
     def _wrap_report(self, rc, res):
         try:
