@@ -369,7 +369,8 @@ void jasper_copyrep_free(jasper_copyrep *r);
  * shorter than 2k-1 (empty ones too) are legal and give zeros.  The table is not modified.
  *
  * Limits: only ISOLATED substitutions are reported.  Two differences less than k apart hide each other, because every window that covers
- * one of them holds the other allele of the other.  Insertions and deletions are not reported.
+ * one of them holds the other allele of the other.  Insertions and deletions are not reported here: jasper_indel_scan below lists
+ * them (same-base insertions and any deletion of up to 16 bytes) from the same dense scan, together with everything this call returns.
  *
  * On the device a dense scan probes, per window, the window's last base replaced by each of the other three; a solid one makes the
  * window's end a candidate (a necessary condition: one of the k terms of m), and a second kernel checks each candidate's k windows.  The
@@ -392,6 +393,69 @@ int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n);            
 double jasper_varscan_seconds(const jasper_varscan *r);                          /* device time, HIP events */
 int jasper_varscan_retried(const jasper_varscan *r);
 void jasper_varscan_free(jasper_varscan *r);
+
+/* Indel scan: WHERE on the sequences the reads hold a solid insertion or deletion against the sequence -- a length difference between the
+ * haplotypes of a diploid genome, or a length error the polisher has not repaired.  The length-changing half of the variant scan: the
+ * same table (whole, wide, or attached owner-sharded), the same dense scan, and a result that also holds what jasper_variant_scan returns.
+ *
+ * What it replaces: nothing -- this is an EXTENSION.  The reference repairs such differences inside its walk (src/jasper.py: fix_insert,
+ * fix_del, fix_same_base_del, fix_same_base_insertion) and reports nothing.  For a sequence s of n bytes (case folded), the table's
+ * k >= 2, thre >= 1 and max_len in 1..16 (anything else is JASPER_ERR with a message that names the argument, even with nothing to scan);
+ * F = s[p-k+1 .. p-1], the k-1 bytes before p; cnt() = the table's count of a canonical k-mer, clamped to 2^32-1 as jasper_lookup clamps:
+ *   ins(p, x, L)   for 1 <= L <= max_len and a base x != s[p]: the reads hold x repeated L times between bytes p-1 and p.
+ *                  evaluated  iff k-1 <= p <= n-k+1 and all bytes s[p-k+1 .. p+k-2] are ACGTacgt
+ *                  alt_min    the minimum of cnt over the k+L-1 windows of  A = F + x^L + s[p .. p+k-2]
+ *                  ref_min    the minimum of cnt over the k-1 windows of s that start at p-k+1 .. p-1 (those that hold s[p-1] and s[p])
+ *                  Only same-base insertions are in scope (what fix_same_base_del repairs); because x != s[p] each has exactly one
+ *                  representation, the right-most one.
+ *   del(p, L)      for 1 <= L <= max_len and s[p+L] != s[p]; x = s[p+L]: the reads lack s[p .. p+L-1] (any deleted string).
+ *                  evaluated  iff k-1 <= p, p+L+k-2 <= n-1 and all bytes s[p-k+1 .. p+L+k-2] are bases
+ *                  alt_min    the minimum of cnt over the k-1 windows of  A = F + s[p+L .. p+L+k-2]
+ *                  ref_min    the minimum of cnt over the k+L-1 windows of s that start at p-k+1 .. p+L-1 (those that hold a deleted byte)
+ *                  s[p+L] != s[p] is right-normalisation again.
+ *   record         a hypothesis that is evaluated and has alt_min >= thre gives one {seq, pos = p, type, len = L, base = x, ref_min,
+ *                  alt_min, kind}: kind het (1) when ref_min >= thre, error (2) otherwise, as for substitutions.  Hypotheses are
+ *                  independent: a substitution, an insertion and several deletions at one p can all be records (low-complexity sequence).
+ *   per sequence   four counters: ins_het, ins_error, del_het, del_error
+ * Records are ordered by (seq, pos, type, len, base); the key is unique, so the list is identical on every call.  Sequences shorter than
+ * 2k-2 (empty ones too) are legal and give zeros.  The table is not modified.
+ *
+ * Limits: insertions of mixed bases and lengths above 16 are not reported, and, as for substitutions, two differences less than k apart
+ * hide each other.
+ *
+ * On the device the variant scan's dense scan runs unchanged: its candidate (p, x) -- the window that ends at p is solid with its last
+ * base replaced by x -- is the first k-mer of A for ins(p, x, L) and for del(p, L) with s[p+L] == x.  One more kernel tests these
+ * hypotheses per candidate, then the substitution check runs over the same candidates.  The record list can hold more records than there
+ * are candidates; the library sizes it by itself and repeats the indel check (not the scan) once when there were more
+ * (jasper_indelscan_retried).
+ *   jasper_indel_scan              sequences in host memory
+ *   jasper_indel_scan_device       sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the table's device; offsets is a host array of
+ *                                  n_seqs+1 entries
+ *   jasper_indelscan_counts        out4 = ins_het, ins_error, del_het, del_error of one sequence
+ *   jasper_indelscan_records       the record list (owned by the result)
+ *   jasper_indelscan_variants      the substitution result, owned by the indel result (do not free it): counts, records and candidates
+ *                                  equal those of jasper_variant_scan on the same input
+ *   jasper_indelscan_seconds       device time of the scan and all check kernels (HIP events)
+ *   jasper_indelscan_check_seconds ... of the indel check alone
+ *   jasper_indelscan_lookups       table lookups the indel check made (for measurements: time per lookup) */
+typedef struct jasper_indelscan jasper_indelscan;
+typedef struct jasper_indel {
+    int64_t pos;
+    uint32_t seq, ref_min, alt_min;
+    uint16_t len;
+    uint8_t type /* 1 ins, 2 del */, base /* 'A','C','G','T': x */, kind /* 1 het, 2 error */, pad[7] /* 0 */;
+} jasper_indel; /* 32 B */
+int jasper_indel_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out);
+int jasper_indel_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out);
+int jasper_indelscan_num_seqs(const jasper_indelscan *r);
+int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]);   /* ins_het, ins_error, del_het, del_error */
+int jasper_indelscan_records(const jasper_indelscan *r, const jasper_indel **recs, uint64_t *n);
+const jasper_varscan *jasper_indelscan_variants(const jasper_indelscan *r);
+double jasper_indelscan_seconds(const jasper_indelscan *r);                         /* device time, HIP events */
+double jasper_indelscan_check_seconds(const jasper_indelscan *r);
+int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n);
+int jasper_indelscan_retried(const jasper_indelscan *r);
+void jasper_indelscan_free(jasper_indelscan *r);
 
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1

@@ -46,6 +46,14 @@ class Variant(C.Structure):
 
 assert C.sizeof(Variant) == 24
 
+
+class Indel(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("len", C.c_uint16), ("type", C.c_uint8),
+                ("base", C.c_uint8), ("kind", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+assert C.sizeof(Indel) == 32
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -147,6 +155,17 @@ SYMBOLS = {
     "jasper_varscan_seconds": (C.c_double, [_P]),
     "jasper_varscan_retried": (C.c_int, [_P]),
     "jasper_varscan_free": (None, [_P]),
+    "jasper_indel_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_indel_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_indelscan_num_seqs": (C.c_int, [_P]),
+    "jasper_indelscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_records": (C.c_int, [_P, C.POINTER(C.POINTER(Indel)), C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_variants": (_P, [_P]),
+    "jasper_indelscan_seconds": (C.c_double, [_P]),
+    "jasper_indelscan_check_seconds": (C.c_double, [_P]),
+    "jasper_indelscan_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_retried": (C.c_int, [_P]),
+    "jasper_indelscan_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

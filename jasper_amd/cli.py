@@ -3,6 +3,7 @@ sentinel files and log lines; the Jellyfish + per-batch python processes are rep
 polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
+                            [--indels [--indel-max-len N]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -104,6 +105,8 @@ class Options:
         self.peak = None             # --peak: the read count of a single-copy k-mer (default: from the histogram)
         self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
         self.variants = False
+        self.indels = False
+        self.indel_max_len = None    # --indel-max-len: longest insertion / deletion the indel scan tries (default 4, at most 16)
 
 
 def parse_args(argv):
@@ -158,6 +161,10 @@ def parse_args(argv):
             o.copies_min_run = nxt; i += 1
         elif key == "--variants":                                      # extension: heterozygous and unpolished substitution sites (_variants)
             o.variants = True
+        elif key == "--indels":                                        # extension: insertions and deletions the reads hold against the contigs (_indels)
+            o.indels = True
+        elif key == "--indel-max-len":
+            o.indel_max_len = nxt; i += 1
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1196,6 +1203,57 @@ def _variants(o, table):
         sys.stderr.write("[variants] device seconds: before %.6f after %.6f; candidates %d %d\n" % (vs0.seconds, vs1.seconds, vs0.candidates, vs1.candidates))
 
 
+INDEL_MAX_LEN_DEFAULT = 4
+
+
+def indel_flags(max_len):
+    """--indel-max-len as given (a string or None) -> the longest indel to try; exits on anything but an integer in 1..16"""
+    if max_len is None:
+        return INDEL_MAX_LEN_DEFAULT
+    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 16:
+        error_exit("--indel-max-len takes an integer from 1 to 16; it is %s" % max_len)
+    return int(max_len)
+
+
+def scan_indels(table, contigs, thre, max_len):
+    """the indel scan of whole contigs [(name token, sequence)] -> (names, lengths, IndelScan), whose .variants is what scan_variants
+    gives; exits on a threshold of 0, which would call every alternative solid"""
+    from . import report
+    if thre < 1:
+        error_exit("--indels needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.indel_scan([s for _, s in contigs], thre, max_len)
+
+
+def _indels(o, table):
+    """--indels (an extension, no counterpart in src/jasper.sh): the input assembly's contigs and the polished contigs scanned through
+    the read table while it is still in HBM for same-base insertions and for deletions that the reads hold, into
+    `$QUERY_FN.indels.tsv` and `$QUERY_FN.indels.{before,after}.vcf` (jasper_amd/indels.py) -- `before` in the input's coordinates,
+    `after` in the polished FASTA's.  The threshold is the polisher's (threshold.txt).  With --variants as well each stage is still
+    ONE scan: the variant files are written from its substitution half, byte for byte those of --variants alone."""
+    from . import indels, report, variants
+    qfn, k = o.query_fn, table.k
+    max_len = indel_flags(o.indel_max_len)
+    thresh = int(open("threshold.txt").read().split()[0])
+    asm0, asm1 = read_assembly(o.query), read_assembly(qfn + ".polished.fasta")
+    names, len0, is0 = scan_indels(table, asm0, thresh, max_len)
+    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len)
+    if o.variants:
+        vs0, vs1 = is0.variants, is1.variants
+        len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
+        variants.write_atomic(qfn + ".variants.tsv", variants.variants_tsv_text(names, [("before", len0, vs0.counts), ("after", len1a, cnt1a)]))
+        variants.write_atomic(qfn + ".variants.before.vcf", variants.vcf_text(k, thresh, names, len0, vs0.records))
+        variants.write_atomic(qfn + ".variants.after.vcf", variants.vcf_text(k, thresh, names1, len1, vs1.records))
+        log(variants.log_text(vs0.counts, cnt1a))
+    len1a, cnt1a = report.align(names, names1, len1, is1.counts)
+    indels.write_atomic(qfn + ".indels.tsv", indels.indels_tsv_text(names, [("before", len0, is0.counts), ("after", len1a, cnt1a)]))
+    indels.write_atomic(qfn + ".indels.before.vcf", indels.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], is0.records))
+    indels.write_atomic(qfn + ".indels.after.vcf", indels.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], is1.records))
+    log(indels.log_text(is0.counts, cnt1a))
+    if _timing_on():
+        sys.stderr.write("[indels] device seconds: before %.6f (check %.6f) after %.6f (check %.6f); candidates %d %d\n" %
+                         (is0.seconds, is0.check_seconds, is1.seconds, is1.check_seconds, is0.variants.candidates, is1.variants.candidates))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1229,6 +1287,8 @@ def run(argv):
     ranks = _Ranks(*_init_multi(o))
     if o.copies:
         copies_flags(o.peak, o.copies_min_run)      # (a bad value ends the run before it starts, not after the polishing)
+    if o.indels:
+        indel_flags(o.indel_max_len)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
@@ -1315,7 +1375,11 @@ def run(argv):
         ranks.together((lambda: _spectra_copies(o, table, histo_file)) if ranks.is0 else (lambda: None),
                        "Writing the k-mer spectrum failed" if not o.copies else "Writing the copy-number scan failed")
         _timing("k-mer spectrum" if not o.copies else "k-mer spectrum + copy-number scan" if o.spectra else "copy-number scan")
-    if o.variants:
+    if o.indels:
+        # as for --report: rank 0 alone, through every owner's shard of the attached table; one scan per stage serves --variants too
+        ranks.together((lambda: _indels(o, table)) if ranks.is0 else (lambda: None), "Writing the indel scan failed")
+        _timing("variant + indel scan" if o.variants else "indel scan")
+    elif o.variants:
         # as for --report: rank 0 alone, through every owner's shard of the attached table
         ranks.together((lambda: _variants(o, table)) if ranks.is0 else (lambda: None), "Writing the variant scan failed")
         _timing("variant scan")

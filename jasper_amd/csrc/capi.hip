@@ -10,6 +10,7 @@
 #include "spectra.hpp"
 #include "copies.hpp"
 #include "variants.hpp"
+#include "indels.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -51,6 +52,10 @@ struct jasper_copyrep {
 };
 struct jasper_varscan {
     VariantOut r;
+};
+struct jasper_indelscan {
+    IndelOut r;
+    jasper_varscan var;                  // r.var moved here: what jasper_indelscan_variants hands out
 };
 struct jasper_report {
     ReportOut r;
@@ -862,5 +867,52 @@ int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n) {
 double jasper_varscan_seconds(const jasper_varscan *r) { return r ? r->r.seconds : 0.0; }
 int jasper_varscan_retried(const jasper_varscan *r) { return r ? r->r.retried : 0; }
 void jasper_varscan_free(jasper_varscan *r) { delete r; }
+
+// ---- indel scan (indels.hip) ----
+static_assert(sizeof(jasper_indel) == sizeof(Indel) && offsetof(jasper_indel, len) == offsetof(Indel, len) && offsetof(jasper_indel, type) == offsetof(Indel, type) &&
+                  offsetof(jasper_indel, base) == offsetof(Indel, base) && offsetof(jasper_indel, kind) == offsetof(Indel, kind),
+              "jasper_indel is Indel");
+static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
+                          int max_len, jasper_indelscan **out) {
+    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_indelscan *r = new jasper_indelscan();
+    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, r->r, g_err)
+                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    r->var.r = std::move(r->r.var);
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_indel_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, out);
+}
+int jasper_indel_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, out);
+}
+int jasper_indelscan_num_seqs(const jasper_indelscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
+int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
+    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_indelscan_records(const jasper_indelscan *r, const jasper_indel **recs, uint64_t *n) {
+    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *recs = reinterpret_cast<const jasper_indel *>(r->r.recs.data());
+    *n = r->r.recs.size();
+    return JASPER_OK;
+}
+const jasper_varscan *jasper_indelscan_variants(const jasper_indelscan *r) { return r ? &r->var : nullptr; }
+double jasper_indelscan_seconds(const jasper_indelscan *r) { return r ? r->r.seconds : 0.0; }
+double jasper_indelscan_check_seconds(const jasper_indelscan *r) { return r ? r->r.check_seconds : 0.0; }
+int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n) {
+    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = r->r.lookups;
+    return JASPER_OK;
+}
+int jasper_indelscan_retried(const jasper_indelscan *r) { return r ? r->r.retried : 0; }
+void jasper_indelscan_free(jasper_indelscan *r) { delete r; }
 
 }  // extern "C"

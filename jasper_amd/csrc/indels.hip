@@ -1,0 +1,338 @@
+// indels.hip -- indel scan: same-base insertions and deletions of up to 16 bytes that the reads hold against the sequence, as per-sequence
+// counters and one record per hypothesis that is solid (semantics: include/jasper_hip.h, jasper_indel_scan).
+//
+// An extension.  The reference repairs such differences inside its walk (src/jasper.py: fix_insert, fix_del, fix_same_base_del,
+// fix_same_base_insertion) and reports nothing.  The dense scan is that of variants.hip, unchanged: its candidate (p, x) -- the window
+// that ends at p is solid with its last base replaced by x -- is window 0 of the alternative string of ins(p, x, L) and of del(p, L) with
+// s[p + L] == x, hence necessary for all of them.
+//
+//   indels_check_kernel   one wave per candidate.  The wave loads the context bytes s[p-k+1 .. p+max_len+k-2] once (up to 142: lane l holds
+//                         bytes l, l + 64 and l + 128; a byte past the sequence's end counts as "no base").  Nothing is evaluated unless
+//                         the first 2k - 2 of them are bases (that is the condition of an insertion, and every deletion's includes it).
+//                         Six ballots turn the context into two bit planes of three wave-uniform words.  A hypothesis is a VIRTUAL
+//                         string -- the context with x^L put in before byte k - 1, or with L bytes taken out from there -- which is a
+//                         few shifts and masks of those words in scalar registers; a lane cuts the window it owns out of the planes
+//                         (a funnel shift, a bit reversal and an interleave per plane: no loop over the k bases, no shuffle).
+//                           prefix   windows j < max_len of F + x^max_len, lane j.  Window j is shared by every ins(.., L > j), and window 0
+//                                    is window 0 of every deletion.  The first one below thre bounds the L that can still pass; a prefix
+//                                    minimum over the 16 lanes gives each L its part of alt_min.
+//                           ins L    for L up to that bound: windows L .. k+L-2, lane j - L  (k - 1 lookups)
+//                           del L    for every L with s[p + L] == x whose bytes are bases: windows 1 .. k-2  (k - 2 lookups)
+//                           ref      only when a hypothesis passed: windows 0 .. k+L-2 of s for the largest deletion L that passed (k - 2
+//                                    for insertions alone), lane j and, past 64, lane j - 64 a second one; looked up once, then one
+//                                    masked minimum per hypothesis that passed.
+//                         The hypotheses that passed are bits of a wave-uniform mask (bit L - 1: ins L, bit 15 + L: del L); lane b keeps
+//                         the minima of bit b and writes its record.  Places are reserved with one returning cursor add per wave, and a
+//                         wave writes all its records or none.
+//
+// The record list starts at candidates + 4096 entries; a check that found more has counted them and is repeated once with exactly that
+// room.  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
+#include "indels.hpp"
+#include <algorithm>
+#include <cstring>
+
+namespace jk {
+
+#define HIPCHK(x)                                                                     \
+    do {                                                                              \
+        hipError_t e_ = (x);                                                          \
+        if (e_ != hipSuccess) {                                                       \
+            err = std::string(#x) + ": " + hipGetErrorString(e_);                     \
+            return -1;                                                                \
+        }                                                                             \
+    } while (0)
+
+enum { IC_CURSOR = 0, IC_LOOKUPS = 1, IC_WORDS = 4 };                    // control words: records wanted, table lookups made
+
+__device__ __forceinline__ uint32_t id_min32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t u = __shfl_xor(v, o);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+// A string of up to 192 two-bit codes as two bit planes of three wave-uniform words each: bit i of a plane = that bit of code i.
+struct Plane { unsigned long long a, b, c; };
+__device__ __forceinline__ Plane pl_shl(Plane t, int L) {      // 1 <= L < 64
+    Plane u;
+    u.c = (t.c << L) | (t.b >> (64 - L));
+    u.b = (t.b << L) | (t.a >> (64 - L));
+    u.a = t.a << L;
+    return u;
+}
+__device__ __forceinline__ Plane pl_shr(Plane t, int L) {      // 1 <= L < 64
+    Plane u;
+    u.a = (t.a >> L) | (t.b << (64 - L));
+    u.b = (t.b >> L) | (t.c << (64 - L));
+    u.c = t.c >> L;
+    return u;
+}
+// one plane of the virtual strings; t = that plane of the context, m = the low k - 1 bits (F), xbit = that bit of x
+__device__ __forceinline__ Plane pl_prefix(Plane t, unsigned long long m, bool xbit) {      // F x x x ..
+    Plane u;
+    u.a = (t.a & m) | (xbit ? ~m : 0ull);
+    u.b = u.c = xbit ? ~0ull : 0ull;
+    return u;
+}
+__device__ __forceinline__ Plane pl_ins(Plane t, unsigned long long m, int k, int L, bool xbit) {      // F + x^L + the context from k - 1 on
+    Plane u = t;
+    u.a &= ~m;
+    u = pl_shl(u, L);
+    u.a |= t.a & m;
+    if (xbit) {
+        const unsigned long long xm = (1ull << L) - 1ull;
+        u.a |= xm << (k - 1);
+        u.b |= xm >> (64 - (k - 1));                    // (1 <= k - 1 <= 63)
+    }
+    return u;
+}
+__device__ __forceinline__ Plane pl_del(Plane t, unsigned long long m, int L) {      // F + the context from k - 1 + L on
+    Plane u = pl_shr(t, L);
+    u.a = (u.a & ~m) | (t.a & m);
+    return u;
+}
+__device__ __forceinline__ unsigned long long pl_extract(Plane t, int s) {      // bits s .. s + 63, s < 128
+    const int o = s & 63;
+    const unsigned long long x = s < 64 ? t.a : t.b, y = s < 64 ? t.b : t.c;
+    return o ? (x >> o) | (y << (64 - o)) : x;
+}
+__device__ __forceinline__ unsigned long long id_spread(uint32_t v) {      // bit i -> bit 2i
+    unsigned long long x = v;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+// the k-mer of the window that starts at code s < 128 of the string (lo, hi): code s + i is bit pair k - 1 - i
+__device__ __forceinline__ u128 id_kmer(Plane lo, Plane hi, int s, int k) {
+    const unsigned long long r0 = brev64(pl_extract(lo, s)) >> (64 - k), r1 = brev64(pl_extract(hi, s)) >> (64 - k);
+    return mk(id_spread((uint32_t)(r0 >> 32)) | (id_spread((uint32_t)(r1 >> 32)) << 1), id_spread((uint32_t)r0) | (id_spread((uint32_t)r1) << 1));
+}
+
+__device__ __forceinline__ uint32_t id_count(const TableDev &R, u128 fwd, int k) {
+    const u128 rc = revcomp(fwd, k);
+    return clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
+}
+
+__global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int max_len,
+                                                           const Variant *__restrict__ cand, uint64_t ncand, Indel *__restrict__ out, unsigned long long cap,
+                                                           unsigned long long *__restrict__ ctl) {
+    const int lane = threadIdx.x & 63;
+    const int k = R.k;
+    const int CL = 2 * k - 2 + max_len;                 // context bytes: at most 142
+    const uint64_t nwv = (uint64_t)gridDim.x * 4;
+    unsigned long long nlook = 0;                       // (wave-uniform) lookups of this wave
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ncand; i += nwv) {
+        const int64_t p = cand[i].pos;
+        const uint32_t seq = cand[i].seq;
+        const int x = cand[i].alt & 3;
+        const int64_t o0 = offs[seq];
+        const int64_t n = offs[seq + 1] - o0;
+        const uint8_t *__restrict__ txt = text + o0;
+        if (p < k - 1 || p >= n) continue;              // (wave-uniform; the scan writes no such candidate)
+        const int64_t b0 = p - k + 1;
+        int c0 = -1, c1 = -1, c2 = -1;                  // codes of context bytes lane, lane + 64, lane + 128
+        if (lane < CL && b0 + lane < n) c0 = code(txt[b0 + lane]);
+        if (lane + 64 < CL && b0 + lane + 64 < n) c1 = code(txt[b0 + lane + 64]);
+        if (lane + 128 < CL && b0 + lane + 128 < n) c2 = code(txt[b0 + lane + 128]);
+        const unsigned long long n0 = __ballot(c0 < 0), n1 = __ballot(c1 < 0), n2 = __ballot(c2 < 0);
+        const int bases = n0 ? (int)__builtin_ctzll(n0) : n1 ? 64 + (int)__builtin_ctzll(n1) : n2 ? 128 + (int)__builtin_ctzll(n2) : 192;      // ... in a row from byte 0
+        const int refc = __shfl(c0, k - 1);
+        if (bases < 2 * k - 2 || refc == x) continue;   // no insertion is evaluated, hence no deletion either
+        const unsigned long long e0 = __ballot(c0 == x), e1 = __ballot(c1 == x);
+        const Plane clo = {__ballot(c0 & 1), __ballot(c1 & 1), __ballot(c2 & 1)}, chi = {__ballot(c0 & 2), __ballot(c1 & 2), __ballot(c2 & 2)};      // the context
+        const unsigned long long fm = (1ull << (k - 1)) - 1ull;      // its first k - 1 codes: F
+        uint32_t dels = 0;                              // bit L: del(p, L) is evaluated and s[p + L] == x
+        for (int L = 1; L <= max_len; ++L) {
+            const int at = k - 1 + L;                   // <= 79
+            const bool isx = at < 64 ? (e0 >> at) & 1ull : (e1 >> (at - 64)) & 1ull;
+            if (isx && bases >= L + 2 * k - 2) dels |= 1u << L;
+        }
+        // prefix: windows j < max_len of F + x x x ..
+        uint32_t cnt = 0xFFFFFFFFu;
+        if (lane < max_len) cnt = id_count(R, id_kmer(pl_prefix(clo, fm, x & 1), pl_prefix(chi, fm, x & 2), lane, k), k);
+        nlook += (unsigned)max_len;
+        const unsigned long long fail = __ballot(lane < max_len && cnt < thre);
+        const int Lp = fail ? (int)__builtin_ctzll(fail) : max_len;      // ins(.., L) can pass for L <= Lp only
+        uint32_t pm = cnt;                              // lane j < 16: the minimum over windows 0 .. j
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            const uint32_t u = __shfl_up(pm, o);
+            if (lane >= o) pm = u < pm ? u : pm;
+        }
+        const uint32_t cnt0 = __shfl(cnt, 0);
+        uint32_t pass = 0;                              // (wave-uniform) bit L - 1: ins L passed; bit 15 + L: del L passed
+        uint32_t my_amin = 0, my_rmin = 0;              // lane b: the minima of hypothesis bit b
+        for (int L = 1; L <= Lp; ++L) {
+            uint32_t a = 0xFFFFFFFFu;
+            if (lane < k - 1) a = id_count(R, id_kmer(pl_ins(clo, fm, k, L, x & 1), pl_ins(chi, fm, k, L, x & 2), L + lane, k), k);
+            nlook += (unsigned)(k - 1);
+            a = id_min32(a);
+            const uint32_t pl = __shfl(pm, L - 1);
+            a = pl < a ? pl : a;
+            if (a >= thre) {
+                pass |= 1u << (L - 1);
+                if (lane == L - 1) my_amin = a;
+            }
+        }
+        if (cnt0 >= thre) {
+            for (int L = 1; L <= max_len; ++L) {
+                if (!((dels >> L) & 1u)) continue;
+                uint32_t a = 0xFFFFFFFFu;
+                if (k > 2) {
+                    if (lane < k - 2) a = id_count(R, id_kmer(pl_del(clo, fm, L), pl_del(chi, fm, L), 1 + lane, k), k);
+                    nlook += (unsigned)(k - 2);
+                    a = id_min32(a);
+                }
+                a = cnt0 < a ? cnt0 : a;
+                if (a >= thre) {
+                    pass |= 1u << (15 + L);
+                    if (lane == 15 + L) my_amin = a;
+                }
+            }
+        }
+        if (pass == 0) continue;
+        // ref: windows 0 .. jmax of s, once
+        const int Ld = (pass >> 16) ? 32 - __clz(pass >> 16) : 0;        // the largest deletion that passed
+        const int jmax = Ld ? k + Ld - 2 : k - 2;                         // <= 78
+        uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;                      // windows lane and lane + 64
+        if (lane <= jmax) ra = id_count(R, id_kmer(clo, chi, lane, k), k);
+        if (lane + 64 <= jmax) rb = id_count(R, id_kmer(clo, chi, lane + 64, k), k);
+        nlook += (unsigned)(jmax + 1);
+        if (pass & 0xFFFFu) {
+            const uint32_t r = id_min32(lane <= k - 2 ? ra : 0xFFFFFFFFu);
+            if (lane < 16) my_rmin = r;
+        }
+        for (int L = 1; L <= Ld; ++L) {
+            if (!((pass >> (15 + L)) & 1u)) continue;
+            const int lim = k + L - 2;
+            uint32_t r = lane <= lim ? ra : 0xFFFFFFFFu;
+            r = lane + 64 <= lim && rb < r ? rb : r;
+            r = id_min32(r);
+            if (lane == 15 + L) my_rmin = r;
+        }
+        unsigned long long base = 0;
+        const unsigned total = __popc(pass);
+        if (lane == 0) base = atomicAdd(&ctl[IC_CURSOR], (unsigned long long)total);
+        base = __shfl(base, 0);
+        if (base + total > cap) continue;               // (a wave writes all its records or none: the retry has room for every one)
+        if (lane < 32 && ((pass >> lane) & 1u)) {
+            Indel v;
+            v.pos = p;
+            v.seq = seq;
+            v.ref_min = my_rmin;
+            v.alt_min = my_amin;
+            v.len = (uint16_t)((lane & 15) + 1);
+            v.type = lane < 16 ? IT_INS : IT_DEL;
+            v.base = (uint8_t)((0x54474341u >> (8 * x)) & 0xFFu);         // "ACGT"
+            v.kind = my_rmin >= thre ? VK_HET : VK_ERROR;
+            for (int q = 0; q < 7; ++q) v.pad[q] = 0;
+            out[base + __popc(pass & ((1u << lane) - 1u))] = v;
+        }
+    }
+    if (lane == 0 && nlook) atomicAdd(&ctl[IC_LOOKUPS], nlook);
+}
+
+namespace {
+struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+}  // namespace
+
+static int indel_check_args(const Table &T, uint32_t thre, int max_len, std::string &err) {
+    if (thre < 1) { err = "indel scan: the threshold (thre) must be at least 1"; return -1; }
+    if (T.k < 2) { err = "indel scan: k must be at least 2"; return -1; }
+    if (max_len < 1 || max_len > INDEL_MAX_LEN) { err = "indel scan: max_len must be in 1..16"; return -1; }
+    return 0;
+}
+
+int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, IndelOut &out, std::string &err) {
+    if (n_seqs < 0 || (n_seqs && !offsets)) { err = "indel scan: bad arguments"; return -1; }
+    if (indel_check_args(T, thre, max_len, err)) return -1;
+    HIPCHK(hipSetDevice(T.device));
+    if (T.materialize(err)) return -1;       // a logically empty table holds garbage until it is zeroed
+    out = IndelOut();
+    out.counts.assign((size_t)n_seqs * 4, 0);
+    out.var.counts.assign((size_t)n_seqs * 3, 0);
+    VariantStage S;
+    if (variant_scan_stage(T, n_seqs, d_text, offsets, thre, "indel scan", out.var, S, err)) return -1;
+    if (S.ntiles == 0) return 0;
+    hipStream_t st = T.stream;
+    const uint64_t ncand = S.ncand;
+    if (ncand) {
+        const int W = Table::WS_INDELS;
+        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 2, IC_WORDS * sizeof(unsigned long long), err);
+        if (!d_ctl) return -1;
+        Events ev;
+        for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+        unsigned long long cap = ncand + 4096, ctl[IC_WORDS] = {0, 0, 0, 0};
+        Indel *d_rec = nullptr;
+        for (int attempt = 0;; ++attempt) {
+            d_rec = (Indel *)T.workspace(W + 1, cap * sizeof(Indel), err);
+            if (!d_rec) return -1;
+            HIPCHK(hipMemsetAsync(d_ctl, 0, IC_WORDS * sizeof(unsigned long long), st));
+            HIPCHK(hipEventRecord(ev.e[0], st));
+            hipLaunchKernelGGL(indels_check_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, max_len,
+                               S.d_cand, ncand, d_rec, cap, d_ctl);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ev.e[1], st));
+            HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+            HIPCHK(jk_stream_wait(st));
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+            out.check_seconds += ms * 1e-3;
+            if (ctl[IC_CURSOR] <= cap) break;
+            if (attempt) { err = "indel scan: the number of records changed between two checks"; return -1; }
+            cap = ctl[IC_CURSOR];            // the check counted what it could not write: exactly this much room is needed
+            out.retried = 1;
+        }
+        out.lookups = ctl[IC_LOOKUPS];
+        out.recs.resize(ctl[IC_CURSOR]);
+        if (!out.recs.empty()) HIPCHK(hipMemcpyAsync(out.recs.data(), d_rec, out.recs.size() * sizeof(Indel), hipMemcpyDeviceToHost, st));
+        HIPCHK(jk_stream_wait(st));
+    }
+    if (variant_check_stage(T, n_seqs, d_text, thre, "indel scan", S, out.var, err)) return -1;
+    out.seconds = out.var.seconds + out.check_seconds;
+    std::sort(out.recs.begin(), out.recs.end(), [](const Indel &a, const Indel &b) {
+        return a.seq != b.seq ? a.seq < b.seq : a.pos != b.pos ? a.pos < b.pos : a.type != b.type ? a.type < b.type : a.len != b.len ? a.len < b.len : a.base < b.base;
+    });
+    for (const Indel &v : out.recs) {
+        if (v.seq >= (uint32_t)n_seqs || (v.type != IT_INS && v.type != IT_DEL) || (v.kind != VK_HET && v.kind != VK_ERROR)) {
+            err = "indel scan: a record the check cannot have written";
+            return -1;
+        }
+        ++out.counts[4 * (size_t)v.seq + 2 * (v.type - 1) + (v.kind - 1)];
+    }
+    return 0;
+}
+
+int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, IndelOut &out, std::string &err) {
+    if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "indel scan: bad arguments"; return -1; }
+    if (indel_check_args(T, thre, max_len, err)) return -1;
+    HIPCHK(hipSetDevice(T.device));
+    std::vector<int64_t> offs((size_t)n_seqs + 1, 0);
+    for (int i = 0; i < n_seqs; ++i) {
+        if (lens[i] < 0 || (lens[i] && !seqs[i])) { err = "indel scan: bad sequence"; return -1; }
+        offs[i + 1] = offs[i] + lens[i];
+    }
+    const size_t total = (size_t)offs[n_seqs];
+    uint8_t *d_text = (uint8_t *)T.workspace(Table::WS_INDELS, total + 16, err);
+    if (!d_text) return -1;
+    std::vector<char> all;                  // one copy for many short sequences; it lives until the scan's last wait has returned
+    const char *src = n_seqs == 1 ? seqs[0] : nullptr;
+    if (n_seqs > 1) {
+        all.resize(total);
+        for (int i = 0; i < n_seqs; ++i)
+            if (lens[i]) memcpy(all.data() + offs[i], seqs[i], (size_t)lens[i]);
+        src = all.data();
+    }
+    if (total) HIPCHK(hipMemcpyAsync(d_text, src, total, hipMemcpyHostToDevice, T.stream));
+    return indel_scan_device(T, n_seqs, d_text, offs.data(), thre, max_len, out, err);
+}
+
+}  // namespace jk

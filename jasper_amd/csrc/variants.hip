@@ -27,7 +27,8 @@
 //                            arrival; the host sorts the (small) accepted list by (seq, pos, alt), a unique key.
 //
 // The candidate list starts at windows / 64 + 64K entries; a scan that found more has counted them and is repeated once with exactly
-// that room.
+// that room.  The host side is two stages -- variant_scan_stage (tiles, scan, retry) and variant_check_stage (check, compact, sort) --
+// because the indel scan (indels.hip) runs the first, its own check over the raw candidates, and then the second.
 #include "variants.hpp"
 #include <algorithm>
 #include <cstring>
@@ -277,31 +278,28 @@ struct Events {
 };
 }  // namespace
 
-int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, VariantOut &out, std::string &err) {
-    if (n_seqs < 0 || (n_seqs && !offsets)) { err = "variant scan: bad arguments"; return -1; }
-    if (thre < 1) { err = "variant scan: the threshold must be at least 1"; return -1; }
-    HIPCHK(hipSetDevice(T.device));
-    if (T.materialize(err)) return -1;       // a logically empty table holds garbage until it is zeroed
+// The scan stage that the variant scan and the indel scan (indels.hip) share: the tile list, the launch of variants_scan_kernel, and the
+// retry with exactly the counted room.  On return S names the candidate list and the per-sequence counters in the workspace; ntiles == 0
+// (nothing to scan) leaves the rest of S unset.  `what` starts the error messages.
+int variant_scan_stage(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, const char *what, VariantOut &out, VariantStage &S,
+                       std::string &err) {
+    const std::string w(what);
+    S = VariantStage();
     const int k = T.k;
-    out.counts.assign((size_t)n_seqs * 3, 0);
-    out.recs.clear();
-    out.candidates = 0;
-    out.seconds = 0;
-    out.retried = 0;
     std::vector<VsTile> tiles;
     uint64_t windows = 0;
     for (int i = 0; i < n_seqs; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i] < 0) { err = "variant scan: offsets must not decrease"; return -1; }
+        if (offsets[i + 1] < offsets[i] || offsets[i] < 0) { err = w + ": offsets must not decrease"; return -1; }
         const int64_t n = offsets[i + 1] - offsets[i];
-        const uint64_t w = n >= k ? (uint64_t)(n - k + 1) : 0;
-        windows += w;
-        const uint64_t nt = (w + RP_TILE - 1) / RP_TILE;
-        if (nt > 0xFFFFFFFFull) { err = "variant scan: sequence too long"; return -1; }
+        const uint64_t nw = n >= k ? (uint64_t)(n - k + 1) : 0;
+        windows += nw;
+        const uint64_t nt = (nw + RP_TILE - 1) / RP_TILE;
+        if (nt > 0xFFFFFFFFull) { err = w + ": sequence too long"; return -1; }
         for (uint64_t q = 0; q < nt; ++q) tiles.push_back(VsTile{(uint32_t)i, (uint32_t)q});
     }
     const uint64_t ntiles = tiles.size();
     if (ntiles == 0) return 0;
-    if (!d_text) { err = "variant scan: null text"; return -1; }
+    if (!d_text) { err = w + ": null text"; return -1; }
     hipStream_t st = T.stream;
     const int W = Table::WS_VARIANTS;
     int64_t *d_offs = (int64_t *)T.workspace(W + 1, ((size_t)n_seqs + 1) * sizeof(int64_t), err);
@@ -311,7 +309,7 @@ int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64
     if (!d_offs || !d_tiles || !d_cnt) return -1;
     unsigned long long *d_ctl = d_cnt + (size_t)n_seqs;
     Events ev;
-    for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+    for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreate(&ev.e[i]));
     HIPCHK(hipMemcpyAsync(d_offs, offsets, ((size_t)n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), ntiles * sizeof(VsTile), hipMemcpyHostToDevice, st));
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
@@ -331,30 +329,47 @@ int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64
         HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
         out.seconds += ms * 1e-3;
         if (ctl[VC_CURSOR] <= cap) break;
-        if (attempt) { err = "variant scan: the number of candidates changed between two scans"; return -1; }
+        if (attempt) { err = w + ": the number of candidates changed between two scans"; return -1; }
         cap = ctl[VC_CURSOR];            // the scan counted what it could not write: exactly this much room is needed
         out.retried = 1;
     }
-    const uint64_t ncand = ctl[VC_CURSOR];
-    out.candidates = ncand;
+    S.ntiles = ntiles;
+    S.ncand = ctl[VC_CURSOR];
+    S.d_offs = d_offs;
+    S.d_cnt = d_cnt;
+    S.d_ctl = d_ctl;
+    S.d_cand = d_cand;
+    out.candidates = S.ncand;
+    return 0;
+}
+
+// The check stage: variants_check_kernel over the candidates of S (it rewrites them in place), variants_compact_kernel, the sort and the
+// counters.
+int variant_check_stage(Table &T, int n_seqs, const uint8_t *d_text, uint32_t thre, const char *what, const VariantStage &S, VariantOut &out, std::string &err) {
+    const std::string w(what);
+    hipStream_t st = T.stream;
+    const uint64_t ncand = S.ncand;
+    unsigned long long ctl[VC_WORDS] = {0, 0, 0, 0};
     std::vector<unsigned long long> cnt((size_t)n_seqs);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cnt.data(), S.d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (ncand) {
-        Variant *d_out = (Variant *)T.workspace(W + 5, ncand * sizeof(Variant), err);
+        Events ev;
+        for (int i = 2; i < 4; ++i) HIPCHK(hipEventCreate(&ev.e[i]));
+        Variant *d_out = (Variant *)T.workspace(Table::WS_VARIANTS + 5, ncand * sizeof(Variant), err);
         if (!d_out) return -1;
         HIPCHK(hipEventRecord(ev.e[2], st));
-        hipLaunchKernelGGL(variants_check_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, d_offs, T.d, thre, d_cand, ncand);
+        hipLaunchKernelGGL(variants_check_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, S.d_cand, ncand);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(variants_compact_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 255) / 256, 256 * 8)), dim3(256), 0, st, d_cand, ncand, d_out, d_ctl);
+        hipLaunchKernelGGL(variants_compact_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 255) / 256, 256 * 8)), dim3(256), 0, st, S.d_cand, ncand, d_out, S.d_ctl);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev.e[3], st));
-        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ctl, S.d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
         out.seconds += ms * 1e-3;
         const uint64_t nrec = ctl[VC_ACCEPTED];
-        if (nrec > ncand) { err = "variant scan: more records than candidates"; return -1; }
+        if (nrec > ncand) { err = w + ": more records than candidates"; return -1; }
         out.recs.resize(nrec);
         if (nrec) HIPCHK(hipMemcpyAsync(out.recs.data(), d_out, nrec * sizeof(Variant), hipMemcpyDeviceToHost, st));
     }
@@ -364,10 +379,26 @@ int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64
     });
     for (int i = 0; i < n_seqs; ++i) out.counts[3 * (size_t)i] = cnt[(size_t)i];
     for (const Variant &v : out.recs) {
-        if (v.seq >= (uint32_t)n_seqs || (v.kind != VK_HET && v.kind != VK_ERROR)) { err = "variant scan: a record the check cannot have written"; return -1; }
+        if (v.seq >= (uint32_t)n_seqs || (v.kind != VK_HET && v.kind != VK_ERROR)) { err = w + ": a record the check cannot have written"; return -1; }
         ++out.counts[3 * (size_t)v.seq + v.kind];
     }
     return 0;
+}
+
+int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, VariantOut &out, std::string &err) {
+    if (n_seqs < 0 || (n_seqs && !offsets)) { err = "variant scan: bad arguments"; return -1; }
+    if (thre < 1) { err = "variant scan: the threshold must be at least 1"; return -1; }
+    HIPCHK(hipSetDevice(T.device));
+    if (T.materialize(err)) return -1;       // a logically empty table holds garbage until it is zeroed
+    out.counts.assign((size_t)n_seqs * 3, 0);
+    out.recs.clear();
+    out.candidates = 0;
+    out.seconds = 0;
+    out.retried = 0;
+    VariantStage S;
+    if (variant_scan_stage(T, n_seqs, d_text, offsets, thre, "variant scan", out, S, err)) return -1;
+    if (S.ntiles == 0) return 0;
+    return variant_check_stage(T, n_seqs, d_text, thre, "variant scan", S, out, err);
 }
 
 int variant_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, VariantOut &out, std::string &err) {

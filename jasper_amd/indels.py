@@ -1,0 +1,121 @@
+"""Indel scan: the writers of `*.indels.tsv` and `*.indels*.vcf` (cli --indels, kmerqc --indels).
+
+An extension: the reference repairs length errors inside its walk (src/jasper.py: fix_insert, fix_del, fix_same_base_del,
+fix_same_base_insertion) and reports nothing.  The scan (KmerTable.indel_scan; semantics in include/jasper_hip.h,
+jasper_indel_scan) lists the positions of the contigs where the reads hold a solid same-base insertion or a solid deletion of up
+to `max_len` bytes: `het` when the contig's own sequence is solid there too (a length difference between the haplotypes), `error`
+when only the alternative is (a length error the polisher has not repaired).
+
+Limits: insertions of mixed bases and lengths above 16 are not listed, and two differences less than k apart hide each other.
+
+The scan reports every indel at its right-most position; the VCF writer moves it to the left-most one (`left_align`), as VCF asks.
+Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
+"""
+from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+
+TSV_HEADER = "#contig\tstage\tlength\tins_het\tins_error\tdel_het\tdel_error\n"
+KINDS = {1: "het", 2: "error"}
+TYPES = {1: "ins", 2: "del"}
+TYPE_NUMBERS = {"ins": 1, "del": 2}
+ZERO = (0, 0, 0, 0)
+_FOLD = {65: 65, 67: 67, 71: 71, 84: 84, 97: 65, 99: 67, 103: 71, 116: 84}      # ACGTacgt -> ACGT
+
+
+def _row(name, stage, length, c):
+    return "%s\t%s\t%d\t%d\t%d\t%d\t%d\n" % ((name, stage, length) + tuple(c))
+
+
+def totals(counts):
+    """column sums of the (ins_het, ins_error, del_het, del_error) of the contigs that have any (None = contig missing)"""
+    return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
+
+
+def indels_tsv_text(names, stages):
+    """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and four counters, or None for a contig
+    that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
+    contig `*` with the sums."""
+    out = [TSV_HEADER]
+    for i, name in enumerate(names):
+        for stage, lengths, counts in stages:
+            c = counts[i]
+            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
+    for stage, lengths, counts in stages:
+        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
+    return "".join(out)
+
+
+def _letter(v):
+    return v if isinstance(v, str) else chr(int(v))
+
+
+def _rec_fields(r):
+    """(seq, pos, type number, len, base, ref_min, alt_min, kind) of a record of IndelScan.records or of a tuple in the order of
+    IndelScan.record_tuples()"""
+    if hasattr(r, "dtype"):
+        return (int(r["seq"]), int(r["pos"]), int(r["type"]), int(r["len"]), _letter(r["base"]), int(r["ref_min"]), int(r["alt_min"]), int(r["kind"]))
+    seq, pos, typ, ln, base, rmin, amin, kind = r
+    return int(seq), int(pos), TYPE_NUMBERS[typ] if isinstance(typ, str) else int(typ), int(ln), _letter(base), int(rmin), int(amin), int(kind)
+
+
+def _bytes(s):
+    return s.encode("latin-1") if isinstance(s, str) else s
+
+
+def left_align(seq, q, typ, length, base):
+    """the left-most position of an indel the scan reported at q (0-based: the deleted bytes are seq[q .. q+length-1], the insertion
+    lies before byte q).  A deletion moves to q - 1 while q > 1, seq[q-1] is a base and equals (case folded) seq[q+length-1]; an
+    insertion of `base` repeated moves while q > 1 and seq[q-1] is that base.  typ: 1 / 'ins' or 2 / 'del'."""
+    s = _bytes(seq)
+    if typ in (1, "ins"):
+        x = ord(_letter(base))
+        while q > 1 and _FOLD.get(s[q - 1]) == x:
+            q -= 1
+    else:
+        while q > 1 and _FOLD.get(s[q - 1]) is not None and _FOLD.get(s[q - 1]) == _FOLD.get(s[q + length - 1]):
+            q -= 1
+    return q
+
+
+def vcf_lines(names, seqs, records):
+    """[(seq, POS, type number, len, ALT, REF, INFO)] sorted: every record left-aligned, POS = the 1-based position of the anchor byte"""
+    out = []
+    for seq, pos, typ, ln, base, rmin, amin, kind in (_rec_fields(r) for r in records):
+        s = _bytes(seqs[seq])
+        q = left_align(s, pos, typ, ln, base)
+        anchor = s[q - 1:q].decode("latin-1").upper()
+        if typ == 1:
+            ref, alt = anchor, anchor + base * ln
+        else:
+            ref, alt = anchor + s[q:q + ln].decode("latin-1").upper(), anchor
+        out.append((seq, q, typ, ln, alt, ref, "KIND=%s;TYPE=%s;LEN=%d;RC=%d;AC=%d" % (KINDS[kind], TYPES[typ], ln, rmin, amin)))
+    out.sort()
+    return out
+
+
+def vcf_text(k, thre, max_len, names, lengths, seqs, records):
+    """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record, left-aligned and ordered by (contig,
+    POS, TYPE (ins before del), LEN, ALT) whatever order they come in: name, POS, ., REF, ALT, ., .,
+    KIND=het|error;TYPE=ins|del;LEN=L;RC=ref_min;AC=alt_min.  seqs[i] = contig i's sequence (the anchor and the deleted bases are
+    read from it)."""
+    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd indel scan, k=%d, threshold=%d, max_len=%d\n" % (k, thre, max_len)]
+    for name, ln in zip(names, lengths):
+        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
+    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="het: the contig\'s sequence and the alternative are both solid in the reads; '
+               'error: only the alternative is">\n')
+    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="ins: the reads hold LEN more copies of one base; del: the reads lack LEN bytes">\n')
+    out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="length of the insertion or deletion">\n')
+    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
+    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
+    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+    for seq, q, _typ, _ln, alt, ref, info in vcf_lines(names, seqs, records):
+        out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], q, ref, alt, info))
+    return "".join(out)
+
+
+def stage_log_text(counts):
+    """`A het and B error insertions, C het and D error deletions` of one stage"""
+    return "%d het and %d error insertions, %d het and %d error deletions" % totals(counts)
+
+
+def log_text(counts0, counts1):
+    return "Indel scan: before polishing %s; after polishing %s" % (stage_log_text(counts0), stage_log_text(counts1))

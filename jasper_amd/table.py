@@ -187,6 +187,37 @@ class VariantScan:
         return [(int(r["seq"]), int(r["pos"]), chr(int(r["ref"])), chr(int(r["alt"])), int(r["ref_min"]), int(r["alt_min"]), int(r["kind"])) for r in self.records]
 
 
+INDEL_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("len", "<u2"), ("type", "u1"), ("base", "u1"), ("kind", "u1"),
+               ("pad", "u1", (7,))]
+INDEL_TYPES = {1: "ins", 2: "del"}
+
+
+class IndelScan:
+    """indel scan of a set of sequences against the reads' table (include/jasper_hip.h: jasper_indel_scan): `counts[i]` = (ins_het,
+    ins_error, del_het, del_error) of sequence i, `records` = numpy structured array (INDEL_DTYPE) of the insertions (type 1) and
+    deletions (type 2) ordered by (seq, pos, type, len, base), `variants` = the VariantScan of the same input (one dense scan serves
+    both), `seconds` = device time of the scan and all check kernels, `check_seconds` = of the indel check alone, `lookups` = table
+    lookups that check made.  The files made from it: jasper_amd/indels.py."""
+
+    def __init__(self, counts, records, variants, seconds, check_seconds, lookups, retried):
+        self.counts = counts
+        self.records = records
+        self.variants = variants
+        self.seconds = seconds
+        self.check_seconds = check_seconds
+        self.lookups = lookups
+        self.retried = retried
+
+    def __eq__(self, other):
+        return (isinstance(other, IndelScan) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
+                and self.variants == other.variants)
+
+    def record_tuples(self):
+        """[(seq, pos, 'ins' | 'del', len, base, ref_min, alt_min, kind)], base as a one-letter string"""
+        return [(int(r["seq"]), int(r["pos"]), INDEL_TYPES[int(r["type"])], int(r["len"]), chr(int(r["base"])), int(r["ref_min"]), int(r["alt_min"]),
+                 int(r["kind"])) for r in self.records]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -661,28 +692,78 @@ class KmerTable:
         rc = self._L.jasper_variant_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), C.byref(res))
         return self._wrap_varscan(rc, res)
 
-    def _wrap_varscan(self, rc, res):
+    # ---- indel scan (an extension: the length-changing half of the variant scan, from the same dense scan) --
+    def indel_scan(self, seqs, thre, max_len=4):
+        """the same-base insertions and the deletions of up to max_len (1..16) bytes that the reads hold against the sequences, and
+        the substitution sites of variant_scan with them (thre >= 1, k >= 2) -> IndelScan; the table is not modified"""
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = self._L.jasper_indel_scan(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
+        return self._wrap_indelscan(rc, res)
+
+    def indel_scan_device(self, d_text, offsets, thre, max_len=4):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_indel_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
+        return self._wrap_indelscan(rc, res)
+
+    def _wrap_indelscan(self, rc, res):
         try:
             check(rc)
             import numpy as np
             counts = []
-            c3 = (C.c_uint64 * 3)()
-            for i in range(self._L.jasper_varscan_num_seqs(res)):
-                check(self._L.jasper_varscan_counts(res, i, c3))
-                counts.append(tuple(int(v) for v in c3))
-            rp = C.POINTER(_lib.Variant)()
+            c4 = (C.c_uint64 * 4)()
+            for i in range(self._L.jasper_indelscan_num_seqs(res)):
+                check(self._L.jasper_indelscan_counts(res, i, c4))
+                counts.append(tuple(int(v) for v in c4))
+            rp = C.POINTER(_lib.Indel)()
             rn = C.c_uint64(0)
-            check(self._L.jasper_varscan_records(res, C.byref(rp), C.byref(rn)))
+            check(self._L.jasper_indelscan_records(res, C.byref(rp), C.byref(rn)))
             if rn.value:
-                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Variant)), dtype=VARIANT_DTYPE).copy()
+                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Indel)), dtype=INDEL_DTYPE).copy()
             else:
-                recs = np.zeros(0, dtype=VARIANT_DTYPE)
-            nc = C.c_uint64(0)
-            check(self._L.jasper_varscan_candidates(res, C.byref(nc)))
-            return VariantScan(counts, recs, int(nc.value), self._L.jasper_varscan_seconds(res), bool(self._L.jasper_varscan_retried(res)))
+                recs = np.zeros(0, dtype=INDEL_DTYPE)
+            nl = C.c_uint64(0)
+            check(self._L.jasper_indelscan_lookups(res, C.byref(nl)))
+            var = self._read_varscan(C.c_void_p(self._L.jasper_indelscan_variants(res)))      # (owned by res: read, not freed)
+            return IndelScan(counts, recs, var, self._L.jasper_indelscan_seconds(res), self._L.jasper_indelscan_check_seconds(res), int(nl.value),
+                             bool(self._L.jasper_indelscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_indelscan_free(res)
+
+    def _wrap_varscan(self, rc, res):
+        try:
+            check(rc)
+            return self._read_varscan(res)
         finally:
             if res:
                 self._L.jasper_varscan_free(res)
+
+    def _read_varscan(self, res):
+        import numpy as np
+        counts = []
+        c3 = (C.c_uint64 * 3)()
+        for i in range(self._L.jasper_varscan_num_seqs(res)):
+            check(self._L.jasper_varscan_counts(res, i, c3))
+            counts.append(tuple(int(v) for v in c3))
+        rp = C.POINTER(_lib.Variant)()
+        rn = C.c_uint64(0)
+        check(self._L.jasper_varscan_records(res, C.byref(rp), C.byref(rn)))
+        if rn.value:
+            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Variant)), dtype=VARIANT_DTYPE).copy()
+        else:
+            recs = np.zeros(0, dtype=VARIANT_DTYPE)
+        nc = C.c_uint64(0)
+        check(self._L.jasper_varscan_candidates(res, C.byref(nc)))
+        return VariantScan(counts, recs, int(nc.value), self._L.jasper_varscan_seconds(res), bool(self._L.jasper_varscan_retried(res)))
 
     def _wrap_report(self, rc, res):
         try:

@@ -1,0 +1,99 @@
+"""The indel scan's check kernel next to its yardstick, on bench.py's workload (47 Mb synthetic assembly, 30x reads, k = 37).
+
+    python tools/prof_indels.py trace|time       (run on the GPU box; tools/prof_indels.sh puts `trace` under rocprofv3)
+
+R = the counted read table, the text = the assembly as ONE sequence, the threshold = the derived one.
+trace: each of these after a warm-up call of the same kind, all in one process so that one kernel trace holds them: the variant scan
+       (variants_scan_kernel; variants_check_kernel, the yardstick: one wave per candidate, 2k table lookups each), then the indel scan
+       at max_len 4 and at max_len 16 (the same scan kernel, indels_check_kernel, then the variant check and compact kernels again).
+       Prints the lookups indels_check_kernel counted (jasper_indelscan_lookups) for either max_len.
+time:  no profiler: jasper_indelscan_seconds and _check_seconds of five scans after a warm-up for either max_len, and
+       jasper_varscan_seconds the same way
+summarize DIR TRACE_LOG: per kernel of a rocprofv3 --kernel-trace CSV under DIR, the durations of its dispatches in order, and from them
+       and the lookup counts of TRACE_LOG the time per lookup of indels_check_kernel (max_len 4: its dispatch 2 of 4, max_len 16: the
+       last) and of variants_check_kernel (its dispatch 2: the variant scan's measured call; 2k lookups per candidate), and their ratio
+"""
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def summarize(d, log):
+    out = {}
+    for fn in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        rows = sorted(csv.DictReader(open(fn)), key=lambda r: int(r["Start_Timestamp"]))
+        for r in rows:
+            name = r["Kernel_Name"].split("(")[0]
+            if "variants_" in name or "indels_" in name:
+                out.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, us in sorted(out.items()):
+        print(json.dumps({"kernel": name, "dispatches_us": [round(x, 1) for x in us]}))
+    head = [json.loads(ln) for ln in open(log) if ln.startswith("{")][-1]
+    ind = [us for name, us in out.items() if "indels_check_kernel" in name]
+    var = [us for name, us in out.items() if "variants_check_kernel" in name]
+    if ind and var and len(ind[0]) == 4 and len(var[0]) == 6 and not head["retried"]:
+        y_us, y_look = var[0][1], 2 * head["k"] * head["candidates"]
+        res = {"variants_check_us": round(y_us, 1), "variants_check_lookups": y_look, "variants_check_ns_per_lookup": round(1e3 * y_us / y_look, 4)}
+        for ml, us in ((4, ind[0][1]), (16, ind[0][3])):
+            look = head["lookups_%d" % ml]
+            res.update({"indels_check_us_%d" % ml: round(us, 1), "indels_check_lookups_%d" % ml: look,
+                        "lookups_per_candidate_%d" % ml: round(look / head["candidates"], 2),
+                        "indels_check_ns_per_lookup_%d" % ml: round(1e3 * us / look, 4),
+                        "ratio_%d" % ml: round((us / look) / (y_us / y_look), 3)})
+        print(json.dumps(res))
+
+
+def main():
+    mode = sys.argv[1]
+    if mode == "summarize":
+        return summarize(sys.argv[2], sys.argv[3])
+    import torch
+    import bench
+    from jasper_amd import KmerTable, polisher
+    dev = torch.device("cuda", 0)
+    reads, names, seqs, (d_asm, offs), asm_len, bs, nreads = bench.build_workload(torch, dev, 0, 1, 47.0, 2)
+    r = KmerTable(bench.K, min_slots=max(1 << 21, int(1.25 * nreads * bench.READ_LEN * 2.1 / 10)))      # (sized as bench.py sizes it)
+    r.count_bases_device(reads.data_ptr(), reads.numel())
+    r.sync()
+    thr = int(polisher.threshold_from_histo_rows(r.histo_rows())[0])
+    ri = r.info()
+    text = [0, offs[-1]]
+    head = {"mode": mode, "k": bench.K, "bases": asm_len, "thr": thr, "r_slots": ri["slots"], "r_distinct": ri["distinct"]}
+    if mode == "trace":
+        for _ in range(2):
+            vs = r.variant_scan_device(d_asm, text, thr)
+        head["varscan_seconds"] = vs.seconds
+        for ml in (4, 16):
+            for _ in range(2):
+                isc = r.indel_scan_device(d_asm, text, thr, ml)
+            head.update({"indelscan_seconds_%d" % ml: isc.seconds, "check_seconds_%d" % ml: isc.check_seconds, "lookups_%d" % ml: isc.lookups,
+                         "counts_%d" % ml: isc.counts[0], "records_%d" % ml: len(isc.records)})
+    else:
+        vsecs = []
+        for _ in range(6):
+            vs = r.variant_scan_device(d_asm, text, thr)
+            vsecs.append(vs.seconds)
+        head["varscan_seconds"] = vsecs[1:]
+        for ml in (4, 16):
+            secs, chk, wall = [], [], []
+            for _ in range(6):
+                t0 = time.perf_counter()
+                isc = r.indel_scan_device(d_asm, text, thr, ml)
+                wall.append(time.perf_counter() - t0)
+                secs.append(isc.seconds)
+                chk.append(isc.check_seconds)
+            head.update({"indelscan_seconds_%d" % ml: secs[1:], "check_seconds_%d" % ml: chk[1:], "wall_seconds_%d" % ml: wall[1:], "lookups_%d" % ml: isc.lookups,
+                         "counts_%d" % ml: isc.counts[0], "records_%d" % ml: len(isc.records)})
+    head.update({"candidates": isc.variants.candidates, "variant_counts": isc.variants.counts[0], "same_variants": isc.variants == vs, "retried": isc.retried})
+    print(json.dumps(head))
+    r.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,15 @@
+#!/bin/bash
+# run on the GPU box: one kernel trace that holds the variant scan's kernels (the yardstick: variants_check_kernel, 2k lookups per
+# candidate) and indels_check_kernel at max_len 4 and 16, each after a warm-up call; then the indel scan's own event time of five calls
+# with the profiler off
+cd "$(dirname "$0")/.."
+export TMPDIR=/tmp
+OUT=${1:-prof_indels_out}      # where the traces and logs go
+mkdir -p $OUT
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 tools/prof_indels.py trace > $OUT/trace.log 2>&1 &&
+timeout -k 10 300 python3 tools/prof_indels.py time > $OUT/time.log 2>&1
+rc=$?
+tail -3 $OUT/trace.log $OUT/time.log
+python3 tools/prof_indels.py summarize $OUT/trace $OUT/trace.log | tee $OUT/summary_trace.json
+find $OUT -name '*kernel_stats.csv'
+exit $rc
