@@ -5,10 +5,10 @@
 // An extension the reference has no counterpart for.  It is the dense scan of report.hip joined with the second table of
 // spectra.hip: the spectrum says how many distinct k-mers are collapsed or duplicated, this says where on the contigs they are.
 //
-//   copies_scan_kernel    report_scan_kernel's tile: RP_TILE windows of ONE sequence per workgroup iteration, thread t owns the 16
-//                         windows that end at origin + 16t .., stage16 staging with the 64-base halo, rolling forward and reverse
-//                         k-mers.  Per window ONE mix (the hash does not depend on a table's size) and TWO probes: R through
-//                         read_slots (the owner's shard when R is attached), A whole.  The home-slot loads of a batch of four windows
+//   copies_scan_kernel    the dense scans' tile (scan_tile.hpp: staging with the 64-base halo, the rolling state before a thread's
+//                         first window, the reservation of places in the list).  Per window ONE mix (the hash does not depend on a
+//                         table's size) and TWO probes: R through read_slots (the owner's shard when R is attached), A whole.  The
+//                         home-slot loads of a batch of four windows
 //                         are in flight before any is resolved; A's four loads go out after R's four are resolved (CP_A_EARLY: with
 //                         them -- DESIGN 4.5 has both measurements).  Both counts stay in LDS (2 x 16 KB) with a 64-bit sum per
 //                         group of 16; a thread's windows are two 16-bit class masks (excess / deficit).  A run starts where a class
@@ -17,10 +17,8 @@
 //                         groups by their stored sums -- to the run's or the tile's end.  The tile's PARTIAL runs go to a list (one
 //                         cursor add per tile) with the class of the tile's first and last window; five adds per tile into the
 //                         per-sequence counters.  Nothing per window leaves the CU.
-//   copies_heads_kernel   one workgroup: a partial run is the HEAD of a final run unless it continues the last partial run of the
-//                         tile before it (same sequence, the same non-zero class on both sides of the seam); exclusive sum of heads.
-//   copies_stitch_kernel  one wave per tile: each head is copied to its final place; the head that is open at its tile's end first
-//                         absorbs the continuing partial runs OF ITS KIND of the tiles after it.
+// The heads and stitch kernels that make final runs of the partial ones, and the host stage, are the shared ones of scan_tile.hpp; a run
+// continues across a tile seam when both sides have the same non-zero class, and absorbs only partial runs OF ITS KIND.
 //
 // The class of a window needs e = (2c + peak) div (2 peak) only in comparison with a; with P = peak * a (< 2^64):
 //   e > a  <=>  (2c + peak) / (2 peak) >= a + 1  <=>  2c >= 2P + peak        e < a  <=>  (2c + peak) / (2 peak) < a  <=>  2c + peak < 2P
@@ -29,8 +27,7 @@
 // The list of partial runs starts at windows / 64 + 64K entries, as the report's; a scan that needed more has counted how many and
 // is repeated once with exactly that room.
 #include "copies.hpp"
-#include <algorithm>
-#include <cstring>
+#include "scan_tile.hpp"
 
 #ifndef CP_A_EARLY
 #define CP_A_EARLY 0
@@ -43,46 +40,19 @@
 
 namespace jk {
 
-#define HIPCHK(x)                                                                     \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            err = std::string(#x) + ": " + hipGetErrorString(e_);                     \
-            return -1;                                                                \
-        }                                                                             \
-    } while (0)
-
-struct CpTile { uint32_t seq, idx; };                                    // tile idx (windows idx * RP_TILE ..) of sequence seq
-struct CpTileOut { unsigned long long base; uint32_t nruns, ends; };     // its partial runs: part[base .. base + nruns); ends = first class | last class << 2
-enum { CC_CURSOR = 0, CC_HEADS = 1, CC_WORDS = 4 };                      // control words: partial runs wanted, final runs
 enum { CP_NCOUNT = 5 };                                                  // device counters per sequence: valid, excess, deficit, sum_reads, sum_asm
 
-__device__ __forceinline__ uint32_t cp_first(uint32_t ends) { return ends & 3u; }
-__device__ __forceinline__ uint32_t cp_last(uint32_t ends) { return (ends >> 2) & 3u; }
-
-__device__ __forceinline__ uint32_t cp_incl_scan32(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t cp_sum32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long cp_sum64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
+__device__ __forceinline__ uint32_t kind_of(CopyRun r) { return r.kind; }
+__device__ __forceinline__ CopyRun absorb(CopyRun r, CopyRun p) {
+    r.n_kmers += p.n_kmers;
+    r.sum_reads += p.sum_reads;
+    r.sum_asm += p.sum_asm;
+    return r;
 }
 
-__global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, const CpTile *__restrict__ tiles,
+__global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, const ScanTile *__restrict__ tiles,
                                                                  uint64_t ntiles, TableDev R, TableDev A, uint32_t thre, uint32_t peak,
-                                                                 unsigned long long *__restrict__ counts, CpTileOut *__restrict__ tout, CopyRun *__restrict__ part,
+                                                                 unsigned long long *__restrict__ counts, TileRuns *__restrict__ tout, CopyRun *__restrict__ part,
                                                                  unsigned long long cap, unsigned long long *__restrict__ ctl) {
     __shared__ uint32_t s_code[RP_THREADS + RP_HALO];
     __shared__ uint32_t s_inv[RP_THREADS + RP_HALO];
@@ -96,35 +66,18 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
     __shared__ uint32_t s_tot[3];                       // valid, excess, deficit windows of the tile
     __shared__ unsigned long long s_sum[2];             // sums of c and of a over the tile's valid windows
     __shared__ unsigned long long s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     const int k = R.k;
     const u128 kmask = maskbits(2 * k);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const CpTile D = tiles[tile];
-        const int64_t o0 = offs[D.seq];
-        const int64_t n = offs[D.seq + 1] - o0;
-        const uint8_t *__restrict__ txt = text + o0;
-        const int64_t w0 = (int64_t)D.idx * RP_TILE;    // the tile's first window
-        const int64_t origin = w0 + k - 1;              // ... ends here
+        const ScanTile D = tiles[tile];
         if (t < 3) s_tot[t] = 0;
         if (t < 2) s_sum[t] = 0ull;
+        int64_t n, w0, e0;
         uint32_t c, iv;
-        stage16(txt, origin + (int64_t)t * RP_GROUP, n, c, iv);
-        s_code[t + RP_HALO] = c;
-        s_inv[t + RP_HALO] = iv;
-        if (t < RP_HALO) {
-            uint32_t hc, hiv;
-            stage16(txt, origin - (int64_t)(RP_HALO - t) * RP_GROUP, n, hc, hiv);
-            s_code[t] = hc;
-            s_inv[t] = hiv;
-        }
-        __syncthreads();
-        const uint32_t w4 = s_code[t], w3 = s_code[t + 1], w2 = s_code[t + 2], w1 = s_code[t + 3];
-        const uint64_t ivprev = ((uint64_t)s_inv[t] << 48) | ((uint64_t)s_inv[t + 1] << 32) | ((uint64_t)s_inv[t + 2] << 16) | (uint64_t)s_inv[t + 3];
-        u128 fwd = band(mk(((uint64_t)w4 << 32) | w3, ((uint64_t)w2 << 32) | w1), kmask);
-        u128 rc = revcomp(fwd, k);
-        int run = ivprev ? (int)__builtin_ctzll(ivprev) : 64;
-        const int64_t e0 = origin + (int64_t)t * RP_GROUP;
+        u128 fwd, rc;
+        int run;
+        tile_prologue<RP_HALO>(text, offs, D, k, kmask, s_code, s_inv, n, w0, e0, c, iv, fwd, rc, run);
         uint32_t vm = 0, em = 0, dm = 0;
         unsigned long long gc = 0, ga = 0;
         CP_PRAGMA_UNROLL(CP_BATCH_UNROLL)
@@ -182,8 +135,8 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
         s_gc[t] = gc;
         s_ga[t] = ga;
         {
-            const uint32_t cv = cp_sum32(__popc(vm)), ce = cp_sum32(__popc(em)), cd = cp_sum32(__popc(dm));
-            const unsigned long long sc = cp_sum64(gc), sa = cp_sum64(ga);
+            const uint32_t cv = wave_sum(__popc(vm)), ce = wave_sum(__popc(em)), cd = wave_sum(__popc(dm));
+            const unsigned long long sc = wave_sum(gc), sa = wave_sum(ga);
             if (lane == 0) {
                 atomicAdd(&s_tot[0], cv);
                 atomicAdd(&s_tot[1], ce);
@@ -198,34 +151,18 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
         const uint32_t se = em & ~((em << 1) | pe) & 0xFFFFu, sd = dm & ~((dm << 1) | pd) & 0xFFFFu;
         const uint32_t startmask = se | sd;             // (no window has both classes)
         const uint32_t ns = __popc(startmask);
-        const uint32_t incl = cp_incl_scan32(ns);
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RP_THREADS / 64; ++w) {
-            woff += w < wave ? s_wsum[w] : 0u;
-            total += s_wsum[w];
-        }
+        const TileSlots S = tile_reserve(ns, s_wsum, &s_base, &ctl[SC_CURSOR]);
         if (t == 0) {
-            const unsigned long long b = total ? atomicAdd(&ctl[CC_CURSOR], (unsigned long long)total) : 0ull;
-            s_base = b;
-            CpTileOut O;
-            O.base = b;
-            O.nruns = total;
             const uint32_t e0m = s_ex[0], d0m = s_de[0], eLm = s_ex[RP_THREADS - 1], dLm = s_de[RP_THREADS - 1];
             const uint32_t first = (e0m & 1u) ? CP_EXCESS : (d0m & 1u) ? CP_DEFICIT : CP_NONE;
             const uint32_t last = ((eLm >> 15) & 1u) ? CP_EXCESS : ((dLm >> 15) & 1u) ? CP_DEFICIT : CP_NONE;
-            O.ends = first | (last << 2);
-            tout[tile] = O;
+            tout[tile] = TileRuns{S.base0, S.total, first | (last << 2)};
         }
         if (t < 3 && s_tot[t]) atomicAdd(&counts[(unsigned long long)CP_NCOUNT * D.seq + t], (unsigned long long)s_tot[t]);
         if (t >= 3 && t < 5 && s_sum[t - 3]) atomicAdd(&counts[(unsigned long long)CP_NCOUNT * D.seq + t], s_sum[t - 3]);
-        __syncthreads();
-        const unsigned long long base = s_base;
-        if (base + total <= cap) {
+        unsigned long long at;
+        if (tile_granted(S, &s_base, cap, at)) {
             uint32_t sm = startmask;
-            unsigned long long at = base + woff + incl - ns;
             while (sm) {
                 const int b0 = __builtin_ctz(sm);
                 sm &= sm - 1;
@@ -265,70 +202,7 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
     }
 }
 
-// 1 if the first partial run of tile i continues the last one of tile i - 1: the same class on both sides of the seam
-__device__ __forceinline__ uint32_t cp_cont(const CpTile *__restrict__ tiles, const CpTileOut *__restrict__ tout, uint64_t i) {
-    if (i == 0 || tiles[i].idx == 0) return 0u;         // (idx > 0: tile i - 1 is the tile before it in the same sequence)
-    const uint32_t f = cp_first(tout[i].ends);
-    return f != CP_NONE && f == cp_last(tout[i - 1].ends) ? 1u : 0u;
-}
-
-constexpr int CH_THREADS = 1024;
-__global__ __launch_bounds__(CH_THREADS) void copies_heads_kernel(const CpTile *__restrict__ tiles, const CpTileOut *__restrict__ tout, uint64_t ntiles,
-                                                                  unsigned long long *__restrict__ head_base, unsigned long long *__restrict__ ctl) {
-    __shared__ unsigned long long s_w[CH_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t per = (ntiles + CH_THREADS - 1) / CH_THREADS;
-    const uint64_t lo = (uint64_t)t * per < ntiles ? (uint64_t)t * per : ntiles, hi = lo + per < ntiles ? lo + per : ntiles;
-    unsigned long long sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += tout[i].nruns - cp_cont(tiles, tout, i);
-    unsigned long long incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    unsigned long long at = incl - sum;
-    for (int w = 0; w < wave; ++w) at += s_w[w];
-    for (uint64_t i = lo; i < hi; ++i) {
-        head_base[i] = at;
-        at += tout[i].nruns - cp_cont(tiles, tout, i);
-    }
-    if (t == CH_THREADS - 1) ctl[CC_HEADS] = at;
-}
-
-__global__ __launch_bounds__(256) void copies_stitch_kernel(const CpTile *__restrict__ tiles, const CpTileOut *__restrict__ tout,
-                                                            const unsigned long long *__restrict__ head_base, uint64_t ntiles, const CopyRun *__restrict__ part,
-                                                            CopyRun *__restrict__ out) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t nwv = (uint64_t)gridDim.x * 4;
-    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ntiles; i += nwv) {
-        const CpTileOut O = tout[i];
-        const uint32_t cont = cp_cont(tiles, tout, i);
-        for (uint32_t j = lane + cont; j < O.nruns; j += 64) {
-            CopyRun r = part[O.base + j];
-            if (j == O.nruns - 1 && cp_last(O.ends) != CP_NONE) {      // (the run that holds the tile's last window is its last one: r.kind is that class)
-                for (uint64_t q = i + 1; q < ntiles && tiles[q].idx != 0; ++q) {
-                    const CpTileOut Q = tout[q];
-                    if (cp_first(Q.ends) != r.kind) break;
-                    const CopyRun p = part[Q.base];
-                    r.n_kmers += p.n_kmers;
-                    r.sum_reads += p.sum_reads;
-                    r.sum_asm += p.sum_asm;
-                    if (Q.nruns != 1 || cp_last(Q.ends) != r.kind) break;      // that run ends inside tile q
-                }
-            }
-            out[head_base[i] + j - cont] = r;
-        }
-    }
-}
-
 namespace {
-struct Events {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 int check_pair(Table &R, Table &A, uint32_t peak, std::string &err) {
     if (&R == &A) { err = "copy report: the read table and the assembly table are the same table"; return -1; }
     if (R.k != A.k) { err = "copy report: the tables have different k (" + std::to_string(R.k) + " and " + std::to_string(A.k) + ")"; return -1; }
@@ -345,87 +219,43 @@ int copies_report_device(Table &R, Table &A, int n_seqs, const uint8_t *d_text, 
     HIPCHK(hipSetDevice(R.device));
     // a logically empty table holds garbage until it is zeroed: both tables are probed
     if (A.materialize(err) || R.materialize(err)) return -1;
-    const int k = R.k;
     out.counts.assign((size_t)n_seqs * 6, 0);
     out.runs.clear();
     out.seconds = 0;
     out.retried = 0;
-    std::vector<CpTile> tiles;
-    uint64_t windows = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i] < 0) { err = "copy report: offsets must not decrease"; return -1; }
-        const int64_t n = offsets[i + 1] - offsets[i];
-        const uint64_t w = n >= k ? (uint64_t)(n - k + 1) : 0;
-        out.counts[6 * (size_t)i] = w;
-        windows += w;
-        const uint64_t nt = (w + RP_TILE - 1) / RP_TILE;
-        if (nt > 0xFFFFFFFFull) { err = "copy report: sequence too long"; return -1; }
-        for (uint64_t q = 0; q < nt; ++q) tiles.push_back(CpTile{(uint32_t)i, (uint32_t)q});
-    }
-    const uint64_t ntiles = tiles.size();
+    TileList L;
+    if (build_tiles(R.k, n_seqs, d_text, offsets, "copy report", out.counts.data(), 6, L, err)) return -1;
+    const uint64_t ntiles = L.tiles.size();
     if (ntiles == 0) return 0;
-    if (!d_text) { err = "copy report: null text"; return -1; }
     hipStream_t st = R.stream;
     const int W = Table::WS_COPIES;
-    int64_t *d_offs = (int64_t *)R.workspace(W + 1, ((size_t)n_seqs + 1) * sizeof(int64_t), err);
-    CpTile *d_tiles = (CpTile *)R.workspace(W + 2, ntiles * sizeof(CpTile), err);
-    CpTileOut *d_tout = (CpTileOut *)R.workspace(W + 3, ntiles * sizeof(CpTileOut), err);
+    TileRuns *d_tout = (TileRuns *)R.workspace(W + 3, ntiles * sizeof(TileRuns), err);
     unsigned long long *d_head = (unsigned long long *)R.workspace(W + 4, ntiles * sizeof(unsigned long long), err);
-    const size_t cnt_words = (size_t)n_seqs * CP_NCOUNT + CC_WORDS;
+    const size_t cnt_words = (size_t)n_seqs * CP_NCOUNT + SC_WORDS;
     unsigned long long *d_cnt = (unsigned long long *)R.workspace(W + 5, cnt_words * sizeof(unsigned long long), err);
-    if (!d_offs || !d_tiles || !d_tout || !d_head || !d_cnt) return -1;
-    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * CP_NCOUNT;
-    Events ev;
-    for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
-    HIPCHK(hipEventRecord(ev.e[4], A.stream));        // whatever A's stream still does to A comes first
-    HIPCHK(hipStreamWaitEvent(st, ev.e[4], 0));
-    HIPCHK(hipMemcpyAsync(d_offs, offsets, ((size_t)n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), ntiles * sizeof(CpTile), hipMemcpyHostToDevice, st));
+    if (!d_tout || !d_head || !d_cnt) return -1;
+    Events order;
+    HIPCHK(hipEventCreate(&order.e[0]));
+    HIPCHK(hipEventRecord(order.e[0], A.stream));      // whatever A's stream still does to A comes first
+    HIPCHK(hipStreamWaitEvent(st, order.e[0], 0));
+    if (upload_tiles(R, W, n_seqs, offsets, L, err)) return -1;
+    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * CP_NCOUNT, ctl[SC_WORDS] = {0, 0, 0, 0};
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
-    unsigned long long cap = windows / 64 + 65536, ctl[CC_WORDS] = {0, 0, 0, 0};
     CopyRun *d_part = nullptr;
-    for (int attempt = 0;; ++attempt) {
+    auto scan = [&](unsigned long long cap) {
         d_part = (CopyRun *)R.workspace(W + 6, cap * sizeof(CopyRun), err);
         if (!d_part) return -1;
-        HIPCHK(hipMemsetAsync(d_cnt, 0, cnt_words * sizeof(unsigned long long), st));
-        HIPCHK(hipEventRecord(ev.e[0], st));
-        hipLaunchKernelGGL(copies_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, d_offs, d_tiles, ntiles, R.d, A.d, thre, peak, d_cnt, d_tout, d_part, cap,
+        hipLaunchKernelGGL(copies_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, R.d, A.d, thre, peak, d_cnt, d_tout, d_part, cap,
                            d_ctl);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[1], st));
-        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        out.seconds += ms * 1e-3;
-        if (ctl[CC_CURSOR] <= cap) break;
-        if (attempt) { err = "copy report: the number of partial runs changed between two scans"; return -1; }
-        cap = ctl[CC_CURSOR];            // the scan counted what it could not write: exactly this much room is needed
-        out.retried = 1;
-    }
-    const uint64_t nparts = ctl[CC_CURSOR];
+        return 0;
+    };
+    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, "copy report: the number of partial runs changed between two scans", ctl, out.seconds, out.retried,
+                    err, scan))
+        return -1;
+    const uint64_t nparts = ctl[SC_CURSOR];
     std::vector<unsigned long long> cnt((size_t)n_seqs * CP_NCOUNT);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (nparts) {
-        CopyRun *d_out = (CopyRun *)R.workspace(W + 7, nparts * sizeof(CopyRun), err);
-        if (!d_out) return -1;
-        HIPCHK(hipEventRecord(ev.e[2], st));
-        hipLaunchKernelGGL(copies_heads_kernel, dim3(1), dim3(CH_THREADS), 0, st, d_tiles, d_tout, ntiles, d_head, d_ctl);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(copies_stitch_kernel, dim3((unsigned)std::min<uint64_t>((ntiles + 3) / 4, 256 * 16)), dim3(256), 0, st, d_tiles, d_tout, d_head, ntiles, d_part,
-                           d_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[3], st));
-        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
-        out.seconds += ms * 1e-3;
-        const uint64_t nruns = ctl[CC_HEADS];
-        if (nruns > nparts) { err = "copy report: more runs than partial runs"; return -1; }
-        out.runs.resize(nruns);
-        if (nruns) HIPCHK(hipMemcpyAsync(out.runs.data(), d_out, nruns * sizeof(CopyRun), hipMemcpyDeviceToHost, st));
-    }
+    if (nparts && stitch_runs(R, W + 7, L, d_tout, d_head, d_part, nparts, d_ctl, "copy report", out.runs, out.seconds, err)) return -1;
     HIPCHK(jk_stream_wait(st));
     for (int i = 0; i < n_seqs; ++i)
         for (int c = 0; c < CP_NCOUNT; ++c) out.counts[6 * (size_t)i + 1 + c] = cnt[CP_NCOUNT * (size_t)i + c];
@@ -435,24 +265,9 @@ int copies_report_device(Table &R, Table &A, int n_seqs, const uint8_t *d_text, 
 int copies_report_host(Table &R, Table &A, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak, CopyOut &out, std::string &err) {
     if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "copy report: bad arguments"; return -1; }
     if (check_pair(R, A, peak, err)) return -1;
-    HIPCHK(hipSetDevice(R.device));
-    std::vector<int64_t> offs((size_t)n_seqs + 1, 0);
-    for (int i = 0; i < n_seqs; ++i) {
-        if (lens[i] < 0 || (lens[i] && !seqs[i])) { err = "copy report: bad sequence"; return -1; }
-        offs[i + 1] = offs[i] + lens[i];
-    }
-    const size_t total = (size_t)offs[n_seqs];
-    uint8_t *d_text = (uint8_t *)R.workspace(Table::WS_COPIES, total + 16, err);
-    if (!d_text) return -1;
-    if (n_seqs == 1) {
-        if (total) HIPCHK(hipMemcpyAsync(d_text, seqs[0], total, hipMemcpyHostToDevice, R.stream));
-        return copies_report_device(R, A, n_seqs, d_text, offs.data(), thre, peak, out, err);
-    }
-    std::vector<char> all(total);      // one copy for many short sequences; it lives until the scan's last wait has returned
-    for (int i = 0; i < n_seqs; ++i)
-        if (lens[i]) memcpy(all.data() + offs[i], seqs[i], (size_t)lens[i]);
-    if (total) HIPCHK(hipMemcpyAsync(d_text, all.data(), total, hipMemcpyHostToDevice, R.stream));
-    return copies_report_device(R, A, n_seqs, d_text, offs.data(), thre, peak, out, err);
+    HostText H;
+    if (pack_host_text(R, Table::WS_COPIES, n_seqs, seqs, lens, "copy report", H, err)) return -1;
+    return copies_report_device(R, A, n_seqs, H.d_text, H.offs.data(), thre, peak, out, err);
 }
 
 }  // namespace jk

@@ -26,32 +26,13 @@
 //                         wave writes all its records or none.
 //
 // The record list starts at candidates + 4096 entries; a check that found more has counted them and is repeated once with exactly that
-// room.  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
+// room (run_counted, scan_tile.hpp: the dense scans' repeat, here around the check).  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
 #include "indels.hpp"
-#include <algorithm>
-#include <cstring>
+#include "scan_tile.hpp"
 
 namespace jk {
 
-#define HIPCHK(x)                                                                     \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            err = std::string(#x) + ": " + hipGetErrorString(e_);                     \
-            return -1;                                                                \
-        }                                                                             \
-    } while (0)
-
-enum { IC_CURSOR = 0, IC_LOOKUPS = 1, IC_WORDS = 4 };                    // control words: records wanted, table lookups made
-
-__device__ __forceinline__ uint32_t id_min32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t u = __shfl_xor(v, o);
-        v = u < v ? u : v;
-    }
-    return v;
-}
+enum { IC_LOOKUPS = 1 };                                                 // control word 1: table lookups made
 
 // A string of up to 192 two-bit codes as two bit planes of three wave-uniform words each: bit i of a plane = that bit of code i.
 struct Plane { unsigned long long a, b, c; };
@@ -158,12 +139,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
         nlook += (unsigned)max_len;
         const unsigned long long fail = __ballot(lane < max_len && cnt < thre);
         const int Lp = fail ? (int)__builtin_ctzll(fail) : max_len;      // ins(.., L) can pass for L <= Lp only
-        uint32_t pm = cnt;                              // lane j < 16: the minimum over windows 0 .. j
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            const uint32_t u = __shfl_up(pm, o);
-            if (lane >= o) pm = u < pm ? u : pm;
-        }
+        const uint32_t pm = wave_prefix_min32<16>(cnt);      // lane j < 16: the minimum over windows 0 .. j
         const uint32_t cnt0 = __shfl(cnt, 0);
         uint32_t pass = 0;                              // (wave-uniform) bit L - 1: ins L passed; bit 15 + L: del L passed
         uint32_t my_amin = 0, my_rmin = 0;              // lane b: the minima of hypothesis bit b
@@ -171,7 +147,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
             uint32_t a = 0xFFFFFFFFu;
             if (lane < k - 1) a = id_count(R, id_kmer(pl_ins(clo, fm, k, L, x & 1), pl_ins(chi, fm, k, L, x & 2), L + lane, k), k);
             nlook += (unsigned)(k - 1);
-            a = id_min32(a);
+            a = wave_min32(a);
             const uint32_t pl = __shfl(pm, L - 1);
             a = pl < a ? pl : a;
             if (a >= thre) {
@@ -186,7 +162,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
                 if (k > 2) {
                     if (lane < k - 2) a = id_count(R, id_kmer(pl_del(clo, fm, L), pl_del(chi, fm, L), 1 + lane, k), k);
                     nlook += (unsigned)(k - 2);
-                    a = id_min32(a);
+                    a = wave_min32(a);
                 }
                 a = cnt0 < a ? cnt0 : a;
                 if (a >= thre) {
@@ -204,7 +180,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
         if (lane + 64 <= jmax) rb = id_count(R, id_kmer(clo, chi, lane + 64, k), k);
         nlook += (unsigned)(jmax + 1);
         if (pass & 0xFFFFu) {
-            const uint32_t r = id_min32(lane <= k - 2 ? ra : 0xFFFFFFFFu);
+            const uint32_t r = wave_min32(lane <= k - 2 ? ra : 0xFFFFFFFFu);
             if (lane < 16) my_rmin = r;
         }
         for (int L = 1; L <= Ld; ++L) {
@@ -212,12 +188,12 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
             const int lim = k + L - 2;
             uint32_t r = lane <= lim ? ra : 0xFFFFFFFFu;
             r = lane + 64 <= lim && rb < r ? rb : r;
-            r = id_min32(r);
+            r = wave_min32(r);
             if (lane == 15 + L) my_rmin = r;
         }
         unsigned long long base = 0;
         const unsigned total = __popc(pass);
-        if (lane == 0) base = atomicAdd(&ctl[IC_CURSOR], (unsigned long long)total);
+        if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
         base = __shfl(base, 0);
         if (base + total > cap) continue;               // (a wave writes all its records or none: the retry has room for every one)
         if (lane < 32 && ((pass >> lane) & 1u)) {
@@ -236,13 +212,6 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
     }
     if (lane == 0 && nlook) atomicAdd(&ctl[IC_LOOKUPS], nlook);
 }
-
-namespace {
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
 
 static int indel_check_args(const Table &T, uint32_t thre, int max_len, std::string &err) {
     if (thre < 1) { err = "indel scan: the threshold (thre) must be at least 1"; return -1; }
@@ -266,33 +235,20 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
     const uint64_t ncand = S.ncand;
     if (ncand) {
         const int W = Table::WS_INDELS;
-        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 2, IC_WORDS * sizeof(unsigned long long), err);
+        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 2, SC_WORDS * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
         if (!d_ctl) return -1;
-        Events ev;
-        for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
-        unsigned long long cap = ncand + 4096, ctl[IC_WORDS] = {0, 0, 0, 0};
         Indel *d_rec = nullptr;
-        for (int attempt = 0;; ++attempt) {
+        auto check = [&](unsigned long long cap) {
             d_rec = (Indel *)T.workspace(W + 1, cap * sizeof(Indel), err);
             if (!d_rec) return -1;
-            HIPCHK(hipMemsetAsync(d_ctl, 0, IC_WORDS * sizeof(unsigned long long), st));
-            HIPCHK(hipEventRecord(ev.e[0], st));
             hipLaunchKernelGGL(indels_check_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, max_len,
                                S.d_cand, ncand, d_rec, cap, d_ctl);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ev.e[1], st));
-            HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-            HIPCHK(jk_stream_wait(st));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-            out.check_seconds += ms * 1e-3;
-            if (ctl[IC_CURSOR] <= cap) break;
-            if (attempt) { err = "indel scan: the number of records changed between two checks"; return -1; }
-            cap = ctl[IC_CURSOR];            // the check counted what it could not write: exactly this much room is needed
-            out.retried = 1;
-        }
+            return 0;
+        };
+        if (run_counted(st, d_ctl, SC_WORDS, d_ctl, ncand + 4096, "indel scan: the number of records changed between two checks", ctl, out.check_seconds, out.retried, err, check))
+            return -1;
         out.lookups = ctl[IC_LOOKUPS];
-        out.recs.resize(ctl[IC_CURSOR]);
+        out.recs.resize(ctl[SC_CURSOR]);
         if (!out.recs.empty()) HIPCHK(hipMemcpyAsync(out.recs.data(), d_rec, out.recs.size() * sizeof(Indel), hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
     }
@@ -314,25 +270,9 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
 int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, IndelOut &out, std::string &err) {
     if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "indel scan: bad arguments"; return -1; }
     if (indel_check_args(T, thre, max_len, err)) return -1;
-    HIPCHK(hipSetDevice(T.device));
-    std::vector<int64_t> offs((size_t)n_seqs + 1, 0);
-    for (int i = 0; i < n_seqs; ++i) {
-        if (lens[i] < 0 || (lens[i] && !seqs[i])) { err = "indel scan: bad sequence"; return -1; }
-        offs[i + 1] = offs[i] + lens[i];
-    }
-    const size_t total = (size_t)offs[n_seqs];
-    uint8_t *d_text = (uint8_t *)T.workspace(Table::WS_INDELS, total + 16, err);
-    if (!d_text) return -1;
-    std::vector<char> all;                  // one copy for many short sequences; it lives until the scan's last wait has returned
-    const char *src = n_seqs == 1 ? seqs[0] : nullptr;
-    if (n_seqs > 1) {
-        all.resize(total);
-        for (int i = 0; i < n_seqs; ++i)
-            if (lens[i]) memcpy(all.data() + offs[i], seqs[i], (size_t)lens[i]);
-        src = all.data();
-    }
-    if (total) HIPCHK(hipMemcpyAsync(d_text, src, total, hipMemcpyHostToDevice, T.stream));
-    return indel_scan_device(T, n_seqs, d_text, offs.data(), thre, max_len, out, err);
+    HostText H;
+    if (pack_host_text(T, Table::WS_INDELS, n_seqs, seqs, lens, "indel scan", H, err)) return -1;
+    return indel_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, max_len, out, err);
 }
 
 }  // namespace jk

@@ -6,9 +6,8 @@
 // this is the dense scan of report.hip asking another question of the same table: not "is this window's k-mer there" but "would it
 // be there with another last base".
 //
-//   variants_scan_kernel     report_scan_kernel's tile: RP_TILE windows of ONE sequence per workgroup iteration, thread t owns the 16
-//                            windows that end at origin + 16t .., stage16 staging, rolling forward and reverse k-mers.  The halo is
-//                            128 bases, not 64: a position p is `evaluated` when the 2k - 1 bytes around it are bases, which the
+//   variants_scan_kernel     the dense scans' tile (scan_tile.hpp: staging, the rolling state before a thread's first window).  The halo
+//                            is 128 bases, not 64: a position p is `evaluated` when the 2k - 1 bytes around it are bases, which the
 //                            thread that owns byte p + k - 1 sees as a run of at least 2k - 1 bases ending there (up to 127 back).
 //                            For a valid window that ends at p the three alternatives of its last base come from the rolling state
 //                            (fwd ^ d in the low bit pair, rc ^ (d << 2(k-1)), d = 1, 2, 3: (3-a) ^ (3-b) = a ^ b); each is
@@ -16,8 +15,8 @@
 //                            count >= thre makes (seq, p, alt) a CANDIDATE: that is the j = 0 term of the minimum over the k windows
 //                            that cover p, hence necessary.  VS_BATCH windows' home-slot loads (3 each) are in flight before any is
 //                            resolved (DESIGN 4.6 has the register figures of 4, 2 and 1).  A thread's candidates are a 48-bit mask;
-//                            places in the list are reserved as the report reserves its partial runs: a block-wide scan, one cursor
-//                            add per tile.  One more add per tile counts the evaluated positions of the sequence.
+//                            places in the list are reserved as every dense scan reserves them (scan_tile.hpp: a block-wide scan, one
+//                            cursor add per tile).  One more add per tile counts the evaluated positions of the sequence.
 //   variants_check_kernel    one wave per candidate, lane j < k owns the window that starts at p - k + 1 + j.  The wave loads the
 //                            2k - 1 context bytes once (lane l: bytes l and l + 64); the candidate is dropped unless p <= n - k and
 //                            all of them are bases.  Each lane gathers its k-mer from the wave's registers, forms it with the
@@ -27,11 +26,11 @@
 //                            arrival; the host sorts the (small) accepted list by (seq, pos, alt), a unique key.
 //
 // The candidate list starts at windows / 64 + 64K entries; a scan that found more has counted them and is repeated once with exactly
-// that room.  The host side is two stages -- variant_scan_stage (tiles, scan, retry) and variant_check_stage (check, compact, sort) --
-// because the indel scan (indels.hip) runs the first, its own check over the raw candidates, and then the second.
+// that room (run_counted in scan_tile.hpp, where the text packing and the tile list are too).  The host side is two stages --
+// variant_scan_stage (tiles, scan, retry) and variant_check_stage (check, compact, sort) -- because the indel scan (indels.hip) runs the
+// first, its own check over the raw candidates, and then the second.
 #include "variants.hpp"
-#include <algorithm>
-#include <cstring>
+#include "scan_tile.hpp"
 
 #ifndef VS_BATCH
 #define VS_BATCH 2             // windows whose three home-slot loads are in flight together: 4, 2 or 1
@@ -44,44 +43,11 @@
 
 namespace jk {
 
-#define HIPCHK(x)                                                                     \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            err = std::string(#x) + ": " + hipGetErrorString(e_);                     \
-            return -1;                                                                \
-        }                                                                             \
-    } while (0)
-
 static_assert(VS_BATCH == 1 || VS_BATCH == 2 || VS_BATCH == 4, "VS_BATCH divides a thread's 16 windows");
 constexpr int VS_HALO = 8;                                               // groups of 16 bases staged before a tile: 128 >= 2k - 1
-struct VsTile { uint32_t seq, idx; };                                    // tile idx (windows idx * RP_TILE ..) of sequence seq
-enum { VC_CURSOR = 0, VC_ACCEPTED = 1, VC_WORDS = 4 };                   // control words: candidates wanted, records accepted
+enum { VC_ACCEPTED = 1 };                                                // control word 1: records accepted
 
-__device__ __forceinline__ uint32_t vs_incl_scan32(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t vs_sum32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint32_t vs_min32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t u = __shfl_xor(v, o);
-        v = u < v ? u : v;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(RP_THREADS) void variants_scan_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, const VsTile *__restrict__ tiles,
+__global__ __launch_bounds__(RP_THREADS) void variants_scan_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, const ScanTile *__restrict__ tiles,
                                                                    uint64_t ntiles, TableDev R, uint32_t thre, unsigned long long *__restrict__ counts,
                                                                    Variant *__restrict__ cand, unsigned long long cap, unsigned long long *__restrict__ ctl) {
     __shared__ uint32_t s_code[RP_THREADS + VS_HALO];
@@ -89,36 +55,17 @@ __global__ __launch_bounds__(RP_THREADS) void variants_scan_kernel(const uint8_t
     __shared__ uint32_t s_wsum[RP_THREADS / 64];
     __shared__ uint32_t s_eval;                         // evaluated positions of the tile
     __shared__ unsigned long long s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     const int k = R.k;
     const u128 kmask = maskbits(2 * k);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const VsTile D = tiles[tile];
-        const int64_t o0 = offs[D.seq];
-        const int64_t n = offs[D.seq + 1] - o0;
-        const uint8_t *__restrict__ txt = text + o0;
-        const int64_t w0 = (int64_t)D.idx * RP_TILE;    // the tile's first window
-        const int64_t origin = w0 + k - 1;              // ... ends here
+        const ScanTile D = tiles[tile];
         if (t == 0) s_eval = 0;
+        int64_t n, w0, e0;
         uint32_t c, iv;
-        stage16(txt, origin + (int64_t)t * RP_GROUP, n, c, iv);
-        s_code[t + VS_HALO] = c;
-        s_inv[t + VS_HALO] = iv;
-        if (t < VS_HALO) {
-            uint32_t hc, hiv;
-            stage16(txt, origin - (int64_t)(VS_HALO - t) * RP_GROUP, n, hc, hiv);
-            s_code[t] = hc;
-            s_inv[t] = hiv;
-        }
-        __syncthreads();
-        const uint32_t w4 = s_code[t + 4], w3 = s_code[t + 5], w2 = s_code[t + 6], w1 = s_code[t + 7];
-        const uint64_t ivfar = ((uint64_t)s_inv[t] << 48) | ((uint64_t)s_inv[t + 1] << 32) | ((uint64_t)s_inv[t + 2] << 16) | (uint64_t)s_inv[t + 3];
-        const uint64_t ivprev = ((uint64_t)s_inv[t + 4] << 48) | ((uint64_t)s_inv[t + 5] << 32) | ((uint64_t)s_inv[t + 6] << 16) | (uint64_t)s_inv[t + 7];
-        u128 fwd = band(mk(((uint64_t)w4 << 32) | w3, ((uint64_t)w2 << 32) | w1), kmask);
-        u128 rc = revcomp(fwd, k);
-        // bases in a row that end right before my first one, up to 128
-        int run = ivprev ? (int)__builtin_ctzll(ivprev) : 64 + (ivfar ? (int)__builtin_ctzll(ivfar) : 64);
-        const int64_t e0 = origin + (int64_t)t * RP_GROUP;
+        u128 fwd, rc;
+        int run;                                        // bases in a row that end right before my first one, up to 128
+        tile_prologue<VS_HALO>(text, offs, D, k, kmask, s_code, s_inv, n, w0, e0, c, iv, fwd, rc, run);
         unsigned long long cm = 0;                      // bit 3j + d - 1: the window that ends at e0 + j with its last base ^ d is solid
         uint32_t evm = 0;                               // bit j: the position k - 1 before e0 + j is evaluated
         VS_PRAGMA_UNROLL(VS_BATCH_UNROLL)
@@ -156,27 +103,14 @@ __global__ __launch_bounds__(RP_THREADS) void variants_scan_kernel(const uint8_t
             }
         }
         {
-            const uint32_t ce = vs_sum32(__popc(evm));
+            const uint32_t ce = wave_sum(__popc(evm));
             if (lane == 0 && ce) atomicAdd(&s_eval, ce);
         }
         const uint32_t ns = __popcll(cm);
-        const uint32_t incl = vs_incl_scan32(ns);
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        uint32_t woff = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RP_THREADS / 64; ++w) {
-            woff += w < wave ? s_wsum[w] : 0u;
-            total += s_wsum[w];
-        }
-        if (t == 0) {
-            s_base = total ? atomicAdd(&ctl[VC_CURSOR], (unsigned long long)total) : 0ull;
-            if (s_eval) atomicAdd(&counts[D.seq], (unsigned long long)s_eval);
-        }
-        __syncthreads();
-        const unsigned long long base = s_base;
-        if (base + total <= cap) {                      // (a tile writes all its candidates or none: the retry has room for every one)
-            unsigned long long at = base + woff + incl - ns;
+        const TileSlots S = tile_reserve(ns, s_wsum, &s_base, &ctl[SC_CURSOR]);
+        if (t == 0 && s_eval) atomicAdd(&counts[D.seq], (unsigned long long)s_eval);
+        unsigned long long at;
+        if (tile_granted(S, &s_base, cap, at)) {
             while (cm) {
                 const int b = __builtin_ctzll(cm);
                 cm &= cm - 1;
@@ -236,8 +170,8 @@ __global__ __launch_bounds__(256) void variants_check_kernel(const uint8_t *__re
                 rmin = clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
                 amin = clamp32(table_get(R, mix(lt(ra, fa) ? ra : fa, R.B)));
             }
-            rmin = vs_min32(rmin);
-            amin = vs_min32(amin);
+            rmin = wave_min32(rmin);
+            amin = wave_min32(amin);
         }
         if (lane == 0) {
             const bool solid = keep && amin >= thre;
@@ -271,71 +205,36 @@ __global__ __launch_bounds__(256) void variants_compact_kernel(const Variant *__
     }
 }
 
-namespace {
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
-
 // The scan stage that the variant scan and the indel scan (indels.hip) share: the tile list, the launch of variants_scan_kernel, and the
 // retry with exactly the counted room.  On return S names the candidate list and the per-sequence counters in the workspace; ntiles == 0
 // (nothing to scan) leaves the rest of S unset.  `what` starts the error messages.
 int variant_scan_stage(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, const char *what, VariantOut &out, VariantStage &S,
                        std::string &err) {
-    const std::string w(what);
     S = VariantStage();
-    const int k = T.k;
-    std::vector<VsTile> tiles;
-    uint64_t windows = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i] < 0) { err = w + ": offsets must not decrease"; return -1; }
-        const int64_t n = offsets[i + 1] - offsets[i];
-        const uint64_t nw = n >= k ? (uint64_t)(n - k + 1) : 0;
-        windows += nw;
-        const uint64_t nt = (nw + RP_TILE - 1) / RP_TILE;
-        if (nt > 0xFFFFFFFFull) { err = w + ": sequence too long"; return -1; }
-        for (uint64_t q = 0; q < nt; ++q) tiles.push_back(VsTile{(uint32_t)i, (uint32_t)q});
-    }
-    const uint64_t ntiles = tiles.size();
+    TileList L;
+    if (build_tiles(T.k, n_seqs, d_text, offsets, what, nullptr, 0, L, err)) return -1;
+    const uint64_t ntiles = L.tiles.size();
     if (ntiles == 0) return 0;
-    if (!d_text) { err = w + ": null text"; return -1; }
     hipStream_t st = T.stream;
     const int W = Table::WS_VARIANTS;
-    int64_t *d_offs = (int64_t *)T.workspace(W + 1, ((size_t)n_seqs + 1) * sizeof(int64_t), err);
-    VsTile *d_tiles = (VsTile *)T.workspace(W + 2, ntiles * sizeof(VsTile), err);
-    const size_t cnt_words = (size_t)n_seqs + VC_WORDS;
+    const size_t cnt_words = (size_t)n_seqs + SC_WORDS;
     unsigned long long *d_cnt = (unsigned long long *)T.workspace(W + 3, cnt_words * sizeof(unsigned long long), err);
-    if (!d_offs || !d_tiles || !d_cnt) return -1;
-    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs;
-    Events ev;
-    for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreate(&ev.e[i]));
-    HIPCHK(hipMemcpyAsync(d_offs, offsets, ((size_t)n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), ntiles * sizeof(VsTile), hipMemcpyHostToDevice, st));
+    if (!d_cnt || upload_tiles(T, W, n_seqs, offsets, L, err)) return -1;
+    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs, ctl[SC_WORDS] = {0, 0, 0, 0};
     const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
-    unsigned long long cap = windows / 64 + 65536, ctl[VC_WORDS] = {0, 0, 0, 0};
     Variant *d_cand = nullptr;
-    for (int attempt = 0;; ++attempt) {
+    auto scan = [&](unsigned long long cap) {
         d_cand = (Variant *)T.workspace(W + 4, cap * sizeof(Variant), err);
         if (!d_cand) return -1;
-        HIPCHK(hipMemsetAsync(d_cnt, 0, cnt_words * sizeof(unsigned long long), st));
-        HIPCHK(hipEventRecord(ev.e[0], st));
-        hipLaunchKernelGGL(variants_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, d_offs, d_tiles, ntiles, T.d, thre, d_cnt, d_cand, cap, d_ctl);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[1], st));
-        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        out.seconds += ms * 1e-3;
-        if (ctl[VC_CURSOR] <= cap) break;
-        if (attempt) { err = w + ": the number of candidates changed between two scans"; return -1; }
-        cap = ctl[VC_CURSOR];            // the scan counted what it could not write: exactly this much room is needed
-        out.retried = 1;
-    }
+        hipLaunchKernelGGL(variants_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, T.d, thre, d_cnt, d_cand, cap, d_ctl);
+        return 0;
+    };
+    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, std::string(what) + ": the number of candidates changed between two scans", ctl, out.seconds,
+                    out.retried, err, scan))
+        return -1;
     S.ntiles = ntiles;
-    S.ncand = ctl[VC_CURSOR];
-    S.d_offs = d_offs;
+    S.ncand = ctl[SC_CURSOR];
+    S.d_offs = L.d_offs;
     S.d_cnt = d_cnt;
     S.d_ctl = d_ctl;
     S.d_cand = d_cand;
@@ -349,25 +248,23 @@ int variant_check_stage(Table &T, int n_seqs, const uint8_t *d_text, uint32_t th
     const std::string w(what);
     hipStream_t st = T.stream;
     const uint64_t ncand = S.ncand;
-    unsigned long long ctl[VC_WORDS] = {0, 0, 0, 0};
+    unsigned long long ctl[SC_WORDS] = {0, 0, 0, 0};
     std::vector<unsigned long long> cnt((size_t)n_seqs);
     HIPCHK(hipMemcpyAsync(cnt.data(), S.d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (ncand) {
         Events ev;
-        for (int i = 2; i < 4; ++i) HIPCHK(hipEventCreate(&ev.e[i]));
+        if (ev.create(err)) return -1;
         Variant *d_out = (Variant *)T.workspace(Table::WS_VARIANTS + 5, ncand * sizeof(Variant), err);
         if (!d_out) return -1;
-        HIPCHK(hipEventRecord(ev.e[2], st));
+        HIPCHK(hipEventRecord(ev.e[0], st));
         hipLaunchKernelGGL(variants_check_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, S.d_cand, ncand);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(variants_compact_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 255) / 256, 256 * 8)), dim3(256), 0, st, S.d_cand, ncand, d_out, S.d_ctl);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[3], st));
+        HIPCHK(hipEventRecord(ev.e[1], st));
         HIPCHK(hipMemcpyAsync(ctl, S.d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
-        out.seconds += ms * 1e-3;
+        if (ev.add_seconds(out.seconds, err)) return -1;
         const uint64_t nrec = ctl[VC_ACCEPTED];
         if (nrec > ncand) { err = w + ": more records than candidates"; return -1; }
         out.recs.resize(nrec);
@@ -404,24 +301,9 @@ int variant_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64
 int variant_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, VariantOut &out, std::string &err) {
     if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "variant scan: bad arguments"; return -1; }
     if (thre < 1) { err = "variant scan: the threshold must be at least 1"; return -1; }
-    HIPCHK(hipSetDevice(T.device));
-    std::vector<int64_t> offs((size_t)n_seqs + 1, 0);
-    for (int i = 0; i < n_seqs; ++i) {
-        if (lens[i] < 0 || (lens[i] && !seqs[i])) { err = "variant scan: bad sequence"; return -1; }
-        offs[i + 1] = offs[i] + lens[i];
-    }
-    const size_t total = (size_t)offs[n_seqs];
-    uint8_t *d_text = (uint8_t *)T.workspace(Table::WS_VARIANTS, total + 16, err);
-    if (!d_text) return -1;
-    if (n_seqs == 1) {
-        if (total) HIPCHK(hipMemcpyAsync(d_text, seqs[0], total, hipMemcpyHostToDevice, T.stream));
-        return variant_scan_device(T, n_seqs, d_text, offs.data(), thre, out, err);
-    }
-    std::vector<char> all(total);      // one copy for many short sequences; it lives until the scan's last wait has returned
-    for (int i = 0; i < n_seqs; ++i)
-        if (lens[i]) memcpy(all.data() + offs[i], seqs[i], (size_t)lens[i]);
-    if (total) HIPCHK(hipMemcpyAsync(d_text, all.data(), total, hipMemcpyHostToDevice, T.stream));
-    return variant_scan_device(T, n_seqs, d_text, offs.data(), thre, out, err);
+    HostText H;
+    if (pack_host_text(T, Table::WS_VARIANTS, n_seqs, seqs, lens, "variant scan", H, err)) return -1;
+    return variant_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, out, err);
 }
 
 }  // namespace jk

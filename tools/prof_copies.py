@@ -5,7 +5,7 @@
 R = the counted read table, A = the assembly counted into a table of its own, the text = the assembly as ONE sequence.
 trace: each of these after a warm-up call of the same kind, all in one process so that one kernel trace holds them: report_scan_kernel over
        the text (the yardstick: the same tile, ONE random probe per window), then the copy scan (copies_scan_kernel: two probes per window;
-       copies_heads_kernel, copies_stitch_kernel)
+       scan_heads_kernel, scan_stitch_kernel: the dense scans' shared ones)
 time:  no profiler: jasper_copyrep_seconds of five scans after a warm-up, and their wall time
 summarize DIR: per kernel of a rocprofv3 --kernel-trace CSV under DIR, the durations of its dispatches in order (the measured call's are the
        last ones), and the ratio copies_scan_kernel / report_scan_kernel of the last dispatches
@@ -27,7 +27,7 @@ def summarize(d):
         rows = sorted(csv.DictReader(open(fn)), key=lambda r: int(r["Start_Timestamp"]))
         for r in rows:
             name = r["Kernel_Name"].split("(")[0]
-            if "copies_" in name or "report_" in name:
+            if "copies_" in name or "report_" in name or "scan_heads" in name or "scan_stitch" in name:
                 out.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for name, us in sorted(out.items()):
         print(json.dumps({"kernel": name, "dispatches_us": [round(x, 1) for x in us]}))

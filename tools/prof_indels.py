@@ -64,7 +64,7 @@ def main():
     thr = int(polisher.threshold_from_histo_rows(r.histo_rows())[0])
     ri = r.info()
     text = [0, offs[-1]]
-    head = {"mode": mode, "k": bench.K, "bases": asm_len, "thr": thr, "r_slots": ri["slots"], "r_distinct": ri["distinct"]}
+    head = {"mode": mode, "lib": os.environ.get("JASPER_AMD_LIB", ""), "k": bench.K, "bases": asm_len, "thr": thr, "r_slots": ri["slots"], "r_distinct": ri["distinct"]}
     if mode == "trace":
         for _ in range(2):
             vs = r.variant_scan_device(d_asm, text, thr)

@@ -25,7 +25,7 @@ def summarize(d):
         rows = sorted(csv.DictReader(open(fn)), key=lambda r: int(r["Start_Timestamp"]))
         for r in rows:
             name = r["Kernel_Name"].split("(")[0]
-            if "report_" in name or "scan_classify" in name:
+            if "report_" in name or "scan_heads" in name or "scan_stitch" in name or "scan_classify" in name:
                 out.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for name, us in sorted(out.items()):
         print(json.dumps({"kernel": name, "dispatches_us": [round(x, 1) for x in us]}))
@@ -58,7 +58,7 @@ def main():
             wall.append(time.perf_counter() - t0)
             secs.append(rep.seconds)
         tot = rep.counts[0]
-        print(json.dumps({"mode": mode, "bases": asm_len, "thr": thr, "counts": tot, "runs": len(rep.runs), "retried": rep.retried,
+        print(json.dumps({"mode": mode, "lib": os.environ.get("JASPER_AMD_LIB", ""), "bases": asm_len, "thr": thr, "counts": tot, "runs": len(rep.runs), "retried": rep.retried,
                           "report_seconds": secs[1:], "wall_seconds": wall[1:], "gbp_per_s": [asm_len / s / 1e9 for s in secs[1:]]}))
     t.close()
 

@@ -28,7 +28,7 @@ def summarize(d):
         rows = sorted(csv.DictReader(open(fn)), key=lambda r: int(r["Start_Timestamp"]))
         for r in rows:
             name = r["Kernel_Name"].split("(")[0]
-            if "variants_" in name or "report_" in name:
+            if "variants_" in name or "report_" in name or "scan_heads" in name or "scan_stitch" in name:
                 out.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for name, us in sorted(out.items()):
         print(json.dumps({"kernel": name, "dispatches_us": [round(x, 1) for x in us]}))
