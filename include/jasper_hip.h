@@ -420,8 +420,8 @@ void jasper_varscan_free(jasper_varscan *r);
  * Records are ordered by (seq, pos, type, len, base); the key is unique, so the list is identical on every call.  Sequences shorter than
  * 2k-2 (empty ones too) are legal and give zeros.  The table is not modified.
  *
- * Limits: insertions of mixed bases and lengths above 16 are not reported, and, as for substitutions, two differences less than k apart
- * hide each other.
+ * Limits: insertions of mixed bases are reported only by jasper_indel_scan_mixed below, lengths above 16 are not reported, and, as for
+ * substitutions, two differences less than k apart hide each other.
  *
  * On the device the variant scan's dense scan runs unchanged: its candidate (p, x) -- the window that ends at p is solid with its last
  * base replaced by x -- is the first k-mer of A for ins(p, x, L) and for del(p, L) with s[p+L] == x.  One more kernel tests these
@@ -456,6 +456,55 @@ double jasper_indelscan_check_seconds(const jasper_indelscan *r);
 int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n);
 int jasper_indelscan_retried(const jasper_indelscan *r);
 void jasper_indelscan_free(jasper_indelscan *r);
+
+/* Mixed-base insertions: jasper_indel_scan plus the insertions of ANY string of up to max_len bases.
+ *
+ * What it replaces: nothing -- an EXTENSION of the extension above.  jasper_indel_scan lists every deletion but only the insertions of
+ * one repeated base, so of a pair of haplotypes that differ by a mixed string it sees the difference from one side only.  The
+ * reference's fix_insert / fix_del repair such insertions inside the walk and report nothing.  Notation as above, FRONT =
+ * JASPER_INDEL_FRONT = 64:
+ *   ins(p, y)      for a string y of L bases, 1 <= L <= max_len <= 16, with y[0] != s[p] (the right-most position: y before p with
+ *                  s[p] == y[0] is y[1:] + y[0] before p + 1).
+ *                  evaluated  exactly when ins(p, x, L) is: k-1 <= p <= n-k+1 and all bytes s[p-k+1 .. p+k-2] are bases
+ *                  alternative string  A = F + y + s[p .. p+k-2], of k+L-1 windows
+ *   the search     at a candidate (p, x), evaluated and with cnt(F + x) >= thre:  S_1 = {x};  for t >= 2
+ *                      S_t = { yz : y in S_(t-1), z in ACGT, cnt(the last k bytes of F + y + z) >= thre }
+ *                  -- the prefixes of length t all of whose windows so far are solid.  It runs t = 1, 2, .. and ends at the first of:
+ *                  t > max_len; S_t empty; |S_t| > FRONT.  In the last case the site is COMPLEX: counted once per (p, x), and nothing
+ *                  of length >= t is reported there.  Exactly FRONT prefixes are still searched.
+ *   record         every y in S_t of a level that was reached, with y != x^t, whose k-1 windows t .. k+t-2 of A are >= thre as well:
+ *                  {seq, pos = p, len = t, bases = y, ref_min, alt_min, kind}.  alt_min = the minimum over all k+t-1 windows of A;
+ *                  ref_min = the minimum over the k-1 windows of s that start at p-k+1 .. p-1, as for ins(p, x, L); kind het (1) when
+ *                  ref_min >= thre, error (2) otherwise.
+ *   per sequence   three counters: mixed_het, mixed_error, complex
+ * The rule is one of sets, not of a search order: the list, ordered by (seq, pos, len, y), is identical on every call.  Same-base
+ * insertions x^t and all deletions stay what jasper_indel_scan reports (complex sites do not touch them); the mixed list never repeats
+ * them.  Every accessor above returns for such a result exactly what it returns for jasper_indel_scan on the same input.
+ *
+ * On the device one more kernel runs between the indel check and the substitution check: one wave per candidate, a breadth-first
+ * search with the frontier S_t held one prefix per lane.
+ *   jasper_indel_scan_mixed, _mixed_device   as jasper_indel_scan / _device
+ *   jasper_indelscan_mixed_counts    out3 = mixed_het, mixed_error, complex of one sequence
+ *   jasper_indelscan_mixed_records   the mixed record list (owned by the result)
+ *   jasper_indelscan_mixed_seconds   device time of the search kernel (part of jasper_indelscan_seconds)
+ *   jasper_indelscan_mixed_lookups   table lookups it made;  jasper_indelscan_mixed_retried: it was repeated with a larger list
+ *   jasper_indel_front               JASPER_INDEL_FRONT as the library was built
+ * For a result of jasper_indel_scan / _device the mixed accessors give zeros and n = 0. */
+#define JASPER_INDEL_FRONT 64
+typedef struct jasper_mixed_ins {
+    int64_t pos;
+    uint32_t seq, ref_min, alt_min, bases /* base i of y in bits 2i..2i+1, A C G T = 0 1 2 3, 0 above 2*len */;
+    uint16_t len;
+    uint8_t kind /* 1 het, 2 error */, pad[5] /* 0 */;
+} jasper_mixed_ins; /* 32 B */
+int jasper_indel_scan_mixed(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out);
+int jasper_indel_scan_mixed_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out);
+int jasper_indelscan_mixed_counts(const jasper_indelscan *r, int seq, uint64_t out3[3]);   /* mixed_het, mixed_error, complex */
+int jasper_indelscan_mixed_records(const jasper_indelscan *r, const jasper_mixed_ins **recs, uint64_t *n);
+double jasper_indelscan_mixed_seconds(const jasper_indelscan *r);
+int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n);
+int jasper_indelscan_mixed_retried(const jasper_indelscan *r);
+int jasper_indel_front(void);
 
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1

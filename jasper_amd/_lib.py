@@ -54,6 +54,14 @@ class Indel(C.Structure):
 
 assert C.sizeof(Indel) == 32
 
+
+class MixedIns(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("bases", C.c_uint32), ("len", C.c_uint16),
+                ("kind", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+assert C.sizeof(MixedIns) == 32
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -166,6 +174,14 @@ SYMBOLS = {
     "jasper_indelscan_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "jasper_indelscan_retried": (C.c_int, [_P]),
     "jasper_indelscan_free": (None, [_P]),
+    "jasper_indel_scan_mixed": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_indel_scan_mixed_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_indelscan_mixed_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_mixed_records": (C.c_int, [_P, C.POINTER(C.POINTER(MixedIns)), C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_mixed_seconds": (C.c_double, [_P]),
+    "jasper_indelscan_mixed_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_mixed_retried": (C.c_int, [_P]),
+    "jasper_indel_front": (C.c_int, []),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

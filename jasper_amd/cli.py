@@ -3,7 +3,7 @@ sentinel files and log lines; the Jellyfish + per-batch python processes are rep
 polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
-                            [--indels [--indel-max-len N]]
+                            [--indels [--indel-max-len N] [--indel-mixed]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -106,6 +106,7 @@ class Options:
         self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
         self.variants = False
         self.indels = False
+        self.indel_mixed = False
         self.indel_max_len = None    # --indel-max-len: longest insertion / deletion the indel scan tries (default 4, at most 16)
 
 
@@ -163,6 +164,8 @@ def parse_args(argv):
             o.variants = True
         elif key == "--indels":                                        # extension: insertions and deletions the reads hold against the contigs (_indels)
             o.indels = True
+        elif key == "--indel-mixed":                                   # extension: the indel scan also lists insertions of mixed bases
+            o.indel_mixed = True
         elif key == "--indel-max-len":
             o.indel_max_len = nxt; i += 1
         else:
@@ -1215,13 +1218,19 @@ def indel_flags(max_len):
     return int(max_len)
 
 
-def scan_indels(table, contigs, thre, max_len):
+def indel_mixed_flag(mixed, indels):
+    """--indel-mixed is a mode of --indels: alone it ends the run"""
+    if mixed and not indels:
+        error_exit("--indel-mixed needs --indels: it adds the insertions of mixed bases to the indel scan")
+
+
+def scan_indels(table, contigs, thre, max_len, mixed=False):
     """the indel scan of whole contigs [(name token, sequence)] -> (names, lengths, IndelScan), whose .variants is what scan_variants
     gives; exits on a threshold of 0, which would call every alternative solid"""
     from . import report
     if thre < 1:
         error_exit("--indels needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.indel_scan([s for _, s in contigs], thre, max_len)
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], (table.indel_scan([s for _, s in contigs], thre, max_len, mixed=True) if mixed else table.indel_scan([s for _, s in contigs], thre, max_len))
 
 
 def _indels(o, table):
@@ -1235,8 +1244,9 @@ def _indels(o, table):
     max_len = indel_flags(o.indel_max_len)
     thresh = int(open("threshold.txt").read().split()[0])
     asm0, asm1 = read_assembly(o.query), read_assembly(qfn + ".polished.fasta")
-    names, len0, is0 = scan_indels(table, asm0, thresh, max_len)
-    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len)
+    mixed = o.indel_mixed
+    names, len0, is0 = scan_indels(table, asm0, thresh, max_len, mixed)
+    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len, mixed)
     if o.variants:
         vs0, vs1 = is0.variants, is1.variants
         len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
@@ -1245,13 +1255,25 @@ def _indels(o, table):
         variants.write_atomic(qfn + ".variants.after.vcf", variants.vcf_text(k, thresh, names1, len1, vs1.records))
         log(variants.log_text(vs0.counts, cnt1a))
     len1a, cnt1a = report.align(names, names1, len1, is1.counts)
-    indels.write_atomic(qfn + ".indels.tsv", indels.indels_tsv_text(names, [("before", len0, is0.counts), ("after", len1a, cnt1a)]))
-    indels.write_atomic(qfn + ".indels.before.vcf", indels.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], is0.records))
-    indels.write_atomic(qfn + ".indels.after.vcf", indels.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], is1.records))
+    if mixed:
+        mix1a = report.align(names, names1, len1, is1.mixed.counts)[1]
+        stages = [("before", len0, is0.counts, is0.mixed.counts), ("after", len1a, cnt1a, mix1a)]
+    else:
+        stages = [("before", len0, is0.counts), ("after", len1a, cnt1a)]
+    indels.write_atomic(qfn + ".indels.tsv", indels.indels_tsv_text(names, stages))
+    indels.write_atomic(qfn + ".indels.before.vcf", indels.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], is0.records,
+                                                                    is0.mixed.records if mixed else None))
+    indels.write_atomic(qfn + ".indels.after.vcf", indels.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], is1.records,
+                                                                   is1.mixed.records if mixed else None))
     log(indels.log_text(is0.counts, cnt1a))
+    if mixed:
+        log(indels.mixed_log_text(is0.mixed.counts, mix1a))
     if _timing_on():
         sys.stderr.write("[indels] device seconds: before %.6f (check %.6f) after %.6f (check %.6f); candidates %d %d\n" %
                          (is0.seconds, is0.check_seconds, is1.seconds, is1.check_seconds, is0.variants.candidates, is1.variants.candidates))
+        if mixed:
+            sys.stderr.write("[indels] mixed search device seconds: before %.6f after %.6f; lookups %d %d\n" %
+                             (is0.mixed.seconds, is1.mixed.seconds, is0.mixed.lookups, is1.mixed.lookups))
 
 
 def _init_multi(o):
@@ -1289,6 +1311,7 @@ def run(argv):
         copies_flags(o.peak, o.copies_min_run)      # (a bad value ends the run before it starts, not after the polishing)
     if o.indels:
         indel_flags(o.indel_max_len)
+    indel_mixed_flag(o.indel_mixed, o.indels)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177

@@ -872,13 +872,17 @@ void jasper_varscan_free(jasper_varscan *r) { delete r; }
 static_assert(sizeof(jasper_indel) == sizeof(Indel) && offsetof(jasper_indel, len) == offsetof(Indel, len) && offsetof(jasper_indel, type) == offsetof(Indel, type) &&
                   offsetof(jasper_indel, base) == offsetof(Indel, base) && offsetof(jasper_indel, kind) == offsetof(Indel, kind),
               "jasper_indel is Indel");
+static_assert(sizeof(jasper_mixed_ins) == sizeof(MixedIns) && offsetof(jasper_mixed_ins, bases) == offsetof(MixedIns, bases) &&
+                  offsetof(jasper_mixed_ins, len) == offsetof(MixedIns, len) && offsetof(jasper_mixed_ins, kind) == offsetof(MixedIns, kind),
+              "jasper_mixed_ins is MixedIns");
+static_assert(JASPER_INDEL_FRONT == INDEL_FRONT, "the header's cap is the kernel's");
 static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
-                          int max_len, jasper_indelscan **out) {
+                          int max_len, bool mixed, jasper_indelscan **out) {
     if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
     *out = nullptr;
     jasper_indelscan *r = new jasper_indelscan();
-    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, r->r, g_err)
-                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, r->r, g_err);
+    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, mixed, r->r, g_err)
+                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, mixed, r->r, g_err);
     if (rc) { delete r; return JASPER_ERR; }
     r->var.r = std::move(r->r.var);
     *out = r;
@@ -886,11 +890,19 @@ static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, 
 }
 int jasper_indel_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, out);
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, false, out);
 }
 int jasper_indel_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, out);
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, false, out);
+}
+int jasper_indel_scan_mixed(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, true, out);
+}
+int jasper_indel_scan_mixed_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, true, out);
 }
 int jasper_indelscan_num_seqs(const jasper_indelscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
 int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
@@ -913,6 +925,25 @@ int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n) {
     return JASPER_OK;
 }
 int jasper_indelscan_retried(const jasper_indelscan *r) { return r ? r->r.retried : 0; }
+int jasper_indelscan_mixed_counts(const jasper_indelscan *r, int seq, uint64_t out3[3]) {
+    if (!r || !out3 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 3; ++i) out3[i] = r->r.mixed ? r->r.mixed_counts[3 * (size_t)seq + i] : 0;
+    return JASPER_OK;
+}
+int jasper_indelscan_mixed_records(const jasper_indelscan *r, const jasper_mixed_ins **recs, uint64_t *n) {
+    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *recs = reinterpret_cast<const jasper_mixed_ins *>(r->r.mixed_recs.data());
+    *n = r->r.mixed_recs.size();
+    return JASPER_OK;
+}
+double jasper_indelscan_mixed_seconds(const jasper_indelscan *r) { return r ? r->r.mixed_seconds : 0.0; }
+int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n) {
+    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = r->r.mixed_lookups;
+    return JASPER_OK;
+}
+int jasper_indelscan_mixed_retried(const jasper_indelscan *r) { return r ? r->r.mixed_retried : 0; }
+int jasper_indel_front(void) { return INDEL_FRONT; }
 void jasper_indelscan_free(jasper_indelscan *r) { delete r; }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // indels.hip -- indel scan: same-base insertions and deletions of up to 16 bytes that the reads hold against the sequence, as per-sequence
-// counters and one record per hypothesis that is solid (semantics: include/jasper_hip.h, jasper_indel_scan).
+// counters and one record per hypothesis that is solid (semantics: include/jasper_hip.h, jasper_indel_scan); on request also the insertions
+// of mixed bases (jasper_indel_scan_mixed).
 //
 // An extension.  The reference repairs such differences inside its walk (src/jasper.py: fix_insert, fix_del, fix_same_base_del,
 // fix_same_base_insertion) and reports nothing.  The dense scan is that of variants.hip, unchanged: its candidate (p, x) -- the window
@@ -24,6 +25,22 @@
 //                         The hypotheses that passed are bits of a wave-uniform mask (bit L - 1: ins L, bit 15 + L: del L); lane b keeps
 //                         the minima of bit b and writes its record.  Places are reserved with one returning cursor add per wave, and a
 //                         wave writes all its records or none.
+//
+//   indels_mixed_kernel   (only when the caller asks for mixed insertions) one wave per candidate (p, x): a bounded breadth-first search
+//                         over the inserted string y, y[0] == x.  The frontier S_t -- the prefixes of length t all of whose windows of
+//                         F + y are solid -- is at most INDEL_FRONT = 64 prefixes, one per lane: y as 2-bit codes in a word (first base
+//                         in the highest pair, so that lane order is lexicographic order) and the minimum over its t windows.
+//                           rejoin   per level: window t of F + y + s[p ..], the first that holds s[p], lane i for its own prefix
+//                                    (128-bit arithmetic on F's k-mer, one lookup per prefix that is not x^t); then, in a wave-uniform
+//                                    loop over the prefixes that passed, windows t+1 .. k+t-2 cut out of the planes with y put in
+//                                    (pl_ins_y), lane j owning window t + 1 + j  (k - 2 lookups)
+//                           ref      windows 0 .. k-2 of s, once per candidate and only when something passed
+//                           extend   (prefix, z) spread over four lanes each, sixteen prefixes a round: the last k bases of F + y + z.
+//                                    The ballot of a round is in (parent, z) order already, so a child's place is a popcount; it moves
+//                                    through a per-wave LDS strip of 64 x 8 bytes.  More than 64 children: the site is complex, counted
+//                                    once, and the wave stops there.  Four lookups per prefix.
+//                         The records of a level (at most 64, lane i its own) take one returning cursor add; a level writes all its
+//                         records or none.  Same-base strings x^t stay in the frontier but are never written: they are the check's.
 //
 // The record list starts at candidates + 4096 entries; a check that found more has counted them and is repeated once with exactly that
 // room (run_counted, scan_tile.hpp: the dense scans' repeat, here around the check).  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
@@ -213,6 +230,164 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
     if (lane == 0 && nlook) atomicAdd(&ctl[IC_LOOKUPS], nlook);
 }
 
+// ---- mixed-base insertions ------------------------------------------------------------------------------------------------------------
+enum { MC_LOOKUPS = 1, MC_COMPLEX = 2 };                                 // control words 1 and 2: table lookups made; complex sites
+
+__device__ __forceinline__ uint32_t id_squeeze(uint32_t x) {      // bit 2i -> bit i
+    x &= 0x55555555u;
+    x = (x | (x >> 1)) & 0x33333333u;
+    x = (x | (x >> 2)) & 0x0F0F0F0Fu;
+    x = (x | (x >> 4)) & 0x00FF00FFu;
+    x = (x | (x >> 8)) & 0x0000FFFFu;
+    return x;
+}
+// pl_ins for any string: F + y + the context from k - 1 on; ybit = that plane of y (bit j = base j, L bits)
+__device__ __forceinline__ Plane pl_ins_y(Plane t, unsigned long long m, int k, int L, unsigned long long ybit) {
+    Plane u = t;
+    u.a &= ~m;
+    u = pl_shl(u, L);
+    u.a |= t.a & m;
+    u.a |= ybit << (k - 1);
+    u.b |= ybit >> (64 - (k - 1));                      // (1 <= k - 1 <= 63)
+    return u;
+}
+__device__ __forceinline__ uint32_t id_min(uint32_t a, uint32_t b) { return b < a ? b : a; }
+
+__global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int max_len,
+                                                           const Variant *__restrict__ cand, uint64_t ncand, MixedIns *__restrict__ out, unsigned long long cap,
+                                                           unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ cplx) {
+    __shared__ uint2 s_strip[4][INDEL_FRONT];           // a wave's next frontier: (y, running minimum)
+    const int lane = threadIdx.x & 63;
+    uint2 *strip = s_strip[threadIdx.x >> 6];
+    const int k = R.k;
+    const int CL = 2 * k - 2;                           // context bytes: at most 126
+    const u128 kmask = maskbits(2 * k);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint64_t nwv = (uint64_t)gridDim.x * 4;
+    unsigned long long nlook = 0, ncomplex = 0;         // (wave-uniform)
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ncand; i += nwv) {
+        const int64_t p = cand[i].pos;
+        const uint32_t seq = cand[i].seq;
+        const int x = cand[i].alt & 3;
+        const int64_t o0 = offs[seq];
+        const int64_t n = offs[seq + 1] - o0;
+        const uint8_t *__restrict__ txt = text + o0;
+        if (p < k - 1 || p >= n) continue;              // (wave-uniform; the scan writes no such candidate)
+        const int64_t b0 = p - k + 1;
+        int c0 = -1, c1 = -1;                           // codes of context bytes lane and lane + 64
+        if (lane < CL && b0 + lane < n) c0 = code(txt[b0 + lane]);
+        if (lane + 64 < CL && b0 + lane + 64 < n) c1 = code(txt[b0 + lane + 64]);
+        const unsigned long long n0 = __ballot(c0 < 0), n1 = __ballot(c1 < 0);
+        const int bases = n0 ? (int)__builtin_ctzll(n0) : n1 ? 64 + (int)__builtin_ctzll(n1) : 128;
+        const int refc = __shfl(c0, k - 1);
+        if (bases < CL || refc == x) continue;          // not evaluated
+        const Plane clo = {__ballot(c0 > 0 && (c0 & 1)), __ballot(c1 > 0 && (c1 & 1)), 0ull}, chi = {__ballot(c0 > 0 && (c0 & 2)), __ballot(c1 > 0 && (c1 & 2)), 0ull};
+        const unsigned long long fm = (1ull << (k - 1)) - 1ull;
+        const u128 F = shr(id_kmer(clo, chi, 0, k), 2); // the k - 1 bases before p
+        // level 1: S_1 = {x}
+        uint32_t yk = (uint32_t)x, mn = 0xFFFFFFFFu;    // lane i < nf: prefix i, first base in the highest pair, and the minimum over its windows
+        int nf = 1;
+        if (lane == 0) mn = id_count(R, band(bor(shl(F, 2), mk(0, (uint64_t)x)), kmask), k);
+        nlook += 1;
+        if ((uint32_t)__shfl(mn, 0) < thre) continue;
+        bool have_ref = false;
+        uint32_t rmin = 0;
+        for (int t = 1;; ++t) {
+            // rejoin: window t, lane i for prefix i
+            const uint32_t xt = (0x55555555u * (uint32_t)x) & (t == 16 ? 0xFFFFFFFFu : (1u << (2 * t)) - 1u);
+            const bool act = lane < nf && yk != xt;
+            const unsigned long long actm = __ballot(act);
+            uint32_t a = 0xFFFFFFFFu;
+            if (act) {
+                const u128 w = band(bor(shl(F, 2 * t), mk(0, yk)), kmask);      // the last k bases of F + y
+                a = id_count(R, band(bor(shl(w, 2), mk(0, (uint64_t)refc)), kmask), k);
+            }
+            nlook += (unsigned)__popcll(actm);
+            a = id_min(a, mn);
+            const unsigned long long P = __ballot(act && a >= thre);
+            unsigned long long recm = 0;                // (wave-uniform) bit i: prefix i is a record
+            uint32_t my_amin = a;
+            if (k > 2) {
+                for (unsigned long long q = P; q; q &= q - 1ull) {
+                    const int j = (int)__builtin_ctzll(q);
+                    const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)yk, j), aj = (uint32_t)__builtin_amdgcn_readlane((int)a, j);
+                    const unsigned long long rv = brev64((unsigned long long)yj) >> (64 - 2 * t);      // base b: its high bit at 2b, its low bit at 2b + 1
+                    const unsigned long long yhi = id_squeeze((uint32_t)rv), ylo = id_squeeze((uint32_t)(rv >> 1));
+                    uint32_t b = 0xFFFFFFFFu;
+                    if (lane < k - 2) b = id_count(R, id_kmer(pl_ins_y(clo, fm, k, t, ylo), pl_ins_y(chi, fm, k, t, yhi), t + 1 + lane, k), k);
+                    nlook += (unsigned)(k - 2);
+                    b = id_min(wave_min32(b), aj);
+                    if (b >= thre) {
+                        recm |= 1ull << j;
+                        if (lane == j) my_amin = b;
+                    }
+                }
+            } else {
+                recm = P;
+            }
+            if (recm) {
+                if (!have_ref) {                        // windows 0 .. k-2 of s, once
+                    uint32_t r = 0xFFFFFFFFu;
+                    if (lane < k - 1) r = id_count(R, id_kmer(clo, chi, lane, k), k);
+                    nlook += (unsigned)(k - 1);
+                    rmin = wave_min32(r);
+                    have_ref = true;
+                }
+                unsigned long long base = 0;
+                const unsigned total = __popcll(recm);
+                if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
+                base = __shfl(base, 0);
+                if (base + total <= cap && ((recm >> lane) & 1ull)) {      // (a level writes all its records or none)
+                    MixedIns v;
+                    v.pos = p;
+                    v.seq = seq;
+                    v.ref_min = rmin;
+                    v.alt_min = my_amin;
+                    v.bases = (uint32_t)(revpairs64((uint64_t)yk) >> (64 - 2 * t));      // base i in bits 2i, 2i + 1
+                    v.len = (uint16_t)t;
+                    v.kind = rmin >= thre ? VK_HET : VK_ERROR;
+                    for (int q = 0; q < 5; ++q) v.pad[q] = 0;
+                    out[base + __popcll(recm & below)] = v;
+                }
+            }
+            if (t >= max_len) break;
+            // extend: sixteen prefixes a round, (prefix, z) on lane 4 * prefix + z
+            int tot = 0;
+            for (int r0 = 0; r0 < nf; r0 += 16) {
+                const int src = r0 + (lane >> 2);       // <= 63
+                const uint32_t ny = ((uint32_t)__shfl(yk, src) << 2) | (uint32_t)(lane & 3), pm = (uint32_t)__shfl(mn, src);
+                uint32_t c = 0;
+                if (src < nf) c = id_count(R, band(bor(shl(F, 2 * (t + 1)), mk(0, ny)), kmask), k);
+                const bool ok = src < nf && c >= thre;
+                const unsigned long long B = __ballot(ok);
+                const int at = tot + __popcll(B & below);
+                if (ok && at < INDEL_FRONT) strip[at] = make_uint2(ny, id_min(pm, c));
+                tot += __popcll(B);
+            }
+            nlook += 4u * (unsigned)nf;
+            if (tot > INDEL_FRONT) {                    // complex: nothing of length > t is reported here
+                ++ncomplex;
+                if (lane == 0) atomicAdd(&cplx[seq], 1ull);
+                break;
+            }
+            if (tot == 0) break;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (lane < tot) {
+                const uint2 v = strip[lane];
+                yk = v.x;
+                mn = v.y;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            nf = tot;
+        }
+    }
+    if (lane == 0 && nlook) atomicAdd(&ctl[MC_LOOKUPS], nlook);
+    if (lane == 0 && ncomplex) atomicAdd(&ctl[MC_COMPLEX], ncomplex);
+}
+
 static int indel_check_args(const Table &T, uint32_t thre, int max_len, std::string &err) {
     if (thre < 1) { err = "indel scan: the threshold (thre) must be at least 1"; return -1; }
     if (T.k < 2) { err = "indel scan: k must be at least 2"; return -1; }
@@ -220,7 +395,7 @@ static int indel_check_args(const Table &T, uint32_t thre, int max_len, std::str
     return 0;
 }
 
-int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, IndelOut &out, std::string &err) {
+int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err) {
     if (n_seqs < 0 || (n_seqs && !offsets)) { err = "indel scan: bad arguments"; return -1; }
     if (indel_check_args(T, thre, max_len, err)) return -1;
     HIPCHK(hipSetDevice(T.device));
@@ -228,6 +403,8 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
     out = IndelOut();
     out.counts.assign((size_t)n_seqs * 4, 0);
     out.var.counts.assign((size_t)n_seqs * 3, 0);
+    out.mixed = mixed;
+    if (mixed) out.mixed_counts.assign((size_t)n_seqs * 3, 0);
     VariantStage S;
     if (variant_scan_stage(T, n_seqs, d_text, offsets, thre, "indel scan", out.var, S, err)) return -1;
     if (S.ntiles == 0) return 0;
@@ -252,8 +429,38 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
         if (!out.recs.empty()) HIPCHK(hipMemcpyAsync(out.recs.data(), d_rec, out.recs.size() * sizeof(Indel), hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
     }
+    std::vector<unsigned long long> cplx;
+    if (ncand && mixed) {
+        const int W = Table::WS_MIXED;
+        const size_t words = SC_WORDS + (size_t)n_seqs;      // the control words, then the complex sites per sequence
+        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 1, words * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
+        if (!d_ctl) return -1;
+        MixedIns *d_rec = nullptr;
+        auto search = [&](unsigned long long cap) {
+            d_rec = (MixedIns *)T.workspace(W, cap * sizeof(MixedIns), err);
+            if (!d_rec) return -1;
+            hipLaunchKernelGGL(indels_mixed_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, max_len,
+                               S.d_cand, ncand, d_rec, cap, d_ctl, d_ctl + SC_WORDS);
+            return 0;
+        };
+        if (run_counted(st, d_ctl, words, d_ctl, ncand + 4096, "indel scan: the number of mixed insertions changed between two searches", ctl, out.mixed_seconds,
+                        out.mixed_retried, err, search))
+            return -1;
+        out.mixed_lookups = ctl[MC_LOOKUPS];
+        out.mixed_recs.resize(ctl[SC_CURSOR]);
+        cplx.resize((size_t)n_seqs);
+        if (!out.mixed_recs.empty()) HIPCHK(hipMemcpyAsync(out.mixed_recs.data(), d_rec, out.mixed_recs.size() * sizeof(MixedIns), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cplx.data(), d_ctl + SC_WORDS, cplx.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(jk_stream_wait(st));
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < cplx.size(); ++i) {
+            out.mixed_counts[3 * i + 2] = cplx[i];
+            sum += cplx[i];
+        }
+        if (sum != ctl[MC_COMPLEX]) { err = "indel scan: the complex sites per sequence do not add up"; return -1; }
+    }
     if (variant_check_stage(T, n_seqs, d_text, thre, "indel scan", S, out.var, err)) return -1;
-    out.seconds = out.var.seconds + out.check_seconds;
+    out.seconds = out.var.seconds + out.check_seconds + out.mixed_seconds;
     std::sort(out.recs.begin(), out.recs.end(), [](const Indel &a, const Indel &b) {
         return a.seq != b.seq ? a.seq < b.seq : a.pos != b.pos ? a.pos < b.pos : a.type != b.type ? a.type < b.type : a.len != b.len ? a.len < b.len : a.base < b.base;
     });
@@ -264,15 +471,31 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
         }
         ++out.counts[4 * (size_t)v.seq + 2 * (v.type - 1) + (v.kind - 1)];
     }
+    auto korder = [](const MixedIns &v) {               // y with its first base in the highest pair: numeric order is lexicographic order
+        uint32_t r = 0;
+        for (int i = 0; i < (int)v.len; ++i) r = (r << 2) | ((v.bases >> (2 * i)) & 3u);
+        return r;
+    };
+    for (const MixedIns &v : out.mixed_recs) {
+        if (v.seq >= (uint32_t)n_seqs || v.pos < 0 || (v.kind != VK_HET && v.kind != VK_ERROR) || v.len < 1 || (int)v.len > max_len ||
+            (v.len < 16 && (v.bases >> (2 * v.len)) != 0u)) {
+            err = "indel scan: a mixed insertion the search cannot have written";
+            return -1;
+        }
+        ++out.mixed_counts[3 * (size_t)v.seq + (v.kind - 1)];
+    }
+    std::sort(out.mixed_recs.begin(), out.mixed_recs.end(), [&](const MixedIns &a, const MixedIns &b) {
+        return a.seq != b.seq ? a.seq < b.seq : a.pos != b.pos ? a.pos < b.pos : a.len != b.len ? a.len < b.len : korder(a) < korder(b);
+    });
     return 0;
 }
 
-int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, IndelOut &out, std::string &err) {
+int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err) {
     if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "indel scan: bad arguments"; return -1; }
     if (indel_check_args(T, thre, max_len, err)) return -1;
     HostText H;
     if (pack_host_text(T, Table::WS_INDELS, n_seqs, seqs, lens, "indel scan", H, err)) return -1;
-    return indel_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, max_len, out, err);
+    return indel_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, max_len, mixed, out, err);
 }
 
 }  // namespace jk

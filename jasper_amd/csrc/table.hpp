@@ -357,7 +357,8 @@ struct Table {
                          WS_COPIES = WS_SPECTRA + 1,                                     // the copy-number scan's buffers (copies.hip)
                          WS_VARIANTS = WS_COPIES + 8,                                    // the variant scan's buffers (variants.hip)
                          WS_INDELS = WS_VARIANTS + 8,                                    // the indel scan's text, records and control words (indels.hip)
-                         WS_SLOTS = WS_INDELS + 4;
+                         WS_MIXED = WS_INDELS + 4,                                       // the mixed-insertion search's records and control words (indels.hip)
+                         WS_SLOTS = WS_MIXED + 2;
     WsBuf ws[WS_SLOTS];   // 0..WS_POLISH_MAX-1: polisher (polish_host.hip, in allocation order); WS_COUNT..+3: partitioned counting
     hipStream_t polish_stream[POLISH_LANES_MAX] = {nullptr, nullptr, nullptr, nullptr};      // [0] unused (= stream); created on first use
     hipEvent_t polish_ev = nullptr;

@@ -6,7 +6,12 @@ jasper_indel_scan) lists the positions of the contigs where the reads hold a sol
 to `max_len` bytes: `het` when the contig's own sequence is solid there too (a length difference between the haplotypes), `error`
 when only the alternative is (a length error the polisher has not repaired).
 
-Limits: insertions of mixed bases and lengths above 16 are not listed, and two differences less than k apart hide each other.
+With the mixed half of the scan (`indel_scan(.., mixed=True)`, --indel-mixed; semantics: jasper_indel_scan_mixed) the insertions of
+mixed bases are listed as well: three more columns in the TSV (mixed_het, mixed_error and complex, the sites where more than 64
+prefixes of one length were solid and the search stopped) and more `TYPE=ins` lines in the VCF.
+
+Limits: insertions of mixed bases are listed only with the mixed half, lengths above 16 are not listed, and two differences less than
+k apart hide each other.
 
 The scan reports every indel at its right-most position; the VCF writer moves it to the left-most one (`left_align`), as VCF asks.
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
@@ -17,7 +22,9 @@ TSV_HEADER = "#contig\tstage\tlength\tins_het\tins_error\tdel_het\tdel_error\n"
 KINDS = {1: "het", 2: "error"}
 TYPES = {1: "ins", 2: "del"}
 TYPE_NUMBERS = {"ins": 1, "del": 2}
+MIXED_COLUMNS = "\tmixed_het\tmixed_error\tcomplex"
 ZERO = (0, 0, 0, 0)
+ZERO3 = (0, 0, 0)
 _FOLD = {65: 65, 67: 67, 71: 71, 84: 84, 97: 65, 99: 67, 103: 71, 116: 84}      # ACGTacgt -> ACGT
 
 
@@ -30,17 +37,34 @@ def totals(counts):
     return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
 
 
+def mixed_totals(mcounts):
+    """column sums of the (mixed_het, mixed_error, complex) of the contigs that have any"""
+    return tuple(sum(c[i] for c in mcounts if c is not None) for i in range(3))
+
+
+def _more(c3):
+    return "\t%d\t%d\t%d\n" % tuple(c3)
+
+
 def indels_tsv_text(names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and four counters, or None for a contig
     that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
-    contig `*` with the sums."""
-    out = [TSV_HEADER]
+    contig `*` with the sums.  Stages of the mixed scan are (stage name, lengths, counts, mixed counts): every row, the header
+    included, then ends in the three columns mixed_het, mixed_error, complex."""
+    mixed = any(len(st) > 3 for st in stages)
+    stages = [tuple(st) + (None,) * (4 - len(st)) for st in stages]
+    out = [TSV_HEADER[:-1] + MIXED_COLUMNS + "\n" if mixed else TSV_HEADER]
+
+    def row(name, stage, length, c, m):
+        return _row(name, stage, length, c)[:-1] + _more(m) if mixed else _row(name, stage, length, c)
+
     for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
+        for stage, lengths, counts, mc in stages:
             c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
+            m = mc[i] if mc is not None and c is not None and mc[i] is not None else ZERO3
+            out.append(row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO, m))
+    for stage, lengths, counts, mc in stages:
+        out.append(row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts), mixed_totals(mc) if mc is not None else ZERO3))
     return "".join(out)
 
 
@@ -76,9 +100,36 @@ def left_align(seq, q, typ, length, base):
     return q
 
 
-def vcf_lines(names, seqs, records):
+def _mixed_fields(r):
+    """(seq, pos, len, y, ref_min, alt_min, kind) of a record of MixedInsertions.records or of a tuple in the order of its
+    record_tuples()"""
+    if hasattr(r, "dtype"):
+        ln = int(r["len"])
+        return (int(r["seq"]), int(r["pos"]), ln, "".join("ACGT"[(int(r["bases"]) >> (2 * i)) & 3] for i in range(ln)), int(r["ref_min"]), int(r["alt_min"]),
+                int(r["kind"]))
+    seq, pos, ln, y, rmin, amin, kind = r
+    return int(seq), int(pos), int(ln), y if isinstance(y, str) else bytes(y).decode("latin-1"), int(rmin), int(amin), int(kind)
+
+
+def left_align_mixed(seq, q, y):
+    """the left-most form (q, y) of the insertion of the string y before byte q: while q > 1 and seq[q-1] is a base equal (case folded)
+    to y's last base, y is rotated -- its last base moves to its front -- and q moves one to the left"""
+    s = _bytes(seq)
+    y = y.upper()
+    while q > 1 and _FOLD.get(s[q - 1]) == ord(y[-1]):
+        y = y[-1] + y[:-1]
+        q -= 1
+    return q, y
+
+
+def vcf_lines(names, seqs, records, mixed_records=()):
     """[(seq, POS, type number, len, ALT, REF, INFO)] sorted: every record left-aligned, POS = the 1-based position of the anchor byte"""
     out = []
+    for seq, pos, ln, y, rmin, amin, kind in (_mixed_fields(r) for r in mixed_records):
+        s = _bytes(seqs[seq])
+        q, y = left_align_mixed(s, pos, y)
+        anchor = s[q - 1:q].decode("latin-1").upper()
+        out.append((seq, q, 1, ln, anchor + y, anchor, "KIND=%s;TYPE=ins;LEN=%d;RC=%d;AC=%d" % (KINDS[kind], ln, rmin, amin)))
     for seq, pos, typ, ln, base, rmin, amin, kind in (_rec_fields(r) for r in records):
         s = _bytes(seqs[seq])
         q = left_align(s, pos, typ, ln, base)
@@ -92,22 +143,25 @@ def vcf_lines(names, seqs, records):
     return out
 
 
-def vcf_text(k, thre, max_len, names, lengths, seqs, records):
+def vcf_text(k, thre, max_len, names, lengths, seqs, records, mixed_records=None):
     """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record, left-aligned and ordered by (contig,
     POS, TYPE (ins before del), LEN, ALT) whatever order they come in: name, POS, ., REF, ALT, ., .,
     KIND=het|error;TYPE=ins|del;LEN=L;RC=ref_min;AC=alt_min.  seqs[i] = contig i's sequence (the anchor and the deleted bases are
-    read from it)."""
-    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd indel scan, k=%d, threshold=%d, max_len=%d\n" % (k, thre, max_len)]
+    read from it).  mixed_records (not None: the scan had its mixed half) are the insertions of mixed bases: `TYPE=ins` lines in the
+    same order, REF = the anchor, ALT = the anchor and the inserted string."""
+    mixed = mixed_records is not None
+    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd indel scan, k=%d, threshold=%d, max_len=%d%s\n" % (k, thre, max_len, ", mixed" if mixed else "")]
     for name, ln in zip(names, lengths):
         out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
     out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="het: the contig\'s sequence and the alternative are both solid in the reads; '
                'error: only the alternative is">\n')
-    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="ins: the reads hold LEN more copies of one base; del: the reads lack LEN bytes">\n')
+    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="ins: the reads hold LEN more %s; del: the reads lack LEN bytes">\n' %
+               ("bases" if mixed else "copies of one base"))
     out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="length of the insertion or deletion">\n')
     out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
     out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
     out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
-    for seq, q, _typ, _ln, alt, ref, info in vcf_lines(names, seqs, records):
+    for seq, q, _typ, _ln, alt, ref, info in vcf_lines(names, seqs, records, mixed_records if mixed else ()):
         out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], q, ref, alt, info))
     return "".join(out)
 
@@ -115,6 +169,15 @@ def vcf_text(k, thre, max_len, names, lengths, seqs, records):
 def stage_log_text(counts):
     """`A het and B error insertions, C het and D error deletions` of one stage"""
     return "%d het and %d error insertions, %d het and %d error deletions" % totals(counts)
+
+
+def mixed_stage_log_text(mcounts):
+    """`A het and B error mixed insertions, C complex sites` of one stage"""
+    return "%d het and %d error mixed insertions, %d complex sites" % mixed_totals(mcounts)
+
+
+def mixed_log_text(mcounts0, mcounts1):
+    return "Mixed insertions: before polishing %s; after polishing %s" % (mixed_stage_log_text(mcounts0), mixed_stage_log_text(mcounts1))
 
 
 def log_text(counts0, counts1):

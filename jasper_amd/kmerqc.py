@@ -1,7 +1,7 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
-                                [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N]]
+                                [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -32,8 +32,9 @@ With --variants the contigs are also scanned for positions where the reads hold 
 
 With --indels the contigs are also scanned for same-base insertions and for deletions of up to --indel-max-len bytes (default 4, at
 most 16) that the reads hold (KmerTable.indel_scan; with --variants as well it is one scan for both), and two more files are written
-(jasper_amd/indels.py); the threshold must be at least 1.  Insertions of mixed bases, lengths above 16 and differences less than k
-apart are not listed:
+(jasper_amd/indels.py); the threshold must be at least 1.  Lengths above 16 and differences less than k apart are not listed, and
+insertions of mixed bases only with --indel-mixed (KmerTable.indel_scan(.., mixed=True): one more search kernel per scan), which adds
+the columns mixed_het, mixed_error and complex to the TSV, `TYPE=ins` lines to the VCF and one log line:
 
     PREFIX.indels.tsv        per contig one row of stage `asm`: het and error insertions, het and error deletions; then contig `*`
     PREFIX.indels.vcf        VCFv4.2, one left-aligned line per insertion or deletion: KIND=het|error;TYPE=ins|del;LEN=..
@@ -46,11 +47,11 @@ import sys
 from . import cli, copies, indels, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run",
             "--indel-max-len": "indel_max_len"}
@@ -60,8 +61,8 @@ def parse_args(argv):
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--variants", "--indels"):
-            o[key[2:]] = True
+        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed"):
+            o[key[2:].replace("-", "_")] = True
             i += 1
             continue
         if key not in keys or i + 1 >= len(argv):
@@ -89,6 +90,7 @@ def run(argv):
     if a["variants"] and given is not None and given < 1:
         cli.error_exit("--variants needs a threshold of at least 1; --threshold %d was given" % given)
     max_len = cli.indel_flags(a["indel_max_len"]) if a["indels"] else None
+    cli.indel_mixed_flag(a["indel_mixed"], a["indels"])
     if a["indels"] and given is not None and given < 1:
         cli.error_exit("--indels needs a threshold of at least 1; --threshold %d was given" % given)
     if a["jf"] is not None:
@@ -123,7 +125,7 @@ def run(argv):
             crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
         finally:
             asm.close()
-    iscan = cli.scan_indels(table, contigs, given, max_len)[2] if a["indels"] else None
+    iscan = cli.scan_indels(table, contigs, given, max_len, a["indel_mixed"])[2] if a["indels"] else None
     vscan = (iscan.variants if iscan is not None else cli.scan_variants(table, contigs, given)[2]) if a["variants"] else None
     table.close()
     prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
@@ -146,9 +148,15 @@ def run(argv):
         variants.write_atomic(prefix + ".variants.vcf", variants.vcf_text(k, given, names, lengths, vscan.records))
         cli.log("Variant scan: %s in %s.variants.vcf" % (variants.stage_log_text(vscan.counts), prefix))
     if iscan is not None:
-        indels.write_atomic(prefix + ".indels.tsv", indels.indels_tsv_text(names, [("asm", lengths, iscan.counts)]))
-        indels.write_atomic(prefix + ".indels.vcf", indels.vcf_text(k, given, max_len, names, lengths, [s for _, s in contigs], iscan.records))
+        mixed = iscan.mixed
+        indels.write_atomic(prefix + ".indels.tsv", indels.indels_tsv_text(names, [("asm", lengths, iscan.counts) + ((mixed.counts,) if mixed is not None else ())]))
+        indels.write_atomic(prefix + ".indels.vcf", indels.vcf_text(k, given, max_len, names, lengths, [s for _, s in contigs], iscan.records,
+                                                                    mixed.records if mixed is not None else None))
         cli.log("Indel scan: %s in %s.indels.vcf" % (indels.stage_log_text(iscan.counts), prefix))
+        if mixed is not None:
+            cli.log("Mixed insertions: %s in %s.indels.vcf" % (indels.mixed_stage_log_text(mixed.counts), prefix))
+            if cli._timing_on():
+                sys.stderr.write("[indels] mixed search device seconds: %.6f; lookups %d\n" % (mixed.seconds, mixed.lookups))
     return 0
 
 

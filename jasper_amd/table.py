@@ -192,14 +192,40 @@ INDEL_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "
 INDEL_TYPES = {1: "ins", 2: "del"}
 
 
+MIXED_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("bases", "<u4"), ("len", "<u2"), ("kind", "u1"), ("pad", "u1", (5,))]
+
+
+class MixedInsertions:
+    """the mixed half of an indel scan (include/jasper_hip.h: jasper_indel_scan_mixed): `counts[i]` = (mixed_het, mixed_error, complex)
+    of sequence i, `records` = numpy structured array (MIXED_DTYPE) of the insertions of mixed bases ordered by (seq, pos, len, inserted
+    string; base i of it is bits 2i..2i+1 of `bases`, A C G T = 0 1 2 3), `seconds` = device time of the search kernel, `lookups` =
+    table lookups it made, `retried` = it was repeated with a larger record list."""
+
+    def __init__(self, counts, records, seconds, lookups, retried):
+        self.counts = counts
+        self.records = records
+        self.seconds = seconds
+        self.lookups = lookups
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, MixedInsertions) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
+
+    def record_tuples(self):
+        """[(seq, pos, len, y, ref_min, alt_min, kind)], y = the inserted string"""
+        return [(int(r["seq"]), int(r["pos"]), int(r["len"]), "".join("ACGT"[(int(r["bases"]) >> (2 * i)) & 3] for i in range(int(r["len"]))),
+                 int(r["ref_min"]), int(r["alt_min"]), int(r["kind"])) for r in self.records]
+
+
 class IndelScan:
     """indel scan of a set of sequences against the reads' table (include/jasper_hip.h: jasper_indel_scan): `counts[i]` = (ins_het,
     ins_error, del_het, del_error) of sequence i, `records` = numpy structured array (INDEL_DTYPE) of the insertions (type 1) and
     deletions (type 2) ordered by (seq, pos, type, len, base), `variants` = the VariantScan of the same input (one dense scan serves
     both), `seconds` = device time of the scan and all check kernels, `check_seconds` = of the indel check alone, `lookups` = table
-    lookups that check made.  The files made from it: jasper_amd/indels.py."""
+    lookups that check made, `mixed` = None or the MixedInsertions of a scan with mixed=True (not part of ==: a scan with it equals
+    the scan without it).  The files made from it: jasper_amd/indels.py."""
 
-    def __init__(self, counts, records, variants, seconds, check_seconds, lookups, retried):
+    def __init__(self, counts, records, variants, seconds, check_seconds, lookups, retried, mixed=None):
         self.counts = counts
         self.records = records
         self.variants = variants
@@ -207,6 +233,7 @@ class IndelScan:
         self.check_seconds = check_seconds
         self.lookups = lookups
         self.retried = retried
+        self.mixed = mixed
 
     def __eq__(self, other):
         return (isinstance(other, IndelScan) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
@@ -693,28 +720,49 @@ class KmerTable:
         return self._wrap_varscan(rc, res)
 
     # ---- indel scan (an extension: the length-changing half of the variant scan, from the same dense scan) --
-    def indel_scan(self, seqs, thre, max_len=4):
+    def indel_scan(self, seqs, thre, max_len=4, mixed=False):
         """the same-base insertions and the deletions of up to max_len (1..16) bytes that the reads hold against the sequences, and
-        the substitution sites of variant_scan with them (thre >= 1, k >= 2) -> IndelScan; the table is not modified"""
+        the substitution sites of variant_scan with them (thre >= 1, k >= 2) -> IndelScan; with `mixed` also the insertions of mixed
+        bases (IndelScan.mixed); the table is not modified"""
         n = len(seqs)
         bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
         cs = (C.c_char_p * max(n, 1))(*bs)
         lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
         res = C.c_void_p()
-        rc = self._L.jasper_indel_scan(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
-        return self._wrap_indelscan(rc, res)
+        fn = self._L.jasper_indel_scan_mixed if mixed else self._L.jasper_indel_scan
+        rc = fn(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
+        return self._wrap_indelscan(rc, res, mixed)
 
-    def indel_scan_device(self, d_text, offsets, thre, max_len=4):
+    def indel_scan_device(self, d_text, offsets, thre, max_len=4, mixed=False):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
         n = len(offsets) - 1
         ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
         offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
         res = C.c_void_p()
-        rc = self._L.jasper_indel_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
-        return self._wrap_indelscan(rc, res)
+        fn = self._L.jasper_indel_scan_mixed_device if mixed else self._L.jasper_indel_scan_device
+        rc = fn(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
+        return self._wrap_indelscan(rc, res, mixed)
 
-    def _wrap_indelscan(self, rc, res):
+    def _read_mixed(self, res):
+        import numpy as np
+        counts = []
+        c3 = (C.c_uint64 * 3)()
+        for i in range(self._L.jasper_indelscan_num_seqs(res)):
+            check(self._L.jasper_indelscan_mixed_counts(res, i, c3))
+            counts.append(tuple(int(v) for v in c3))
+        rp = C.POINTER(_lib.MixedIns)()
+        rn = C.c_uint64(0)
+        check(self._L.jasper_indelscan_mixed_records(res, C.byref(rp), C.byref(rn)))
+        if rn.value:
+            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.MixedIns)), dtype=MIXED_DTYPE).copy()
+        else:
+            recs = np.zeros(0, dtype=MIXED_DTYPE)
+        nl = C.c_uint64(0)
+        check(self._L.jasper_indelscan_mixed_lookups(res, C.byref(nl)))
+        return MixedInsertions(counts, recs, self._L.jasper_indelscan_mixed_seconds(res), int(nl.value), bool(self._L.jasper_indelscan_mixed_retried(res)))
+
+    def _wrap_indelscan(self, rc, res, mixed=False):
         try:
             check(rc)
             import numpy as np
@@ -734,7 +782,7 @@ class KmerTable:
             check(self._L.jasper_indelscan_lookups(res, C.byref(nl)))
             var = self._read_varscan(C.c_void_p(self._L.jasper_indelscan_variants(res)))      # (owned by res: read, not freed)
             return IndelScan(counts, recs, var, self._L.jasper_indelscan_seconds(res), self._L.jasper_indelscan_check_seconds(res), int(nl.value),
-                             bool(self._L.jasper_indelscan_retried(res)))
+                             bool(self._L.jasper_indelscan_retried(res)), self._read_mixed(res) if mixed else None)
         finally:
             if res:
                 self._L.jasper_indelscan_free(res)

@@ -8,7 +8,7 @@ only the alternative is (a substitution the polisher has not made).
 
 Limits: only isolated substitutions are listed.  Two differences less than k apart hide each other, because every k-mer that
 covers one of them holds the other allele of the other; insertions and deletions are listed by the indel scan (jasper_amd/indels.py,
---indels), which leaves out insertions of mixed bases, lengths above 16 and, again, differences less than k apart.
+--indels; insertions of mixed bases with --indel-mixed), which leaves out lengths above 16 and, again, differences less than k apart.
 
 Nothing here touches the GPU: the functions take names, lengths, counters and records.
 """

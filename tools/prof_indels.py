@@ -1,6 +1,6 @@
 """The indel scan's check kernel next to its yardstick, on bench.py's workload (47 Mb synthetic assembly, 30x reads, k = 37).
 
-    python tools/prof_indels.py trace|time       (run on the GPU box; tools/prof_indels.sh puts `trace` under rocprofv3)
+    python tools/prof_indels.py trace|time|trace_mixed|time_mixed       (run on the GPU box; tools/prof_indels.sh puts the traces under rocprofv3)
 
 R = the counted read table, the text = the assembly as ONE sequence, the threshold = the derived one.
 trace: each of these after a warm-up call of the same kind, all in one process so that one kernel trace holds them: the variant scan
@@ -9,6 +9,11 @@ trace: each of these after a warm-up call of the same kind, all in one process s
        Prints the lookups indels_check_kernel counted (jasper_indelscan_lookups) for either max_len.
 time:  no profiler: jasper_indelscan_seconds and _check_seconds of five scans after a warm-up for either max_len, and
        jasper_varscan_seconds the same way
+trace_mixed: one process, one kernel trace: the indel scan WITH its mixed half at max_len 4 and 16, each after a warm-up call, so that
+       indels_mixed_kernel and its yardstick indels_check_kernel see the same candidates at the same max_len.  Prints the lookups, records
+       and complex sites the search counted.
+time_mixed: no profiler: jasper_indelscan_mixed_seconds of five scans after a warm-up for either max_len
+summarize_mixed DIR TRACE_LOG: the dispatches of the two kernels (2 of 4 and the last), time per candidate and per lookup of each
 summarize DIR TRACE_LOG: per kernel of a rocprofv3 --kernel-trace CSV under DIR, the durations of its dispatches in order, and from them
        and the lookup counts of TRACE_LOG the time per lookup of indels_check_kernel (max_len 4: its dispatch 2 of 4, max_len 16: the
        last) and of variants_check_kernel (its dispatch 2: the variant scan's measured call; 2k lookups per candidate), and their ratio
@@ -49,10 +54,31 @@ def summarize(d, log):
         print(json.dumps(res))
 
 
+def summarize_mixed(d, log):
+    out = {}
+    for fn in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        for r in sorted(csv.DictReader(open(fn)), key=lambda r: int(r["Start_Timestamp"])):
+            name = r["Kernel_Name"].split("(")[0]
+            if "indels_" in name:
+                out.setdefault("mixed" if "indels_mixed_kernel" in name else "check", []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    head = [json.loads(ln) for ln in open(log) if ln.startswith("{")][-1]
+    print(json.dumps({k: [round(x, 1) for x in v] for k, v in out.items()}))
+    if len(out.get("mixed", [])) == 4 and len(out.get("check", [])) == 4:
+        res, nc = {}, head["candidates"]
+        for ml, i in ((4, 1), (16, 3)):
+            for kern, look in (("check", head["lookups_%d" % ml]), ("mixed", head["mixed_lookups_%d" % ml])):
+                us = out[kern][i]
+                res.update({"%s_us_%d" % (kern, ml): round(us, 1), "%s_lookups_%d" % (kern, ml): look, "%s_lookups_per_candidate_%d" % (kern, ml): round(look / nc, 2),
+                            "%s_ns_per_candidate_%d" % (kern, ml): round(1e3 * us / nc, 2), "%s_ns_per_lookup_%d" % (kern, ml): round(1e3 * us / look, 4)})
+        print(json.dumps(res))
+
+
 def main():
     mode = sys.argv[1]
     if mode == "summarize":
         return summarize(sys.argv[2], sys.argv[3])
+    if mode == "summarize_mixed":
+        return summarize_mixed(sys.argv[2], sys.argv[3])
     import torch
     import bench
     from jasper_amd import KmerTable, polisher
@@ -74,6 +100,17 @@ def main():
                 isc = r.indel_scan_device(d_asm, text, thr, ml)
             head.update({"indelscan_seconds_%d" % ml: isc.seconds, "check_seconds_%d" % ml: isc.check_seconds, "lookups_%d" % ml: isc.lookups,
                          "counts_%d" % ml: isc.counts[0], "records_%d" % ml: len(isc.records)})
+    elif mode in ("trace_mixed", "time_mixed"):
+        for ml in (4, 16):
+            secs = []
+            for _ in range(2 if mode == "trace_mixed" else 6):
+                isc = r.indel_scan_device(d_asm, text, thr, ml, mixed=True)
+                secs.append(isc.mixed.seconds)
+            head.update({"mixed_seconds_%d" % ml: secs[1:], "check_seconds_%d" % ml: isc.check_seconds, "indelscan_seconds_%d" % ml: isc.seconds,
+                         "lookups_%d" % ml: isc.lookups, "mixed_lookups_%d" % ml: isc.mixed.lookups, "mixed_counts_%d" % ml: isc.mixed.counts[0],
+                         "mixed_records_%d" % ml: len(isc.mixed.records), "mixed_retried_%d" % ml: isc.mixed.retried,
+                         "mixed_lengths_%d" % ml: sorted({int(v) for v in isc.mixed.records["len"]})})
+        vs = isc.variants
     else:
         vsecs = []
         for _ in range(6):

@@ -9,7 +9,15 @@ mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 tools/prof_indels.py trace > $OUT/trace.log 2>&1 &&
 timeout -k 10 300 python3 tools/prof_indels.py time > $OUT/time.log 2>&1
 rc=$?
-tail -3 $OUT/trace.log $OUT/time.log
+tail -n 3 $OUT/trace.log $OUT/time.log
 python3 tools/prof_indels.py summarize $OUT/trace $OUT/trace.log | tee $OUT/summary_trace.json
+# the mixed half: a trace of its own (indels_mixed_kernel next to indels_check_kernel on the same candidates), then its event time
+if [ $rc -eq 0 ]; then
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_mixed -- python3 tools/prof_indels.py trace_mixed > $OUT/trace_mixed.log 2>&1 &&
+    timeout -k 10 300 python3 tools/prof_indels.py time_mixed > $OUT/time_mixed.log 2>&1
+    rc=$?
+    tail -n 3 $OUT/trace_mixed.log $OUT/time_mixed.log
+    python3 tools/prof_indels.py summarize_mixed $OUT/trace_mixed $OUT/trace_mixed.log | tee $OUT/summary_trace_mixed.json
+fi
 find $OUT -name '*kernel_stats.csv'
 exit $rc
