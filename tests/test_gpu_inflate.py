@@ -186,7 +186,7 @@ def fq_records(seed, n):
 @pytest.fixture(scope="module")
 def three_files(tmp_path_factory):
     d = tmp_path_factory.mktemp("gz3")
-    t1, t2, t3 = fq_records(11, 6000), fq_records(12, 9000), fq_records(13, 7000)
+    t1, t2, t3 = fq_records(11, 6000), fq_records(12, 30000), fq_records(13, 7000)     # (b.fq.gz: more than 2 MB compressed, for 1 MB slabs)
     (d / "a.fq").write_bytes(t1)
     (d / "b.fq.gz").write_bytes(gzip.compress(t2, 6, mtime=0))
     (d / "c.fq.gz").write_bytes(gzip.compress(t3, 1, mtime=0))
@@ -267,3 +267,98 @@ def test_cli_gzip_reads_on_the_device(hip, tmp_path):
     from test_gpu_cli_e2e import fasta_records
     assert fasta_records(tmp_path / "asm.fa.polished.fasta") == fasta_records(os.path.join(E2E, "asm.fa.polished.fasta"))
     assert open(tmp_path / "asm.fa.fixes.csv", newline="").read() == open(os.path.join(E2E, "asm.fa.fixes.csv"), newline="").read()
+
+
+# ---- slab seams: with JASPER_INGEST_GZ_DEVICE_SLAB_MB=1 the files above are 3-5 slabs, as every real read file is many -----------------
+# (what next_slab carries from one slab to the next: the position inside a 4096-byte page, the decoder that ends past the slab's nominal
+# end, the window kept on the device or uploaded from the host after a gap, the member's CRC, length and valid window so far)
+@pytest.fixture
+def slab_1mb(monkeypatch):
+    monkeypatch.setenv("JASPER_INGEST_GZ_DEVICE_SLAB_MB", "1")
+
+
+@pytest.mark.parametrize("level", [1, 6, 9])
+def test_slabs_levels(hip, tmp_path, FQ, slab_1mb, level):
+    blob = gzip.compress(FQ, level, mtime=0)
+    st = check_same(hip, tmp_path, blob, FQ)
+    assert st["host_bytes"] == 0 and st["members"] == 1
+    assert st["slabs"] >= max(3, len(blob) >> 20), st
+
+
+def test_slabs_members(hip, tmp_path, FQ, slab_1mb):
+    a, b, c = FQ[:5_000_000], FQ[5_000_000:10_000_000], FQ[10_000_000:]
+    blob = gzip.compress(a, 6, mtime=0) + gzip.compress(b, 1, mtime=0) + gzip.compress(b"", 6, mtime=0) + gzip.compress(b"", 9, mtime=0) + gzip.compress(c, 9, mtime=0)
+    st = check_same(hip, tmp_path, blob, FQ)
+    assert st["members"] == 5 and st["slabs"] >= 3, st
+    parts = [FQ[i:i + 4096] for i in range(0, len(FQ), 4096)]
+    st = check_same(hip, tmp_path, b"".join(gzip.compress(x, 6, mtime=0) for x in parts), FQ)
+    assert st["members"] == len(parts) and st["slabs"] >= 3, st
+
+
+def test_slabs_gap_in_the_middle(hip, tmp_path, FQ, slab_1mb):
+    """30 MB of 'A' inside the reads overflow every arena: the host fills that slab to its end, and the next slab starts on the device
+    from the window the host uploaded"""
+    text = FQ[:3_000_000] + b"A" * 30_000_000 + FQ[3_000_000:]
+    st = check_same(hip, tmp_path, gzip.compress(text, 6, mtime=0), text, device_only=False)
+    assert st["host_bytes"] > 0 and st["slabs"] >= 4 and st["device_bytes"] >= 3_000_000 + 1_000_000, st
+
+
+def test_slabs_stored_stretch(hip, tmp_path, FQ, slab_1mb):
+    """a level-0 member of 3 MB (stored blocks: no findable start) lies across slab seams between two level-6 members"""
+    blob = gzip.compress(FQ[:4_000_000], 6, mtime=0) + gzip.compress(FQ[4_000_000:7_000_000], 0, mtime=0) + gzip.compress(FQ[7_000_000:], 6, mtime=0)
+    st = check_same(hip, tmp_path, blob, FQ, device_only=False)
+    assert st["members"] == 3 and st["slabs"] >= 3, st
+
+
+def test_slabs_damage_beyond_the_first(hip, tmp_path, FQ, slab_1mb):
+    z = gzip.compress(FQ, 6, mtime=0)
+    assert len(z) > 3 << 20
+    cases = []
+    for frac in (0.6, 0.9):
+        f = bytearray(z)
+        f[int(len(z) * frac)] ^= 0x04
+        cases.append(bytes(f))
+    cases.append(z[:int(len(z) * 0.7)])
+    len_bad = bytearray(z)
+    len_bad[-2] ^= 0x01
+    cases.append(bytes(len_bad))
+    p = tmp_path / "d.gz"
+    for i, blob in enumerate(cases):
+        p.write_bytes(blob)
+        rc_d, _, st = dev_inflate(hip, p)
+        rc_h, _, _ = host_inflate(hip, p)
+        assert rc_d != 0 and rc_h != 0, (i, st)
+        assert st["slabs"] >= 2, (i, st)
+
+
+def test_slabs_through_ingest(hip, three_files, slab_1mb, monkeypatch):
+    """count_files and the read feed with the device inflater in 1 MB slabs: the oracle's histogram"""
+    from jasper_amd import KmerTable
+    from oracle import oracle as O
+    paths, text, gz_len = three_files
+    assert os.path.getsize(paths[1]) > 2 << 20
+    k = 25
+    db = O.OracleDB(k)
+    db.count_text(text.decode())
+    monkeypatch.setenv("JASPER_INGEST_GZ_DEVICE_CHUNK", str(CHUNK))
+    monkeypatch.setenv("JASPER_INGEST_GZ", "device")
+    t = KmerTable(k, min_slots=1 << 20)
+    t.count_files(paths)
+    st = t.last_inflate()
+    assert t.histogram() == db.histo() and t.info()["distinct"] == db.distinct()
+    assert st["slabs"] >= 3 and st["host_bytes"] == 0 and st["device_bytes"] == gz_len, st
+    t.close()
+    src = KmerTable(k, min_slots=1 << 16)
+    dst = KmerTable(k, min_slots=1 << 20)
+    src.feed_start([(p, 0, -1) for p in paths])
+    while True:
+        ptr, n = src.feed_next()
+        if n == 0:
+            break
+        dst.count_bases_device(ptr, n)
+        src.feed_release()
+    st = src.last_inflate()
+    assert dst.histogram() == db.histo() and dst.info()["distinct"] == db.distinct()
+    assert st["slabs"] >= 3 and st["host_bytes"] == 0 and st["device_bytes"] == gz_len, st
+    src.close()
+    dst.close()
