@@ -421,7 +421,7 @@ void jasper_varscan_free(jasper_varscan *r);
  * 2k-2 (empty ones too) are legal and give zeros.  The table is not modified.
  *
  * Limits: insertions of mixed bases are reported only by jasper_indel_scan_mixed below, lengths above 16 are not reported, and, as for
- * substitutions, two differences less than k apart hide each other.
+ * substitutions, two differences less than k apart hide each other (the error side of such clusters: jasper_compound_scan).
  *
  * On the device the variant scan's dense scan runs unchanged: its candidate (p, x) -- the window that ends at p is solid with its last
  * base replaced by x -- is the first k-mer of A for ins(p, x, L) and for del(p, L) with s[p+L] == x.  One more kernel tests these
@@ -505,6 +505,71 @@ double jasper_indelscan_mixed_seconds(const jasper_indelscan *r);
 int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n);
 int jasper_indelscan_mixed_retried(const jasper_indelscan *r);
 int jasper_indel_front(void);
+
+/* Compound scan: WHAT the reads hold in place of a cluster of differences that hide each other from the two scans above.
+ *
+ * What it replaces: nothing -- an EXTENSION.  Two differences less than k apart leave no solid single-edit alternative: every window that
+ * covers one of them holds the sequence's wrong base at the other, so jasper_variant_scan and jasper_indel_scan stay silent, and all that
+ * shows is a run of unreliable windows in jasper_kmer_report.  The reference repairs such clusters inside its walk where it can and
+ * reports nothing.  The read table is a de Bruijn graph of the reads; this scan walks its solid k-mers from the left flank of such a run
+ * and lists every string that rejoins the sequence on the right flank: several substitutions, or a substitution and a length error.
+ * For a sequence s (case folded), the table's k >= 2, thre >= 1 and max_len in 1..64 (anything else is JASPER_ERR with a message that
+ * names the argument, even with nothing to scan); cnt() = the table's count of a canonical k-mer, clamped to 2^32-1 as jasper_lookup
+ * clamps; FRONT = JASPER_COMPOUND_FRONT = JASPER_INDEL_FRONT = 64:
+ *   sites          a maximal run of unreliable windows exactly as jasper_kmer_report lists it, (start, n_kmers, min_count); R =
+ *                  n_kmers - k + 1.  The run is a SITE when 1 <= R <= max_len and LONG when R > max_len: long runs are counted and not
+ *                  searched.  Runs with n_kmers < k are neither: pure insertions, or runs that end at an edge or a non-base byte; they
+ *                  stay with the other scans.  For a site a = start + k - 1, q = start + n_kmers, F = s[a-k+1 .. a-1] and G =
+ *                  s[q .. q+k-2]: both lie inside the bytes the run's windows cover, so they are bases and in bounds, at a sequence's
+ *                  first and last window too.  The sequence's own R bytes s[a .. q) are what is replaced.
+ *   repl(a, R, y)  the reads hold the string y in place of those R bytes; its alternative string is A = F + y + G, of k-1+|y| windows.
+ *   the search     S_0 = {empty};  S_t = { yz : y in S_(t-1), z in ACGT, cnt(the last k bases of F + y + z) >= thre }.  It runs t = 1,
+ *                  2, .. and ends at the first of: t > max_len; S_t empty; |S_t| > FRONT.  In the last case the site is COMPLEX: counted
+ *                  once; records of lengths < t that were found stay, nothing of length >= t is listed.
+ *   record         every y in an S_t that was reached whose windows t .. t+k-2 of A -- those that hold a base of G -- are >= thre as
+ *                  well: {seq, pos = a, ref_len = R, len = t, bases = y, ref_min, alt_min}.  alt_min = the minimum of cnt over all
+ *                  k-1+t windows of A; ref_min = the run's min_count, below thre by construction: every record is an ERROR, there is no
+ *                  kind.  Exception: R = 1 and t = 1 is the variant scan's error and is never listed.  Deletions (t = 0) are not
+ *                  searched: they stay the indel scan's.  Window 0 of A is F + y[0] and the sequence's own window there is unreliable,
+ *                  so y[0] != s[a] needs no rule of its own; the same holds for y's last base and s[q-1].
+ *   per sequence   five counters: sites, bridged (sites with at least one record), records, long, complex
+ * The rule is one of sets, not of a search order: the list, ordered by (seq, pos, len, y), is identical on every call.  The table is
+ * not modified.
+ *
+ * Limits: compound HET sites are out of scope -- where both alleles are solid there is no unreliable run (the variant scan lists the
+ * left end of such a site); replacements longer than 64 bases are not listed.
+ *
+ * On the device jasper_kmer_report's scan runs unchanged; the host picks the sites and the long runs from its runs, and one more
+ * kernel searches the sites, one wave each, with the frontier S_t held one prefix per lane.  With no site nothing more is allocated
+ * or launched.  The result holds the whole report, so one call answers both questions.
+ *   jasper_compound_scan, _device   as jasper_kmer_report / _device, with max_len
+ *   jasper_compscan_counts          out5 = sites, bridged, records, long, complex of one sequence
+ *   jasper_compscan_records         the record list (owned by the result)
+ *   jasper_compscan_report          the report of the same input, owned by the result (do not free it): every jasper_report_* accessor
+ *                                   gives what it gives for jasper_kmer_report
+ *   jasper_compscan_seconds         device time (HIP events) of the search kernel alone (*search) and of it and the dense scan (*total)
+ *   jasper_compscan_lookups         table lookups the search made;  jasper_compscan_retried: it was repeated with a larger list
+ *   jasper_compound_front           JASPER_COMPOUND_FRONT as the library was built */
+#define JASPER_COMPOUND_FRONT JASPER_INDEL_FRONT
+typedef struct jasper_compscan jasper_compscan;
+typedef struct jasper_compound {
+    int64_t pos;
+    uint32_t seq, ref_min, alt_min, ref_len;
+    uint64_t bases[2]; /* base i of y in bits 2i..2i+1 of bases[i / 32], A C G T = 0 1 2 3, 0 above 2*len */
+    uint16_t len;
+    uint8_t pad[6] /* 0 */;
+} jasper_compound; /* 48 B */
+int jasper_compound_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_compscan **out);
+int jasper_compound_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_compscan **out);
+int jasper_compscan_num_seqs(const jasper_compscan *r);
+int jasper_compscan_counts(const jasper_compscan *r, int seq, uint64_t out5[5]);   /* sites, bridged, records, long, complex */
+int jasper_compscan_records(const jasper_compscan *r, const jasper_compound **recs, uint64_t *n);
+const jasper_report *jasper_compscan_report(const jasper_compscan *r);
+int jasper_compscan_lookups(const jasper_compscan *r, uint64_t *n);
+int jasper_compscan_seconds(const jasper_compscan *r, double *search, double *total);
+int jasper_compscan_retried(const jasper_compscan *r);
+int jasper_compound_front(void);
+void jasper_compscan_free(jasper_compscan *r);
 
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1

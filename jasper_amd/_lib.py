@@ -62,6 +62,14 @@ class MixedIns(C.Structure):
 
 assert C.sizeof(MixedIns) == 32
 
+
+class Compound(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("ref_len", C.c_uint32), ("bases", C.c_uint64 * 2),
+                ("len", C.c_uint16), ("pad", C.c_uint8 * 6)]
+
+
+assert C.sizeof(Compound) == 48
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -182,6 +190,17 @@ SYMBOLS = {
     "jasper_indelscan_mixed_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "jasper_indelscan_mixed_retried": (C.c_int, [_P]),
     "jasper_indel_front": (C.c_int, []),
+    "jasper_compound_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_compound_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
+    "jasper_compscan_num_seqs": (C.c_int, [_P]),
+    "jasper_compscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_compscan_records": (C.c_int, [_P, C.POINTER(C.POINTER(Compound)), C.POINTER(C.c_uint64)]),
+    "jasper_compscan_report": (_P, [_P]),
+    "jasper_compscan_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_compscan_seconds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "jasper_compscan_retried": (C.c_int, [_P]),
+    "jasper_compound_front": (C.c_int, []),
+    "jasper_compscan_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

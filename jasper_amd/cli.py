@@ -3,7 +3,7 @@ sentinel files and log lines; the Jellyfish + per-batch python processes are rep
 polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
-                            [--indels [--indel-max-len N] [--indel-mixed]]
+                            [--indels [--indel-max-len N] [--indel-mixed]] [--compound [--compound-max-len N]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -108,6 +108,8 @@ class Options:
         self.indels = False
         self.indel_mixed = False
         self.indel_max_len = None    # --indel-max-len: longest insertion / deletion the indel scan tries (default 4, at most 16)
+        self.compound = False
+        self.compound_max_len = None # --compound-max-len: longest replacement the compound scan searches (default 64, at most 64)
 
 
 def parse_args(argv):
@@ -168,6 +170,10 @@ def parse_args(argv):
             o.indel_mixed = True
         elif key == "--indel-max-len":
             o.indel_max_len = nxt; i += 1
+        elif key == "--compound":                                      # extension: what the reads hold for clusters of differences (_compound)
+            o.compound = True
+        elif key == "--compound-max-len":
+            o.compound_max_len = nxt; i += 1
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1054,16 +1060,22 @@ def scan_contigs(table, contigs, thre):
     return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.kmer_report([s for _, s in contigs], thre)
 
 
-def _report(o, table):
+def _report_stages(o, table):
+    """the two dense scans of --report: ((names, lengths, KmerReport) of the input assembly, ... of the polished FASTA).  The threshold
+    is the one the polisher used (threshold.txt)."""
+    thresh = int(open("threshold.txt").read().split()[0])
+    return scan_contigs(table, read_assembly(o.query), thresh), scan_contigs(table, read_assembly(o.query_fn + ".polished.fasta"), thresh)
+
+
+def _report(o, table, stages):
     """--report (an extension, no counterpart in src/jasper.sh): two dense scans through the table while it is still in HBM -- the
     input assembly's contigs and the polished contigs, WHOLE contigs read back from the two FASTA files, so the windows that span
     two chunk records are there -- into `$QUERY_FN.kmer_qv.tsv` and `$QUERY_FN.unreliable.{before,after}.bed` (jasper_amd/report.py).
-    The threshold is the one the polisher used (threshold.txt); k is the table's (a -j database decides it)."""
+    k is the table's (a -j database decides it).  `stages` are the two scans: _report_stages, or with --compound the reports that its
+    scans hold (_compound_scans), so that each stage is still ONE dense scan."""
     from . import report
     qfn, k = o.query_fn, table.k
-    thresh = int(open("threshold.txt").read().split()[0])
-    names, len0, rep0 = scan_contigs(table, read_assembly(o.query), thresh)
-    names1, len1, rep1 = scan_contigs(table, read_assembly(qfn + ".polished.fasta"), thresh)
+    (names, len0, rep0), (names1, len1, rep1) = stages
     len1a, cnt1a = report.align(names, names1, len1, rep1.counts)
     report.write_atomic(qfn + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("before", len0, rep0.counts), ("after", len1a, cnt1a)]))
     report.write_atomic(qfn + ".unreliable.before.bed", report.bed_text(k, names, rep0.runs))
@@ -1276,6 +1288,56 @@ def _indels(o, table):
                              (is0.mixed.seconds, is1.mixed.seconds, is0.mixed.lookups, is1.mixed.lookups))
 
 
+COMPOUND_MAX_LEN_DEFAULT = 64
+
+
+def compound_flags(max_len):
+    """--compound-max-len as given (a string or None) -> the longest replacement to search; exits on anything but an integer in 1..64"""
+    if max_len is None:
+        return COMPOUND_MAX_LEN_DEFAULT
+    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 64:
+        error_exit("--compound-max-len takes an integer from 1 to 64; it is %s" % max_len)
+    return int(max_len)
+
+
+def scan_compound(table, contigs, thre, max_len):
+    """the compound scan of whole contigs [(name token, sequence)] -> (names, lengths, CompoundScan), whose .report is what
+    scan_contigs gives; exits on a threshold of 0, for which no k-mer is unreliable and every string solid"""
+    from . import report
+    if thre < 1:
+        error_exit("--compound needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.compound_scan([s for _, s in contigs], thre, max_len)
+
+
+def _compound_scans(o, table):
+    """the two compound scans of a run -- the input assembly's contigs and the polished contigs, through the read table while it is
+    still in HBM: what _compound writes its files from and, with --report, _report too"""
+    max_len = compound_flags(o.compound_max_len)
+    thresh = int(open("threshold.txt").read().split()[0])
+    asm0, asm1 = read_assembly(o.query), read_assembly(o.query_fn + ".polished.fasta")
+    return dict(thresh=thresh, max_len=max_len, asm0=asm0, asm1=asm1, before=scan_compound(table, asm0, thresh, max_len),
+                after=scan_compound(table, asm1, thresh, max_len))
+
+
+def _compound(o, table, scans):
+    """--compound (an extension, no counterpart in src/jasper.sh): for the runs of unreliable k-mers that clusters of differences
+    leave, what the reads hold in their place, into `$QUERY_FN.compound.tsv` and `$QUERY_FN.compound.{before,after}.vcf`
+    (jasper_amd/compound.py) -- `before` in the input's coordinates, `after` in the polished FASTA's.  The threshold is the
+    polisher's (threshold.txt)."""
+    from . import compound, report
+    qfn, k = o.query_fn, table.k
+    thresh, max_len, asm0, asm1 = scans["thresh"], scans["max_len"], scans["asm0"], scans["asm1"]
+    (names, len0, cs0), (names1, len1, cs1) = scans["before"], scans["after"]
+    len1a, cnt1a = report.align(names, names1, len1, cs1.counts)
+    compound.write_atomic(qfn + ".compound.tsv", compound.compound_tsv_text(names, [("before", len0, cs0.counts), ("after", len1a, cnt1a)]))
+    compound.write_atomic(qfn + ".compound.before.vcf", compound.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], cs0.records))
+    compound.write_atomic(qfn + ".compound.after.vcf", compound.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], cs1.records))
+    log(compound.log_text(cs0.counts, cnt1a))
+    if _timing_on():
+        sys.stderr.write("[compound] search device seconds: before %.6f after %.6f; lookups %d %d\n" %
+                         (cs0.search_seconds, cs1.search_seconds, cs0.lookups, cs1.lookups))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1312,6 +1374,8 @@ def run(argv):
     if o.indels:
         indel_flags(o.indel_max_len)
     indel_mixed_flag(o.indel_mixed, o.indels)
+    if o.compound:
+        compound_flags(o.compound_max_len)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
@@ -1388,10 +1452,18 @@ def run(argv):
         _join(ranks, o, job, in_job, join_writer, batch_size, passes - 1, contigs)
     if ranks.is0:
         _qv_block(passes, kmer)                                                         # :235-257
+    scans = {}
+    if o.compound:
+        # as for --report: rank 0 alone, through every owner's shard of the attached table.  The scans come first because their dense half
+        # is the report's; the files and the log line are written after the other extensions' (_compound)
+        ranks.together((lambda: scans.update(_compound_scans(o, table))) if ranks.is0 else (lambda: None), "The compound scan failed")
+        _timing("compound scan")
     if o.report:
         # rank 0 alone scans, through the attached owner-sharded table; the other ranks wait for its outcome here and at the barrier
         # that precedes detach (unmeasured over RCCL, like everything multi-GPU here)
-        ranks.together((lambda: _report(o, table)) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
+        def stages():
+            return [(n, ln, cs.report) for n, ln, cs in (scans["before"], scans["after"])] if o.compound else _report_stages(o, table)
+        ranks.together((lambda: _report(o, table, stages())) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
         _timing("k-mer report")
     if o.spectra or o.copies:
         # as for --report: rank 0 alone, its sweeps and scans go through every owner's shard of the attached table
@@ -1406,6 +1478,8 @@ def run(argv):
         # as for --report: rank 0 alone, through every owner's shard of the attached table
         ranks.together((lambda: _variants(o, table)) if ranks.is0 else (lambda: None), "Writing the variant scan failed")
         _timing("variant scan")
+    if o.compound:
+        ranks.together((lambda: _compound(o, table, scans)) if ranks.is0 else (lambda: None), "Writing the compound scan failed")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

@@ -1,0 +1,96 @@
+"""Compound scan: the writers of `*.compound.tsv` and `*.compound*.vcf` (cli --compound, kmerqc --compound).
+
+An extension: the reference repairs clusters of differences inside its walk where it can and reports nothing.  Two differences less
+than k apart hide each other from the variant and the indel scan: every window that covers one holds the contig's wrong base at the
+other, so no single-edit alternative is solid.  What shows is a run of unreliable k-mers of k + R - 1 windows, R the bytes from the
+first difference to the last.  The scan (KmerTable.compound_scan; semantics in include/jasper_hip.h, jasper_compound_scan) walks the
+solid k-mers of the reads from the left flank of every such run with R <= max_len and lists each string of up to max_len bases that
+rejoins the contig on the right flank: several substitutions (`TYPE=mnp`, as long as what it replaces) or a substitution and a length
+error (`TYPE=complex`).  Every record is an error -- the contig's own k-mers there are unreliable.
+
+Per contig the TSV counts the sites (runs that were searched), the bridged ones (at least one record), the records, the long runs
+(R > max_len: not searched) and the complex sites (more than 64 prefixes of one length were solid: the search stopped there).
+
+Limits: compound het sites are out of scope (where both alleles are solid there is no unreliable run), deletions alone stay the
+indel scan's and a single substitution the variant scan's, and nothing longer than 64 bases is listed.
+
+Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
+"""
+from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .table import compound_string
+
+TSV_HEADER = "#contig\tstage\tlength\tsites\tbridged\trecords\tlong\tcomplex\n"
+ZERO = (0, 0, 0, 0, 0)
+
+
+def _row(name, stage, length, c):
+    return "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % ((name, stage, length) + tuple(c))
+
+
+def totals(counts):
+    """column sums of the (sites, bridged, records, long, complex) of the contigs that have any (None = contig missing)"""
+    return tuple(sum(c[i] for c in counts if c is not None) for i in range(5))
+
+
+def compound_tsv_text(names, stages):
+    """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and five counters, or None for a contig
+    that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
+    contig `*` with the sums."""
+    out = [TSV_HEADER]
+    for i, name in enumerate(names):
+        for stage, lengths, counts in stages:
+            c = counts[i]
+            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
+    for stage, lengths, counts in stages:
+        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
+    return "".join(out)
+
+
+def _rec_fields(r):
+    """(seq, pos, ref_len, len, y, ref_min, alt_min) of a record of CompoundScan.records or of a tuple in the order of
+    CompoundScan.record_tuples()"""
+    if hasattr(r, "dtype"):
+        return (int(r["seq"]), int(r["pos"]), int(r["ref_len"]), int(r["len"]), compound_string(r["bases"], r["len"]), int(r["ref_min"]), int(r["alt_min"]))
+    seq, pos, rlen, ln, y, rmin, amin = r
+    return int(seq), int(pos), int(rlen), int(ln), y if isinstance(y, str) else bytes(y).decode("latin-1"), int(rmin), int(amin)
+
+
+def vcf_lines(seqs, records):
+    """[(seq, POS, len, ALT, REF, INFO)] sorted by (contig, POS, LEN, ALT): POS = a + 1, REF = the contig's R bytes as they stand"""
+    out = []
+    for seq, pos, rlen, ln, y, rmin, amin in (_rec_fields(r) for r in records):
+        s = seqs[seq]
+        ref = s[pos:pos + rlen]
+        ref = ref if isinstance(ref, str) else bytes(ref).decode("latin-1")
+        out.append((seq, pos + 1, ln, y, ref, "KIND=error;TYPE=%s;RLEN=%d;LEN=%d;RC=%d;AC=%d" % ("mnp" if rlen == ln else "complex", rlen, ln, rmin, amin)))
+    out.sort()
+    return out
+
+
+def vcf_text(k, thre, max_len, names, lengths, seqs, records):
+    """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record ordered by (contig, POS, LEN, ALT)
+    whatever order they come in: name, POS, ., REF, ALT, ., ., KIND=error;TYPE=mnp|complex;RLEN=R;LEN=t;RC=ref_min;AC=alt_min.
+    seqs[i] = contig i's sequence: REF is read from it.  Both alleles are non-empty, so there is no anchor base."""
+    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd compound scan, k=%d, threshold=%d, max_len=%d\n" % (k, thre, max_len)]
+    for name, ln in zip(names, lengths):
+        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
+    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="error: only the alternative is solid in the reads; the contig\'s own k-mers there are '
+               'unreliable">\n')
+    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="mnp: ALT is as long as REF; complex: the lengths differ">\n')
+    out.append('##INFO=<ID=RLEN,Number=1,Type=Integer,Description="bytes of the contig that are replaced">\n')
+    out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="bases the reads hold in their place">\n')
+    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
+    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
+    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+    for seq, pos1, _ln, alt, ref, info in vcf_lines(seqs, records):
+        out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], pos1, ref, alt, info))
+    return "".join(out)
+
+
+def stage_log_text(counts):
+    """`A sites, B bridged, C records, D long runs, E complex sites` of one stage"""
+    return "%d sites, %d bridged, %d records, %d long runs, %d complex sites" % totals(counts)
+
+
+def log_text(counts0, counts1):
+    return "Compound scan: before polishing %s; after polishing %s" % (stage_log_text(counts0), stage_log_text(counts1))

@@ -11,6 +11,7 @@
 #include "copies.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
+#include "compound.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -59,6 +60,10 @@ struct jasper_indelscan {
 };
 struct jasper_report {
     ReportOut r;
+};
+struct jasper_compscan {
+    CompoundOut r;
+    jasper_report rep;                   // the report of the same call, written by the scan itself: what jasper_compscan_report hands out
 };
 static_assert(sizeof(jasper_kmer_run) == sizeof(KmerRun) && offsetof(jasper_kmer_run, n_absent) == offsetof(KmerRun, n_absent) &&
                   offsetof(jasper_kmer_run, seq) == offsetof(KmerRun, seq) && offsetof(jasper_kmer_run, min_count) == offsetof(KmerRun, min_count),
@@ -945,5 +950,58 @@ int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n) {
 int jasper_indelscan_mixed_retried(const jasper_indelscan *r) { return r ? r->r.mixed_retried : 0; }
 int jasper_indel_front(void) { return INDEL_FRONT; }
 void jasper_indelscan_free(jasper_indelscan *r) { delete r; }
+
+// ---- compound scan (compound.hip) ----
+static_assert(sizeof(jasper_compound) == sizeof(Compound) && offsetof(jasper_compound, ref_len) == offsetof(Compound, ref_len) &&
+                  offsetof(jasper_compound, bases) == offsetof(Compound, bases) && offsetof(jasper_compound, len) == offsetof(Compound, len),
+              "jasper_compound is Compound");
+static_assert(sizeof(jasper_compound) == 48, "jasper_compound is 48 bytes");
+static_assert(JASPER_COMPOUND_FRONT == COMPOUND_FRONT && COMPOUND_FRONT == INDEL_FRONT, "the header's cap is the kernel's, and the mixed search's");
+static int compscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
+                         int max_len, jasper_compscan **out) {
+    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_compscan *r = new jasper_compscan();
+    const int rc = d_text || offsets ? compound_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, r->rep.r, r->r, g_err)
+                                     : compound_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, r->rep.r, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_compound_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_compscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return compscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, out);
+}
+int jasper_compound_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_compscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return compscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, out);
+}
+int jasper_compscan_num_seqs(const jasper_compscan *r) { return r ? (int)(r->r.counts.size() / 5) : 0; }
+int jasper_compscan_counts(const jasper_compscan *r, int seq, uint64_t out5[5]) {
+    if (!r || !out5 || seq < 0 || (size_t)seq >= r->r.counts.size() / 5) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 5; ++i) out5[i] = r->r.counts[5 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_compscan_records(const jasper_compscan *r, const jasper_compound **recs, uint64_t *n) {
+    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *recs = reinterpret_cast<const jasper_compound *>(r->r.recs.data());
+    *n = r->r.recs.size();
+    return JASPER_OK;
+}
+const jasper_report *jasper_compscan_report(const jasper_compscan *r) { return r ? &r->rep : nullptr; }
+int jasper_compscan_lookups(const jasper_compscan *r, uint64_t *n) {
+    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = r->r.lookups;
+    return JASPER_OK;
+}
+int jasper_compscan_seconds(const jasper_compscan *r, double *search, double *total) {
+    if (!r) { g_err = "bad argument"; return JASPER_ERR; }
+    if (search) *search = r->r.search_seconds;
+    if (total) *total = r->r.seconds;
+    return JASPER_OK;
+}
+int jasper_compscan_retried(const jasper_compscan *r) { return r ? r->r.retried : 0; }
+int jasper_compound_front(void) { return COMPOUND_FRONT; }
+void jasper_compscan_free(jasper_compscan *r) { delete r; }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
                                 [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]]
+                                [--compound [--compound-max-len N]]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -39,29 +40,37 @@ the columns mixed_het, mixed_error and complex to the TSV, `TYPE=ins` lines to t
     PREFIX.indels.tsv        per contig one row of stage `asm`: het and error insertions, het and error deletions; then contig `*`
     PREFIX.indels.vcf        VCFv4.2, one left-aligned line per insertion or deletion: KIND=het|error;TYPE=ins|del;LEN=..
 
+With --compound the runs of unreliable k-mers that two or more differences less than k apart leave -- which hide each other from
+--variants and --indels -- are searched for what the reads hold in their place, up to --compound-max-len bases (default 64, at most
+64; KmerTable.compound_scan, whose dense scan is the report's: still one per run), and two more files are written
+(jasper_amd/compound.py); the threshold must be at least 1:
+
+    PREFIX.compound.tsv      per contig one row of stage `asm`: sites, bridged, records, long, complex; then contig `*`
+    PREFIX.compound.vcf      VCFv4.2, one line per replacement: KIND=error;TYPE=mnp|complex;RLEN=..;LEN=..
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 """
 import os
 import sys
 
-from . import cli, copies, indels, polisher, report, spectra, variants
+from . import cli, compound, copies, indels, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]] [--compound [--compound-max-len N]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, compound=False, compound_max_len=None)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run",
-            "--indel-max-len": "indel_max_len"}
+            "--indel-max-len": "indel_max_len", "--compound-max-len": "compound_max_len"}
     i = 0
     while i < len(argv):
         key = argv[i]
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed"):
+        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--compound"):
             o[key[2:].replace("-", "_")] = True
             i += 1
             continue
@@ -93,6 +102,9 @@ def run(argv):
     cli.indel_mixed_flag(a["indel_mixed"], a["indels"])
     if a["indels"] and given is not None and given < 1:
         cli.error_exit("--indels needs a threshold of at least 1; --threshold %d was given" % given)
+    comp_len = cli.compound_flags(a["compound_max_len"]) if a["compound"] else None
+    if a["compound"] and given is not None and given < 1:
+        cli.error_exit("--compound needs a threshold of at least 1; --threshold %d was given" % given)
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
@@ -116,7 +128,12 @@ def run(argv):
         peak = cli.copies_peak(peak, copies.histogram_from_rows(table.histo_rows()), given)
         min_run = k if min_run is None else min_run
     contigs = cli.read_assembly(a["asm"])
-    names, lengths, rep = cli.scan_contigs(table, contigs, given)
+    cscan = None
+    if a["compound"]:
+        names, lengths, cscan = cli.scan_compound(table, contigs, given, comp_len)      # (its dense scan is the report's)
+        rep = cscan.report
+    else:
+        names, lengths, rep = cli.scan_contigs(table, contigs, given)
     spec = crep = None
     if a["spectra"] or a["copies"]:
         asm = cli.assembly_table(table, contigs)          # counted once, it serves both
@@ -157,6 +174,12 @@ def run(argv):
             cli.log("Mixed insertions: %s in %s.indels.vcf" % (indels.mixed_stage_log_text(mixed.counts), prefix))
             if cli._timing_on():
                 sys.stderr.write("[indels] mixed search device seconds: %.6f; lookups %d\n" % (mixed.seconds, mixed.lookups))
+    if cscan is not None:
+        compound.write_atomic(prefix + ".compound.tsv", compound.compound_tsv_text(names, [("asm", lengths, cscan.counts)]))
+        compound.write_atomic(prefix + ".compound.vcf", compound.vcf_text(k, given, comp_len, names, lengths, [s for _, s in contigs], cscan.records))
+        cli.log("Compound scan: %s in %s.compound.vcf" % (compound.stage_log_text(cscan.counts), prefix))
+        if cli._timing_on():
+            sys.stderr.write("[compound] search device seconds: %.6f; lookups %d\n" % (cscan.search_seconds, cscan.lookups))
     return 0
 
 

@@ -245,6 +245,41 @@ class IndelScan:
                  int(r["kind"])) for r in self.records]
 
 
+COMPOUND_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref_len", "<u4"), ("bases", "<u8", (2,)), ("len", "<u2"),
+                  ("pad", "u1", (6,))]
+
+
+def compound_string(bases, length):
+    """y of a compound record: base i is bits 2i..2i+1 of bases[i // 32], A C G T = 0 1 2 3"""
+    return "".join("ACGT"[(int(bases[i >> 5]) >> (2 * (i & 31))) & 3] for i in range(int(length)))
+
+
+class CompoundScan:
+    """compound scan of a set of sequences against the reads' table (include/jasper_hip.h: jasper_compound_scan): `counts[i]` = (sites,
+    bridged, records, long, complex) of sequence i, `records` = numpy structured array (COMPOUND_DTYPE) of the replacements the reads
+    hold for clusters of differences, ordered by (seq, pos, len, y), `report` = the KmerReport of the same input (one dense scan
+    serves both), `seconds` = device time of the dense scan and the search, `search_seconds` = of the search kernel alone, `lookups`
+    = table lookups it made, `retried` = it was repeated with a larger record list.  The files made from it: jasper_amd/compound.py."""
+
+    def __init__(self, counts, records, report, seconds, search_seconds, lookups, retried):
+        self.counts = counts
+        self.records = records
+        self.report = report
+        self.seconds = seconds
+        self.search_seconds = search_seconds
+        self.lookups = lookups
+        self.retried = retried
+
+    def __eq__(self, other):
+        return (isinstance(other, CompoundScan) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
+                and self.report == other.report)
+
+    def record_tuples(self):
+        """[(seq, pos, ref_len, len, y, ref_min, alt_min)], y = the replacement"""
+        return [(int(r["seq"]), int(r["pos"]), int(r["ref_len"]), int(r["len"]), compound_string(r["bases"], r["len"]), int(r["ref_min"]), int(r["alt_min"]))
+                for r in self.records]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -744,6 +779,60 @@ class KmerTable:
         rc = fn(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
         return self._wrap_indelscan(rc, res, mixed)
 
+    # ---- compound scan (an extension: what the reads hold in place of differences that hide each other) ------
+    def compound_scan(self, seqs, thre, max_len=64):
+        """the replacements of up to max_len (1..64) bases that the reads hold for the runs of unreliable k-mers that two or more
+        differences less than k apart leave, and the kmer_report of the same input (thre >= 1, k >= 2) -> CompoundScan; the table is
+        not modified"""
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = self._L.jasper_compound_scan(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
+        return self._wrap_compscan(rc, res)
+
+    def compound_scan_device(self, d_text, offsets, thre, max_len=64):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_compound_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
+        return self._wrap_compscan(rc, res)
+
+    @staticmethod
+    def compound_front():
+        """the most prefixes of one length the compound search keeps (a wider level makes the site complex)"""
+        return int(_lib.lib().jasper_compound_front())
+
+    def _wrap_compscan(self, rc, res):
+        try:
+            check(rc)
+            import numpy as np
+            counts = []
+            c5 = (C.c_uint64 * 5)()
+            for i in range(self._L.jasper_compscan_num_seqs(res)):
+                check(self._L.jasper_compscan_counts(res, i, c5))
+                counts.append(tuple(int(v) for v in c5))
+            rp = C.POINTER(_lib.Compound)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_compscan_records(res, C.byref(rp), C.byref(rn)))
+            if rn.value:
+                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Compound)), dtype=COMPOUND_DTYPE).copy()
+            else:
+                recs = np.zeros(0, dtype=COMPOUND_DTYPE)
+            nl = C.c_uint64(0)
+            check(self._L.jasper_compscan_lookups(res, C.byref(nl)))
+            search, total = C.c_double(0), C.c_double(0)
+            check(self._L.jasper_compscan_seconds(res, C.byref(search), C.byref(total)))
+            rep = self._read_report(C.c_void_p(self._L.jasper_compscan_report(res)))      # (owned by res: read, not freed)
+            return CompoundScan(counts, recs, rep, total.value, search.value, int(nl.value), bool(self._L.jasper_compscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_compscan_free(res)
+
     def _read_mixed(self, res):
         import numpy as np
         counts = []
@@ -816,23 +905,26 @@ class KmerTable:
     def _wrap_report(self, rc, res):
         try:
             check(rc)
-            import numpy as np
-            counts = []
-            c4 = (C.c_uint64 * 4)()
-            for i in range(self._L.jasper_report_num_seqs(res)):
-                check(self._L.jasper_report_counts(res, i, c4))
-                counts.append(tuple(int(v) for v in c4))
-            rp = C.POINTER(_lib.KmerRun)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_report_runs(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.KmerRun)), dtype=KMERRUN_DTYPE).copy()
-            else:
-                runs = np.zeros(0, dtype=KMERRUN_DTYPE)
-            return KmerReport(counts, runs, self._L.jasper_report_seconds(res), bool(self._L.jasper_report_retried(res)))
+            return self._read_report(res)
         finally:
             if res:
                 self._L.jasper_report_free(res)
+
+    def _read_report(self, res):
+        import numpy as np
+        counts = []
+        c4 = (C.c_uint64 * 4)()
+        for i in range(self._L.jasper_report_num_seqs(res)):
+            check(self._L.jasper_report_counts(res, i, c4))
+            counts.append(tuple(int(v) for v in c4))
+        rp = C.POINTER(_lib.KmerRun)()
+        rn = C.c_uint64(0)
+        check(self._L.jasper_report_runs(res, C.byref(rp), C.byref(rn)))
+        if rn.value:
+            runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.KmerRun)), dtype=KMERRUN_DTYPE).copy()
+        else:
+            runs = np.zeros(0, dtype=KMERRUN_DTYPE)
+        return KmerReport(counts, runs, self._L.jasper_report_seconds(res), bool(self._L.jasper_report_retried(res)))
 
     def _wrap_result(self, rc, res, n, want_str):
         try:
