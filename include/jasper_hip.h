@@ -369,7 +369,8 @@ void jasper_copyrep_free(jasper_copyrep *r);
  * shorter than 2k-1 (empty ones too) are legal and give zeros.  The table is not modified.
  *
  * Limits: only ISOLATED substitutions are reported.  Two differences less than k apart hide each other, because every window that covers
- * one of them holds the other allele of the other.  Insertions and deletions are not reported here: jasper_indel_scan below lists
+ * one of them holds the other allele of the other (jasper_compound_scan lists such clusters where the sequence is wrong,
+ * jasper_indel_scan_clusters where both alleles are solid).  Insertions and deletions are not reported here: jasper_indel_scan below lists
  * them (same-base insertions and any deletion of up to 16 bytes) from the same dense scan, together with everything this call returns.
  *
  * On the device a dense scan probes, per window, the window's last base replaced by each of the other three; a solid one makes the
@@ -421,7 +422,8 @@ void jasper_varscan_free(jasper_varscan *r);
  * 2k-2 (empty ones too) are legal and give zeros.  The table is not modified.
  *
  * Limits: insertions of mixed bases are reported only by jasper_indel_scan_mixed below, lengths above 16 are not reported, and, as for
- * substitutions, two differences less than k apart hide each other (the error side of such clusters: jasper_compound_scan).
+ * substitutions, two differences less than k apart hide each other (the error side of such clusters: jasper_compound_scan; the het
+ * side: jasper_indel_scan_clusters below).
  *
  * On the device the variant scan's dense scan runs unchanged: its candidate (p, x) -- the window that ends at p is solid with its last
  * base replaced by x -- is the first k-mer of A for ins(p, x, L) and for del(p, L) with s[p+L] == x.  One more kernel tests these
@@ -506,6 +508,67 @@ int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n);
 int jasper_indelscan_mixed_retried(const jasper_indelscan *r);
 int jasper_indel_front(void);
 
+/* Het clusters: jasper_indel_scan plus the clusters of heterozygous differences that every single-edit check rejects.
+ *
+ * What it replaces: nothing -- an EXTENSION of the extension above.  Of two heterozygous differences less than k apart, at p and p2 > p,
+ * the dense scan hands over the candidate (p, x), and the substitution and the indel check then reject it: every later window that covers
+ * p also covers p2, where the sequence holds the other haplotype's allele.  At p2 there is no candidate at all.  jasper_compound_scan
+ * covers only the error side of such clusters, where the sequence's own k-mers are unreliable.  This search starts at the rejected
+ * candidates and walks the reads' solid k-mers until they rejoin the sequence -- where, is not known in advance.  Notation: s a sequence
+ * of n bytes, case folded; the table's k >= 2, thre >= 1, cluster_len = N in 1..64 (anything else is JASPER_ERR with a message that names
+ * the argument, even with nothing to scan); cnt() as above; FRONT = JASPER_INDEL_FRONT = 64:
+ *   candidate (p, x)  as the dense scan writes it, unchanged: the window s[p-k+1 .. p] is k bases, x is a base other than s[p], and
+ *                  cnt(F + x) >= thre with F = s[p-k+1 .. p-1].
+ *   repl(p, R, y)  for 1 <= R <= N and a string y of t bases, 1 <= t <= N, y[0] = x: the reads hold y where the sequence holds
+ *                  s[p .. p+R).  The alternative string is A = F + y + G_R with G_R = s[p+R .. p+R+k-2], of k-1+t windows.
+ *                  evaluated   all bytes s[p-k+1 .. p+R+k-2] exist and are bases
+ *                  ref_min(R)  the minimum of cnt over the k+R-1 windows of s that start at p-k+1 .. p+R-1: those that hold a replaced byte
+ *                  R_max(p)    the largest R <= N for which repl is evaluated and ref_min(R) >= thre (both are monotone in R), or 0.  A
+ *                              candidate with R_max = 0 is NOT SEARCHED: the sequence's own k-mers there are unreliable, and that site
+ *                              is jasper_compound_scan's.
+ *                  normal form y[0] != s[p] holds by the candidate; y[t-1] != s[p+R-1], otherwise the same haplotype has a shorter form;
+ *                              (R, t) != (1, 1), which is the variant scan's record.  Pure insertions and pure deletions never pass the
+ *                              last-base rule and stay the indel scan's: nothing is listed twice.
+ *   the search     at a searched candidate: S_1 = {x}.  After level t's record test a prefix y of S_t is CLOSED, and is not extended,
+ *                  when the last k-1 bases of F + y equal s[p+R-k+1 .. p+R-1] for some R in 1..R_max: it has been back on the sequence
+ *                  for k-1 bases, and whatever differs next is a site of its own with a candidate of its own.
+ *                      S_(t+1) = { yz : y in S_t, y not closed, z in ACGT, cnt(the last k bases of F + y + z) >= thre }
+ *                  It ends at the first of: t > N; S_t empty; |S_t| > FRONT.  In the last case the candidate is COMPLEX: counted once;
+ *                  records of lengths < t stay, nothing of length >= t is listed.
+ *   record         every (R, y) with y in a level that was reached, 1 <= R <= R_max and normal form, whose windows t .. t+k-2 of A are
+ *                  all >= thre: {seq, pos = p, ref_len = R, len = t, bases = y, ref_min = ref_min(R), alt_min}.  alt_min = the minimum
+ *                  over all k-1+t windows of A.  Every record is HET: ref_min >= thre by construction; there is no kind.
+ *   per sequence   four counters: searched (candidates with R_max >= 1), sites (searched candidates with at least one record), records,
+ *                  complex
+ * The rule is one of sets, not of a search order: the list, ordered by (seq, pos, ref_len, len, y), is identical on every call.  Every
+ * accessor of jasper_indelscan above returns for such a result exactly what it returns without cluster_len.
+ *
+ * On the device one more kernel runs over the candidates before the substitution check rewrites them: one wave per candidate, the
+ * reference windows first (a candidate with R_max = 0 leaves there), then a breadth-first search with the frontier one prefix per lane
+ * and the rejoin tests one R per lane.
+ *   jasper_indel_scan_clusters, _clusters_device   as jasper_indel_scan / _device, with mixed (0 or 1: the mixed half as well) and cluster_len
+ *   jasper_indelscan_cluster_counts    out4 = searched, sites, records, complex of one sequence
+ *   jasper_indelscan_cluster_records   the record list (owned by the result)
+ *   jasper_indelscan_cluster_seconds   device time of the search kernel (part of jasper_indelscan_seconds)
+ *   jasper_indelscan_cluster_lookups   table lookups it made;  jasper_indelscan_cluster_retried: it was repeated with a larger list
+ * For a result of the entry points above the cluster accessors give zeros and n = 0. */
+typedef struct jasper_het_cluster {
+    int64_t pos;
+    uint32_t seq, ref_min, alt_min, ref_len;
+    uint64_t bases[2]; /* base i of y in bits 2i..2i+1 of bases[i / 32], A C G T = 0 1 2 3, 0 above 2*len */
+    uint16_t len;
+    uint8_t pad[6] /* 0 */;
+} jasper_het_cluster; /* 48 B, laid out like jasper_compound */
+int jasper_indel_scan_clusters(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, int mixed, int cluster_len,
+                               jasper_indelscan **out);
+int jasper_indel_scan_clusters_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, int mixed,
+                                      int cluster_len, jasper_indelscan **out);
+int jasper_indelscan_cluster_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]);   /* searched, sites, records, complex */
+int jasper_indelscan_cluster_records(const jasper_indelscan *r, const jasper_het_cluster **recs, uint64_t *n);
+double jasper_indelscan_cluster_seconds(const jasper_indelscan *r);
+int jasper_indelscan_cluster_lookups(const jasper_indelscan *r, uint64_t *n);
+int jasper_indelscan_cluster_retried(const jasper_indelscan *r);
+
 /* Compound scan: WHAT the reads hold in place of a cluster of differences that hide each other from the two scans above.
  *
  * What it replaces: nothing -- an EXTENSION.  Two differences less than k apart leave no solid single-edit alternative: every window that
@@ -536,8 +599,8 @@ int jasper_indel_front(void);
  * The rule is one of sets, not of a search order: the list, ordered by (seq, pos, len, y), is identical on every call.  The table is
  * not modified.
  *
- * Limits: compound HET sites are out of scope -- where both alleles are solid there is no unreliable run (the variant scan lists the
- * left end of such a site); replacements longer than 64 bases are not listed.
+ * Limits: compound HET sites -- where both alleles are solid there is no unreliable run -- are not listed here but by
+ * jasper_indel_scan_clusters above; replacements longer than 64 bases are not listed.
  *
  * On the device jasper_kmer_report's scan runs unchanged; the host picks the sites and the long runs from its runs, and one more
  * kernel searches the sites, one wave each, with the frontier S_t held one prefix per lane.  With no site nothing more is allocated

@@ -70,6 +70,13 @@ class Compound(C.Structure):
 
 assert C.sizeof(Compound) == 48
 
+
+class HetCluster(C.Structure):
+    _fields_ = Compound._fields_
+
+
+assert C.sizeof(HetCluster) == 48
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -190,6 +197,13 @@ SYMBOLS = {
     "jasper_indelscan_mixed_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "jasper_indelscan_mixed_retried": (C.c_int, [_P]),
     "jasper_indel_front": (C.c_int, []),
+    "jasper_indel_scan_clusters": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "jasper_indel_scan_clusters_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "jasper_indelscan_cluster_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_cluster_records": (C.c_int, [_P, C.POINTER(C.POINTER(HetCluster)), C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_cluster_seconds": (C.c_double, [_P]),
+    "jasper_indelscan_cluster_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_indelscan_cluster_retried": (C.c_int, [_P]),
     "jasper_compound_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
     "jasper_compound_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.POINTER(_P)]),
     "jasper_compscan_num_seqs": (C.c_int, [_P]),

@@ -3,7 +3,7 @@ sentinel files and log lines; the Jellyfish + per-batch python processes are rep
 polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
-                            [--indels [--indel-max-len N] [--indel-mixed]] [--compound [--compound-max-len N]]
+                            [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -108,6 +108,8 @@ class Options:
         self.indels = False
         self.indel_mixed = False
         self.indel_max_len = None    # --indel-max-len: longest insertion / deletion the indel scan tries (default 4, at most 16)
+        self.het_clusters = False
+        self.het_cluster_max_len = None   # --het-cluster-max-len: longest replacement the het-cluster search lists (default 64, at most 64)
         self.compound = False
         self.compound_max_len = None # --compound-max-len: longest replacement the compound scan searches (default 64, at most 64)
 
@@ -170,6 +172,10 @@ def parse_args(argv):
             o.indel_mixed = True
         elif key == "--indel-max-len":
             o.indel_max_len = nxt; i += 1
+        elif key == "--het-clusters":                                  # extension: the indel scan also lists clusters of het differences less than k apart
+            o.het_clusters = True
+        elif key == "--het-cluster-max-len":
+            o.het_cluster_max_len = nxt; i += 1
         elif key == "--compound":                                      # extension: what the reads hold for clusters of differences (_compound)
             o.compound = True
         elif key == "--compound-max-len":
@@ -1236,13 +1242,31 @@ def indel_mixed_flag(mixed, indels):
         error_exit("--indel-mixed needs --indels: it adds the insertions of mixed bases to the indel scan")
 
 
-def scan_indels(table, contigs, thre, max_len, mixed=False):
+HET_CLUSTER_MAX_LEN_DEFAULT = 64
+
+
+def het_cluster_flags(max_len, clusters=True, indels=True):
+    """--het-cluster-max-len as given (a string or None) -> the longest replacement to list; exits on anything but an integer in
+    1..64.  --het-clusters is a mode of --indels: alone it ends the run"""
+    if clusters and not indels:
+        error_exit("--het-clusters needs --indels: it adds the clusters of heterozygous differences less than k apart to the indel scan")
+    if max_len is None:
+        return HET_CLUSTER_MAX_LEN_DEFAULT
+    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 64:
+        error_exit("--het-cluster-max-len takes an integer from 1 to 64; it is %s" % max_len)
+    return int(max_len)
+
+
+def scan_indels(table, contigs, thre, max_len, mixed=False, clusters=0):
     """the indel scan of whole contigs [(name token, sequence)] -> (names, lengths, IndelScan), whose .variants is what scan_variants
     gives; exits on a threshold of 0, which would call every alternative solid"""
     from . import report
     if thre < 1:
         error_exit("--indels needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], (table.indel_scan([s for _, s in contigs], thre, max_len, mixed=True) if mixed else table.indel_scan([s for _, s in contigs], thre, max_len))
+    more = dict(mixed=True) if mixed else {}
+    if clusters:
+        more["clusters"] = clusters
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.indel_scan([s for _, s in contigs], thre, max_len, **more)
 
 
 def _indels(o, table):
@@ -1257,8 +1281,9 @@ def _indels(o, table):
     thresh = int(open("threshold.txt").read().split()[0])
     asm0, asm1 = read_assembly(o.query), read_assembly(qfn + ".polished.fasta")
     mixed = o.indel_mixed
-    names, len0, is0 = scan_indels(table, asm0, thresh, max_len, mixed)
-    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len, mixed)
+    clusters = het_cluster_flags(o.het_cluster_max_len) if o.het_clusters else 0
+    names, len0, is0 = scan_indels(table, asm0, thresh, max_len, mixed, clusters)
+    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len, mixed, clusters)
     if o.variants:
         vs0, vs1 = is0.variants, is1.variants
         len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
@@ -1280,12 +1305,23 @@ def _indels(o, table):
     log(indels.log_text(is0.counts, cnt1a))
     if mixed:
         log(indels.mixed_log_text(is0.mixed.counts, mix1a))
+    if clusters:
+        from . import hetclusters
+        hc0, hc1 = is0.clusters, is1.clusters
+        hc1a = report.align(names, names1, len1, hc1.counts)[1]
+        hetclusters.write_atomic(qfn + ".het_clusters.tsv", hetclusters.het_clusters_tsv_text(names, [("before", len0, hc0.counts), ("after", len1a, hc1a)]))
+        hetclusters.write_atomic(qfn + ".het_clusters.before.vcf", hetclusters.vcf_text(k, thresh, clusters, names, len0, [s for _, s in asm0], hc0.records))
+        hetclusters.write_atomic(qfn + ".het_clusters.after.vcf", hetclusters.vcf_text(k, thresh, clusters, names1, len1, [s for _, s in asm1], hc1.records))
+        log(hetclusters.log_text(hc0.counts, hc1a))
     if _timing_on():
         sys.stderr.write("[indels] device seconds: before %.6f (check %.6f) after %.6f (check %.6f); candidates %d %d\n" %
                          (is0.seconds, is0.check_seconds, is1.seconds, is1.check_seconds, is0.variants.candidates, is1.variants.candidates))
         if mixed:
             sys.stderr.write("[indels] mixed search device seconds: before %.6f after %.6f; lookups %d %d\n" %
                              (is0.mixed.seconds, is1.mixed.seconds, is0.mixed.lookups, is1.mixed.lookups))
+        if clusters:
+            sys.stderr.write("[indels] het-cluster search device seconds: before %.6f after %.6f; lookups %d %d\n" %
+                             (is0.clusters.seconds, is1.clusters.seconds, is0.clusters.lookups, is1.clusters.lookups))
 
 
 COMPOUND_MAX_LEN_DEFAULT = 64
@@ -1374,6 +1410,8 @@ def run(argv):
     if o.indels:
         indel_flags(o.indel_max_len)
     indel_mixed_flag(o.indel_mixed, o.indels)
+    if o.het_clusters:
+        het_cluster_flags(o.het_cluster_max_len, True, o.indels)
     if o.compound:
         compound_flags(o.compound_max_len)
     if not _nonempty(o.query):

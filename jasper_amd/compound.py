@@ -11,8 +11,8 @@ error (`TYPE=complex`).  Every record is an error -- the contig's own k-mers the
 Per contig the TSV counts the sites (runs that were searched), the bridged ones (at least one record), the records, the long runs
 (R > max_len: not searched) and the complex sites (more than 64 prefixes of one length were solid: the search stopped there).
 
-Limits: compound het sites are out of scope (where both alleles are solid there is no unreliable run), deletions alone stay the
-indel scan's and a single substitution the variant scan's, and nothing longer than 64 bases is listed.
+Limits: compound het sites are not listed here (where both alleles are solid there is no unreliable run) but by the het-cluster
+half of the indel scan (--indels --het-clusters, jasper_amd/hetclusters.py), deletions alone stay the indel scan's and a single substitution the variant scan's, and nothing longer than 64 bases is listed.
 
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
 """

@@ -881,13 +881,17 @@ static_assert(sizeof(jasper_mixed_ins) == sizeof(MixedIns) && offsetof(jasper_mi
                   offsetof(jasper_mixed_ins, len) == offsetof(MixedIns, len) && offsetof(jasper_mixed_ins, kind) == offsetof(MixedIns, kind),
               "jasper_mixed_ins is MixedIns");
 static_assert(JASPER_INDEL_FRONT == INDEL_FRONT, "the header's cap is the kernel's");
+static_assert(sizeof(jasper_het_cluster) == sizeof(HetCluster) && offsetof(jasper_het_cluster, alt_min) == offsetof(HetCluster, alt_min) &&
+                  offsetof(jasper_het_cluster, ref_len) == offsetof(HetCluster, ref_len) && offsetof(jasper_het_cluster, bases) == offsetof(HetCluster, bases) &&
+                  offsetof(jasper_het_cluster, len) == offsetof(HetCluster, len),
+              "jasper_het_cluster is HetCluster");
 static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
-                          int max_len, bool mixed, jasper_indelscan **out) {
+                          int max_len, bool mixed, int cluster_len, jasper_indelscan **out) {
     if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
     *out = nullptr;
     jasper_indelscan *r = new jasper_indelscan();
-    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, mixed, r->r, g_err)
-                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, mixed, r->r, g_err);
+    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, mixed, cluster_len, r->r, g_err)
+                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, mixed, cluster_len, r->r, g_err);
     if (rc) { delete r; return JASPER_ERR; }
     r->var.r = std::move(r->r.var);
     *out = r;
@@ -895,19 +899,31 @@ static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, 
 }
 int jasper_indel_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, false, out);
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, false, 0, out);
 }
 int jasper_indel_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, false, out);
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, false, 0, out);
 }
 int jasper_indel_scan_mixed(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, true, out);
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, true, 0, out);
 }
 int jasper_indel_scan_mixed_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
     if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, true, out);
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, true, 0, out);
+}
+int jasper_indel_scan_clusters(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, int mixed, int cluster_len,
+                               jasper_indelscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    if (cluster_len < 1 || cluster_len > CLUSTER_MAX_LEN) { g_err = "indel scan: cluster_len must be in 1..64"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, mixed != 0, cluster_len, out);
+}
+int jasper_indel_scan_clusters_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, int mixed, int cluster_len,
+                                      jasper_indelscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    if (cluster_len < 1 || cluster_len > CLUSTER_MAX_LEN) { g_err = "indel scan: cluster_len must be in 1..64"; return JASPER_ERR; }
+    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, mixed != 0, cluster_len, out);
 }
 int jasper_indelscan_num_seqs(const jasper_indelscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
 int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
@@ -949,6 +965,24 @@ int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n) {
 }
 int jasper_indelscan_mixed_retried(const jasper_indelscan *r) { return r ? r->r.mixed_retried : 0; }
 int jasper_indel_front(void) { return INDEL_FRONT; }
+int jasper_indelscan_cluster_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
+    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 4; ++i) out4[i] = r->r.cluster_len ? r->r.cluster_counts[4 * (size_t)seq + i] : 0;
+    return JASPER_OK;
+}
+int jasper_indelscan_cluster_records(const jasper_indelscan *r, const jasper_het_cluster **recs, uint64_t *n) {
+    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *recs = reinterpret_cast<const jasper_het_cluster *>(r->r.cluster_recs.data());
+    *n = r->r.cluster_recs.size();
+    return JASPER_OK;
+}
+double jasper_indelscan_cluster_seconds(const jasper_indelscan *r) { return r ? r->r.cluster_seconds : 0.0; }
+int jasper_indelscan_cluster_lookups(const jasper_indelscan *r, uint64_t *n) {
+    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = r->r.cluster_lookups;
+    return JASPER_OK;
+}
+int jasper_indelscan_cluster_retried(const jasper_indelscan *r) { return r ? r->r.cluster_retried : 0; }
 void jasper_indelscan_free(jasper_indelscan *r) { delete r; }
 
 // ---- compound scan (compound.hip) ----

@@ -42,6 +42,29 @@
 //                         The records of a level (at most 64, lane i its own) take one returning cursor add; a level writes all its
 //                         records or none.  Same-base strings x^t stay in the frontier but are never written: they are the check's.
 //
+//   het_cluster_kernel    (only when the caller asks for het clusters, cluster_len = N > 0) one wave per candidate (p, x): the replacements
+//                         of s[p .. p+R) by a string y, y[0] == x, R and |y| up to N, where the sequence and the replacement are both
+//                         solid.  The wave loads the context s[p-k+1 .. p+N+k-2] (up to 190 bytes: lane l holds bytes l, l + 64, l + 128)
+//                         and makes the two bit planes of it.
+//                           ref      the reference windows 0 .. k+R-2 for the largest R whose bytes are bases, in at most two rounds
+//                                    (k - 1 + N <= 127 windows: lane j, then lane j - 64).  After the first round a candidate whose own k
+//                                    windows are not all solid leaves: R_max = 0, the compound scan's.  A prefix minimum over both rounds
+//                                    puts ref_min(R) on lane R - 1, and the ballot of ref_min(R) >= thre is R_max (wave-uniform).
+//                           lane R-1 keeps CW = the k - 1 bases before p + R (closure) and G = the k - 1 bases from p + R on (rejoin).
+//                         Then the breadth-first search of indels_mixed_kernel with y in 128 bits as in compound_search_kernel (first
+//                         base in the highest pair; the shift boundaries t < k, t >= k - 1 and t = 64 are those documented there), per
+//                         level t:
+//                           closure  per prefix, W = the last k - 1 bases of F + y against every lane's CW: one 128-bit compare, one ballot
+//                           extend   (prefix, z) on lane 4 * prefix + z, sixteen prefixes a round.  Every prefix is looked up, the closed
+//                                    ones too: the four answers are window t of F + y + G_R for the R with s[p+R] == z, so lane i keeps its
+//                                    prefix's 4-bit solid mask.  Children of the prefixes that are not closed go through the LDS strip.
+//                           rejoin   per prefix, lane R - 1: normal form and one bit of that mask (no lookup); the R that survive look up
+//                                    windows t+1 .. t+3 one after the other, each lane its own, leaving at the first that fails -- every
+//                                    one of them cuts the field to a quarter in ordinary sequence; what is left runs all k - 1 windows
+//                                    t .. t+k-2 lane-parallel with a wave minimum, in a wave-uniform loop.
+//                         The records of a prefix (at most 64, lane R - 1 its own) take one returning cursor add; a prefix writes all
+//                         its records or none.
+//
 // The record list starts at candidates + 4096 entries; a check that found more has counted them and is repeated once with exactly that
 // room (run_counted, scan_tile.hpp: the dense scans' repeat, here around the check).  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
 #include "indels.hpp"
@@ -388,16 +411,197 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
     if (lane == 0 && ncomplex) atomicAdd(&ctl[MC_COMPLEX], ncomplex);
 }
 
-static int indel_check_args(const Table &T, uint32_t thre, int max_len, std::string &err) {
+// ---- het clusters ----------------------------------------------------------------------------------------------------------------------
+enum { HC_LOOKUPS = 1, HC_COMPLEX = 2, HC_SEARCHED = 3 };                // control words 1 .. 3: table lookups made; complex and searched candidates
+
+__device__ __forceinline__ uint64_t hc_readlane64(uint64_t v, int l) {      // l wave-uniform
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+__device__ __forceinline__ u128 hc_readlane128(u128 v, int l) { return mk(hc_readlane64(v.hi, l), hc_readlane64(v.lo, l)); }
+
+__global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int N,
+                                                          const Variant *__restrict__ cand, uint64_t ncand, HetCluster *__restrict__ out, unsigned long long cap,
+                                                          unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ per) {
+    __shared__ ulonglong2 s_y[4][INDEL_FRONT];          // a wave's next frontier: y (.x low, .y high) ...
+    __shared__ uint32_t s_mn[4][INDEL_FRONT];           // ... and its running minimum
+    const int lane = threadIdx.x & 63;
+    ulonglong2 *strip_y = s_y[threadIdx.x >> 6];
+    uint32_t *strip_mn = s_mn[threadIdx.x >> 6];
+    const int k = R.k;
+    const int CL = 2 * k - 2 + N;                       // context bytes: at most 190
+    const u128 kmask = maskbits(2 * k), fmask = maskbits(2 * (k - 1));
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const uint64_t nwv = (uint64_t)gridDim.x * 4;
+    unsigned long long nlook = 0, ncomplex = 0, nsearched = 0;      // (wave-uniform)
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ncand; i += nwv) {
+        const int64_t p = cand[i].pos;
+        const uint32_t seq = cand[i].seq;
+        const int x = cand[i].alt & 3;
+        const int64_t o0 = offs[seq];
+        const int64_t n = offs[seq + 1] - o0;
+        const uint8_t *__restrict__ txt = text + o0;
+        if (p < k - 1 || p >= n) continue;              // (wave-uniform; the scan writes no such candidate)
+        const int64_t b0 = p - k + 1;
+        int c0 = -1, c1 = -1, c2 = -1;                  // codes of context bytes lane, lane + 64, lane + 128
+        if (lane < CL && b0 + lane < n) c0 = code(txt[b0 + lane]);
+        if (lane + 64 < CL && b0 + lane + 64 < n) c1 = code(txt[b0 + lane + 64]);
+        if (lane + 128 < CL && b0 + lane + 128 < n) c2 = code(txt[b0 + lane + 128]);
+        const unsigned long long n0 = __ballot(c0 < 0), n1 = __ballot(c1 < 0), n2 = __ballot(c2 < 0);
+        const int bases = n0 ? (int)__builtin_ctzll(n0) : n1 ? 64 + (int)__builtin_ctzll(n1) : n2 ? 128 + (int)__builtin_ctzll(n2) : 192;      // ... in a row from byte 0
+        const int refc = __shfl(c0, k - 1);
+        if (bases < 2 * k - 1 || refc == x) continue;   // repl(p, 1, ..) is not evaluated, hence none is
+        const int Rev = bases - (2 * k - 2) < N ? bases - (2 * k - 2) : N;      // the R that are evaluated: 1 .. Rev
+        const Plane clo = {__ballot(c0 > 0 && (c0 & 1)), __ballot(c1 > 0 && (c1 & 1)), __ballot(c2 > 0 && (c2 & 1))},
+                    chi = {__ballot(c0 > 0 && (c0 & 2)), __ballot(c1 > 0 && (c1 & 2)), __ballot(c2 > 0 && (c2 & 2))};
+        // ref: windows 0 .. k+Rev-2 of s, lane j and, past 64, lane j - 64
+        const int jmax = k + Rev - 2;                   // <= 126
+        uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;
+        if (lane <= jmax) ra = id_count(R, id_kmer(clo, chi, lane, k), k);
+        nlook += (unsigned)(jmax < 63 ? jmax + 1 : 64);
+        const uint32_t pma = wave_prefix_min32<64>(ra);
+        if ((uint32_t)__shfl(pma, k - 1) < thre) continue;      // R_max = 0: the sequence's own k-mers are unreliable here
+        if (jmax >= 64) {
+            if (lane + 64 <= jmax) rb = id_count(R, id_kmer(clo, chi, lane + 64, k), k);
+            nlook += (unsigned)(jmax - 63);
+        }
+        const uint32_t pmb = id_min(wave_prefix_min32<64>(rb), (uint32_t)__shfl(pma, 63));
+        const int ri = lane + k - 1;                    // lane R - 1: ref_min(R) is the prefix minimum at window k + R - 2
+        const uint32_t va = (uint32_t)__shfl(pma, ri & 63), vb = (uint32_t)__shfl(pmb, ri & 63);
+        const uint32_t rmin = ri < 64 ? va : vb;
+        const unsigned long long okR = __ballot(lane < Rev && rmin >= thre);
+        const int Rmax = ~okR ? (int)__builtin_ctzll(~okR) : 64;      // (>= 1: window k - 1 passed)
+        ++nsearched;
+        if (lane == 0) atomicAdd(&per[2 * (size_t)seq], 1ull);
+        // lane R - 1 < Rmax: the k - 1 bases before p + R, and the k - 1 bases from p + R on
+        u128 CW = mk(0, 0), G = mk(0, 0);
+        if (lane < Rmax) {
+            CW = shr(id_kmer(clo, chi, lane + 1, k), 2);
+            G = shr(id_kmer(clo, chi, lane + k, k), 2);
+        }
+        const unsigned nb = (unsigned)shr(G, 2 * (k - 2)).lo & 3u, lastref = (unsigned)CW.lo & 3u;      // s[p + R] and s[p + R - 1]
+        const u128 F = shr(id_kmer(clo, chi, 0, k), 2); // the k - 1 bases before p
+        // level 1: S_1 = {x}
+        u128 y = mk(0, (uint64_t)x);                    // lane i < nf: prefix i, first base in the highest pair ...
+        uint32_t mn = 0xFFFFFFFFu;                      // ... and the minimum over its windows
+        int nf = 1;
+        if (lane == 0) mn = id_count(R, band(bor(shl(F, 2), y), kmask), k);
+        nlook += 1;
+        if ((uint32_t)__shfl(mn, 0) < thre) continue;
+        for (int t = 1; t <= N; ++t) {
+            const u128 W = t >= k - 1 ? band(y, fmask) : band(bor(shl(F, 2 * t), y), fmask);      // the last k - 1 bases of F + y
+            // closure: a prefix that has been back on the sequence for k - 1 bases is not extended
+            unsigned long long closedm = 0;             // (wave-uniform) bit i: prefix i is closed
+            for (int i2 = 0; i2 < nf; ++i2) {
+                const u128 Wi = hc_readlane128(W, i2);
+                if (__ballot(lane < Rmax && eq(Wi, CW))) closedm |= 1ull << i2;
+            }
+            // extend: sixteen prefixes a round, (prefix, z) on lane 4 * prefix + z; lane i keeps the solid mask of prefix i
+            const u128 Fs = t + 1 < k ? shl(F, 2 * (t + 1)) : mk(0, 0);      // from t + 1 >= k on the newest window is yz's alone
+            unsigned solid = 0;
+            int tot = 0;
+            for (int r0 = 0; r0 < nf; r0 += 16) {
+                const int src = r0 + (lane >> 2);       // <= 63
+                const u128 ny = bor(shl(mk(__shfl(y.hi, src), __shfl(y.lo, src)), 2), mk(0, (uint64_t)(lane & 3)));      // (at t = 64 the first base is lost: no child then)
+                const uint32_t pm = (uint32_t)__shfl(mn, src);
+                uint32_t c = 0;
+                if (src < nf) c = id_count(R, band(bor(Fs, ny), kmask), k);
+                const bool ok = src < nf && c >= thre;
+                const unsigned long long B = __ballot(ok);
+                if (lane >= r0 && lane < r0 + 16) solid = (unsigned)(B >> (4 * (lane - r0))) & 15u;
+                const bool child = ok && t < N && !((closedm >> src) & 1ull);
+                const unsigned long long C = __ballot(child);
+                const int at = tot + __popcll(C & below);
+                if (child && at < INDEL_FRONT) {
+                    strip_y[at] = make_ulonglong2(ny.lo, ny.hi);
+                    strip_mn[at] = id_min(pm, c);
+                }
+                tot += __popcll(C);
+            }
+            nlook += 4u * (unsigned)nf;
+            // rejoin: the records of level t, prefix by prefix, lane R - 1 for its own R
+            for (int i2 = 0; i2 < nf; ++i2) {
+                const u128 yi = hc_readlane128(y, i2), Wi = hc_readlane128(W, i2);
+                const unsigned sol = (unsigned)__builtin_amdgcn_readlane((int)solid, i2);
+                const uint32_t mni = (uint32_t)__builtin_amdgcn_readlane((int)mn, i2);
+                bool alive = lane < Rmax && ((sol >> nb) & 1u) && ((unsigned)yi.lo & 3u) != lastref && !(t == 1 && lane == 0);
+                unsigned long long am = __ballot(alive);
+                for (int j = 1; j <= 3 && j <= k - 2 && am; ++j) {      // windows t + 1 .. t + 3, each lane its own
+                    if (alive) alive = id_count(R, band(bor(shl(Wi, 2 * (j + 1)), shr(G, 2 * (k - 2 - j))), kmask), k) >= thre;
+                    nlook += (unsigned)__popcll(am);
+                    am = __ballot(alive);
+                }
+                unsigned long long recm = 0;            // (wave-uniform) bit R - 1: (R, prefix i2) is a record
+                uint32_t my_amin = 0;
+                for (unsigned long long q = am; q; q &= q - 1ull) {
+                    const int r = (int)__builtin_ctzll(q);
+                    const u128 Gr = hc_readlane128(G, r);
+                    uint32_t b = 0xFFFFFFFFu;
+                    if (lane < k - 1)                   // window t + lane: the last k - 1 - lane bases of W, then lane + 1 bases of G
+                        b = id_count(R, band(bor(shl(Wi, 2 * (lane + 1)), shr(Gr, 2 * (k - 2 - lane))), kmask), k);
+                    nlook += (unsigned)(k - 1);
+                    b = id_min(wave_min32(b), mni);
+                    if (b >= thre) {
+                        recm |= 1ull << r;
+                        if (lane == r) my_amin = b;
+                    }
+                }
+                if (recm) {
+                    unsigned long long base = 0;
+                    const unsigned total = __popcll(recm);
+                    if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
+                    base = __shfl(base, 0);
+                    if (base + total <= cap && ((recm >> lane) & 1ull)) {      // (a prefix writes all its records or none)
+                        const u128 rv = shr(mk(revpairs64(yi.lo), revpairs64(yi.hi)), 128 - 2 * t);      // base i in bits 2i, 2i + 1
+                        HetCluster v;
+                        v.pos = p;
+                        v.seq = seq;
+                        v.ref_min = rmin;
+                        v.alt_min = my_amin;
+                        v.ref_len = (uint32_t)(lane + 1);
+                        v.bases[0] = rv.lo;
+                        v.bases[1] = rv.hi;
+                        v.len = (uint16_t)t;
+                        for (int z = 0; z < 6; ++z) v.pad[z] = 0;
+                        out[base + __popcll(recm & below)] = v;
+                    }
+                }
+            }
+            if (tot > INDEL_FRONT) {                    // complex: nothing of length > t is listed here
+                ++ncomplex;
+                if (lane == 0) atomicAdd(&per[2 * (size_t)seq + 1], 1ull);
+                break;
+            }
+            if (tot == 0) break;                        // (also t == N: no child is placed then)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (lane < tot) {
+                const ulonglong2 v = strip_y[lane];
+                y = mk(v.y, v.x);
+                mn = strip_mn[lane];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            nf = tot;
+        }
+    }
+    if (lane == 0 && nlook) atomicAdd(&ctl[HC_LOOKUPS], nlook);
+    if (lane == 0 && ncomplex) atomicAdd(&ctl[HC_COMPLEX], ncomplex);
+    if (lane == 0 && nsearched) atomicAdd(&ctl[HC_SEARCHED], nsearched);
+}
+
+static int indel_check_args(const Table &T, uint32_t thre, int max_len, int cluster_len, std::string &err) {
     if (thre < 1) { err = "indel scan: the threshold (thre) must be at least 1"; return -1; }
     if (T.k < 2) { err = "indel scan: k must be at least 2"; return -1; }
     if (max_len < 1 || max_len > INDEL_MAX_LEN) { err = "indel scan: max_len must be in 1..16"; return -1; }
+    if (cluster_len < 0 || cluster_len > CLUSTER_MAX_LEN) { err = "indel scan: cluster_len must be in 1..64"; return -1; }
     return 0;
 }
 
-int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err) {
+int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, bool mixed, int cluster_len, IndelOut &out,
+                      std::string &err) {
     if (n_seqs < 0 || (n_seqs && !offsets)) { err = "indel scan: bad arguments"; return -1; }
-    if (indel_check_args(T, thre, max_len, err)) return -1;
+    if (indel_check_args(T, thre, max_len, cluster_len, err)) return -1;
     HIPCHK(hipSetDevice(T.device));
     if (T.materialize(err)) return -1;       // a logically empty table holds garbage until it is zeroed
     out = IndelOut();
@@ -405,6 +609,8 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
     out.var.counts.assign((size_t)n_seqs * 3, 0);
     out.mixed = mixed;
     if (mixed) out.mixed_counts.assign((size_t)n_seqs * 3, 0);
+    out.cluster_len = cluster_len;
+    if (cluster_len) out.cluster_counts.assign((size_t)n_seqs * 4, 0);
     VariantStage S;
     if (variant_scan_stage(T, n_seqs, d_text, offsets, thre, "indel scan", out.var, S, err)) return -1;
     if (S.ntiles == 0) return 0;
@@ -459,8 +665,39 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
         }
         if (sum != ctl[MC_COMPLEX]) { err = "indel scan: the complex sites per sequence do not add up"; return -1; }
     }
+    if (ncand && cluster_len) {
+        const int W = Table::WS_CLUSTERS;
+        const size_t words = SC_WORDS + 2 * (size_t)n_seqs;      // the control words, then per sequence the searched and the complex candidates
+        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 1, words * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
+        if (!d_ctl) return -1;
+        HetCluster *d_rec = nullptr;
+        auto search = [&](unsigned long long cap) {
+            d_rec = (HetCluster *)T.workspace(W, cap * sizeof(HetCluster), err);
+            if (!d_rec) return -1;
+            hipLaunchKernelGGL(het_cluster_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, cluster_len,
+                               S.d_cand, ncand, d_rec, cap, d_ctl, d_ctl + SC_WORDS);
+            return 0;
+        };
+        if (run_counted(st, d_ctl, words, d_ctl, ncand + 4096, "indel scan: the number of het clusters changed between two searches", ctl, out.cluster_seconds,
+                        out.cluster_retried, err, search))
+            return -1;
+        out.cluster_lookups = ctl[HC_LOOKUPS];
+        out.cluster_recs.resize(ctl[SC_CURSOR]);
+        std::vector<unsigned long long> per(2 * (size_t)n_seqs);
+        if (!out.cluster_recs.empty())
+            HIPCHK(hipMemcpyAsync(out.cluster_recs.data(), d_rec, out.cluster_recs.size() * sizeof(HetCluster), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(per.data(), d_ctl + SC_WORDS, per.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(jk_stream_wait(st));
+        unsigned long long nsearched = 0, ncomplex = 0;
+        for (size_t i = 0; i < (size_t)n_seqs; ++i) {
+            nsearched += out.cluster_counts[4 * i] = per[2 * i];
+            ncomplex += out.cluster_counts[4 * i + 3] = per[2 * i + 1];
+        }
+        if (nsearched != ctl[HC_SEARCHED] || ncomplex != ctl[HC_COMPLEX]) { err = "indel scan: the searched and complex candidates per sequence do not add up"; return -1; }
+        if (het_cluster_finish(out.cluster_recs, n_seqs, cluster_len, out.cluster_counts, err)) return -1;
+    }
     if (variant_check_stage(T, n_seqs, d_text, thre, "indel scan", S, out.var, err)) return -1;
-    out.seconds = out.var.seconds + out.check_seconds + out.mixed_seconds;
+    out.seconds = out.var.seconds + out.check_seconds + out.mixed_seconds + out.cluster_seconds;
     std::sort(out.recs.begin(), out.recs.end(), [](const Indel &a, const Indel &b) {
         return a.seq != b.seq ? a.seq < b.seq : a.pos != b.pos ? a.pos < b.pos : a.type != b.type ? a.type < b.type : a.len != b.len ? a.len < b.len : a.base < b.base;
     });
@@ -490,12 +727,13 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
     return 0;
 }
 
-int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err) {
+int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, bool mixed, int cluster_len, IndelOut &out,
+                    std::string &err) {
     if (n_seqs < 0 || (n_seqs && (!seqs || !lens))) { err = "indel scan: bad arguments"; return -1; }
-    if (indel_check_args(T, thre, max_len, err)) return -1;
+    if (indel_check_args(T, thre, max_len, cluster_len, err)) return -1;
     HostText H;
     if (pack_host_text(T, Table::WS_INDELS, n_seqs, seqs, lens, "indel scan", H, err)) return -1;
-    return indel_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, max_len, mixed, out, err);
+    return indel_scan_device(T, n_seqs, H.d_text, H.offs.data(), thre, max_len, mixed, cluster_len, out, err);
 }
 
 }  // namespace jk

@@ -5,7 +5,11 @@
 // that x follows.  A second check kernel tests those hypotheses (semantics: include/jasper_hip.h, jasper_indel_scan); the substitution
 // check runs over the same candidates afterwards, so one call answers both questions.  With `mixed` a third kernel searches, per
 // candidate, the insertions of mixed bases that start with x (jasper_indel_scan_mixed); without it nothing of that runs or is allocated.
+// With `cluster_len` > 0 a fourth kernel searches, per candidate, the replacements of up to cluster_len bytes by up to cluster_len bases
+// where both the sequence and the replacement are solid -- clusters of heterozygous differences less than k apart, which every
+// single-edit check rejects (jasper_indel_scan_clusters); with 0 nothing of that runs or is allocated.
 #pragma once
+#include "hetcluster_host.hpp"
 #include "variants.hpp"
 
 namespace jk {
@@ -54,9 +58,18 @@ struct IndelOut {
     double mixed_seconds = 0;              // device time of indels_mixed_kernel (part of `seconds`)
     uint64_t mixed_lookups = 0;            // table lookups it made (its last run)
     int mixed_retried = 0;                 // it was repeated with a larger record list
+    // the het-cluster half: empty unless the scan was asked for it
+    int cluster_len = 0;
+    std::vector<uint64_t> cluster_counts;  // 4 per sequence: searched, sites, records, complex
+    std::vector<HetCluster> cluster_recs;  // ordered by (seq, pos, ref_len, len, y)
+    double cluster_seconds = 0;            // device time of het_cluster_kernel (part of `seconds`)
+    uint64_t cluster_lookups = 0;          // table lookups it made (its last run)
+    int cluster_retried = 0;               // it was repeated with a larger record list
 };
 
-int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err);
-int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, bool mixed, IndelOut &out, std::string &err);
+int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t *offsets, uint32_t thre, int max_len, bool mixed, int cluster_len, IndelOut &out,
+                      std::string &err);
+int indel_scan_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, bool mixed, int cluster_len, IndelOut &out,
+                    std::string &err);
 
 }  // namespace jk

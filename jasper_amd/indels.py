@@ -11,7 +11,7 @@ mixed bases are listed as well: three more columns in the TSV (mixed_het, mixed_
 prefixes of one length were solid and the search stopped) and more `TYPE=ins` lines in the VCF.
 
 Limits: insertions of mixed bases are listed only with the mixed half, lengths above 16 are not listed, and two differences less than
-k apart hide each other.
+k apart hide each other (the het-cluster half of the scan lists those where both alleles are solid: jasper_amd/hetclusters.py).
 
 The scan reports every indel at its right-most position; the VCF writer moves it to the left-most one (`left_align`), as VCF asks.
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.

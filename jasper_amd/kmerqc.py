@@ -1,7 +1,7 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
-                                [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]]
+                                [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
                                 [--compound [--compound-max-len N]]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
@@ -33,12 +33,21 @@ With --variants the contigs are also scanned for positions where the reads hold 
 
 With --indels the contigs are also scanned for same-base insertions and for deletions of up to --indel-max-len bytes (default 4, at
 most 16) that the reads hold (KmerTable.indel_scan; with --variants as well it is one scan for both), and two more files are written
-(jasper_amd/indels.py); the threshold must be at least 1.  Lengths above 16 and differences less than k apart are not listed, and
+(jasper_amd/indels.py); the threshold must be at least 1.  Lengths above 16 and differences less than k apart are not listed
+(the latter: --compound and --het-clusters, below), and
 insertions of mixed bases only with --indel-mixed (KmerTable.indel_scan(.., mixed=True): one more search kernel per scan), which adds
 the columns mixed_het, mixed_error and complex to the TSV, `TYPE=ins` lines to the VCF and one log line:
 
     PREFIX.indels.tsv        per contig one row of stage `asm`: het and error insertions, het and error deletions; then contig `*`
     PREFIX.indels.vcf        VCFv4.2, one left-aligned line per insertion or deletion: KIND=het|error;TYPE=ins|del;LEN=..
+
+With --indels --het-clusters the same scan also lists the clusters of heterozygous differences less than k apart, which every
+single-edit check rejects, as replacements of up to --het-cluster-max-len bytes by as many bases (default 64, at most 64;
+KmerTable.indel_scan(.., clusters=N): one more search kernel per scan, no further dense scan), and two more files and one log line
+are written (jasper_amd/hetclusters.py):
+
+    PREFIX.het_clusters.tsv  per contig one row of stage `asm`: searched, sites, records, complex; then contig `*`
+    PREFIX.het_clusters.vcf  VCFv4.2, one line per replacement: KIND=het;TYPE=mnp|complex;RLEN=..;LEN=..
 
 With --compound the runs of unreliable k-mers that two or more differences less than k apart leave -- which hide each other from
 --variants and --indels -- are searched for what the reads hold in their place, up to --compound-max-len bases (default 64, at most
@@ -53,24 +62,24 @@ PREFIX defaults to the assembly's file name.  Nothing is polished and no other f
 import os
 import sys
 
-from . import cli, compound, copies, indels, polisher, report, spectra, variants
+from . import cli, compound, copies, hetclusters, indels, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed]] [--compound [--compound-max-len N]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, compound=False, compound_max_len=None)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run",
-            "--indel-max-len": "indel_max_len", "--compound-max-len": "compound_max_len"}
+            "--indel-max-len": "indel_max_len", "--het-cluster-max-len": "het_cluster_max_len", "--compound-max-len": "compound_max_len"}
     i = 0
     while i < len(argv):
         key = argv[i]
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--compound"):
+        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound"):
             o[key[2:].replace("-", "_")] = True
             i += 1
             continue
@@ -100,6 +109,7 @@ def run(argv):
         cli.error_exit("--variants needs a threshold of at least 1; --threshold %d was given" % given)
     max_len = cli.indel_flags(a["indel_max_len"]) if a["indels"] else None
     cli.indel_mixed_flag(a["indel_mixed"], a["indels"])
+    clusters = cli.het_cluster_flags(a["het_cluster_max_len"], True, a["indels"]) if a["het_clusters"] else 0
     if a["indels"] and given is not None and given < 1:
         cli.error_exit("--indels needs a threshold of at least 1; --threshold %d was given" % given)
     comp_len = cli.compound_flags(a["compound_max_len"]) if a["compound"] else None
@@ -142,7 +152,7 @@ def run(argv):
             crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
         finally:
             asm.close()
-    iscan = cli.scan_indels(table, contigs, given, max_len, a["indel_mixed"])[2] if a["indels"] else None
+    iscan = cli.scan_indels(table, contigs, given, max_len, a["indel_mixed"], clusters)[2] if a["indels"] else None
     vscan = (iscan.variants if iscan is not None else cli.scan_variants(table, contigs, given)[2]) if a["variants"] else None
     table.close()
     prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
@@ -174,6 +184,13 @@ def run(argv):
             cli.log("Mixed insertions: %s in %s.indels.vcf" % (indels.mixed_stage_log_text(mixed.counts), prefix))
             if cli._timing_on():
                 sys.stderr.write("[indels] mixed search device seconds: %.6f; lookups %d\n" % (mixed.seconds, mixed.lookups))
+        hc = iscan.clusters
+        if hc is not None:
+            hetclusters.write_atomic(prefix + ".het_clusters.tsv", hetclusters.het_clusters_tsv_text(names, [("asm", lengths, hc.counts)]))
+            hetclusters.write_atomic(prefix + ".het_clusters.vcf", hetclusters.vcf_text(k, given, clusters, names, lengths, [s for _, s in contigs], hc.records))
+            cli.log("Het clusters: %s in %s.het_clusters.vcf" % (hetclusters.stage_log_text(hc.counts), prefix))
+            if cli._timing_on():
+                sys.stderr.write("[indels] het-cluster search device seconds: %.6f; lookups %d\n" % (hc.seconds, hc.lookups))
     if cscan is not None:
         compound.write_atomic(prefix + ".compound.tsv", compound.compound_tsv_text(names, [("asm", lengths, cscan.counts)]))
         compound.write_atomic(prefix + ".compound.vcf", compound.vcf_text(k, given, comp_len, names, lengths, [s for _, s in contigs], cscan.records))

@@ -223,9 +223,10 @@ class IndelScan:
     deletions (type 2) ordered by (seq, pos, type, len, base), `variants` = the VariantScan of the same input (one dense scan serves
     both), `seconds` = device time of the scan and all check kernels, `check_seconds` = of the indel check alone, `lookups` = table
     lookups that check made, `mixed` = None or the MixedInsertions of a scan with mixed=True (not part of ==: a scan with it equals
-    the scan without it).  The files made from it: jasper_amd/indels.py."""
+    the scan without it), `clusters` = None or the HetClusters of a scan with clusters=N (not part of == either).  The files made from
+    it: jasper_amd/indels.py, jasper_amd/hetclusters.py."""
 
-    def __init__(self, counts, records, variants, seconds, check_seconds, lookups, retried, mixed=None):
+    def __init__(self, counts, records, variants, seconds, check_seconds, lookups, retried, mixed=None, clusters=None):
         self.counts = counts
         self.records = records
         self.variants = variants
@@ -234,6 +235,7 @@ class IndelScan:
         self.lookups = lookups
         self.retried = retried
         self.mixed = mixed
+        self.clusters = clusters
 
     def __eq__(self, other):
         return (isinstance(other, IndelScan) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
@@ -273,6 +275,32 @@ class CompoundScan:
     def __eq__(self, other):
         return (isinstance(other, CompoundScan) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
                 and self.report == other.report)
+
+    def record_tuples(self):
+        """[(seq, pos, ref_len, len, y, ref_min, alt_min)], y = the replacement"""
+        return [(int(r["seq"]), int(r["pos"]), int(r["ref_len"]), int(r["len"]), compound_string(r["bases"], r["len"]), int(r["ref_min"]), int(r["alt_min"]))
+                for r in self.records]
+
+
+HET_CLUSTER_DTYPE = COMPOUND_DTYPE
+
+
+class HetClusters:
+    """the het-cluster half of an indel scan (include/jasper_hip.h: jasper_indel_scan_clusters): `counts[i]` = (searched, sites, records,
+    complex) of sequence i, `records` = numpy structured array (HET_CLUSTER_DTYPE, the layout of COMPOUND_DTYPE) of the replacements
+    where the sequence and the reads' other haplotype are both solid, ordered by (seq, pos, ref_len, len, y), `seconds` = device time
+    of the search kernel, `lookups` = table lookups it made, `retried` = it was repeated with a larger record list.  The files made
+    from it: jasper_amd/hetclusters.py."""
+
+    def __init__(self, counts, records, seconds, lookups, retried):
+        self.counts = counts
+        self.records = records
+        self.seconds = seconds
+        self.lookups = lookups
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, HetClusters) and self.counts == other.counts and self.records.tobytes() == other.records.tobytes()
 
     def record_tuples(self):
         """[(seq, pos, ref_len, len, y, ref_min, alt_min)], y = the replacement"""
@@ -755,26 +783,33 @@ class KmerTable:
         return self._wrap_varscan(rc, res)
 
     # ---- indel scan (an extension: the length-changing half of the variant scan, from the same dense scan) --
-    def indel_scan(self, seqs, thre, max_len=4, mixed=False):
+    def indel_scan(self, seqs, thre, max_len=4, mixed=False, clusters=0):
         """the same-base insertions and the deletions of up to max_len (1..16) bytes that the reads hold against the sequences, and
         the substitution sites of variant_scan with them (thre >= 1, k >= 2) -> IndelScan; with `mixed` also the insertions of mixed
-        bases (IndelScan.mixed); the table is not modified"""
+        bases (IndelScan.mixed); with `clusters` = N (1..64; 0: off) also the clusters of heterozygous differences less than k apart,
+        as replacements of up to N bytes by up to N bases (IndelScan.clusters); the table is not modified"""
         n = len(seqs)
         bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
         cs = (C.c_char_p * max(n, 1))(*bs)
         lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
         res = C.c_void_p()
+        if clusters:
+            rc = self._L.jasper_indel_scan_clusters(self._h, n, cs, lens, int(thre), int(max_len), int(bool(mixed)), int(clusters), C.byref(res))
+            return self._wrap_indelscan(rc, res, mixed, True)
         fn = self._L.jasper_indel_scan_mixed if mixed else self._L.jasper_indel_scan
         rc = fn(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
         return self._wrap_indelscan(rc, res, mixed)
 
-    def indel_scan_device(self, d_text, offsets, thre, max_len=4, mixed=False):
+    def indel_scan_device(self, d_text, offsets, thre, max_len=4, mixed=False, clusters=0):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
         n = len(offsets) - 1
         ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
         offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
         res = C.c_void_p()
+        if clusters:
+            rc = self._L.jasper_indel_scan_clusters_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), int(bool(mixed)), int(clusters), C.byref(res))
+            return self._wrap_indelscan(rc, res, mixed, True)
         fn = self._L.jasper_indel_scan_mixed_device if mixed else self._L.jasper_indel_scan_device
         rc = fn(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
         return self._wrap_indelscan(rc, res, mixed)
@@ -851,7 +886,25 @@ class KmerTable:
         check(self._L.jasper_indelscan_mixed_lookups(res, C.byref(nl)))
         return MixedInsertions(counts, recs, self._L.jasper_indelscan_mixed_seconds(res), int(nl.value), bool(self._L.jasper_indelscan_mixed_retried(res)))
 
-    def _wrap_indelscan(self, rc, res, mixed=False):
+    def _read_clusters(self, res):
+        import numpy as np
+        counts = []
+        c4 = (C.c_uint64 * 4)()
+        for i in range(self._L.jasper_indelscan_num_seqs(res)):
+            check(self._L.jasper_indelscan_cluster_counts(res, i, c4))
+            counts.append(tuple(int(v) for v in c4))
+        rp = C.POINTER(_lib.HetCluster)()
+        rn = C.c_uint64(0)
+        check(self._L.jasper_indelscan_cluster_records(res, C.byref(rp), C.byref(rn)))
+        if rn.value:
+            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.HetCluster)), dtype=HET_CLUSTER_DTYPE).copy()
+        else:
+            recs = np.zeros(0, dtype=HET_CLUSTER_DTYPE)
+        nl = C.c_uint64(0)
+        check(self._L.jasper_indelscan_cluster_lookups(res, C.byref(nl)))
+        return HetClusters(counts, recs, self._L.jasper_indelscan_cluster_seconds(res), int(nl.value), bool(self._L.jasper_indelscan_cluster_retried(res)))
+
+    def _wrap_indelscan(self, rc, res, mixed=False, clusters=False):
         try:
             check(rc)
             import numpy as np
@@ -871,7 +924,7 @@ class KmerTable:
             check(self._L.jasper_indelscan_lookups(res, C.byref(nl)))
             var = self._read_varscan(C.c_void_p(self._L.jasper_indelscan_variants(res)))      # (owned by res: read, not freed)
             return IndelScan(counts, recs, var, self._L.jasper_indelscan_seconds(res), self._L.jasper_indelscan_check_seconds(res), int(nl.value),
-                             bool(self._L.jasper_indelscan_retried(res)), self._read_mixed(res) if mixed else None)
+                             bool(self._L.jasper_indelscan_retried(res)), self._read_mixed(res) if mixed else None, self._read_clusters(res) if clusters else None)
         finally:
             if res:
                 self._L.jasper_indelscan_free(res)

@@ -19,5 +19,15 @@ if [ $rc -eq 0 ]; then
     tail -n 3 $OUT/trace_mixed.log $OUT/time_mixed.log
     python3 tools/prof_indels.py summarize_mixed $OUT/trace_mixed $OUT/trace_mixed.log | tee $OUT/summary_trace_mixed.json
 fi
+# the het-cluster half: a trace of its own (het_cluster_kernel next to indels_mixed_kernel at max_len 16 on the same candidates), its event
+# time, and the diploid leg
+if [ $rc -eq 0 ]; then
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_clusters -- python3 tools/prof_indels.py trace_clusters > $OUT/trace_clusters.log 2>&1 &&
+    timeout -k 10 300 python3 tools/prof_indels.py time_clusters > $OUT/time_clusters.log 2>&1 &&
+    timeout -k 10 300 python3 tools/prof_indels.py diploid_clusters > $OUT/diploid_clusters.log 2>&1
+    rc=$?
+    tail -n 3 $OUT/trace_clusters.log $OUT/time_clusters.log $OUT/diploid_clusters.log
+    python3 tools/prof_indels.py summarize_clusters $OUT/trace_clusters $OUT/trace_clusters.log | tee $OUT/summary_trace_clusters.json
+fi
 find $OUT -name '*kernel_stats.csv'
 exit $rc
