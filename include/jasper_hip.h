@@ -349,6 +349,61 @@ double jasper_copyrep_seconds(const jasper_copyrep *r);                         
 int jasper_copyrep_retried(const jasper_copyrep *r);
 void jasper_copyrep_free(jasper_copyrep *r);
 
+/* Trio hap-mer scan and census: WHERE on the sequences the k-mers lie that only one parent's reads hold, and how many of them an assembly
+ * has.  The tables, all of the same k on the same device and all different handles:
+ *   mat (M), pat (P)  the mother's and the father's reads, whole tables
+ *   child (R)         the child's reads, whole or attached owner-sharded; may be NULL = no inheritance filter
+ *   assembly (A)      census only: a whole table, the contigs counted into it; may be NULL
+ * thre_mat, thre_pat and thre_child are each at least 1 (thre_child too when child is NULL).  A different k, different devices, the
+ * same handle twice, an attached M, P or A, or a threshold of 0 is JASPER_ERR with a message that names the cause.  No table is modified.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart (it is the trio half of a k-mer evaluation).  A
+ * hap-mer here is what Merqury's is: a k-mer of one parent whose count in the OTHER parent is exactly 0 (the difference of the two
+ * parental sets), kept when it is solid in that parent and, with a child table, inherited (solid in the child).
+ *
+ * Scan.  For a sequence of n bytes and the tables' k:
+ *   window i (0 <= i <= n-k)  valid    iff all its k bytes are ACGTacgt (case folded)
+ *                             m, p, c  the counts of its canonical k-mer in M, P, R, each clamped to 2^32-1
+ *                             mat      (class 1) valid, m >= thre_mat, p == 0 and (R is NULL or c >= thre_child)
+ *                             pat      (class 2) valid, p >= thre_pat, m == 0 and (R is NULL or c >= thre_child)
+ *                             class 0  otherwise.  No window has both classes
+ *   per sequence              four counters: windows, valid, mat, pat
+ *   run (= one marker)        a maximal range of consecutive windows of one sequence with the same non-zero class (a window of another
+ *                             class, an invalid window or the sequence's end ends it; a mat window directly followed by a pat window
+ *                             gives two runs that touch): first window, windows, sequence, class
+ * Sequences shorter than k (empty ones too) are legal and give zeros.  Runs are ordered by (seq, start) and the result is the same on
+ * every call.  The library sizes its run buffer by itself and repeats the scan once when there were more runs than it had room for
+ * (jasper_hapscan_retried).  Tiles are those of the report (jasper_report_tile_windows()).  The kernels run on the child's stream, on
+ * the mother's when child is NULL.
+ *   jasper_hapmer_scan         sequences in host memory
+ *   jasper_hapmer_scan_device  sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the tables' device; offsets is a host array of
+ *                              n_seqs+1 entries
+ *   jasper_hapscan_counts      out4 = windows, valid, mat, pat of one sequence
+ *   jasper_hapscan_runs        the run list (owned by the result)
+ *   jasper_hapscan_seconds     device time of the scan's kernels (HIP events)
+ *
+ * Census.  H_mat = the distinct keys x of M with M[x] >= thre_mat, P[x] == 0 and (R NULL or R[x] >= thre_child), counts clamped as above;
+ * H_pat the same with the parents swapped.  out6 = for H_mat, then for H_pat:
+ *   hapmers      |H|
+ *   found        the keys of H with A[x] >= 1
+ *   occurrences  the sum over H of A[x] (a 64-bit sum of the clamped counts)
+ * found and occurrences are 0 when assembly is NULL.  When A was counted from exactly the scanned sequences, occurrences of mat equals the
+ * scan's total of mat windows, and of pat likewise.  device_seconds (may be NULL): device time of the two sweeps, HIP events. */
+typedef struct jasper_hapscan jasper_hapscan;
+typedef struct jasper_hap_run { int64_t start; uint64_t n_kmers; uint32_t seq; uint32_t kind; } jasper_hap_run;
+int jasper_hapmer_scan(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre_mat,
+                       uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out);
+int jasper_hapmer_scan_device(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre_mat,
+                              uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out);
+int jasper_hapscan_num_seqs(const jasper_hapscan *r);
+int jasper_hapscan_counts(const jasper_hapscan *r, int seq, uint64_t out4[4]);   /* windows, valid, mat, pat */
+int jasper_hapscan_runs(const jasper_hapscan *r, const jasper_hap_run **runs, uint64_t *n);
+double jasper_hapscan_seconds(const jasper_hapscan *r);                          /* device time, HIP events */
+int jasper_hapscan_retried(const jasper_hapscan *r);
+void jasper_hapscan_free(jasper_hapscan *r);
+int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *child, jasper_table *assembly, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,
+                         uint64_t out6[6] /* mat: hapmers, found, occurrences; then pat */, double *device_seconds);
+
 /* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
  * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
  * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.

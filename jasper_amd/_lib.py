@@ -39,6 +39,13 @@ class CopyRun(C.Structure):
 assert C.sizeof(CopyRun) == 40
 
 
+class HapRun(C.Structure):
+    _fields_ = [("start", C.c_int64), ("n_kmers", C.c_uint64), ("seq", C.c_uint32), ("kind", C.c_uint32)]
+
+
+assert C.sizeof(HapRun) == 24
+
+
 class Variant(C.Structure):
     _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8),
                 ("kind", C.c_uint8), ("pad", C.c_uint8)]
@@ -169,6 +176,15 @@ SYMBOLS = {
     "jasper_copyrep_seconds": (C.c_double, [_P]),
     "jasper_copyrep_retried": (C.c_int, [_P]),
     "jasper_copyrep_free": (None, [_P]),
+    "jasper_hapmer_scan": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "jasper_hapmer_scan_device": (C.c_int, [_P, _P, _P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "jasper_hapscan_num_seqs": (C.c_int, [_P]),
+    "jasper_hapscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_hapscan_runs": (C.c_int, [_P, C.POINTER(C.POINTER(HapRun)), C.POINTER(C.c_uint64)]),
+    "jasper_hapscan_seconds": (C.c_double, [_P]),
+    "jasper_hapscan_retried": (C.c_int, [_P]),
+    "jasper_hapscan_free": (None, [_P]),
+    "jasper_hapmer_census": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_variant_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_variant_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_varscan_num_seqs": (C.c_int, [_P]),

@@ -4,6 +4,8 @@ polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
                             [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]
+                            [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
+                             [--phase-short-range D] [--phase-max-switches S]]
 
 Differences that are deliberate and documented in DESIGN.md:
   * contigs are written to <asm>.polished.fasta in input order (the reference's order is perl-hash random, :220)
@@ -112,6 +114,14 @@ class Options:
         self.het_cluster_max_len = None   # --het-cluster-max-len: longest replacement the het-cluster search lists (default 64, at most 64)
         self.compound = False
         self.compound_max_len = None # --compound-max-len: longest replacement the compound scan searches (default 64, at most 64)
+        self.hapmers = False         # --hapmers: trio hap-mer markers, phase blocks and switch errors (_hapmers)
+        self.mat = self.mat_jf = self.pat = self.pat_jf = None       # the parents' read files or Jellyfish databases
+        self.mat_threshold = self.pat_threshold = None               # default: from each parent's histogram
+        self.phase_short_range = self.phase_max_switches = None      # defaults: hapmers.SHORT_RANGE, hapmers.MAX_SWITCHES
+
+
+HAPMER_VALUE_FLAGS = {"--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat", "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold",
+                      "--pat-threshold": "pat_threshold", "--phase-short-range": "phase_short_range", "--phase-max-switches": "phase_max_switches"}
 
 
 def parse_args(argv):
@@ -180,6 +190,10 @@ def parse_args(argv):
             o.compound = True
         elif key == "--compound-max-len":
             o.compound_max_len = nxt; i += 1
+        elif key == "--hapmers":                                       # extension: parental markers, phase blocks and switch errors (_hapmers)
+            o.hapmers = True
+        elif key in HAPMER_VALUE_FLAGS:
+            setattr(o, HAPMER_VALUE_FLAGS[key], nxt); i += 1
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1196,6 +1210,166 @@ def _spectra_copies(o, table, histo_file):
             sys.stderr.write("[copies] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
 
 
+def jf_k(path):
+    """k of a Jellyfish binary/sorted database, from its header alone (nothing is loaded); None when there is no such header"""
+    import json
+    try:
+        with open(path, "rb") as f:
+            hlen = int(f.read(9))
+            return int(json.loads(f.read(hlen).rstrip(b"\0").decode())["key_len"]) // 2
+    except (OSError, ValueError, KeyError, TypeError):
+        return None
+
+
+def hapmer_flags(o, k, run_jf=None):
+    """the --hapmers options of `o` (attributes hapmers, mat, mat_jf, pat, pat_jf, mat_threshold, pat_threshold, phase_short_range,
+    phase_max_switches; None or text) checked before anything is counted -> None without --hapmers, else a dict of mat / pat = (read
+    files or None, database or None), thre_mat / thre_pat (int or None = from the parent's histogram), short_range, max_switches.
+    k = the run's -k, run_jf = the run's own database when it has one (its header decides the run's k).  Exits on a parental option
+    without --hapmers, a missing or doubly given parent, a parental database of another k, and anything but integers >= 1."""
+    from . import hapmers
+    given = [f for f, a in sorted(HAPMER_VALUE_FLAGS.items()) if getattr(o, a) is not None]
+    if not o.hapmers:
+        if given:
+            error_exit("%s is an option of the hap-mer scan: give --hapmers as well" % given[0])
+        return None
+    out = {}
+    for who, files, jf in (("mat", o.mat, o.mat_jf), ("pat", o.pat, o.pat_jf)):
+        if (files is None) == (jf is None):
+            error_exit("--hapmers needs both parents: exactly one of --%s (read files) and --%s-jf (Jellyfish database) must be given" % (who, who))
+        if files is not None and (not files.split() or not all(_nonempty(fn) for fn in files.split())):
+            error_exit("--%s: a read file does not exist or is empty" % who)
+        if jf is not None and not _nonempty(jf):
+            error_exit("--%s-jf: %s does not exist or is empty" % (who, jf))
+        out[who] = (files.split() if files is not None else None, jf)
+    try:
+        vals = {}
+        for name, text in (("thre_mat", o.mat_threshold), ("thre_pat", o.pat_threshold), ("short_range", o.phase_short_range), ("max_switches", o.phase_max_switches)):
+            vals[name] = None if text is None else int(text)
+            if vals[name] is not None and vals[name] < 1:
+                raise ValueError
+        if any(vals[n] is not None and vals[n] > 0xFFFFFFFF for n in ("thre_mat", "thre_pat")):
+            raise ValueError
+    except ValueError:
+        error_exit("--mat-threshold, --pat-threshold, --phase-short-range and --phase-max-switches take integers of at least 1")
+    out.update(vals)
+    out["short_range"] = hapmers.SHORT_RANGE if out["short_range"] is None else out["short_range"]
+    out["max_switches"] = hapmers.MAX_SWITCHES if out["max_switches"] is None else out["max_switches"]
+    run_k = k
+    if run_jf is not None and jf_k(run_jf) is not None:
+        run_k = jf_k(run_jf)
+    for who in ("mat", "pat"):
+        jf = out[who][1]
+        if jf is not None:
+            pk = jf_k(jf)
+            if pk is None:
+                error_exit(_jf_failed(jf))
+            if pk != run_k:
+                error_exit("--%s-jf: the database's k is %d, the run's is %d; the parents must be counted with the run's k" % (who, pk, run_k))
+    return out
+
+
+def parent_table(who, files, jf, k, device):
+    """one parent's reads counted into a whole table on `device`, or its database loaded -> KmerTable, the caller closes it.  A table
+    that cannot be made -- unreadable input, or no room for it beside the other tables -- ends the run with a message that carries the
+    library's own: there is no fallback, and no parental table spread over several GPUs."""
+    from .table import KmerTable
+    try:
+        if jf is not None:
+            t = KmerTable.from_jf(jf, device=device)
+        else:
+            size = sum(os.stat(f).st_size for f in files) // 10
+            t = KmerTable(k, min_slots=max(1 << 20, int(1.25 * size)), device=device)
+            try:
+                t.count_files(files)
+            except BaseException:
+                t.close()
+                raise
+    except Exception as e:      # noqa: BLE001
+        error_exit("--hapmers: the %s table could not be made on GPU %d: %s (both parental tables are kept whole on that GPU beside the reads' table)" %
+                   ("maternal" if who == "mat" else "paternal", device, e))
+    if t.k != k:
+        t.close()
+        error_exit("--%s-jf: the database's k is %d, the run's is %d; the parents must be counted with the run's k" % (who, t.k, k))
+    return t
+
+
+def parent_threshold(who, table, given):
+    """--mat-threshold / --pat-threshold, or what the solid-k-mer rule derives from that parent's histogram; exits when it derives none"""
+    from . import polisher
+    if given is not None:
+        return given
+    txt, status = polisher.threshold_from_histo_rows(table.histo_rows())
+    if status != 0 or not txt.split() or int(txt.split()[0]) < 1:
+        error_exit("The %s reads' k-mer histogram gives no threshold. Please give one with --%s-threshold." % ("mother's" if who == "mat" else "father's", who))
+    return int(txt.split()[0])
+
+
+def open_parents(flags, k, device):
+    """both parental tables and their thresholds -> (mat, pat, thre_mat, thre_pat); the caller closes the tables"""
+    mat = parent_table("mat", flags["mat"][0], flags["mat"][1], k, device)
+    try:
+        pat = parent_table("pat", flags["pat"][0], flags["pat"][1], k, device)
+        try:
+            return mat, pat, parent_threshold("mat", mat, flags["thre_mat"]), parent_threshold("pat", pat, flags["thre_pat"])
+        except BaseException:
+            pat.close()
+            raise
+    except BaseException:
+        mat.close()
+        raise
+
+
+def scan_hapmers(table, mat, pat, contigs, thre_mat, thre_pat, thre_child, flags, asm=None):
+    """the hap-mer scan of whole contigs [(name token, sequence)] against the trio's tables and the census against the contigs' own
+    table (`asm` when the caller has it already and keeps it) -> (hapmers.Stage, HapmerCensus, HapmerScan)"""
+    from . import hapmers, report
+    seqs = [s for _, s in contigs]
+    scan = table.hapmer_scan(mat, pat, seqs, thre_mat, thre_pat, thre_child)
+    own = asm is None
+    if own:
+        asm = assembly_table(table, contigs)
+    try:
+        census = table.hapmer_census(mat, pat, asm, thre_mat, thre_pat, thre_child)
+    finally:
+        if own:
+            asm.close()
+    stage = hapmers.Stage(table.k, [report.contig_name(n) for n, _ in contigs], [len(s) for s in seqs], scan.counts, scan.runs, flags["short_range"], flags["max_switches"])
+    return stage, census, scan
+
+
+def _hapmers(o, table, flags):
+    """--hapmers (an extension, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each scanned against the
+    mother's, the father's and the reads' table while the latter is still in HBM, and each counted into a table of its own for the
+    census.  The parental tables are counted or loaded ONCE, whole, on this GPU, and closed afterwards.  Files: `$QUERY_FN.hapmers.tsv`,
+    `$QUERY_FN.hapmer_completeness.tsv`, `$QUERY_FN.hapmers.{before,after}.bed` and `$QUERY_FN.phased_blocks.{before,after}.bed`
+    (jasper_amd/hapmers.py).  The child threshold is the polisher's (threshold.txt).
+    Unlike kmerqc, where one assembly table serves --spectra, --copies and this, the driver counts the two texts AGAIN here when
+    --spectra or --copies has counted them already (_spectra_copies closes its tables before this stage runs): two more counts of an
+    assembly-sized text per run, small beside the parental read sets."""
+    from . import hapmers
+    qfn, k = o.query_fn, table.k
+    thresh = int(open("threshold.txt").read().split()[0])
+    mat, pat, tm, tp = open_parents(flags, k, table.device)
+    try:
+        done = [(stage,) + scan_hapmers(table, mat, pat, read_assembly(path), tm, tp, thresh, flags)
+                for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta"))]
+    finally:
+        mat.close()
+        pat.close()
+    names = done[0][1].names
+    hapmers.write_atomic(qfn + ".hapmers.tsv", hapmers.hapmers_tsv_text(names, [(stage, st) for stage, st, _, _ in done]))
+    hapmers.write_atomic(qfn + ".hapmer_completeness.tsv", hapmers.completeness_text(k, tm, tp, thresh, [(stage, cen) for stage, _, cen, _ in done]))
+    for stage, st, _, _ in done:
+        hapmers.write_atomic("%s.hapmers.%s.bed" % (qfn, stage), hapmers.bed_text(k, st.names, st.runs))
+        hapmers.write_atomic("%s.phased_blocks.%s.bed" % (qfn, stage), hapmers.blocks_bed_text(st.names, st.blocks))
+    log("Hap-mer scan (thresholds mat %d pat %d child %d): before polishing %s; after polishing %s" %
+        (tm, tp, thresh, hapmers.stage_log_text(done[0][1], done[0][2]), hapmers.stage_log_text(done[1][1], done[1][2])))
+    if _timing_on():
+        sys.stderr.write("[hapmers] scan device seconds: before %.6f after %.6f; census device seconds: before %.6f after %.6f\n" %
+                         (done[0][3].seconds, done[1][3].seconds, done[0][2].seconds, done[1][2].seconds))
+
+
 def scan_variants(table, contigs, thre):
     """the variant scan of whole contigs [(name token, sequence)] -> (names, lengths, VariantScan); exits on a threshold of 0, which
     would call every alternative solid"""
@@ -1414,6 +1588,7 @@ def run(argv):
         het_cluster_flags(o.het_cluster_max_len, True, o.indels)
     if o.compound:
         compound_flags(o.compound_max_len)
+    hap = hapmer_flags(o, int(o.kmer) if re.match(r"^[0-9]+$", str(o.kmer)) else 0, o.jf_db)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
@@ -1518,6 +1693,11 @@ def run(argv):
         _timing("variant scan")
     if o.compound:
         ranks.together((lambda: _compound(o, table, scans)) if ranks.is0 else (lambda: None), "Writing the compound scan failed")
+    if hap is not None:
+        # as for --report: rank 0 alone, the child's table through every owner's shard, both parental tables whole on rank 0's GPU
+        # (unmeasured over RCCL, like everything multi-GPU here)
+        ranks.together((lambda: _hapmers(o, table, hap)) if ranks.is0 else (lambda: None), "Writing the hap-mer scan failed")
+        _timing("hap-mer scan")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

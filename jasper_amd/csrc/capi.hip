@@ -9,6 +9,7 @@
 #include "report.hpp"
 #include "spectra.hpp"
 #include "copies.hpp"
+#include "hapmers.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
 #include "compound.hpp"
@@ -50,6 +51,9 @@ static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record
 
 struct jasper_copyrep {
     CopyOut r;
+};
+struct jasper_hapscan {
+    HapOut r;
 };
 struct jasper_varscan {
     VariantOut r;
@@ -830,6 +834,53 @@ int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, u
 double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
 int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
 void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
+
+// ---- trio hap-mer scan and census (hapmers.hip) ----
+static_assert(sizeof(jasper_hap_run) == sizeof(HapRun), "jasper_hap_run is HapRun");
+static int hapscan_call(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text,
+                        const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
+    if (!mat || !pat || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    jasper_hapscan *r = new jasper_hapscan();
+    Table *R = child ? &child->t : nullptr;
+    const int rc = d_text || offsets ? hapmer_scan_device(mat->t, pat->t, R, n_seqs, (const uint8_t *)d_text, offsets, thre_mat, thre_pat, thre_child, r->r, g_err)
+                                     : hapmer_scan_host(mat->t, pat->t, R, n_seqs, seqs, lens, thre_mat, thre_pat, thre_child, r->r, g_err);
+    if (rc) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+int jasper_hapmer_scan(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre_mat,
+                       uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
+    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
+    return hapscan_call(mat, pat, child, n_seqs, seqs, lens, nullptr, nullptr, thre_mat, thre_pat, thre_child, out);
+}
+int jasper_hapmer_scan_device(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre_mat,
+                              uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
+    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
+    return hapscan_call(mat, pat, child, n_seqs, nullptr, nullptr, d_text, offsets, thre_mat, thre_pat, thre_child, out);
+}
+int jasper_hapscan_num_seqs(const jasper_hapscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
+int jasper_hapscan_counts(const jasper_hapscan *r, int seq, uint64_t out4[4]) {
+    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
+    return JASPER_OK;
+}
+int jasper_hapscan_runs(const jasper_hapscan *r, const jasper_hap_run **runs, uint64_t *n) {
+    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *runs = reinterpret_cast<const jasper_hap_run *>(r->r.runs.data());
+    *n = r->r.runs.size();
+    return JASPER_OK;
+}
+double jasper_hapscan_seconds(const jasper_hapscan *r) { return r ? r->r.seconds : 0.0; }
+int jasper_hapscan_retried(const jasper_hapscan *r) { return r ? r->r.retried : 0; }
+void jasper_hapscan_free(jasper_hapscan *r) { delete r; }
+int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *child, jasper_table *assembly, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,
+                         uint64_t out6[6], double *device_seconds) {
+    if (!mat || !pat || !out6) { g_err = "bad argument"; return JASPER_ERR; }
+    return hapmer_census(mat->t, pat->t, child ? &child->t : nullptr, assembly ? &assembly->t : nullptr, thre_mat, thre_pat, thre_child, out6, device_seconds, g_err)
+               ? JASPER_ERR
+               : JASPER_OK;
+}
 
 // ---- variant scan (variants.hip) ----
 static_assert(sizeof(jasper_variant) == sizeof(Variant), "jasper_variant is Variant");

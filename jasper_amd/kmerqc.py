@@ -3,6 +3,8 @@
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
                                 [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
                                 [--compound [--compound-max-len N]]
+                                [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
+                                 [--phase-short-range D] [--phase-max-switches S]]
 
 An extension (the reference has no such tool).  It counts the reads into the HBM table, or loads the database (whose header
 decides k, as for `jasper.sh -j`), derives the threshold for unreliable k-mers the way src/jellyfish.py does from the
@@ -57,29 +59,42 @@ With --compound the runs of unreliable k-mers that two or more differences less 
     PREFIX.compound.tsv      per contig one row of stage `asm`: sites, bridged, records, long, complex; then contig `*`
     PREFIX.compound.vcf      VCFv4.2, one line per replacement: KIND=error;TYPE=mnp|complex;RLEN=..;LEN=..
 
+With --hapmers the reads are the CHILD's of a trio: the mother's and the father's reads are counted into two more tables (or their
+databases loaded: --mat-jf / --pat-jf, of the run's k), the contigs are scanned against all three (KmerTable.hapmer_scan) for the
+k-mers that only one parent holds, the markers are made into phase blocks, and the parents' hap-mers are counted against the
+assembly's table (KmerTable.hapmer_census; that table is counted once and serves --spectra and --copies too).  Each parental
+threshold defaults to what that parent's histogram gives; the child's is the run's.  Four more files (jasper_amd/hapmers.py):
+
+    PREFIX.hapmers.tsv               per contig one row of stage `asm`: mat / pat windows, markers, blocks, block N50, switches; then contig `*`
+    PREFIX.hapmers.bed               one line per marker: contig start end mat|pat n_kmers
+    PREFIX.phased_blocks.bed         one line per phase block (--phase-short-range, default 20000; --phase-max-switches, default 100)
+    PREFIX.hapmer_completeness.tsv   two rows (mat, pat): hap-mers, how many the assembly holds, completeness, occurrences
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 """
 import os
 import sys
 
-from . import cli, compound, copies, hetclusters, indels, polisher, report, spectra, variants
+from . import cli, compound, copies, hapmers, hetclusters, indels, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None)
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None, hapmers=False,
+             mat=None, mat_jf=None, pat=None, pat_jf=None, mat_threshold=None, pat_threshold=None, phase_short_range=None, phase_max_switches=None)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run",
             "--indel-max-len": "indel_max_len", "--het-cluster-max-len": "het_cluster_max_len", "--compound-max-len": "compound_max_len"}
+    keys.update(cli.HAPMER_VALUE_FLAGS)
     i = 0
     while i < len(argv):
         key = argv[i]
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound"):
+        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound", "--hapmers"):
             o[key[2:].replace("-", "_")] = True
             i += 1
             continue
@@ -115,6 +130,9 @@ def run(argv):
     comp_len = cli.compound_flags(a["compound_max_len"]) if a["compound"] else None
     if a["compound"] and given is not None and given < 1:
         cli.error_exit("--compound needs a threshold of at least 1; --threshold %d was given" % given)
+    hap = cli.hapmer_flags(type("HapmerOptions", (), a), k, a["jf"])
+    if hap is not None and given is not None and given < 1:
+        cli.error_exit("--hapmers needs a threshold of at least 1; --threshold %d was given" % given)
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
@@ -144,12 +162,21 @@ def run(argv):
         rep = cscan.report
     else:
         names, lengths, rep = cli.scan_contigs(table, contigs, given)
-    spec = crep = None
-    if a["spectra"] or a["copies"]:
-        asm = cli.assembly_table(table, contigs)          # counted once, it serves both
+    spec = crep = hres = None
+    if a["spectra"] or a["copies"] or hap is not None:
+        asm = cli.assembly_table(table, contigs)          # counted once, it serves all of them
         try:
             spec = cli.assembly_spectrum(table, contigs, asm) if a["spectra"] else None
             crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
+            if hap is not None:
+                if given < 1:
+                    cli.error_exit("--hapmers needs a threshold of at least 1; the histogram gave %d: give --threshold" % given)
+                mat, pat, tm, tp = cli.open_parents(hap, k, table.device)
+                try:
+                    hres = (tm, tp) + cli.scan_hapmers(table, mat, pat, contigs, tm, tp, given, hap, asm)
+                finally:
+                    mat.close()
+                    pat.close()
         finally:
             asm.close()
     iscan = cli.scan_indels(table, contigs, given, max_len, a["indel_mixed"], clusters)[2] if a["indels"] else None
@@ -170,6 +197,15 @@ def run(argv):
         copies.write_atomic(prefix + ".copies.tsv", copies.copies_tsv_text(peak, names, [("asm", lengths, crep.counts)]))
         copies.write_atomic(prefix + ".copies.bed", copies.bed_text(k, peak, names, crep.runs, min_run))
         cli.log("Copy-number scan: peak %d; %s in %s.copies.bed" % (peak, copies.stage_log_text(crep.counts, len(copies.listed(crep.runs, min_run))), prefix))
+    if hres is not None:
+        tm, tp, hstage, census, hscan = hres
+        hapmers.write_atomic(prefix + ".hapmers.tsv", hapmers.hapmers_tsv_text(names, [("asm", hstage)]))
+        hapmers.write_atomic(prefix + ".hapmers.bed", hapmers.bed_text(k, names, hscan.runs))
+        hapmers.write_atomic(prefix + ".phased_blocks.bed", hapmers.blocks_bed_text(names, hstage.blocks))
+        hapmers.write_atomic(prefix + ".hapmer_completeness.tsv", hapmers.completeness_text(k, tm, tp, given, [("asm", census)]))
+        cli.log("Hap-mer scan (thresholds mat %d pat %d child %d): %s in %s.hapmers.bed" % (tm, tp, given, hapmers.stage_log_text(hstage, census), prefix))
+        if cli._timing_on():
+            sys.stderr.write("[hapmers] scan device seconds: %.6f; census device seconds: %.6f\n" % (hscan.seconds, census.seconds))
     if vscan is not None:
         variants.write_atomic(prefix + ".variants.tsv", variants.variants_tsv_text(names, [("asm", lengths, vscan.counts)]))
         variants.write_atomic(prefix + ".variants.vcf", variants.vcf_text(k, given, names, lengths, vscan.records))

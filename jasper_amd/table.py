@@ -161,6 +161,43 @@ class CopyReport:
         return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"]), int(r["sum_asm"])) for r in self.runs]
 
 
+HAPRUN_DTYPE = [("start", "<i8"), ("n_kmers", "<u8"), ("seq", "<u4"), ("kind", "<u4")]
+HAP_KINDS = {1: "mat", 2: "pat"}
+
+
+class HapmerScan:
+    """trio hap-mer scan of a set of sequences against the mother's, the father's and (optionally) the child's table
+    (include/jasper_hip.h: jasper_hapmer_scan): `counts[i]` = (windows, valid, mat, pat) of sequence i, `runs` = numpy structured
+    array (HAPRUN_DTYPE) of the maximal runs of one class = the markers (kind 1 = mat, 2 = pat) ordered by (seq, start), `seconds`
+    = device time of the kernels.  The phase blocks and the files made from it: jasper_amd/hapmers.py."""
+
+    def __init__(self, counts, runs, seconds, retried):
+        self.counts = counts
+        self.runs = runs
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, HapmerScan) and self.counts == other.counts and self.runs.tobytes() == other.runs.tobytes()
+
+    def run_tuples(self):
+        """[(seq, start, n_kmers, kind)]"""
+        return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"])) for r in self.runs]
+
+
+class HapmerCensus:
+    """hap-mer census of a trio's tables against an assembly's (include/jasper_hip.h: jasper_hapmer_census): `mat` and `pat` =
+    (hapmers, found, occurrences), `seconds` = device time of the two sweeps"""
+
+    def __init__(self, mat, pat, seconds):
+        self.mat = mat
+        self.pat = pat
+        self.seconds = seconds
+
+    def __eq__(self, other):
+        return isinstance(other, HapmerCensus) and self.mat == other.mat and self.pat == other.pat
+
+
 VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
 VARIANT_KINDS = {1: "het", 2: "error"}
 
@@ -318,6 +355,14 @@ def _peak32(peak):
     if p < 0 or p > 0xFFFFFFFF:
         raise ValueError("peak must be in [1, 2^32-1]")
     return p
+
+
+def _thre32(thre):
+    """a threshold as the C-ABI's uint32 (0 passes: the library refuses it with a message that names it)"""
+    t = int(thre)
+    if t < 0 or t > 0xFFFFFFFF:
+        raise ValueError("a threshold must be in [1, 2^32-1]")
+    return t
 
 
 class KmerTable:
@@ -759,6 +804,84 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_copyrep_free(res)
+
+    # ---- trio hap-mer scan and census (an extension: no counterpart in the reference) ----------------------
+    @staticmethod
+    def _parent_handle(t, who, what):
+        if not isinstance(t, KmerTable) or not t._h:
+            raise TypeError("%s: the %s table must be an open KmerTable" % (what, who))
+        return t._h
+
+    def hapmer_scan(self, mat, pat, seqs, thre_mat, thre_pat, thre_child=1, child=True):
+        """this table as the child's reads, `mat` / `pat` the mother's and the father's (whole KmerTables of the same k on the same
+        device): per-sequence counters and the runs of windows whose k-mer only one parent holds (solid there, absent from the
+        other, and solid in this table) -> HapmerScan.  child=False: no inheritance filter, this table is not consulted
+        (KmerTable.hapmer_scan_parents is the same without a child table at all).  No table is modified"""
+        return KmerTable.hapmer_scan_parents(mat, pat, seqs, thre_mat, thre_pat, thre_child, _child=self if child else None)
+
+    @staticmethod
+    def hapmer_scan_parents(mat, pat, seqs, thre_mat, thre_pat, thre_child=1, _child=None):
+        """the hap-mer scan without a child table: every solid k-mer of one parent that the other lacks is a marker"""
+        mh, ph = KmerTable._parent_handle(mat, "maternal", "hapmer_scan"), KmerTable._parent_handle(pat, "paternal", "hapmer_scan")
+        ch = KmerTable._parent_handle(_child, "child", "hapmer_scan") if _child is not None else None
+        n = len(seqs)
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+        cs = (C.c_char_p * max(n, 1))(*bs)
+        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        res = C.c_void_p()
+        rc = mat._L.jasper_hapmer_scan(mh, ph, ch, n, cs, lens, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child), C.byref(res))
+        return mat._wrap_hapscan(rc, res)
+
+    def hapmer_scan_device(self, mat, pat, d_text, offsets, thre_mat, thre_pat, thre_child=1, child=True):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        mh, ph = self._parent_handle(mat, "maternal", "hapmer_scan_device"), self._parent_handle(pat, "paternal", "hapmer_scan_device")
+        n = len(offsets) - 1
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        res = C.c_void_p()
+        rc = self._L.jasper_hapmer_scan_device(mh, ph, self._h if child else None, n, C.c_void_p(ptr), offs, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child),
+                                               C.byref(res))
+        return self._wrap_hapscan(rc, res)
+
+    def _wrap_hapscan(self, rc, res):
+        try:
+            check(rc)
+            import numpy as np
+            counts = []
+            c4 = (C.c_uint64 * 4)()
+            for i in range(self._L.jasper_hapscan_num_seqs(res)):
+                check(self._L.jasper_hapscan_counts(res, i, c4))
+                counts.append(tuple(int(v) for v in c4))
+            rp = C.POINTER(_lib.HapRun)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_hapscan_runs(res, C.byref(rp), C.byref(rn)))
+            if rn.value:
+                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.HapRun)), dtype=HAPRUN_DTYPE).copy()
+            else:
+                runs = np.zeros(0, dtype=HAPRUN_DTYPE)
+            return HapmerScan(counts, runs, self._L.jasper_hapscan_seconds(res), bool(self._L.jasper_hapscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_hapscan_free(res)
+
+    def hapmer_census(self, mat, pat, asm=None, thre_mat=1, thre_pat=1, thre_child=1, child=True):
+        """this table as the child's reads: how many hap-mers each parent has (solid there, absent from the other parent, solid in
+        this table), how many of them the assembly's table `asm` holds and how often -> HapmerCensus.  asm=None: found and
+        occurrences are 0; child=False: no inheritance filter"""
+        return KmerTable.hapmer_census_parents(mat, pat, asm, thre_mat, thre_pat, thre_child, _child=self if child else None)
+
+    @staticmethod
+    def hapmer_census_parents(mat, pat, asm=None, thre_mat=1, thre_pat=1, thre_child=1, _child=None):
+        """the hap-mer census without a child table"""
+        mh, ph = KmerTable._parent_handle(mat, "maternal", "hapmer_census"), KmerTable._parent_handle(pat, "paternal", "hapmer_census")
+        ch = KmerTable._parent_handle(_child, "child", "hapmer_census") if _child is not None else None
+        ah = KmerTable._parent_handle(asm, "assembly", "hapmer_census") if asm is not None else None
+        out = (C.c_uint64 * 6)()
+        secs = C.c_double(0)
+        check(mat._L.jasper_hapmer_census(mh, ph, ch, ah, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child), out, C.byref(secs)))
+        v = [int(x) for x in out]
+        return HapmerCensus(tuple(v[:3]), tuple(v[3:]), secs.value)
 
     # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
     def variant_scan(self, seqs, thre):
