@@ -99,6 +99,40 @@ static int result_fetch(jasper_result *r) {
         }                                                             \
     } while (0)
 
+// ---- what the scans' entry points and accessors share ---------------------------------------------------------------------------------
+static bool host_args(int n_seqs, const char *const *seqs, const int64_t *lens) { return n_seqs <= 0 || (seqs && lens); }
+
+// One scan call: args_ok is the entry point's own check of its text arguments, tables whether every table it needs is there.  The result
+// object is made, filled by fill(*r) (0 = done) and handed out, or deleted.
+template <class Res, class Fill> static int scan_call(bool args_ok, bool tables, int n_seqs, Res **out, Fill &&fill) {
+    if (!args_ok || !tables || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    Res *r = new Res();
+    if (fill(*r)) { delete r; return JASPER_ERR; }
+    *out = r;
+    return JASPER_OK;
+}
+// The N counters of sequence seq out of a vector of N per sequence (null: there is no result object).  A half of a scan that did not run
+// left its vector empty: zeros for each of the n_seqs sequences.
+template <int N> static int counts_out(const std::vector<uint64_t> *v, size_t n_seqs, int seq, uint64_t *out) {
+    if (!v || !out || seq < 0 || (size_t)seq >= n_seqs) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < N; ++i) out[i] = v->empty() ? 0 : (*v)[N * (size_t)seq + i];
+    return JASPER_OK;
+}
+template <int N> static int counts_out(const std::vector<uint64_t> *v, int seq, uint64_t *out) { return counts_out<N>(v, v ? v->size() / N : 0, seq, out); }
+template <class Rec, class Pub> static int records_out(const std::vector<Rec> *v, const Pub **out, uint64_t *n) {
+    static_assert(sizeof(Rec) == sizeof(Pub), "public and device record layouts must match");
+    if (!v || !out || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = reinterpret_cast<const Pub *>(v->data());
+    *n = v->size();
+    return JASPER_OK;
+}
+static int word_out(const uint64_t *v, uint64_t *n) {
+    if (!v || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *n = *v;
+    return JASPER_OK;
+}
+
 extern "C" {
 
 const char *jasper_last_error(void) { return g_err.c_str(); }
@@ -753,38 +787,16 @@ void jasper_result_free(jasper_result *r) {
 }
 
 // ---- dense k-mer report (report.hip) ----
-static int report_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
-                       jasper_report **out) {
-    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_report *r = new jasper_report();
-    const int rc = d_text || offsets ? kmer_report_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r->r, g_err)
-                                     : kmer_report_host(t->t, n_seqs, seqs, lens, thre, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    *out = r;
-    return JASPER_OK;
-}
 int jasper_kmer_report(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_report **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return report_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, out);
+    return scan_call(host_args(n_seqs, seqs, lens), t, n_seqs, out, [&](jasper_report &r) { return kmer_report_host(t->t, n_seqs, seqs, lens, thre, r.r, g_err); });
 }
 int jasper_kmer_report_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_report **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return report_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, out);
+    return scan_call(offsets, t, n_seqs, out, [&](jasper_report &r) { return kmer_report_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r.r, g_err); });
 }
 int jasper_report_tile_windows(void) { return RP_TILE; }
 int jasper_report_num_seqs(const jasper_report *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
-int jasper_report_counts(const jasper_report *r, int seq, uint64_t out4[4]) {
-    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_report_runs(const jasper_report *r, const jasper_kmer_run **runs, uint64_t *n) {
-    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *runs = reinterpret_cast<const jasper_kmer_run *>(r->r.runs.data());
-    *n = r->r.runs.size();
-    return JASPER_OK;
-}
+int jasper_report_counts(const jasper_report *r, int seq, uint64_t out4[4]) { return counts_out<4>(r ? &r->r.counts : nullptr, seq, out4); }
+int jasper_report_runs(const jasper_report *r, const jasper_kmer_run **runs, uint64_t *n) { return records_out(r ? &r->r.runs : nullptr, runs, n); }
 double jasper_report_seconds(const jasper_report *r) { return r ? r->r.seconds : 0.0; }
 int jasper_report_retried(const jasper_report *r) { return r ? r->r.retried : 0; }
 void jasper_report_free(jasper_report *r) { delete r; }
@@ -797,80 +809,39 @@ int jasper_table_spectrum(jasper_table *reads, jasper_table *assembly, uint64_t 
 }
 
 // ---- copy-number scan (copies.hip) ----
-static_assert(sizeof(jasper_copy_run) == sizeof(CopyRun), "jasper_copy_run is CopyRun");
-static int copyrep_call(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets,
-                        uint32_t thre, uint32_t peak, jasper_copyrep **out) {
-    if (!reads || !assembly || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_copyrep *r = new jasper_copyrep();
-    const int rc = d_text || offsets ? copies_report_device(reads->t, assembly->t, n_seqs, (const uint8_t *)d_text, offsets, thre, peak, r->r, g_err)
-                                     : copies_report_host(reads->t, assembly->t, n_seqs, seqs, lens, thre, peak, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    *out = r;
-    return JASPER_OK;
-}
 int jasper_copy_report(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak,
                        jasper_copyrep **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return copyrep_call(reads, assembly, n_seqs, seqs, lens, nullptr, nullptr, thre, peak, out);
+    return scan_call(host_args(n_seqs, seqs, lens), reads && assembly, n_seqs, out,
+                     [&](jasper_copyrep &r) { return copies_report_host(reads->t, assembly->t, n_seqs, seqs, lens, thre, peak, r.r, g_err); });
 }
 int jasper_copy_report_device(jasper_table *reads, jasper_table *assembly, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, uint32_t peak,
                               jasper_copyrep **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return copyrep_call(reads, assembly, n_seqs, nullptr, nullptr, d_text, offsets, thre, peak, out);
+    return scan_call(offsets, reads && assembly, n_seqs, out,
+                     [&](jasper_copyrep &r) { return copies_report_device(reads->t, assembly->t, n_seqs, (const uint8_t *)d_text, offsets, thre, peak, r.r, g_err); });
 }
 int jasper_copyrep_num_seqs(const jasper_copyrep *r) { return r ? (int)(r->r.counts.size() / 6) : 0; }
-int jasper_copyrep_counts(const jasper_copyrep *r, int seq, uint64_t out6[6]) {
-    if (!r || !out6 || seq < 0 || (size_t)seq >= r->r.counts.size() / 6) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 6; ++i) out6[i] = r->r.counts[6 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, uint64_t *n) {
-    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *runs = reinterpret_cast<const jasper_copy_run *>(r->r.runs.data());
-    *n = r->r.runs.size();
-    return JASPER_OK;
-}
+int jasper_copyrep_counts(const jasper_copyrep *r, int seq, uint64_t out6[6]) { return counts_out<6>(r ? &r->r.counts : nullptr, seq, out6); }
+int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, uint64_t *n) { return records_out(r ? &r->r.runs : nullptr, runs, n); }
 double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
 int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
 void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
 
 // ---- trio hap-mer scan and census (hapmers.hip) ----
-static_assert(sizeof(jasper_hap_run) == sizeof(HapRun), "jasper_hap_run is HapRun");
-static int hapscan_call(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text,
-                        const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
-    if (!mat || !pat || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_hapscan *r = new jasper_hapscan();
-    Table *R = child ? &child->t : nullptr;
-    const int rc = d_text || offsets ? hapmer_scan_device(mat->t, pat->t, R, n_seqs, (const uint8_t *)d_text, offsets, thre_mat, thre_pat, thre_child, r->r, g_err)
-                                     : hapmer_scan_host(mat->t, pat->t, R, n_seqs, seqs, lens, thre_mat, thre_pat, thre_child, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    *out = r;
-    return JASPER_OK;
-}
 int jasper_hapmer_scan(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre_mat,
                        uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return hapscan_call(mat, pat, child, n_seqs, seqs, lens, nullptr, nullptr, thre_mat, thre_pat, thre_child, out);
+    return scan_call(host_args(n_seqs, seqs, lens), mat && pat, n_seqs, out, [&](jasper_hapscan &r) {
+        return hapmer_scan_host(mat->t, pat->t, child ? &child->t : nullptr, n_seqs, seqs, lens, thre_mat, thre_pat, thre_child, r.r, g_err);
+    });
 }
 int jasper_hapmer_scan_device(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre_mat,
                               uint32_t thre_pat, uint32_t thre_child, jasper_hapscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return hapscan_call(mat, pat, child, n_seqs, nullptr, nullptr, d_text, offsets, thre_mat, thre_pat, thre_child, out);
+    return scan_call(offsets, mat && pat, n_seqs, out, [&](jasper_hapscan &r) {
+        return hapmer_scan_device(mat->t, pat->t, child ? &child->t : nullptr, n_seqs, (const uint8_t *)d_text, offsets, thre_mat, thre_pat, thre_child, r.r, g_err);
+    });
 }
 int jasper_hapscan_num_seqs(const jasper_hapscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
-int jasper_hapscan_counts(const jasper_hapscan *r, int seq, uint64_t out4[4]) {
-    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_hapscan_runs(const jasper_hapscan *r, const jasper_hap_run **runs, uint64_t *n) {
-    if (!r || !runs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *runs = reinterpret_cast<const jasper_hap_run *>(r->r.runs.data());
-    *n = r->r.runs.size();
-    return JASPER_OK;
-}
+int jasper_hapscan_counts(const jasper_hapscan *r, int seq, uint64_t out4[4]) { return counts_out<4>(r ? &r->r.counts : nullptr, seq, out4); }
+int jasper_hapscan_runs(const jasper_hapscan *r, const jasper_hap_run **runs, uint64_t *n) { return records_out(r ? &r->r.runs : nullptr, runs, n); }
 double jasper_hapscan_seconds(const jasper_hapscan *r) { return r ? r->r.seconds : 0.0; }
 int jasper_hapscan_retried(const jasper_hapscan *r) { return r ? r->r.retried : 0; }
 void jasper_hapscan_free(jasper_hapscan *r) { delete r; }
@@ -883,202 +854,110 @@ int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *chi
 }
 
 // ---- variant scan (variants.hip) ----
-static_assert(sizeof(jasper_variant) == sizeof(Variant), "jasper_variant is Variant");
-static int varscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
-                        jasper_varscan **out) {
-    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_varscan *r = new jasper_varscan();
-    const int rc = d_text || offsets ? variant_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r->r, g_err)
-                                     : variant_scan_host(t->t, n_seqs, seqs, lens, thre, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    *out = r;
-    return JASPER_OK;
-}
 int jasper_variant_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_varscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return varscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, out);
+    return scan_call(host_args(n_seqs, seqs, lens), t, n_seqs, out, [&](jasper_varscan &r) { return variant_scan_host(t->t, n_seqs, seqs, lens, thre, r.r, g_err); });
 }
 int jasper_variant_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, jasper_varscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return varscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, out);
+    return scan_call(offsets, t, n_seqs, out, [&](jasper_varscan &r) { return variant_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, r.r, g_err); });
 }
 int jasper_varscan_num_seqs(const jasper_varscan *r) { return r ? (int)(r->r.counts.size() / 3) : 0; }
-int jasper_varscan_counts(const jasper_varscan *r, int seq, uint64_t out3[3]) {
-    if (!r || !out3 || seq < 0 || (size_t)seq >= r->r.counts.size() / 3) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 3; ++i) out3[i] = r->r.counts[3 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_varscan_records(const jasper_varscan *r, const jasper_variant **recs, uint64_t *n) {
-    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *recs = reinterpret_cast<const jasper_variant *>(r->r.recs.data());
-    *n = r->r.recs.size();
-    return JASPER_OK;
-}
-int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n) {
-    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *n = r->r.candidates;
-    return JASPER_OK;
-}
+int jasper_varscan_counts(const jasper_varscan *r, int seq, uint64_t out3[3]) { return counts_out<3>(r ? &r->r.counts : nullptr, seq, out3); }
+int jasper_varscan_records(const jasper_varscan *r, const jasper_variant **recs, uint64_t *n) { return records_out(r ? &r->r.recs : nullptr, recs, n); }
+int jasper_varscan_candidates(const jasper_varscan *r, uint64_t *n) { return word_out(r ? &r->r.candidates : nullptr, n); }
 double jasper_varscan_seconds(const jasper_varscan *r) { return r ? r->r.seconds : 0.0; }
 int jasper_varscan_retried(const jasper_varscan *r) { return r ? r->r.retried : 0; }
 void jasper_varscan_free(jasper_varscan *r) { delete r; }
 
 // ---- indel scan (indels.hip) ----
-static_assert(sizeof(jasper_indel) == sizeof(Indel) && offsetof(jasper_indel, len) == offsetof(Indel, len) && offsetof(jasper_indel, type) == offsetof(Indel, type) &&
-                  offsetof(jasper_indel, base) == offsetof(Indel, base) && offsetof(jasper_indel, kind) == offsetof(Indel, kind),
+static_assert(offsetof(jasper_indel, len) == offsetof(Indel, len) && offsetof(jasper_indel, type) == offsetof(Indel, type) && offsetof(jasper_indel, base) == offsetof(Indel, base) &&
+                  offsetof(jasper_indel, kind) == offsetof(Indel, kind),
               "jasper_indel is Indel");
-static_assert(sizeof(jasper_mixed_ins) == sizeof(MixedIns) && offsetof(jasper_mixed_ins, bases) == offsetof(MixedIns, bases) &&
-                  offsetof(jasper_mixed_ins, len) == offsetof(MixedIns, len) && offsetof(jasper_mixed_ins, kind) == offsetof(MixedIns, kind),
+static_assert(offsetof(jasper_mixed_ins, bases) == offsetof(MixedIns, bases) && offsetof(jasper_mixed_ins, len) == offsetof(MixedIns, len) &&
+                  offsetof(jasper_mixed_ins, kind) == offsetof(MixedIns, kind),
               "jasper_mixed_ins is MixedIns");
 static_assert(JASPER_INDEL_FRONT == INDEL_FRONT, "the header's cap is the kernel's");
-static_assert(sizeof(jasper_het_cluster) == sizeof(HetCluster) && offsetof(jasper_het_cluster, alt_min) == offsetof(HetCluster, alt_min) &&
-                  offsetof(jasper_het_cluster, ref_len) == offsetof(HetCluster, ref_len) && offsetof(jasper_het_cluster, bases) == offsetof(HetCluster, bases) &&
-                  offsetof(jasper_het_cluster, len) == offsetof(HetCluster, len),
+static_assert(offsetof(jasper_het_cluster, alt_min) == offsetof(HetCluster, alt_min) && offsetof(jasper_het_cluster, ref_len) == offsetof(HetCluster, ref_len) &&
+                  offsetof(jasper_het_cluster, bases) == offsetof(HetCluster, bases) && offsetof(jasper_het_cluster, len) == offsetof(HetCluster, len),
               "jasper_het_cluster is HetCluster");
-static int indelscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
+// seqs / lens or d_text / offsets, whichever the entry point has.  cluster_len < 0: an entry point without clusters (the scan runs with 0);
+// the cluster entry points pass max(cluster_len, 0), which has to be in 1..CLUSTER_MAX_LEN -- checked after the text arguments, as before.
+static int indelscan_call(bool args_ok, jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
                           int max_len, bool mixed, int cluster_len, jasper_indelscan **out) {
-    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_indelscan *r = new jasper_indelscan();
-    const int rc = d_text || offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, mixed, cluster_len, r->r, g_err)
-                                     : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, mixed, cluster_len, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    r->var.r = std::move(r->r.var);
-    *out = r;
-    return JASPER_OK;
+    if (args_ok && cluster_len >= 0 && (cluster_len < 1 || cluster_len > CLUSTER_MAX_LEN)) { g_err = "indel scan: cluster_len must be in 1..64"; return JASPER_ERR; }
+    const int cl = std::max(cluster_len, 0);
+    return scan_call(args_ok, t, n_seqs, out, [&](jasper_indelscan &r) {
+        const int rc = offsets ? indel_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, mixed, cl, r.r, g_err)
+                               : indel_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, mixed, cl, r.r, g_err);
+        r.var.r = std::move(r.r.var);
+        return rc;
+    });
 }
 int jasper_indel_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, false, 0, out);
+    return indelscan_call(host_args(n_seqs, seqs, lens), t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, false, -1, out);
 }
 int jasper_indel_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, false, 0, out);
+    return indelscan_call(offsets, t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, false, -1, out);
 }
 int jasper_indel_scan_mixed(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_indelscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, true, 0, out);
+    return indelscan_call(host_args(n_seqs, seqs, lens), t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, true, -1, out);
 }
 int jasper_indel_scan_mixed_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_indelscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, true, 0, out);
+    return indelscan_call(offsets, t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, true, -1, out);
 }
 int jasper_indel_scan_clusters(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, int mixed, int cluster_len,
                                jasper_indelscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    if (cluster_len < 1 || cluster_len > CLUSTER_MAX_LEN) { g_err = "indel scan: cluster_len must be in 1..64"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, mixed != 0, cluster_len, out);
+    return indelscan_call(host_args(n_seqs, seqs, lens), t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, mixed != 0, std::max(cluster_len, 0), out);
 }
 int jasper_indel_scan_clusters_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, int mixed, int cluster_len,
                                       jasper_indelscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    if (cluster_len < 1 || cluster_len > CLUSTER_MAX_LEN) { g_err = "indel scan: cluster_len must be in 1..64"; return JASPER_ERR; }
-    return indelscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, mixed != 0, cluster_len, out);
+    return indelscan_call(offsets, t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, mixed != 0, std::max(cluster_len, 0), out);
 }
 int jasper_indelscan_num_seqs(const jasper_indelscan *r) { return r ? (int)(r->r.counts.size() / 4) : 0; }
-int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
-    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 4; ++i) out4[i] = r->r.counts[4 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_indelscan_records(const jasper_indelscan *r, const jasper_indel **recs, uint64_t *n) {
-    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *recs = reinterpret_cast<const jasper_indel *>(r->r.recs.data());
-    *n = r->r.recs.size();
-    return JASPER_OK;
-}
+int jasper_indelscan_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) { return counts_out<4>(r ? &r->r.counts : nullptr, seq, out4); }
+int jasper_indelscan_records(const jasper_indelscan *r, const jasper_indel **recs, uint64_t *n) { return records_out(r ? &r->r.recs : nullptr, recs, n); }
 const jasper_varscan *jasper_indelscan_variants(const jasper_indelscan *r) { return r ? &r->var : nullptr; }
 double jasper_indelscan_seconds(const jasper_indelscan *r) { return r ? r->r.seconds : 0.0; }
 double jasper_indelscan_check_seconds(const jasper_indelscan *r) { return r ? r->r.check_seconds : 0.0; }
-int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n) {
-    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *n = r->r.lookups;
-    return JASPER_OK;
-}
+int jasper_indelscan_lookups(const jasper_indelscan *r, uint64_t *n) { return word_out(r ? &r->r.lookups : nullptr, n); }
 int jasper_indelscan_retried(const jasper_indelscan *r) { return r ? r->r.retried : 0; }
 int jasper_indelscan_mixed_counts(const jasper_indelscan *r, int seq, uint64_t out3[3]) {
-    if (!r || !out3 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 3; ++i) out3[i] = r->r.mixed ? r->r.mixed_counts[3 * (size_t)seq + i] : 0;
-    return JASPER_OK;
+    return counts_out<3>(r ? &r->r.mixed_counts : nullptr, r ? r->r.counts.size() / 4 : 0, seq, out3);
 }
-int jasper_indelscan_mixed_records(const jasper_indelscan *r, const jasper_mixed_ins **recs, uint64_t *n) {
-    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *recs = reinterpret_cast<const jasper_mixed_ins *>(r->r.mixed_recs.data());
-    *n = r->r.mixed_recs.size();
-    return JASPER_OK;
-}
+int jasper_indelscan_mixed_records(const jasper_indelscan *r, const jasper_mixed_ins **recs, uint64_t *n) { return records_out(r ? &r->r.mixed_recs : nullptr, recs, n); }
 double jasper_indelscan_mixed_seconds(const jasper_indelscan *r) { return r ? r->r.mixed_seconds : 0.0; }
-int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n) {
-    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *n = r->r.mixed_lookups;
-    return JASPER_OK;
-}
+int jasper_indelscan_mixed_lookups(const jasper_indelscan *r, uint64_t *n) { return word_out(r ? &r->r.mixed_lookups : nullptr, n); }
 int jasper_indelscan_mixed_retried(const jasper_indelscan *r) { return r ? r->r.mixed_retried : 0; }
 int jasper_indel_front(void) { return INDEL_FRONT; }
 int jasper_indelscan_cluster_counts(const jasper_indelscan *r, int seq, uint64_t out4[4]) {
-    if (!r || !out4 || seq < 0 || (size_t)seq >= r->r.counts.size() / 4) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 4; ++i) out4[i] = r->r.cluster_len ? r->r.cluster_counts[4 * (size_t)seq + i] : 0;
-    return JASPER_OK;
+    return counts_out<4>(r ? &r->r.cluster_counts : nullptr, r ? r->r.counts.size() / 4 : 0, seq, out4);
 }
 int jasper_indelscan_cluster_records(const jasper_indelscan *r, const jasper_het_cluster **recs, uint64_t *n) {
-    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *recs = reinterpret_cast<const jasper_het_cluster *>(r->r.cluster_recs.data());
-    *n = r->r.cluster_recs.size();
-    return JASPER_OK;
+    return records_out(r ? &r->r.cluster_recs : nullptr, recs, n);
 }
 double jasper_indelscan_cluster_seconds(const jasper_indelscan *r) { return r ? r->r.cluster_seconds : 0.0; }
-int jasper_indelscan_cluster_lookups(const jasper_indelscan *r, uint64_t *n) {
-    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *n = r->r.cluster_lookups;
-    return JASPER_OK;
-}
+int jasper_indelscan_cluster_lookups(const jasper_indelscan *r, uint64_t *n) { return word_out(r ? &r->r.cluster_lookups : nullptr, n); }
 int jasper_indelscan_cluster_retried(const jasper_indelscan *r) { return r ? r->r.cluster_retried : 0; }
 void jasper_indelscan_free(jasper_indelscan *r) { delete r; }
 
 // ---- compound scan (compound.hip) ----
-static_assert(sizeof(jasper_compound) == sizeof(Compound) && offsetof(jasper_compound, ref_len) == offsetof(Compound, ref_len) &&
-                  offsetof(jasper_compound, bases) == offsetof(Compound, bases) && offsetof(jasper_compound, len) == offsetof(Compound, len),
+static_assert(offsetof(jasper_compound, ref_len) == offsetof(Compound, ref_len) && offsetof(jasper_compound, bases) == offsetof(Compound, bases) &&
+                  offsetof(jasper_compound, len) == offsetof(Compound, len),
               "jasper_compound is Compound");
 static_assert(sizeof(jasper_compound) == 48, "jasper_compound is 48 bytes");
 static_assert(JASPER_COMPOUND_FRONT == COMPOUND_FRONT && COMPOUND_FRONT == INDEL_FRONT, "the header's cap is the kernel's, and the mixed search's");
-static int compscan_call(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const void *d_text, const int64_t *offsets, uint32_t thre,
-                         int max_len, jasper_compscan **out) {
-    if (!t || !out || n_seqs < 0) { g_err = "bad argument"; return JASPER_ERR; }
-    *out = nullptr;
-    jasper_compscan *r = new jasper_compscan();
-    const int rc = d_text || offsets ? compound_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, r->rep.r, r->r, g_err)
-                                     : compound_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, r->rep.r, r->r, g_err);
-    if (rc) { delete r; return JASPER_ERR; }
-    *out = r;
-    return JASPER_OK;
-}
 int jasper_compound_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, jasper_compscan **out) {
-    if (n_seqs > 0 && (!seqs || !lens)) { g_err = "bad argument"; return JASPER_ERR; }
-    return compscan_call(t, n_seqs, seqs, lens, nullptr, nullptr, thre, max_len, out);
+    return scan_call(host_args(n_seqs, seqs, lens), t, n_seqs, out,
+                     [&](jasper_compscan &r) { return compound_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, r.rep.r, r.r, g_err); });
 }
 int jasper_compound_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, jasper_compscan **out) {
-    if (!offsets) { g_err = "bad argument"; return JASPER_ERR; }
-    return compscan_call(t, n_seqs, nullptr, nullptr, d_text, offsets, thre, max_len, out);
+    return scan_call(offsets, t, n_seqs, out,
+                     [&](jasper_compscan &r) { return compound_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, r.rep.r, r.r, g_err); });
 }
 int jasper_compscan_num_seqs(const jasper_compscan *r) { return r ? (int)(r->r.counts.size() / 5) : 0; }
-int jasper_compscan_counts(const jasper_compscan *r, int seq, uint64_t out5[5]) {
-    if (!r || !out5 || seq < 0 || (size_t)seq >= r->r.counts.size() / 5) { g_err = "bad argument"; return JASPER_ERR; }
-    for (int i = 0; i < 5; ++i) out5[i] = r->r.counts[5 * (size_t)seq + i];
-    return JASPER_OK;
-}
-int jasper_compscan_records(const jasper_compscan *r, const jasper_compound **recs, uint64_t *n) {
-    if (!r || !recs || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *recs = reinterpret_cast<const jasper_compound *>(r->r.recs.data());
-    *n = r->r.recs.size();
-    return JASPER_OK;
-}
+int jasper_compscan_counts(const jasper_compscan *r, int seq, uint64_t out5[5]) { return counts_out<5>(r ? &r->r.counts : nullptr, seq, out5); }
+int jasper_compscan_records(const jasper_compscan *r, const jasper_compound **recs, uint64_t *n) { return records_out(r ? &r->r.recs : nullptr, recs, n); }
 const jasper_report *jasper_compscan_report(const jasper_compscan *r) { return r ? &r->rep : nullptr; }
-int jasper_compscan_lookups(const jasper_compscan *r, uint64_t *n) {
-    if (!r || !n) { g_err = "bad argument"; return JASPER_ERR; }
-    *n = r->r.lookups;
-    return JASPER_OK;
-}
+int jasper_compscan_lookups(const jasper_compscan *r, uint64_t *n) { return word_out(r ? &r->r.lookups : nullptr, n); }
 int jasper_compscan_seconds(const jasper_compscan *r, double *search, double *total) {
     if (!r) { g_err = "bad argument"; return JASPER_ERR; }
     if (search) *search = r->r.search_seconds;

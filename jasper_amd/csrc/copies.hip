@@ -14,11 +14,13 @@
 //                         group of 16; a thread's windows are two 16-bit class masks (excess / deficit).  A run starts where a class
 //                         bit follows a window that does not have that class (clear, the other class, the thread before's last
 //                         window) or at the tile's first window, and every start walks its run through its class's masks -- whole
-//                         groups by their stored sums -- to the run's or the tile's end.  The tile's PARTIAL runs go to a list (one
+//                         groups by their stored sums -- to the run's or the tile's end (class_starts, tile_ends2 and walk_run of
+//                         scan_tile.hpp; the sums per piece of a run are this kernel's).  The tile's PARTIAL runs go to a list (one
 //                         cursor add per tile) with the class of the tile's first and last window; five adds per tile into the
 //                         per-sequence counters.  Nothing per window leaves the CU.
-// The heads and stitch kernels that make final runs of the partial ones, and the host stage, are the shared ones of scan_tile.hpp; a run
-// continues across a tile seam when both sides have the same non-zero class, and absorbs only partial runs OF ITS KIND.
+// A window's rolling step, the run finder, the heads and stitch kernels that make final runs of the partial ones, and the host stage
+// (run_scan; settle orders A's stream before R's) are the shared ones of scan_tile.hpp; a run continues across a tile seam when both
+// sides have the same non-zero class, and absorbs only partial runs OF ITS KIND.
 //
 // The class of a window needs e = (2c + peak) div (2 peak) only in comparison with a; with P = peak * a (< 2^64):
 //   e > a  <=>  (2c + peak) / (2 peak) >= a + 1  <=>  2c >= 2P + peak        e < a  <=>  (2c + peak) / (2 peak) < a  <=>  2c + peak < 2P
@@ -89,13 +91,7 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
-                const uint32_t cj = (c >> (30 - 2 * j)) & 3u;
-                const bool bad = (iv >> (15 - j)) & 1u;
-                fwd = band(bor(shl(fwd, 2), mk(0, cj)), kmask);
-                rc = bor(shr(rc, 2), shl(mk(0, 3u - cj), 2 * (k - 1)));
-                run = bad ? 0 : run + 1;
-                ok[u] = run >= k && e0 + j < n;
-                hs[u] = mix(lt(rc, fwd) ? rc : fwd, R.B);
+                ok[u] = roll_window(c, iv, j, k, kmask, R.B, e0, n, fwd, rc, run, hs[u]);
                 er[u] = make_ulonglong2(0ull, 0ull);
                 ea[u] = make_ulonglong2(0ull, 0ull);
                 if (ok[u]) {
@@ -147,17 +143,11 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
         }
         __syncthreads();
         // where my runs start: a class bit after a window that does not have that class (the tile's first window starts one anyway)
-        const uint32_t pe = t > 0 ? (s_ex[t - 1] >> 15) & 1u : 0u, pd = t > 0 ? (s_de[t - 1] >> 15) & 1u : 0u;
-        const uint32_t se = em & ~((em << 1) | pe) & 0xFFFFu, sd = dm & ~((dm << 1) | pd) & 0xFFFFu;
+        const uint32_t se = class_starts(em, s_ex), sd = class_starts(dm, s_de);
         const uint32_t startmask = se | sd;             // (no window has both classes)
         const uint32_t ns = __popc(startmask);
         const TileSlots S = tile_reserve(ns, s_wsum, &s_base, &ctl[SC_CURSOR]);
-        if (t == 0) {
-            const uint32_t e0m = s_ex[0], d0m = s_de[0], eLm = s_ex[RP_THREADS - 1], dLm = s_de[RP_THREADS - 1];
-            const uint32_t first = (e0m & 1u) ? CP_EXCESS : (d0m & 1u) ? CP_DEFICIT : CP_NONE;
-            const uint32_t last = ((eLm >> 15) & 1u) ? CP_EXCESS : ((dLm >> 15) & 1u) ? CP_DEFICIT : CP_NONE;
-            tout[tile] = TileRuns{S.base0, S.total, first | (last << 2)};
-        }
+        if (t == 0) tout[tile] = TileRuns{S.base0, S.total, tile_ends2(s_ex, s_de, CP_EXCESS, CP_DEFICIT)};
         if (t < 3 && s_tot[t]) atomicAdd(&counts[(unsigned long long)CP_NCOUNT * D.seq + t], (unsigned long long)s_tot[t]);
         if (t >= 3 && t < 5 && s_sum[t - 3]) atomicAdd(&counts[(unsigned long long)CP_NCOUNT * D.seq + t], s_sum[t - 3]);
         unsigned long long at;
@@ -167,15 +157,11 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
                 const int b0 = __builtin_ctz(sm);
                 sm &= sm - 1;
                 const bool isex = (se >> b0) & 1u;
-                const uint32_t *__restrict__ M = isex ? s_ex : s_de;
-                int pos = t * RP_GROUP + b0;
-                uint64_t nk = 0, sr = 0, sa = 0;
-                while (pos < RP_TILE) {
-                    const int g = pos >> 4, b = pos & 15;
-                    const uint32_t U = M[g] >> b;
-                    const int len = __builtin_ctz(~U);            // (bits 16.. of U are clear: len <= 16 - b)
-                    if (len == 0) break;
-                    if (len == RP_GROUP) {
+                uint64_t sr = 0, sa = 0;
+                CopyRun r;
+                r.start = w0 + t * RP_GROUP + b0;
+                r.n_kmers = walk_run(isex ? s_ex : s_de, t * RP_GROUP + b0, [&](int g, int, int pos, int len) {
+                    if (len == RP_GROUP) {                        // whole groups by their stored sums
                         sr += s_gc[g];
                         sa += s_ga[g];
                     } else {
@@ -184,13 +170,7 @@ __global__ __launch_bounds__(RP_THREADS) void copies_scan_kernel(const uint8_t *
                             sa += s_a[pos + j];
                         }
                     }
-                    nk += len;
-                    pos += len;
-                    if (b + len < RP_GROUP) break;
-                }
-                CopyRun r;
-                r.start = w0 + t * RP_GROUP + b0;
-                r.n_kmers = nk;
+                });
                 r.sum_reads = sr;
                 r.sum_asm = sa;
                 r.seq = D.seq;
@@ -217,49 +197,15 @@ int copies_report_device(Table &R, Table &A, int n_seqs, const uint8_t *d_text, 
     if (n_seqs < 0 || (n_seqs && !offsets)) { err = "copy report: bad arguments"; return -1; }
     if (check_pair(R, A, peak, err)) return -1;
     HIPCHK(hipSetDevice(R.device));
-    // a logically empty table holds garbage until it is zeroed: both tables are probed
-    if (A.materialize(err) || R.materialize(err)) return -1;
-    out.counts.assign((size_t)n_seqs * 6, 0);
-    out.runs.clear();
-    out.seconds = 0;
-    out.retried = 0;
-    TileList L;
-    if (build_tiles(R.k, n_seqs, d_text, offsets, "copy report", out.counts.data(), 6, L, err)) return -1;
-    const uint64_t ntiles = L.tiles.size();
-    if (ntiles == 0) return 0;
-    hipStream_t st = R.stream;
-    const int W = Table::WS_COPIES;
-    TileRuns *d_tout = (TileRuns *)R.workspace(W + 3, ntiles * sizeof(TileRuns), err);
-    unsigned long long *d_head = (unsigned long long *)R.workspace(W + 4, ntiles * sizeof(unsigned long long), err);
-    const size_t cnt_words = (size_t)n_seqs * CP_NCOUNT + SC_WORDS;
-    unsigned long long *d_cnt = (unsigned long long *)R.workspace(W + 5, cnt_words * sizeof(unsigned long long), err);
-    if (!d_tout || !d_head || !d_cnt) return -1;
+    Table *others[1] = {&A};                            // a logically empty table holds garbage until it is zeroed: both tables are probed
     Events order;
-    HIPCHK(hipEventCreate(&order.e[0]));
-    HIPCHK(hipEventRecord(order.e[0], A.stream));      // whatever A's stream still does to A comes first
-    HIPCHK(hipStreamWaitEvent(st, order.e[0], 0));
-    if (upload_tiles(R, W, n_seqs, offsets, L, err)) return -1;
-    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * CP_NCOUNT, ctl[SC_WORDS] = {0, 0, 0, 0};
-    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
-    CopyRun *d_part = nullptr;
-    auto scan = [&](unsigned long long cap) {
-        d_part = (CopyRun *)R.workspace(W + 6, cap * sizeof(CopyRun), err);
-        if (!d_part) return -1;
-        hipLaunchKernelGGL(copies_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, R.d, A.d, thre, peak, d_cnt, d_tout, d_part, cap,
-                           d_ctl);
-        return 0;
-    };
-    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, "copy report: the number of partial runs changed between two scans", ctl, out.seconds, out.retried,
-                    err, scan))
-        return -1;
-    const uint64_t nparts = ctl[SC_CURSOR];
-    std::vector<unsigned long long> cnt((size_t)n_seqs * CP_NCOUNT);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (nparts && stitch_runs(R, W + 7, L, d_tout, d_head, d_part, nparts, d_ctl, "copy report", out.runs, out.seconds, err)) return -1;
-    HIPCHK(jk_stream_wait(st));
-    for (int i = 0; i < n_seqs; ++i)
-        for (int c = 0; c < CP_NCOUNT; ++c) out.counts[6 * (size_t)i + 1 + c] = cnt[CP_NCOUNT * (size_t)i + c];
-    return 0;
+    if (settle(R, others, 1, order, err)) return -1;
+    return run_scan(R, Table::WS_COPIES, "copy report", n_seqs, d_text, offsets, CP_NCOUNT, 6, out.counts, out.runs, out.seconds, out.retried, err,
+                    [&](unsigned grid, hipStream_t st, const TileList &L, uint64_t ntiles, unsigned long long *d_cnt, TileRuns *d_tout, CopyRun *d_part, unsigned long long cap,
+                        unsigned long long *d_ctl) {
+                        hipLaunchKernelGGL(copies_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, R.d, A.d, thre, peak, d_cnt, d_tout, d_part,
+                                           cap, d_ctl);
+                    });
 }
 
 int copies_report_host(Table &R, Table &A, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak, CopyOut &out, std::string &err) {

@@ -13,14 +13,16 @@
 //                         the owner's shard when R is attached); no load registers are kept for R.  A thread's windows are two 16-bit class
 //                         masks (mat / pat) in LDS and nothing else: a run's length follows from the masks, so there are no count arrays
 //                         and no group sums, and LDS per workgroup is 4 168 B where the copy scan has 41 048 B.  Run starts and the walk
-//                         through the class's masks are the copy scan's, without the sums.  The tile's PARTIAL runs go to a list (one
+//                         through the class's masks are the shared run finder (class_starts, tile_ends2, walk_run of scan_tile.hpp)
+//                         with nothing to accumulate per piece.  The tile's PARTIAL runs go to a list (one
 //                         cursor add per tile) with the class of the tile's first and last window; three adds per tile into the
 //                         per-sequence counters.
 //   hapmer_census_kernel  a sweep over M's slots in the shape of spectra_reads_kernel: slots whose count is below the threshold are dropped
 //                         before any probe, the others probe P with the loads of the batch in flight together, the survivors (P has none)
 //                         probe R and then A.  Three counters per thread, summed per wave and per workgroup, three global adds per
 //                         workgroup.  Launched twice, the parents swapped.
-// The heads and stitch kernels that make final runs of the partial ones, and the host stage, are the shared ones of scan_tile.hpp.
+// A window's rolling step, the heads and stitch kernels that make final runs of the partial ones, and the host stage (settle, run_scan)
+// are the shared ones of scan_tile.hpp; the census orders its four tables with the same settle.
 #include "hapmers.hpp"
 #include "scan_tile.hpp"
 #include "spectra.hpp"
@@ -73,13 +75,7 @@ __global__ __launch_bounds__(RP_THREADS) void hapmer_scan_kernel(const uint8_t *
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
-                const uint32_t cj = (c >> (30 - 2 * j)) & 3u;
-                const bool bad = (iv >> (15 - j)) & 1u;
-                fwd = band(bor(shl(fwd, 2), mk(0, cj)), kmask);
-                rc = bor(shr(rc, 2), shl(mk(0, 3u - cj), 2 * (k - 1)));
-                run = bad ? 0 : run + 1;
-                ok[u] = run >= k && e0 + j < n;
-                hs[u] = mix(lt(rc, fwd) ? rc : fwd, M.B);
+                ok[u] = roll_window(c, iv, j, k, kmask, M.B, e0, n, fwd, rc, run, hs[u]);
                 em[u] = make_ulonglong2(0ull, 0ull);
                 ep[u] = make_ulonglong2(0ull, 0ull);
                 if (ok[u]) {                            // (M and P are whole tables: their own slot arrays)
@@ -116,17 +112,11 @@ __global__ __launch_bounds__(RP_THREADS) void hapmer_scan_kernel(const uint8_t *
         }
         __syncthreads();
         // where my runs start: a class bit after a window that does not have that class (the tile's first window starts one anyway)
-        const uint32_t qm = t > 0 ? (s_ma[t - 1] >> 15) & 1u : 0u, qp = t > 0 ? (s_pa[t - 1] >> 15) & 1u : 0u;
-        const uint32_t sm_ = mm & ~((mm << 1) | qm) & 0xFFFFu, sp_ = pm & ~((pm << 1) | qp) & 0xFFFFu;
+        const uint32_t sm_ = class_starts(mm, s_ma), sp_ = class_starts(pm, s_pa);
         const uint32_t startmask = sm_ | sp_;           // (no window has both classes)
         const uint32_t ns = __popc(startmask);
         const TileSlots S = tile_reserve(ns, s_wsum, &s_base, &ctl[SC_CURSOR]);
-        if (t == 0) {
-            const uint32_t m0 = s_ma[0], p0 = s_pa[0], mL = s_ma[RP_THREADS - 1], pL = s_pa[RP_THREADS - 1];
-            const uint32_t first = (m0 & 1u) ? HM_MAT : (p0 & 1u) ? HM_PAT : HM_NONE;
-            const uint32_t last = ((mL >> 15) & 1u) ? HM_MAT : ((pL >> 15) & 1u) ? HM_PAT : HM_NONE;
-            tout[tile] = TileRuns{S.base0, S.total, first | (last << 2)};
-        }
+        if (t == 0) tout[tile] = TileRuns{S.base0, S.total, tile_ends2(s_ma, s_pa, HM_MAT, HM_PAT)};
         if (t < HM_NCOUNT && s_tot[t]) atomicAdd(&counts[(unsigned long long)HM_NCOUNT * D.seq + t], (unsigned long long)s_tot[t]);
         unsigned long long at;
         if (tile_granted(S, &s_base, cap, at)) {
@@ -135,21 +125,9 @@ __global__ __launch_bounds__(RP_THREADS) void hapmer_scan_kernel(const uint8_t *
                 const int b0 = __builtin_ctz(sm);
                 sm &= sm - 1;
                 const bool ismat = (sm_ >> b0) & 1u;
-                const uint32_t *__restrict__ K = ismat ? s_ma : s_pa;
-                int pos = t * RP_GROUP + b0;
-                uint64_t nk = 0;
-                while (pos < RP_TILE) {
-                    const int g = pos >> 4, b = pos & 15;
-                    const uint32_t U = K[g] >> b;
-                    const int len = __builtin_ctz(~U);            // (bits 16.. of U are clear: len <= 16 - b)
-                    if (len == 0) break;
-                    nk += len;
-                    pos += len;
-                    if (b + len < RP_GROUP) break;
-                }
                 HapRun r;
                 r.start = w0 + t * RP_GROUP + b0;
-                r.n_kmers = nk;
+                r.n_kmers = walk_run(ismat ? s_ma : s_pa, t * RP_GROUP + b0, [](int, int, int, int) {});      // (a run's length is all there is to it)
                 r.seq = D.seq;
                 r.kind = ismat ? HM_MAT : HM_PAT;
                 part[at++] = r;
@@ -240,19 +218,6 @@ int check_trio(const char *what, Table &M, Table &P, Table *R, Table *A, uint32_
     if (thre_child < 1) { err = w + ": the child threshold must be at least 1 (it is 0)"; return -1; }
     return 0;
 }
-// every table zeroed if it is only logically empty, and whatever the other tables' streams still do to them ordered before T's stream
-int settle(Table &T, Table *const *others, int n, Events &order, std::string &err) {
-    if (T.materialize(err)) return -1;
-    for (int i = 0; i < n; ++i)
-        if (others[i] && others[i]->materialize(err)) return -1;
-    HIPCHK(hipEventCreate(&order.e[0]));
-    for (int i = 0; i < n; ++i) {
-        if (!others[i] || others[i] == &T) continue;
-        HIPCHK(hipEventRecord(order.e[0], others[i]->stream));
-        HIPCHK(hipStreamWaitEvent(T.stream, order.e[0], 0));
-    }
-    return 0;
-}
 unsigned census_grid(uint64_t nslots) {                // as the spectrum's sweeps: fills the chip, the rest is grid-stride
     uint64_t b = (nslots + (uint64_t)SP_THREADS * SP_BATCH - 1) / ((uint64_t)SP_THREADS * SP_BATCH);
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(b, 1), 256 * 8);
@@ -268,43 +233,12 @@ int hapmer_scan_device(Table &M, Table &P, Table *R, int n_seqs, const uint8_t *
     Table *others[3] = {&M, &P, R};
     Events order;
     if (settle(T, others, 3, order, err)) return -1;
-    out.counts.assign((size_t)n_seqs * 4, 0);
-    out.runs.clear();
-    out.seconds = 0;
-    out.retried = 0;
-    TileList L;
-    if (build_tiles(M.k, n_seqs, d_text, offsets, "hap-mer scan", out.counts.data(), 4, L, err)) return -1;
-    const uint64_t ntiles = L.tiles.size();
-    if (ntiles == 0) return 0;
-    hipStream_t st = T.stream;
-    const int W = Table::WS_HAPMERS;
-    TileRuns *d_tout = (TileRuns *)T.workspace(W + 3, ntiles * sizeof(TileRuns), err);
-    unsigned long long *d_head = (unsigned long long *)T.workspace(W + 4, ntiles * sizeof(unsigned long long), err);
-    const size_t cnt_words = (size_t)n_seqs * HM_NCOUNT + SC_WORDS;
-    unsigned long long *d_cnt = (unsigned long long *)T.workspace(W + 5, cnt_words * sizeof(unsigned long long), err);
-    if (!d_tout || !d_head || !d_cnt) return -1;
-    if (upload_tiles(T, W, n_seqs, offsets, L, err)) return -1;
-    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * HM_NCOUNT, ctl[SC_WORDS] = {0, 0, 0, 0};
-    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
-    HapRun *d_part = nullptr;
-    auto scan = [&](unsigned long long cap) {
-        d_part = (HapRun *)T.workspace(W + 6, cap * sizeof(HapRun), err);
-        if (!d_part) return -1;
-        hipLaunchKernelGGL(hapmer_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, M.d, P.d, R ? R->d : M.d, R ? 1 : 0, thre_mat, thre_pat,
-                           thre_child, d_cnt, d_tout, d_part, cap, d_ctl);
-        return 0;
-    };
-    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, "hap-mer scan: the number of partial runs changed between two scans", ctl, out.seconds, out.retried,
-                    err, scan))
-        return -1;
-    const uint64_t nparts = ctl[SC_CURSOR];
-    std::vector<unsigned long long> cnt((size_t)n_seqs * HM_NCOUNT);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (nparts && stitch_runs(T, W + 7, L, d_tout, d_head, d_part, nparts, d_ctl, "hap-mer scan", out.runs, out.seconds, err)) return -1;
-    HIPCHK(jk_stream_wait(st));
-    for (int i = 0; i < n_seqs; ++i)
-        for (int c = 0; c < HM_NCOUNT; ++c) out.counts[4 * (size_t)i + 1 + c] = cnt[HM_NCOUNT * (size_t)i + c];
-    return 0;
+    return run_scan(T, Table::WS_HAPMERS, "hap-mer scan", n_seqs, d_text, offsets, HM_NCOUNT, 4, out.counts, out.runs, out.seconds, out.retried, err,
+                    [&](unsigned grid, hipStream_t st, const TileList &L, uint64_t ntiles, unsigned long long *d_cnt, TileRuns *d_tout, HapRun *d_part, unsigned long long cap,
+                        unsigned long long *d_ctl) {
+                        hipLaunchKernelGGL(hapmer_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, M.d, P.d, R ? R->d : M.d, R ? 1 : 0, thre_mat,
+                                           thre_pat, thre_child, d_cnt, d_tout, d_part, cap, d_ctl);
+                    });
 }
 
 int hapmer_scan_host(Table &M, Table &P, Table *R, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,

@@ -13,9 +13,10 @@
 //                         (one cursor add per tile), with "open at the tile's start / end" marks; the per-sequence counters get
 //                         three adds per tile.  Nothing per window leaves the CU.
 //
-// The tile's front end (staging, the rolling state before a thread's first window), the reservation of places in the list, the heads
-// and stitch kernels that make final runs of the partial ones, and the host stage (text packing, tile list, the repeat with exactly the
-// counted room) are the dense scans' common parts: scan_tile.hpp.  Here the report has one class, unreliable = 1.
+// The tile's front end (staging, the rolling state before a thread's first window), a window's rolling step, the reservation of places in
+// the list, the run finder (run starts, the tile's ends, the walk through a class's masks), the heads and stitch kernels that make final
+// runs of the partial ones, and the host stage (text packing, tile list, the repeat with exactly the counted room) are the dense scans'
+// common parts: scan_tile.hpp.  Here the report has one class, unreliable = 1, and its own accumulation per piece of a run.
 #include "scan_tile.hpp"
 
 namespace jk {
@@ -61,13 +62,7 @@ __global__ __launch_bounds__(RP_THREADS) void report_scan_kernel(const uint8_t *
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
-                const uint32_t cj = (c >> (30 - 2 * j)) & 3u;
-                const bool bad = (iv >> (15 - j)) & 1u;
-                fwd = band(bor(shl(fwd, 2), mk(0, cj)), kmask);
-                rc = bor(shr(rc, 2), shl(mk(0, 3u - cj), 2 * (k - 1)));
-                run = bad ? 0 : run + 1;
-                ok[u] = run >= k && e0 + j < n;
-                hs[u] = mix(lt(rc, fwd) ? rc : fwd, T.B);
+                ok[u] = roll_window(c, iv, j, k, kmask, T.B, e0, n, fwd, rc, run, hs[u]);
                 ent[u] = make_ulonglong2(0ull, 0ull);
                 if (ok[u]) ent[u] = *reinterpret_cast<const ulonglong2 *>(read_slots(T, hs[u]) + 2 * home_of(hs[u], T.B, T.s));
             }
@@ -96,11 +91,10 @@ __global__ __launch_bounds__(RP_THREADS) void report_scan_kernel(const uint8_t *
         }
         __syncthreads();
         // where my runs start: an unreliable window after one that is not (the tile's first window starts one anyway)
-        const uint32_t carry = t > 0 ? (s_unrel[t - 1] >> 15) & 1u : 0u;
-        const uint32_t startmask = um & ~((um << 1) | carry) & 0xFFFFu;
+        const uint32_t startmask = class_starts(um, s_unrel);
         const uint32_t ns = __popc(startmask);
         const TileSlots S = tile_reserve(ns, s_wsum, &s_base, &ctl[SC_CURSOR]);
-        if (t == 0) tout[tile] = TileRuns{S.base0, S.total, (s_unrel[0] & 1u) | (((s_unrel[RP_THREADS - 1] >> 15) & 1u) << 2)};
+        if (t == 0) tout[tile] = TileRuns{S.base0, S.total, tile_ends(s_unrel)};
         if (t < 3 && s_tot[t]) atomicAdd(&counts[3ull * D.seq + t], (unsigned long long)s_tot[t]);
         unsigned long long at;
         if (tile_granted(S, &s_base, cap, at)) {
@@ -108,25 +102,16 @@ __global__ __launch_bounds__(RP_THREADS) void report_scan_kernel(const uint8_t *
             while (sm) {
                 const int b0 = __builtin_ctz(sm);
                 sm &= sm - 1;
-                int pos = t * RP_GROUP + b0;
-                uint64_t nk = 0, na = 0;
+                uint64_t na = 0;
                 uint32_t mn = 0xFFFFFFFFu;
-                while (pos < RP_TILE) {
-                    const int g = pos >> 4, b = pos & 15;
-                    const uint32_t U = s_unrel[g] >> b;
-                    const int len = __builtin_ctz(~U);            // (bits 16.. of U are clear: len <= 16 - b)
-                    if (len == 0) break;
-                    if (len == RP_GROUP) mn = min(mn, s_gmin[g]);
+                KmerRun r;
+                r.start = w0 + t * RP_GROUP + b0;
+                r.n_kmers = walk_run(s_unrel, t * RP_GROUP + b0, [&](int g, int b, int pos, int len) {
+                    if (len == RP_GROUP) mn = min(mn, s_gmin[g]);      // whole groups by their stored minimum
                     else
                         for (int j = 0; j < len; ++j) mn = min(mn, s_cnt[pos + j]);
                     na += __popc((s_abs[g] >> b) & ((1u << len) - 1u));
-                    nk += len;
-                    pos += len;
-                    if (b + len < RP_GROUP) break;
-                }
-                KmerRun r;
-                r.start = w0 + t * RP_GROUP + b0;
-                r.n_kmers = nk;
+                });
                 r.n_absent = na;
                 r.seq = D.seq;
                 r.min_count = mn;
@@ -141,41 +126,11 @@ int kmer_report_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_
     if (n_seqs < 0 || (n_seqs && !offsets)) { err = "kmer report: bad arguments"; return -1; }
     HIPCHK(hipSetDevice(T.device));
     if (T.materialize(err)) return -1;
-    R.counts.assign((size_t)n_seqs * 4, 0);
-    R.runs.clear();
-    R.seconds = 0;
-    R.retried = 0;
-    TileList L;
-    if (build_tiles(T.k, n_seqs, d_text, offsets, "kmer report", R.counts.data(), 4, L, err)) return -1;
-    const uint64_t ntiles = L.tiles.size();
-    if (ntiles == 0) return 0;
-    hipStream_t st = T.stream;
-    const int W = Table::WS_REPORT;
-    TileRuns *d_tout = (TileRuns *)T.workspace(W + 3, ntiles * sizeof(TileRuns), err);
-    unsigned long long *d_head = (unsigned long long *)T.workspace(W + 4, ntiles * sizeof(unsigned long long), err);
-    const size_t cnt_words = (size_t)n_seqs * 3 + SC_WORDS;
-    unsigned long long *d_cnt = (unsigned long long *)T.workspace(W + 5, cnt_words * sizeof(unsigned long long), err);
-    if (!d_tout || !d_head || !d_cnt || upload_tiles(T, W, n_seqs, offsets, L, err)) return -1;
-    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * 3, ctl[SC_WORDS] = {0, 0, 0, 0};
-    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
-    KmerRun *d_part = nullptr;
-    auto scan = [&](unsigned long long cap) {
-        d_part = (KmerRun *)T.workspace(W + 6, cap * sizeof(KmerRun), err);
-        if (!d_part) return -1;
-        hipLaunchKernelGGL(report_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, T.d, thre, d_cnt, d_tout, d_part, cap, d_ctl);
-        return 0;
-    };
-    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, "kmer report: the number of partial runs changed between two scans", ctl, R.seconds, R.retried, err,
-                    scan))
-        return -1;
-    const uint64_t nparts = ctl[SC_CURSOR];
-    std::vector<unsigned long long> cnt((size_t)n_seqs * 3);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (nparts && stitch_runs(T, W + 7, L, d_tout, d_head, d_part, nparts, d_ctl, "kmer report", R.runs, R.seconds, err)) return -1;
-    HIPCHK(jk_stream_wait(st));
-    for (int i = 0; i < n_seqs; ++i)
-        for (int c = 0; c < 3; ++c) R.counts[4 * (size_t)i + 1 + c] = cnt[3 * (size_t)i + c];
-    return 0;
+    return run_scan(T, Table::WS_REPORT, "kmer report", n_seqs, d_text, offsets, 3, 4, R.counts, R.runs, R.seconds, R.retried, err,
+                    [&](unsigned grid, hipStream_t st, const TileList &L, uint64_t ntiles, unsigned long long *d_cnt, TileRuns *d_tout, KmerRun *d_part, unsigned long long cap,
+                        unsigned long long *d_ctl) {
+                        hipLaunchKernelGGL(report_scan_kernel, dim3(grid), dim3(RP_THREADS), 0, st, d_text, L.d_offs, L.d_tiles, ntiles, T.d, thre, d_cnt, d_tout, d_part, cap, d_ctl);
+                    });
 }
 
 int kmer_report_host(Table &T, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, ReportOut &R, std::string &err) {

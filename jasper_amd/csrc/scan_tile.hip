@@ -1,5 +1,5 @@
 // scan_tile.hip -- the parts of the dense scans' shared stage that are no templates (scan_tile.hpp): the heads kernel and the host side's
-// text packing and tile list.
+// text packing, the ordering of a scan's tables before its stream, and the tile list.
 #include "scan_tile.hpp"
 
 namespace jk {
@@ -49,6 +49,19 @@ int pack_host_text(Table &T, int slot, int n_seqs, const char *const *seqs, cons
         src = H.all.data();
     }
     if (total) HIPCHK(hipMemcpyAsync(H.d_text, src, total, hipMemcpyHostToDevice, T.stream));
+    return 0;
+}
+
+int settle(Table &T, Table *const *others, int n, Events &order, std::string &err) {
+    if (T.materialize(err)) return -1;
+    for (int i = 0; i < n; ++i)
+        if (others[i] && others[i]->materialize(err)) return -1;
+    HIPCHK(hipEventCreate(&order.e[0]));
+    for (int i = 0; i < n; ++i) {
+        if (!others[i] || others[i] == &T) continue;
+        HIPCHK(hipEventRecord(order.e[0], others[i]->stream));
+        HIPCHK(hipStreamWaitEvent(T.stream, order.e[0], 0));
+    }
     return 0;
 }
 

@@ -1,14 +1,20 @@
-// scan_tile.hpp -- what the dense scans (report.hip, copies.hip, variants.hip and, through the last, indels.hip) have in common: everything
-// before and after a scan kernel's probe loop, the two kernels that stitch partial runs, and the host stage around them.
+// scan_tile.hpp -- what the dense scans (report.hip, copies.hip, hapmers.hip, variants.hip and, through the last, indels.hip) have in
+// common: everything before and after a scan kernel's probe loads, the two kernels that stitch partial runs, and the host stage around them.
 //
 // Device side.  A tile is RP_TILE windows of ONE sequence; thread t owns the 16 windows that end at origin + 16t ...
 //   tile_prologue<HALO>   the tile and HALO groups of 16 bases before it staged into LDS (stage16), one barrier, and the thread's rolling
-//                         state before its first window.  The report and the copy scan look 64 bases back (RP_HALO), the variant scan
-//                         128 (VS_HALO): a run of 2k - 1 bases has to be seen.
+//                         state before its first window.  The report, the copy and the hap-mer scan look 64 bases back (RP_HALO), the
+//                         variant scan 128 (VS_HALO): a run of 2k - 1 bases has to be seen.
+//   roll_window           one window of the probe loop of a RUN scan: the rolling k-mer, its hash, and whether there is a k-mer at all.
+//                         What a kernel loads and resolves for it is the kernel's own.
 //   tile_reserve, tile_granted   from a thread's item count to its first place in the scan's global list: a block-wide exclusive sum, ONE
 //                         cursor add per tile, and the rule that a tile writes all its items or none (the cursor has counted them either
 //                         way, so the host can repeat the scan with exactly that room).  One barrier each; the kernel's own per-tile
 //                         bookkeeping goes between the two.
+//   class_starts, tile_ends, tile_ends2, walk_run   the run finder of a run scan.  A class is a 16-bit mask per thread in LDS; a run starts
+//                         where a class bit follows a window without it (the thread before's bit 15 carries over; the tile's first window
+//                         starts one anyway), and every start walks its class's masks to the run's or the tile's end, handing each piece
+//                         inside one group to the kernel's own accumulation.
 //   TileRuns              what a tile of a RUN scan leaves: where its partial runs are and the class of its first and last window.
 //   scan_heads_kernel     one workgroup: a partial run is the HEAD of a final run unless it continues the last partial run of the tile
 //                         before it (tile_continues); exclusive sum of heads per tile = where a tile's final runs go.  Tiles are in
@@ -16,8 +22,10 @@
 //   scan_stitch_kernel    one wave per tile: each head is copied to its final place; the head that holds its tile's last window first
 //                         absorbs the continuing partial runs of its kind of the tiles after it.  The run type brings two overloads:
 //                         Run absorb(Run, Run) and kind_of(Run), by value (by reference costs the CopyRun kernel two VGPRs).
-// Host side: pack_host_text (sequences in host memory -> one device text), build_tiles / upload_tiles, run_counted (launch, read the
-// control words, repeat once with exactly the counted room) and stitch_runs.  Workspace slots stay the caller's: each scan has its own.
+// Host side: pack_host_text (sequences in host memory -> one device text), settle (the tables of a scan zeroed and ordered before one
+// stream), build_tiles / upload_tiles, run_counted (launch, read the control words, repeat once with exactly the counted room), stitch_runs,
+// and run_scan, the whole host stage of a run scan around the caller's one kernel launch.  The workspace base stays the caller's: each scan
+// has its own slots.
 #pragma once
 #include "report.hpp"
 #include <algorithm>
@@ -109,6 +117,19 @@ __device__ __forceinline__ void tile_prologue(const uint8_t *__restrict__ text, 
     }
 }
 
+// Window j (0 .. 15) of my 16: (c, iv) are my bases (stage16), e0 is where window 0 ends, n the sequence's length.  Rolls fwd / rc / run by
+// one base, leaves the canonical k-mer's hash in h (B = 2k: the hash does not depend on a table's size) and says whether the window has a
+// k-mer.
+__device__ __forceinline__ bool roll_window(uint32_t c, uint32_t iv, int j, int k, u128 kmask, int B, int64_t e0, int64_t n, u128 &fwd, u128 &rc, int &run, u128 &h) {
+    const uint32_t cj = (c >> (30 - 2 * j)) & 3u;
+    const bool bad = (iv >> (15 - j)) & 1u;
+    fwd = band(bor(shl(fwd, 2), mk(0, cj)), kmask);
+    rc = bor(shr(rc, 2), shl(mk(0, 3u - cj), 2 * (k - 1)));
+    run = bad ? 0 : run + 1;
+    h = mix(lt(rc, fwd) ? rc : fwd, B);
+    return run >= k && e0 + j < n;
+}
+
 // A thread's ns items of the tile: `first` is its first place among the tile's `total`.  Thread 0 adds total to *cursor and leaves the tile's
 // place in the global list in *s_base (base0 is that place, in thread 0 only).  s_wsum holds RP_THREADS / 64 words.  One barrier.
 struct TileSlots { uint32_t first, total; unsigned long long base0; };
@@ -134,6 +155,39 @@ __device__ __forceinline__ bool tile_granted(TileSlots S, const unsigned long lo
     const unsigned long long base = *s_base;
     at = base + S.first;
     return base + S.total <= cap;
+}
+
+// ---- the run finder: s_mask[g] bit j = window 16g + j of the tile has the class; every thread's word is written and a barrier has passed ----
+// where my runs of a class start (mask = my own word): a class bit after a window that does not have the class
+__device__ __forceinline__ uint32_t class_starts(uint32_t mask, const uint32_t *s_mask) {
+    const int t = threadIdx.x;
+    const uint32_t carry = t > 0 ? (s_mask[t - 1] >> 15) & 1u : 0u;
+    return mask & ~((mask << 1) | carry) & 0xFFFFu;
+}
+// TileRuns::ends of a tile with one class (kind 1) ...
+__device__ __forceinline__ uint32_t tile_ends(const uint32_t *s_mask) { return (s_mask[0] & 1u) | (((s_mask[RP_THREADS - 1] >> 15) & 1u) << 2); }
+// ... and with two classes that no window has both of
+__device__ __forceinline__ uint32_t tile_ends2(const uint32_t *s_a, const uint32_t *s_b, uint32_t kind_a, uint32_t kind_b) {
+    const uint32_t a0 = s_a[0], b0 = s_b[0], aL = s_a[RP_THREADS - 1], bL = s_b[RP_THREADS - 1];
+    const uint32_t first = (a0 & 1u) ? kind_a : (b0 & 1u) ? kind_b : 0u;
+    const uint32_t last = ((aL >> 15) & 1u) ? kind_a : ((bL >> 15) & 1u) ? kind_b : 0u;
+    return first | (last << 2);
+}
+// The run of the class K that starts at window pos of the tile, walked to its or the tile's end: its length.  piece(g, b, pos, len) is
+// called for every stretch of it inside one group: windows pos .. pos + len) = bits b .. b + len) of group g (len == RP_GROUP: the whole group).
+template <class Piece> __device__ __forceinline__ uint64_t walk_run(const uint32_t *__restrict__ K, int pos, Piece &&piece) {
+    uint64_t nk = 0;
+    while (pos < RP_TILE) {
+        const int g = pos >> 4, b = pos & 15;
+        const uint32_t U = K[g] >> b;
+        const int len = __builtin_ctz(~U);            // (bits 16.. of U are clear: len <= 16 - b)
+        if (len == 0) break;
+        piece(g, b, pos, len);
+        nk += len;
+        pos += len;
+        if (b + len < RP_GROUP) break;
+    }
+    return nk;
 }
 
 // 1 if the first partial run of tile i continues the last one of tile i - 1: the same non-zero class on both sides of the seam
@@ -191,6 +245,11 @@ struct HostText {
     std::vector<char> all;
 };
 int pack_host_text(Table &T, int slot, int n_seqs, const char *const *seqs, const int64_t *lens, const char *what, HostText &H, std::string &err);
+
+// Every table of a scan zeroed if it is only logically empty, and whatever the other tables' streams still do to them ordered before T's
+// stream, the one the scan runs on.  Entries of `others` may be null or T itself.  `order` has to live until the scan has been queued.
+// (Hidden: it was file-local before it was shared, and the library's list of exported symbols stays what it was.)
+__attribute__((visibility("hidden"))) int settle(Table &T, Table *const *others, int n, Events &order, std::string &err);
 
 // The tiles of n_seqs sequences, in (sequence, position) order, and how many windows they hold.  per_seq, if given, gets each sequence's
 // windows at per_seq[stride * i].  No tile is not an error (the caller has nothing to scan); tiles without a text are.
@@ -255,6 +314,49 @@ int stitch_runs(Table &T, int out_slot, const TileList &L, const TileRuns *d_tou
     if (nruns > nparts) { err = std::string(what) + ": more runs than partial runs"; return -1; }
     runs.resize(nruns);
     if (nruns) HIPCHK(hipMemcpyAsync(runs.data(), d_out, nruns * sizeof(Run), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// The host stage of a run scan on T's stream and workspace slots W + 1 .. W + 7, after the caller has checked its arguments and settled
+// its tables: `counts` gets `stride` words per sequence (the windows, then the kernel's ncount device counters), `runs` the final runs in
+// (sequence, start) order.  launch(grid, st, L, ntiles, d_cnt, d_tout, d_part, cap, d_ctl) is the caller's one kernel launch.  `seconds`
+// is the event time of the scan kernel (both attempts if it was repeated) and of the two stitch kernels.
+template <class Run, class Launch>
+int run_scan(Table &T, int W, const char *what, int n_seqs, const uint8_t *d_text, const int64_t *offsets, int ncount, size_t stride, std::vector<uint64_t> &counts,
+             std::vector<Run> &runs, double &seconds, int &retried, std::string &err, Launch &&launch) {
+    counts.assign((size_t)n_seqs * stride, 0);
+    runs.clear();
+    seconds = 0;
+    retried = 0;
+    TileList L;
+    if (build_tiles(T.k, n_seqs, d_text, offsets, what, counts.data(), stride, L, err)) return -1;
+    const uint64_t ntiles = L.tiles.size();
+    if (ntiles == 0) return 0;
+    hipStream_t st = T.stream;
+    TileRuns *d_tout = (TileRuns *)T.workspace(W + 3, ntiles * sizeof(TileRuns), err);
+    unsigned long long *d_head = (unsigned long long *)T.workspace(W + 4, ntiles * sizeof(unsigned long long), err);
+    const size_t cnt_words = (size_t)n_seqs * ncount + SC_WORDS;
+    unsigned long long *d_cnt = (unsigned long long *)T.workspace(W + 5, cnt_words * sizeof(unsigned long long), err);
+    if (!d_tout || !d_head || !d_cnt || upload_tiles(T, W, n_seqs, offsets, L, err)) return -1;
+    unsigned long long *d_ctl = d_cnt + (size_t)n_seqs * ncount, ctl[SC_WORDS] = {0, 0, 0, 0};
+    const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 256 * 8);
+    Run *d_part = nullptr;
+    auto scan = [&](unsigned long long cap) {
+        d_part = (Run *)T.workspace(W + 6, cap * sizeof(Run), err);
+        if (!d_part) return -1;
+        launch(grid, st, L, ntiles, d_cnt, d_tout, d_part, cap, d_ctl);
+        return 0;
+    };
+    if (run_counted(st, d_cnt, cnt_words, d_ctl, L.windows / 64 + 65536, std::string(what) + ": the number of partial runs changed between two scans", ctl, seconds, retried,
+                    err, scan))
+        return -1;
+    const uint64_t nparts = ctl[SC_CURSOR];
+    std::vector<unsigned long long> cnt((size_t)n_seqs * ncount);
+    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (nparts && stitch_runs(T, W + 7, L, d_tout, d_head, d_part, nparts, d_ctl, what, runs, seconds, err)) return -1;
+    HIPCHK(jk_stream_wait(st));
+    for (int i = 0; i < n_seqs; ++i)
+        for (int c = 0; c < ncount; ++c) counts[stride * (size_t)i + 1 + c] = cnt[(size_t)ncount * i + c];
     return 0;
 }
 

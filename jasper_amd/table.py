@@ -365,6 +365,42 @@ def _thre32(thre):
     return t
 
 
+def _seq_args(seqs):
+    """sequences (str or bytes) as the arguments of a host-text entry point: (n, char *[n], int64 lens[n])"""
+    n = len(seqs)
+    bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
+    return n, (C.c_char_p * max(n, 1))(*bs), (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+
+
+def _text_args(d_text, offsets):
+    """sequences back to back in HBM as the arguments of a device-text entry point: (n, void *, int64 offsets[n + 1]); d_text is a
+    device pointer (int) or an object with .data_ptr()"""
+    n = len(offsets) - 1
+    ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+    return n, C.c_void_p(ptr), (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+
+
+def _counts(num_seqs_fn, counts_fn, res, width):
+    """the `width` counters per sequence of a scan's result -> list of tuples"""
+    out = []
+    c = (C.c_uint64 * width)()
+    for i in range(num_seqs_fn(res)):
+        check(counts_fn(res, i, c))
+        out.append(tuple(int(v) for v in c))
+    return out
+
+
+def _records(records_fn, res, ctype, dtype):
+    """the record array of a scan's result -> numpy structured array (a copy: the result may be freed)"""
+    import numpy as np
+    rp = C.POINTER(ctype)()
+    rn = C.c_uint64(0)
+    check(records_fn(res, C.byref(rp), C.byref(rn)))
+    if rn.value:
+        return np.frombuffer(C.string_at(rp, rn.value * C.sizeof(ctype)), dtype=dtype).copy()
+    return np.zeros(0, dtype=dtype)
+
+
 class KmerTable:
     def __init__(self, k, min_slots=1 << 20, device=0):
         self._L = _lib.lib()
@@ -696,11 +732,8 @@ class KmerTable:
 
     # ---- one batch through the polisher -------------------------------------------------------------
     def polish_batch(self, seqs, solid_thre, passes, fix=True):
-        n = len(seqs)
         want_str = any(isinstance(s, str) for s in seqs)       # bytes in -> bytes out (no 1-byte-per-char round trip)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = self._L.jasper_polish_batch(self._h, n, cs, lens, int(solid_thre), int(passes), 1 if fix else 0, C.byref(res))
         return self._wrap_result(rc, res, n, want_str)
@@ -709,20 +742,15 @@ class KmerTable:
         """chunk records already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the chunk
         texts back to back, offsets the n+1 chunk boundaries.  The polished text stays in HBM (PolishResult.seq_device)
         and is copied to the host on first use of seq_view / seqs."""
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_polish_batch_device(self._h, n, C.c_void_p(ptr), offs, int(solid_thre), int(passes), 1 if fix else 0, C.byref(res))
+        rc = self._L.jasper_polish_batch_device(self._h, n, ptr, offs, int(solid_thre), int(passes), 1 if fix else 0, C.byref(res))
         return self._wrap_result(rc, res, n, False)
 
     # ---- dense k-mer report (an extension: no counterpart in the reference) ------------------------------
     def kmer_report(self, seqs, thre):
         """per-sequence counters and runs of unreliable k-mers (count < thre) of `seqs` (str or bytes) -> KmerReport"""
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = self._L.jasper_kmer_report(self._h, n, cs, lens, int(thre), C.byref(res))
         return self._wrap_report(rc, res)
@@ -730,11 +758,9 @@ class KmerTable:
     def kmer_report_device(self, d_text, offsets, thre):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_kmer_report_device(self._h, n, C.c_void_p(ptr), offs, int(thre), C.byref(res))
+        rc = self._L.jasper_kmer_report_device(self._h, n, ptr, offs, int(thre), C.byref(res))
         return self._wrap_report(rc, res)
 
     @staticmethod
@@ -765,10 +791,7 @@ class KmerTable:
         per-sequence counters and the runs of windows whose read count supports more (excess) or fewer (deficit) copies than the
         assembly holds, `peak` = the read count of a single-copy k-mer -> CopyReport; neither table is modified"""
         ah = self._assembly_handle(assembly_table, "copy_report")
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = self._L.jasper_copy_report(self._h, ah, n, cs, lens, int(thre), _peak32(peak), C.byref(res))
         return self._wrap_copyrep(rc, res)
@@ -777,29 +800,16 @@ class KmerTable:
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
         ah = self._assembly_handle(assembly_table, "copy_report_device")
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_copy_report_device(self._h, ah, n, C.c_void_p(ptr), offs, int(thre), _peak32(peak), C.byref(res))
+        rc = self._L.jasper_copy_report_device(self._h, ah, n, ptr, offs, int(thre), _peak32(peak), C.byref(res))
         return self._wrap_copyrep(rc, res)
 
     def _wrap_copyrep(self, rc, res):
         try:
             check(rc)
-            import numpy as np
-            counts = []
-            c6 = (C.c_uint64 * 6)()
-            for i in range(self._L.jasper_copyrep_num_seqs(res)):
-                check(self._L.jasper_copyrep_counts(res, i, c6))
-                counts.append(tuple(int(v) for v in c6))
-            rp = C.POINTER(_lib.CopyRun)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_copyrep_runs(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.CopyRun)), dtype=COPYRUN_DTYPE).copy()
-            else:
-                runs = np.zeros(0, dtype=COPYRUN_DTYPE)
+            counts = _counts(self._L.jasper_copyrep_num_seqs, self._L.jasper_copyrep_counts, res, 6)
+            runs = _records(self._L.jasper_copyrep_runs, res, _lib.CopyRun, COPYRUN_DTYPE)
             return CopyReport(counts, runs, self._L.jasper_copyrep_seconds(res), bool(self._L.jasper_copyrep_retried(res)))
         finally:
             if res:
@@ -824,10 +834,7 @@ class KmerTable:
         """the hap-mer scan without a child table: every solid k-mer of one parent that the other lacks is a marker"""
         mh, ph = KmerTable._parent_handle(mat, "maternal", "hapmer_scan"), KmerTable._parent_handle(pat, "paternal", "hapmer_scan")
         ch = KmerTable._parent_handle(_child, "child", "hapmer_scan") if _child is not None else None
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = mat._L.jasper_hapmer_scan(mh, ph, ch, n, cs, lens, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child), C.byref(res))
         return mat._wrap_hapscan(rc, res)
@@ -836,30 +843,17 @@ class KmerTable:
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
         mh, ph = self._parent_handle(mat, "maternal", "hapmer_scan_device"), self._parent_handle(pat, "paternal", "hapmer_scan_device")
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_hapmer_scan_device(mh, ph, self._h if child else None, n, C.c_void_p(ptr), offs, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child),
+        rc = self._L.jasper_hapmer_scan_device(mh, ph, self._h if child else None, n, ptr, offs, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child),
                                                C.byref(res))
         return self._wrap_hapscan(rc, res)
 
     def _wrap_hapscan(self, rc, res):
         try:
             check(rc)
-            import numpy as np
-            counts = []
-            c4 = (C.c_uint64 * 4)()
-            for i in range(self._L.jasper_hapscan_num_seqs(res)):
-                check(self._L.jasper_hapscan_counts(res, i, c4))
-                counts.append(tuple(int(v) for v in c4))
-            rp = C.POINTER(_lib.HapRun)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_hapscan_runs(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.HapRun)), dtype=HAPRUN_DTYPE).copy()
-            else:
-                runs = np.zeros(0, dtype=HAPRUN_DTYPE)
+            counts = _counts(self._L.jasper_hapscan_num_seqs, self._L.jasper_hapscan_counts, res, 4)
+            runs = _records(self._L.jasper_hapscan_runs, res, _lib.HapRun, HAPRUN_DTYPE)
             return HapmerScan(counts, runs, self._L.jasper_hapscan_seconds(res), bool(self._L.jasper_hapscan_retried(res)))
         finally:
             if res:
@@ -887,10 +881,7 @@ class KmerTable:
     def variant_scan(self, seqs, thre):
         """the positions of the sequences where the reads hold a solid single-base alternative (count of all k covering windows
         >= thre >= 1) -> VariantScan; the table is not modified"""
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = self._L.jasper_variant_scan(self._h, n, cs, lens, int(thre), C.byref(res))
         return self._wrap_varscan(rc, res)
@@ -898,11 +889,9 @@ class KmerTable:
     def variant_scan_device(self, d_text, offsets, thre):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_variant_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), C.byref(res))
+        rc = self._L.jasper_variant_scan_device(self._h, n, ptr, offs, int(thre), C.byref(res))
         return self._wrap_varscan(rc, res)
 
     # ---- indel scan (an extension: the length-changing half of the variant scan, from the same dense scan) --
@@ -911,10 +900,7 @@ class KmerTable:
         the substitution sites of variant_scan with them (thre >= 1, k >= 2) -> IndelScan; with `mixed` also the insertions of mixed
         bases (IndelScan.mixed); with `clusters` = N (1..64; 0: off) also the clusters of heterozygous differences less than k apart,
         as replacements of up to N bytes by up to N bases (IndelScan.clusters); the table is not modified"""
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         if clusters:
             rc = self._L.jasper_indel_scan_clusters(self._h, n, cs, lens, int(thre), int(max_len), int(bool(mixed)), int(clusters), C.byref(res))
@@ -926,15 +912,13 @@ class KmerTable:
     def indel_scan_device(self, d_text, offsets, thre, max_len=4, mixed=False, clusters=0):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
         if clusters:
-            rc = self._L.jasper_indel_scan_clusters_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), int(bool(mixed)), int(clusters), C.byref(res))
+            rc = self._L.jasper_indel_scan_clusters_device(self._h, n, ptr, offs, int(thre), int(max_len), int(bool(mixed)), int(clusters), C.byref(res))
             return self._wrap_indelscan(rc, res, mixed, True)
         fn = self._L.jasper_indel_scan_mixed_device if mixed else self._L.jasper_indel_scan_device
-        rc = fn(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
+        rc = fn(self._h, n, ptr, offs, int(thre), int(max_len), C.byref(res))
         return self._wrap_indelscan(rc, res, mixed)
 
     # ---- compound scan (an extension: what the reads hold in place of differences that hide each other) ------
@@ -942,10 +926,7 @@ class KmerTable:
         """the replacements of up to max_len (1..64) bases that the reads hold for the runs of unreliable k-mers that two or more
         differences less than k apart leave, and the kmer_report of the same input (thre >= 1, k >= 2) -> CompoundScan; the table is
         not modified"""
-        n = len(seqs)
-        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in seqs]
-        cs = (C.c_char_p * max(n, 1))(*bs)
-        lens = (C.c_int64 * max(n, 1))(*[len(b) for b in bs])
+        n, cs, lens = _seq_args(seqs)
         res = C.c_void_p()
         rc = self._L.jasper_compound_scan(self._h, n, cs, lens, int(thre), int(max_len), C.byref(res))
         return self._wrap_compscan(rc, res)
@@ -953,11 +934,9 @@ class KmerTable:
     def compound_scan_device(self, d_text, offsets, thre, max_len=64):
         """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
         sequences back to back, offsets the n+1 boundaries"""
-        n = len(offsets) - 1
-        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
-        offs = (C.c_int64 * (n + 1))(*[int(o) for o in offsets])
+        n, ptr, offs = _text_args(d_text, offsets)
         res = C.c_void_p()
-        rc = self._L.jasper_compound_scan_device(self._h, n, C.c_void_p(ptr), offs, int(thre), int(max_len), C.byref(res))
+        rc = self._L.jasper_compound_scan_device(self._h, n, ptr, offs, int(thre), int(max_len), C.byref(res))
         return self._wrap_compscan(rc, res)
 
     @staticmethod
@@ -968,19 +947,8 @@ class KmerTable:
     def _wrap_compscan(self, rc, res):
         try:
             check(rc)
-            import numpy as np
-            counts = []
-            c5 = (C.c_uint64 * 5)()
-            for i in range(self._L.jasper_compscan_num_seqs(res)):
-                check(self._L.jasper_compscan_counts(res, i, c5))
-                counts.append(tuple(int(v) for v in c5))
-            rp = C.POINTER(_lib.Compound)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_compscan_records(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Compound)), dtype=COMPOUND_DTYPE).copy()
-            else:
-                recs = np.zeros(0, dtype=COMPOUND_DTYPE)
+            counts = _counts(self._L.jasper_compscan_num_seqs, self._L.jasper_compscan_counts, res, 5)
+            recs = _records(self._L.jasper_compscan_records, res, _lib.Compound, COMPOUND_DTYPE)
             nl = C.c_uint64(0)
             check(self._L.jasper_compscan_lookups(res, C.byref(nl)))
             search, total = C.c_double(0), C.c_double(0)
@@ -992,37 +960,15 @@ class KmerTable:
                 self._L.jasper_compscan_free(res)
 
     def _read_mixed(self, res):
-        import numpy as np
-        counts = []
-        c3 = (C.c_uint64 * 3)()
-        for i in range(self._L.jasper_indelscan_num_seqs(res)):
-            check(self._L.jasper_indelscan_mixed_counts(res, i, c3))
-            counts.append(tuple(int(v) for v in c3))
-        rp = C.POINTER(_lib.MixedIns)()
-        rn = C.c_uint64(0)
-        check(self._L.jasper_indelscan_mixed_records(res, C.byref(rp), C.byref(rn)))
-        if rn.value:
-            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.MixedIns)), dtype=MIXED_DTYPE).copy()
-        else:
-            recs = np.zeros(0, dtype=MIXED_DTYPE)
+        counts = _counts(self._L.jasper_indelscan_num_seqs, self._L.jasper_indelscan_mixed_counts, res, 3)
+        recs = _records(self._L.jasper_indelscan_mixed_records, res, _lib.MixedIns, MIXED_DTYPE)
         nl = C.c_uint64(0)
         check(self._L.jasper_indelscan_mixed_lookups(res, C.byref(nl)))
         return MixedInsertions(counts, recs, self._L.jasper_indelscan_mixed_seconds(res), int(nl.value), bool(self._L.jasper_indelscan_mixed_retried(res)))
 
     def _read_clusters(self, res):
-        import numpy as np
-        counts = []
-        c4 = (C.c_uint64 * 4)()
-        for i in range(self._L.jasper_indelscan_num_seqs(res)):
-            check(self._L.jasper_indelscan_cluster_counts(res, i, c4))
-            counts.append(tuple(int(v) for v in c4))
-        rp = C.POINTER(_lib.HetCluster)()
-        rn = C.c_uint64(0)
-        check(self._L.jasper_indelscan_cluster_records(res, C.byref(rp), C.byref(rn)))
-        if rn.value:
-            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.HetCluster)), dtype=HET_CLUSTER_DTYPE).copy()
-        else:
-            recs = np.zeros(0, dtype=HET_CLUSTER_DTYPE)
+        counts = _counts(self._L.jasper_indelscan_num_seqs, self._L.jasper_indelscan_cluster_counts, res, 4)
+        recs = _records(self._L.jasper_indelscan_cluster_records, res, _lib.HetCluster, HET_CLUSTER_DTYPE)
         nl = C.c_uint64(0)
         check(self._L.jasper_indelscan_cluster_lookups(res, C.byref(nl)))
         return HetClusters(counts, recs, self._L.jasper_indelscan_cluster_seconds(res), int(nl.value), bool(self._L.jasper_indelscan_cluster_retried(res)))
@@ -1030,19 +976,8 @@ class KmerTable:
     def _wrap_indelscan(self, rc, res, mixed=False, clusters=False):
         try:
             check(rc)
-            import numpy as np
-            counts = []
-            c4 = (C.c_uint64 * 4)()
-            for i in range(self._L.jasper_indelscan_num_seqs(res)):
-                check(self._L.jasper_indelscan_counts(res, i, c4))
-                counts.append(tuple(int(v) for v in c4))
-            rp = C.POINTER(_lib.Indel)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_indelscan_records(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Indel)), dtype=INDEL_DTYPE).copy()
-            else:
-                recs = np.zeros(0, dtype=INDEL_DTYPE)
+            counts = _counts(self._L.jasper_indelscan_num_seqs, self._L.jasper_indelscan_counts, res, 4)
+            recs = _records(self._L.jasper_indelscan_records, res, _lib.Indel, INDEL_DTYPE)
             nl = C.c_uint64(0)
             check(self._L.jasper_indelscan_lookups(res, C.byref(nl)))
             var = self._read_varscan(C.c_void_p(self._L.jasper_indelscan_variants(res)))      # (owned by res: read, not freed)
@@ -1061,19 +996,8 @@ class KmerTable:
                 self._L.jasper_varscan_free(res)
 
     def _read_varscan(self, res):
-        import numpy as np
-        counts = []
-        c3 = (C.c_uint64 * 3)()
-        for i in range(self._L.jasper_varscan_num_seqs(res)):
-            check(self._L.jasper_varscan_counts(res, i, c3))
-            counts.append(tuple(int(v) for v in c3))
-        rp = C.POINTER(_lib.Variant)()
-        rn = C.c_uint64(0)
-        check(self._L.jasper_varscan_records(res, C.byref(rp), C.byref(rn)))
-        if rn.value:
-            recs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.Variant)), dtype=VARIANT_DTYPE).copy()
-        else:
-            recs = np.zeros(0, dtype=VARIANT_DTYPE)
+        counts = _counts(self._L.jasper_varscan_num_seqs, self._L.jasper_varscan_counts, res, 3)
+        recs = _records(self._L.jasper_varscan_records, res, _lib.Variant, VARIANT_DTYPE)
         nc = C.c_uint64(0)
         check(self._L.jasper_varscan_candidates(res, C.byref(nc)))
         return VariantScan(counts, recs, int(nc.value), self._L.jasper_varscan_seconds(res), bool(self._L.jasper_varscan_retried(res)))
@@ -1087,38 +1011,20 @@ class KmerTable:
                 self._L.jasper_report_free(res)
 
     def _read_report(self, res):
-        import numpy as np
-        counts = []
-        c4 = (C.c_uint64 * 4)()
-        for i in range(self._L.jasper_report_num_seqs(res)):
-            check(self._L.jasper_report_counts(res, i, c4))
-            counts.append(tuple(int(v) for v in c4))
-        rp = C.POINTER(_lib.KmerRun)()
-        rn = C.c_uint64(0)
-        check(self._L.jasper_report_runs(res, C.byref(rp), C.byref(rn)))
-        if rn.value:
-            runs = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(_lib.KmerRun)), dtype=KMERRUN_DTYPE).copy()
-        else:
-            runs = np.zeros(0, dtype=KMERRUN_DTYPE)
+        counts = _counts(self._L.jasper_report_num_seqs, self._L.jasper_report_counts, res, 4)
+        runs = _records(self._L.jasper_report_runs, res, _lib.KmerRun, KMERRUN_DTYPE)
         return KmerReport(counts, runs, self._L.jasper_report_seconds(res), bool(self._L.jasper_report_retried(res)))
 
     def _wrap_result(self, rc, res, n, want_str):
         try:
             check(rc)
-            import numpy as np
             aux = []
             for i in range(n):
                 ap = C.c_void_p()
                 an = C.c_uint64(0)
                 check(self._L.jasper_result_aux(res, i, C.byref(ap), C.byref(an)))
                 aux.append(C.string_at(ap, an.value) if an.value else b"")
-            rp = C.POINTER(FixRec)()
-            rn = C.c_uint64(0)
-            check(self._L.jasper_result_records(res, C.byref(rp), C.byref(rn)))
-            if rn.value:
-                raw = np.frombuffer(C.string_at(rp, rn.value * C.sizeof(FixRec)), dtype=FIXREC_DTYPE).copy()
-            else:
-                raw = np.zeros(0, dtype=FIXREC_DTYPE)
+            raw = _records(self._L.jasper_result_records, res, FixRec, FIXREC_DTYPE)
             qv = (C.c_int64 * 4)()
             check(self._L.jasper_result_qv(res, qv))
             nl = C.c_uint64(0)
