@@ -689,6 +689,82 @@ int jasper_compscan_retried(const jasper_compscan *r);
 int jasper_compound_front(void);
 void jasper_compscan_free(jasper_compscan *r);
 
+/* Repair: the error records of the scans above APPLIED to the sequences on the GPU, in rounds.
+ *
+ * What it replaces: nothing -- an EXTENSION, and the step after the scans.  An error record is a place where the sequence's own k-mers are
+ * unreliable and the reads hold exactly one solid alternative; all of them have one shape, "the reads hold the string y where the sequence
+ * holds the R bytes from p on".  The reference repairs inside its walk and never looks again; this call acts on what the walk has left.
+ * Given the table's k >= 2, thre >= 1, indel_max_len in 1..16, compound_max_len in 1..64 and rounds = N in 1..8 (anything else is JASPER_ERR
+ * with a message that names the argument, even with nothing to scan):
+ *   edit           (seq, pos, rlen, y, alt_min, ref_min, source) replaces s[pos .. pos+rlen) by y, 0..64 bases, upper case; q = pos + rlen.
+ *                  Only records of kind error become edits (het records are never applied: both alleles are in the reads):
+ *                      source 1 sub       variant (p, alt)      pos p, rlen 1, y = alt
+ *                      source 2 ins       ins(p, x, L)          pos p, rlen 0, y = x repeated L times
+ *                      source 3 del       del(p, L)             pos p, rlen L, y empty
+ *                      source 4 mixed     mixed ins(p, y)       pos p, rlen 0, y
+ *                      source 5 compound  (a, R, y)             pos a, rlen R, y
+ *                  Two records that give the same (seq, pos, rlen, y) are one edit (the lower source stays).
+ *   one round      jasper_indel_scan_mixed (it holds the variant scan) and jasper_compound_scan (it holds the report) on the current
+ *                  text; their records made edits; then
+ *                      ambiguous  edits that share (seq, pos, rlen, |y|, alt_min) and differ in y are all set aside and counted
+ *                      order      the rest by (rlen + |y| ascending, alt_min descending, seq, pos, rlen, y)
+ *                      accepted   in that order, an edit unless it CONFLICTS with one accepted before it; a conflict is counted and left
+ *                                 to the next round's scans.  Two edits a, b of one sequence with (pos_a, q_a) <= (pos_b, q_b) conflict
+ *                                 iff pos_b - q_a < k - 1.  A record's evidence is the windows of F + y + G, F and G the sequence's k-1
+ *                                 bytes on either side: with at least k-1 bytes between them neither edit lies in the other's flanks, so
+ *                                 every window that overlaps an applied y or spans an applied deletion is one a scan has found solid.
+ *                  The accepted edits are applied together.  A round that accepts nothing ends the loop.
+ *   the loop       at most N rounds.  `before` is the report of round 1's text; `after` the report of the round that accepted nothing,
+ *                  or, if round N still applied edits, one more jasper_kmer_report of the final text.
+ *   per round      records (edits after duplicates were dropped = accepted + conflicts + ambiguous), accepted, conflicts, ambiguous,
+ *                  unreliable_before, unreliable_after: the unreliable windows of all sequences before and after the round's edits.
+ *                  unreliable_after = unreliable_before - the unreliable windows w of the old text with pos-k+1 <= w < pos+rlen, summed
+ *                  over the accepted edits; that is at least 1 per edit.
+ * Bytes that are not replaced stay as they stand: lower case, N, anything.  The table is not modified.
+ *
+ * Limits: het records are never applied; runs longer than compound_max_len and complex sites stay; ties (ambiguous edits) are skipped.
+ *
+ * On the device the text is uploaded once and downloaded once: the scans read it in HBM, per round only records come down and edits
+ * go up, and one kernel writes the new text into a second buffer -- a gather-copy, one workgroup per tile of jasper_repair_tile_bytes() OUTPUT
+ * bytes, 16 bytes per lane, the edits that touch a tile staged through LDS.
+ *   jasper_repair, _device          as jasper_kmer_report / _device, with the lengths and rounds; the input text is not written
+ *   jasper_apply_edits, _device     the kernel alone on a caller's list: ordered by (seq, pos), every edit inside its sequence, |y| <= 64,
+ *                                   no bits above 2|y|, and two edits of one sequence at least one byte apart (pos_b - q_a >= 1); anything
+ *                                   else is JASPER_ERR and nothing is launched.  source, round, ref_min and alt_min are not read.
+ *   jasper_repair_tile_bytes        output bytes per workgroup of the kernel (tests aim at the seams)
+ *   jasper_repaired_num_seqs, _seq  the final sequences (owned by the result)
+ *   jasper_repaired_edits           every applied edit, ordered by (round, seq, pos); pos counts in the text that round read (round 1: the
+ *                                   input)
+ *   jasper_repaired_rounds          one entry per round that scanned (the last accepted nothing, unless the loop ran out of rounds)
+ *   jasper_repaired_before, _after  the two reports, owned by the result (do not free them)
+ *   jasper_repaired_seconds         device time (HIP events) of the apply kernel alone (*apply) and of it and all scans (*total)
+ * For a result of jasper_apply_edits there are no edits, no rounds and two empty reports. */
+typedef struct jasper_repaired jasper_repaired;
+typedef struct jasper_edit {
+    int64_t pos;
+    uint32_t seq, ref_min, alt_min, ref_len;
+    uint64_t bases[2]; /* base i of y in bits 2i..2i+1 of bases[i / 32], A C G T = 0 1 2 3, 0 above 2*len */
+    uint16_t len;
+    uint8_t source /* 1 sub, 2 ins, 3 del, 4 mixed, 5 compound */, round /* 1 ..; 0 in a caller's list */, pad[4] /* 0 */;
+} jasper_edit; /* 48 B, laid out like jasper_compound */
+typedef struct jasper_repair_round { uint64_t records, accepted, conflicts, ambiguous, unreliable_before, unreliable_after; } jasper_repair_round; /* 48 B */
+int jasper_repair(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int indel_max_len, int compound_max_len, int rounds,
+                  jasper_repaired **out);
+int jasper_repair_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int indel_max_len, int compound_max_len, int rounds,
+                         jasper_repaired **out);
+int jasper_apply_edits(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const jasper_edit *edits, uint64_t n_edits, jasper_repaired **out);
+int jasper_apply_edits_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, const jasper_edit *edits, uint64_t n_edits,
+                              jasper_repaired **out);
+int jasper_repair_tile_bytes(void);
+int jasper_repaired_num_seqs(const jasper_repaired *r);
+int jasper_repaired_seq(const jasper_repaired *r, int seq, const char **text, int64_t *len);
+int jasper_repaired_edits(const jasper_repaired *r, const jasper_edit **edits, uint64_t *n);
+int jasper_repaired_rounds(const jasper_repaired *r, const jasper_repair_round **rounds, uint64_t *n);
+const jasper_report *jasper_repaired_before(const jasper_repaired *r);
+const jasper_report *jasper_repaired_after(const jasper_repaired *r);
+int jasper_repaired_seconds(const jasper_repaired *r, double *apply, double *total);
+void jasper_repaired_free(jasper_repaired *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

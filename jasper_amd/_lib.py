@@ -84,6 +84,22 @@ class HetCluster(C.Structure):
 
 assert C.sizeof(HetCluster) == 48
 
+
+class Edit(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("alt_min", C.c_uint32), ("ref_len", C.c_uint32), ("bases", C.c_uint64 * 2),
+                ("len", C.c_uint16), ("source", C.c_uint8), ("round", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
+assert C.sizeof(Edit) == 48
+
+
+class RepairRound(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("accepted", C.c_uint64), ("conflicts", C.c_uint64), ("ambiguous", C.c_uint64), ("unreliable_before", C.c_uint64),
+                ("unreliable_after", C.c_uint64)]
+
+
+assert C.sizeof(RepairRound) == 48
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -231,6 +247,19 @@ SYMBOLS = {
     "jasper_compscan_retried": (C.c_int, [_P]),
     "jasper_compound_front": (C.c_int, []),
     "jasper_compscan_free": (None, [_P]),
+    "jasper_repair": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "jasper_repair_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "jasper_apply_edits": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _P, C.c_uint64, C.POINTER(_P)]),
+    "jasper_apply_edits_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), _P, C.c_uint64, C.POINTER(_P)]),
+    "jasper_repair_tile_bytes": (C.c_int, []),
+    "jasper_repaired_num_seqs": (C.c_int, [_P]),
+    "jasper_repaired_seq": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "jasper_repaired_edits": (C.c_int, [_P, C.POINTER(C.POINTER(Edit)), C.POINTER(C.c_uint64)]),
+    "jasper_repaired_rounds": (C.c_int, [_P, C.POINTER(C.POINTER(RepairRound)), C.POINTER(C.c_uint64)]),
+    "jasper_repaired_before": (_P, [_P]),
+    "jasper_repaired_after": (_P, [_P]),
+    "jasper_repaired_seconds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "jasper_repaired_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -4,6 +4,7 @@ polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
                             [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]
+                            [--repair [--repair-rounds N]]
                             [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
                              [--phase-short-range D] [--phase-max-switches S]]
 
@@ -114,6 +115,8 @@ class Options:
         self.het_cluster_max_len = None   # --het-cluster-max-len: longest replacement the het-cluster search lists (default 64, at most 64)
         self.compound = False
         self.compound_max_len = None # --compound-max-len: longest replacement the compound scan searches (default 64, at most 64)
+        self.repair = False          # --repair: apply the scans' error records to the polished contigs, in rounds (_repair)
+        self.repair_rounds = None    # --repair-rounds: at most this many rounds of scan, select and apply (default 3, at most 8)
         self.hapmers = False         # --hapmers: trio hap-mer markers, phase blocks and switch errors (_hapmers)
         self.mat = self.mat_jf = self.pat = self.pat_jf = None       # the parents' read files or Jellyfish databases
         self.mat_threshold = self.pat_threshold = None               # default: from each parent's histogram
@@ -190,6 +193,10 @@ def parse_args(argv):
             o.compound = True
         elif key == "--compound-max-len":
             o.compound_max_len = nxt; i += 1
+        elif key == "--repair":                                        # extension: the scans' error records applied to the polished contigs (_repair)
+            o.repair = True
+        elif key == "--repair-rounds":
+            o.repair_rounds = nxt; i += 1
         elif key == "--hapmers":                                       # extension: parental markers, phase blocks and switch errors (_hapmers)
             o.hapmers = True
         elif key in HAPMER_VALUE_FLAGS:
@@ -1548,6 +1555,55 @@ def _compound(o, table, scans):
                          (cs0.search_seconds, cs1.search_seconds, cs0.lookups, cs1.lookups))
 
 
+REPAIR_ROUNDS_DEFAULT = 3
+
+
+def repair_flags(repair, rounds):
+    """--repair and --repair-rounds as given (a string or None) -> the rounds to run, 0 without --repair; exits on --repair-rounds
+    without --repair and on anything but an integer in 1..8"""
+    if rounds is not None and not repair:
+        error_exit("--repair-rounds needs --repair")
+    if not repair:
+        return 0
+    if rounds is None:
+        return REPAIR_ROUNDS_DEFAULT
+    if not re.match(r"^[0-9]+$", str(rounds)) or not 1 <= int(rounds) <= 8:
+        error_exit("--repair-rounds takes an integer from 1 to 8; it is %s" % rounds)
+    return int(rounds)
+
+
+def run_repair(table, contigs, thre, indel_max_len, compound_max_len, rounds):
+    """the repair stage on whole contigs [(name token, sequence)] -> (names, lengths, Repair); exits on a threshold of 0, for which no
+    k-mer is unreliable and every string solid"""
+    from . import report
+    if thre < 1:
+        error_exit("--repair needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
+    return ([report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs],
+            table.repair([s for _, s in contigs], thre, indel_max_len, compound_max_len, rounds))
+
+
+def _repair(o, table):
+    """--repair (an extension, no counterpart in src/jasper.sh): the error records that the variant, indel and compound scans find on
+    the polished contigs applied to them on the GPU, in rounds, through the read table while it is still in HBM, into
+    `$QUERY_FN.repaired.fasta`, `$QUERY_FN.repairs.tsv` and `$QUERY_FN.repair.tsv` (jasper_amd/repair.py).  The polished FASTA is read,
+    not written.  The threshold is the polisher's (threshold.txt)."""
+    from . import repair
+    qfn, k = o.query_fn, table.k
+    rounds = repair_flags(o.repair, o.repair_rounds)
+    thresh = int(open("threshold.txt").read().split()[0])
+    asm1 = read_assembly(qfn + ".polished.fasta")
+    names, len1, rp = run_repair(table, asm1, thresh, indel_flags(o.indel_max_len), compound_flags(o.compound_max_len), rounds)
+    edits = rp.edit_tuples()
+    with open(qfn + ".polished.fasta", newline="") as f:
+        polished_text = f.read()
+    repair.write_atomic(qfn + ".repaired.fasta", repair.fasta_text(polished_text, rp.seqs))
+    repair.write_atomic(qfn + ".repairs.tsv", repair.repairs_tsv_text(names, repair.round_texts([s for _, s in asm1], edits), edits))
+    repair.write_atomic(qfn + ".repair.tsv", repair.repair_tsv_text(k, names, len1, [len(s) for s in rp.seqs], edits, rp.before.counts, rp.after.counts))
+    log(repair.log_text(k, rp.rounds, rp.before.counts, rp.after.counts))
+    if _timing_on():
+        sys.stderr.write("[repair] device seconds: stage %.6f apply kernel %.6f; rounds %d, edits %d\n" % (rp.seconds, rp.apply_seconds, len(rp.rounds), len(edits)))
+
+
 def _init_multi(o):
     """one process per GPU under `python -m torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment):
     returns (rank, world, torch device) after joining the process group (RCCL; JASPER_AMD_DIST_BACKEND=gloo and
@@ -1587,6 +1643,9 @@ def run(argv):
     if o.het_clusters:
         het_cluster_flags(o.het_cluster_max_len, True, o.indels)
     if o.compound:
+        compound_flags(o.compound_max_len)
+    if repair_flags(o.repair, o.repair_rounds):
+        indel_flags(o.indel_max_len)                # (--repair honours the two scans' lengths, with or without --indels and --compound)
         compound_flags(o.compound_max_len)
     hap = hapmer_flags(o, int(o.kmer) if re.match(r"^[0-9]+$", str(o.kmer)) else 0, o.jf_db)
     if not _nonempty(o.query):
@@ -1698,6 +1757,11 @@ def run(argv):
         # (unmeasured over RCCL, like everything multi-GPU here)
         ranks.together((lambda: _hapmers(o, table, hap)) if ranks.is0 else (lambda: None), "Writing the hap-mer scan failed")
         _timing("hap-mer scan")
+    if o.repair:
+        # as for --report: rank 0 alone, through every owner's shard of the attached table (unmeasured over RCCL, like everything
+        # multi-GPU here); after every other extension, so that their files are what they are without it
+        ranks.together((lambda: _repair(o, table)) if ranks.is0 else (lambda: None), "The repair stage failed")
+        _timing("repair")
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)

@@ -13,6 +13,7 @@
 #include "variants.hpp"
 #include "indels.hpp"
 #include "compound.hpp"
+#include "repair.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -68,6 +69,10 @@ struct jasper_report {
 struct jasper_compscan {
     CompoundOut r;
     jasper_report rep;                   // the report of the same call, written by the scan itself: what jasper_compscan_report hands out
+};
+struct jasper_repaired {
+    RepairOut r;
+    jasper_report before, after;         // r.before / r.after moved here: what jasper_repaired_before / _after hand out
 };
 static_assert(sizeof(jasper_kmer_run) == sizeof(KmerRun) && offsetof(jasper_kmer_run, n_absent) == offsetof(KmerRun, n_absent) &&
                   offsetof(jasper_kmer_run, seq) == offsetof(KmerRun, seq) && offsetof(jasper_kmer_run, min_count) == offsetof(KmerRun, min_count),
@@ -131,6 +136,16 @@ static int word_out(const uint64_t *v, uint64_t *n) {
     if (!v || !n) { g_err = "bad argument"; return JASPER_ERR; }
     *n = *v;
     return JASPER_OK;
+}
+
+// A repair call: scan_call, and the two reports moved to where their accessors hand them out.
+template <class Fill> static int repair_call(bool args_ok, jasper_table *t, int n_seqs, jasper_repaired **out, Fill &&fill) {
+    return scan_call(args_ok, t, n_seqs, out, [&](jasper_repaired &r) {
+        const int rc = fill(r.r);
+        r.before.r = std::move(r.r.before);
+        r.after.r = std::move(r.r.after);
+        return rc;
+    });
 }
 
 extern "C" {
@@ -967,5 +982,50 @@ int jasper_compscan_seconds(const jasper_compscan *r, double *search, double *to
 int jasper_compscan_retried(const jasper_compscan *r) { return r ? r->r.retried : 0; }
 int jasper_compound_front(void) { return COMPOUND_FRONT; }
 void jasper_compscan_free(jasper_compscan *r) { delete r; }
+
+// ---- repair (repair.hip) ----
+static_assert(offsetof(jasper_edit, ref_len) == offsetof(Edit, ref_len) && offsetof(jasper_edit, bases) == offsetof(Edit, bases) && offsetof(jasper_edit, len) == offsetof(Edit, len) &&
+                  offsetof(jasper_edit, source) == offsetof(Edit, source) && offsetof(jasper_edit, round) == offsetof(Edit, round),
+              "jasper_edit is Edit");
+static_assert(sizeof(jasper_edit) == 48 && sizeof(jasper_repair_round) == sizeof(RepairRound), "public and host record layouts must match");
+int jasper_repair(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int indel_max_len, int compound_max_len, int rounds,
+                  jasper_repaired **out) {
+    return repair_call(host_args(n_seqs, seqs, lens), t, n_seqs, out,
+                       [&](RepairOut &r) { return repair_host(t->t, n_seqs, seqs, lens, thre, indel_max_len, compound_max_len, rounds, r, g_err); });
+}
+int jasper_repair_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int indel_max_len, int compound_max_len, int rounds,
+                         jasper_repaired **out) {
+    return repair_call(offsets, t, n_seqs, out,
+                       [&](RepairOut &r) { return repair_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, indel_max_len, compound_max_len, rounds, r, g_err); });
+}
+int jasper_apply_edits(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, const jasper_edit *edits, uint64_t n_edits, jasper_repaired **out) {
+    return repair_call(host_args(n_seqs, seqs, lens), t, n_seqs, out,
+                       [&](RepairOut &r) { return apply_edits_host(t->t, n_seqs, seqs, lens, reinterpret_cast<const Edit *>(edits), n_edits, r, g_err); });
+}
+int jasper_apply_edits_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, const jasper_edit *edits, uint64_t n_edits,
+                              jasper_repaired **out) {
+    return repair_call(offsets, t, n_seqs, out, [&](RepairOut &r) {
+        return apply_edits_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, reinterpret_cast<const Edit *>(edits), n_edits, r, g_err);
+    });
+}
+int jasper_repair_tile_bytes(void) { return REPAIR_TILE; }
+int jasper_repaired_num_seqs(const jasper_repaired *r) { return r && !r->r.offsets.empty() ? (int)(r->r.offsets.size() - 1) : 0; }
+int jasper_repaired_seq(const jasper_repaired *r, int seq, const char **text, int64_t *len) {
+    if (!r || !text || !len || seq < 0 || (size_t)seq + 1 >= r->r.offsets.size()) { g_err = "bad argument"; return JASPER_ERR; }
+    *text = r->r.text.data() + r->r.offsets[seq];
+    *len = r->r.offsets[seq + 1] - r->r.offsets[seq];
+    return JASPER_OK;
+}
+int jasper_repaired_edits(const jasper_repaired *r, const jasper_edit **edits, uint64_t *n) { return records_out(r ? &r->r.edits : nullptr, edits, n); }
+int jasper_repaired_rounds(const jasper_repaired *r, const jasper_repair_round **rounds, uint64_t *n) { return records_out(r ? &r->r.rounds : nullptr, rounds, n); }
+const jasper_report *jasper_repaired_before(const jasper_repaired *r) { return r ? &r->before : nullptr; }
+const jasper_report *jasper_repaired_after(const jasper_repaired *r) { return r ? &r->after : nullptr; }
+int jasper_repaired_seconds(const jasper_repaired *r, double *apply, double *total) {
+    if (!r) { g_err = "bad argument"; return JASPER_ERR; }
+    if (apply) *apply = r->r.apply_seconds;
+    if (total) *total = r->r.seconds;
+    return JASPER_OK;
+}
+void jasper_repaired_free(jasper_repaired *r) { delete r; }
 
 }  // extern "C"

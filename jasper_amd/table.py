@@ -345,6 +345,48 @@ class HetClusters:
                 for r in self.records]
 
 
+EDIT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref_len", "<u4"), ("bases", "<u8", (2,)), ("len", "<u2"), ("source", "u1"),
+              ("round", "u1"), ("pad", "u1", (4,))]
+EDIT_SOURCES = {1: "sub", 2: "ins", 3: "del", 4: "mixed", 5: "compound"}
+
+
+def make_edits(edits):
+    """[(seq, pos, ref_len, y)] -> structured array (EDIT_DTYPE) as KmerTable.apply_edits takes it; y a str or bytes of ACGT"""
+    import numpy as np
+    arr = np.zeros(len(edits), dtype=EDIT_DTYPE)
+    for i, (seq, pos, rlen, y) in enumerate(edits):
+        y = y if isinstance(y, str) else bytes(y).decode("latin-1")
+        v = sum("ACGT".index(ch) << (2 * j) for j, ch in enumerate(y))
+        arr[i] = (pos, seq, 0, 0, rlen, [v & (2**64 - 1), v >> 64], len(y), 0, 0, [0] * 4)
+    return arr
+
+
+class Repair:
+    """the repair stage on a set of sequences (include/jasper_hip.h: jasper_repair): `seqs` = the final sequences as bytes, `edits` =
+    numpy structured array (EDIT_DTYPE) of every applied edit ordered by (round, seq, pos), pos in the coordinates of that round's
+    input, `rounds` = [(records, accepted, conflicts, ambiguous, unreliable_before, unreliable_after)] of every round that scanned,
+    `before` / `after` = the KmerReport of the input and of the final sequences, `seconds` = device time of the scans and the apply
+    kernel, `apply_seconds` = of the apply kernel alone.  The files made from it: jasper_amd/repair.py."""
+
+    def __init__(self, seqs, edits, rounds, before, after, seconds, apply_seconds):
+        self.seqs = seqs
+        self.edits = edits
+        self.rounds = rounds
+        self.before = before
+        self.after = after
+        self.seconds = seconds
+        self.apply_seconds = apply_seconds
+
+    def __eq__(self, other):
+        return (isinstance(other, Repair) and self.seqs == other.seqs and self.edits.tobytes() == other.edits.tobytes() and self.rounds == other.rounds
+                and self.before == other.before and self.after == other.after)
+
+    def edit_tuples(self):
+        """[(round, seq, pos, ref_len, y, source, ref_min, alt_min)], y = the replacement, source = 'sub' | 'ins' | 'del' | 'mixed' | 'compound'"""
+        return [(int(e["round"]), int(e["seq"]), int(e["pos"]), int(e["ref_len"]), compound_string(e["bases"], e["len"]), EDIT_SOURCES[int(e["source"])],
+                 int(e["ref_min"]), int(e["alt_min"])) for e in self.edits]
+
+
 FIXREC_DTYPE = [("index", "<i8"), ("chunk", "<u4"), ("seqno", "<u4"), ("pass_", "u1"), ("kind", "u1"), ("newc", "u1"), ("oldc", "u1"),
                 ("rep", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4")]
 
@@ -958,6 +1000,71 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_compscan_free(res)
+
+    # ---- repair (an extension: the scans' error records applied to the text on the GPU, in rounds) ------------
+    def repair(self, seqs, thre, indel_max_len=4, compound_max_len=64, rounds=3):
+        """the error records of indel_scan(mixed=True) and compound_scan applied to the sequences, in at most `rounds` (1..8) rounds of
+        scan, select and apply (thre >= 1, k >= 2) -> Repair; the table is not modified"""
+        n, cs, lens = _seq_args(seqs)
+        res = C.c_void_p()
+        rc = self._L.jasper_repair(self._h, n, cs, lens, _thre32(thre), int(indel_max_len), int(compound_max_len), int(rounds), C.byref(res))
+        return self._wrap_repaired(rc, res)
+
+    def repair_device(self, d_text, offsets, thre, indel_max_len=4, compound_max_len=64, rounds=3):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries; that text is not written"""
+        n, ptr, offs = _text_args(d_text, offsets)
+        res = C.c_void_p()
+        rc = self._L.jasper_repair_device(self._h, n, ptr, offs, _thre32(thre), int(indel_max_len), int(compound_max_len), int(rounds), C.byref(res))
+        return self._wrap_repaired(rc, res)
+
+    def apply_edits(self, seqs, edits):
+        """the sequences with `edits` applied by the repair stage's kernel -> list of bytes.  edits: a structured array (EDIT_DTYPE; see
+        make_edits) ordered by (seq, pos), every edit inside its sequence and at least one byte after the edit before it; anything else
+        raises and launches nothing"""
+        import numpy as np
+        n, cs, lens = _seq_args(seqs)
+        arr = np.ascontiguousarray(edits, dtype=EDIT_DTYPE)
+        res = C.c_void_p()
+        rc = self._L.jasper_apply_edits(self._h, n, cs, lens, C.c_void_p(arr.ctypes.data if len(arr) else None), len(arr), C.byref(res))
+        return self._wrap_repaired(rc, res).seqs
+
+    def apply_edits_device(self, d_text, offsets, edits):
+        """the same for sequences already in HBM (that text is not written) -> list of bytes"""
+        import numpy as np
+        n, ptr, offs = _text_args(d_text, offsets)
+        arr = np.ascontiguousarray(edits, dtype=EDIT_DTYPE)
+        res = C.c_void_p()
+        rc = self._L.jasper_apply_edits_device(self._h, n, ptr, offs, C.c_void_p(arr.ctypes.data if len(arr) else None), len(arr), C.byref(res))
+        return self._wrap_repaired(rc, res).seqs
+
+    @staticmethod
+    def repair_tile_bytes():
+        """output bytes per workgroup of the repair stage's apply kernel (tests aim at the seams)"""
+        return int(_lib.lib().jasper_repair_tile_bytes())
+
+    def _wrap_repaired(self, rc, res):
+        try:
+            check(rc)
+            seqs = []
+            for i in range(self._L.jasper_repaired_num_seqs(res)):
+                p, ln = C.c_void_p(), C.c_int64(0)
+                check(self._L.jasper_repaired_seq(res, i, C.byref(p), C.byref(ln)))
+                seqs.append(C.string_at(p, ln.value) if ln.value else b"")
+            edits = _records(self._L.jasper_repaired_edits, res, _lib.Edit, EDIT_DTYPE)
+            rp = C.POINTER(_lib.RepairRound)()
+            rn = C.c_uint64(0)
+            check(self._L.jasper_repaired_rounds(res, C.byref(rp), C.byref(rn)))
+            rounds = [(int(rp[i].records), int(rp[i].accepted), int(rp[i].conflicts), int(rp[i].ambiguous), int(rp[i].unreliable_before),
+                       int(rp[i].unreliable_after)) for i in range(rn.value)]
+            before = self._read_report(C.c_void_p(self._L.jasper_repaired_before(res)))      # (owned by res: read, not freed)
+            after = self._read_report(C.c_void_p(self._L.jasper_repaired_after(res)))
+            ap, tot = C.c_double(0), C.c_double(0)
+            check(self._L.jasper_repaired_seconds(res, C.byref(ap), C.byref(tot)))
+            return Repair(seqs, edits, rounds, before, after, tot.value, ap.value)
+        finally:
+            if res:
+                self._L.jasper_repaired_free(res)
 
     def _read_mixed(self, res):
         counts = _counts(self._L.jasper_indelscan_num_seqs, self._L.jasper_indelscan_mixed_counts, res, 3)
