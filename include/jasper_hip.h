@@ -765,6 +765,63 @@ const jasper_report *jasper_repaired_after(const jasper_repaired *r);
 int jasper_repaired_seconds(const jasper_repaired *r, double *apply, double *total);
 void jasper_repaired_free(jasper_repaired *r);
 
+/* Duplication map: WHICH other place holds the second copy of every stretch the assembly holds exactly twice.  Two resident tables of the
+ * same k on the same device -- `reads` (R, whole or attached owner-sharded) and `assembly` (A, a whole table, a different handle from R,
+ * counted from exactly the scanned sequences, as for jasper_copy_report; otherwise JASPER_ERR with a message) -- and a set of sequences,
+ * scanned densely on the GPU twice: pass 1 records where A's count-2 k-mers lie, pass 2 joins every window with its mate.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  jasper_copy_report finds the `deficit` runs of a
+ * duplicated stretch; this says where the other copy is.  `thre` and `peak` (>= 1, else JASPER_ERR) are jasper_copy_report's.  With
+ * offsets[] the starts of the sequences back to back (jasper_dup_map: in the order given, no byte between them):
+ *   window i of sequence s    valid     iff all its k bytes are ACGTacgt (case folded)
+ *                             strand    1 when the reverse complement is the canonical form (rc < fwd), else 0
+ *                             position  offsets[s] + i, encoded with the strand bit as 2 * position + strand
+ *   pass 1 (index)            for every valid window whose k-mer has count exactly 2 in A the encoded position goes into the two 64-bit
+ *                             side words of the k-mer's slot, with atomicMin and atomicMax: the smallest and the largest encoded position
+ *                             seen, whatever the order
+ *   pass 2 (join)             c         R's count of the window's canonical k-mer, clamped to 2^32-1;  a = A's count
+ *                             two-copy  a == 2, the slot's two words are two different positions, and one of them is the window's own;
+ *                                       the other is its MATE
+ *                             unplaced  a == 2 otherwise: A was not counted from these sequences.  Counted, never paired
+ *                             multi     a >= 3.  Counted, never paired: only count exactly 2 is mapped
+ *                             orientation  of a two-copy window: `+` when its strand bit equals its mate's, `-` otherwise
+ *                             deficit   two-copy, c >= thre and (2 c + peak) div (2 peak) < 2: jasper_copy_report's rule at a = 2
+ *   run                       a maximal range of consecutive windows start .. start+n-1 of one sequence that are all two-copy, all of one
+ *                             orientation, and whose mates are colinear: mate(start+j) = mate(start) + j for `+`, mate(start) - j for
+ *                             `-`.  Two adjacent two-copy windows whose mates are not colinear or whose orientations differ end one run
+ *                             and start the next, with no gap between them.  For k >= 2 the mates of a run lie in one sequence
+ *   per sequence              seven counters: windows, valid, two_copy, deficit, multi, unplaced, sum_reads (the sum of c over its
+ *                             two-copy windows)
+ *   jasper_dup_run            start, seq: the run's first window;  n_kmers: its windows;  sum_reads, n_deficit: over them;
+ *                             mate_seq, mate_start: the sequence and the LEFTMOST window of the mate stretch (for `-` the mate of the
+ *                             run's last window);  strand: 0 for `+`, 1 for `-`;  pad: 0
+ * Runs are exact k-mer matches: a substitution in one copy cuts a run into two on one diagonal, k windows apart.  Runs are not chained and
+ * nothing is purged.  Sequences shorter than k (empty ones too) are legal and give zeros.  Runs are ordered by (seq, start); every run
+ * has its mirror image in the list (start <-> mate_start, seq <-> mate_seq, the same strand and n_kmers).  Neither table is modified and
+ * the result is the same on every call.  The library sizes its run buffer by itself and repeats pass 2 once when there were more runs
+ * than it had room for (jasper_dupmap_retried).  Tiles are those of the report (jasper_report_tile_windows()).
+ *   jasper_dup_map          sequences in host memory
+ *   jasper_dup_map_device   sequence i = d_text[offsets[i] .. offsets[i+1]) in HBM on the tables' device; offsets is a host array of
+ *                           n_seqs+1 entries
+ *   jasper_dupmap_counts    out7 = windows, valid, two_copy, deficit, multi, unplaced, sum_reads of one sequence
+ *   jasper_dupmap_runs      the run list (owned by the result)
+ *   jasper_dupmap_seconds   device time (HIP events): *index = the side array's fill and pass 1, *scan = pass 2 and the stitching of its
+ *                           runs; either pointer may be NULL */
+typedef struct jasper_dupmap jasper_dupmap;
+typedef struct jasper_dup_run {
+    int64_t start; int64_t mate_start; uint64_t n_kmers; uint64_t sum_reads; uint64_t n_deficit; uint32_t seq; uint32_t mate_seq; uint32_t strand; uint32_t pad;
+} jasper_dup_run; /* 56 B */
+int jasper_dup_map(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak,
+                   jasper_dupmap **out);
+int jasper_dup_map_device(jasper_table *reads, jasper_table *assembly, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, uint32_t peak,
+                          jasper_dupmap **out);
+int jasper_dupmap_num_seqs(const jasper_dupmap *r);
+int jasper_dupmap_counts(const jasper_dupmap *r, int seq, uint64_t out7[7]);   /* windows, valid, two_copy, deficit, multi, unplaced, sum_reads */
+int jasper_dupmap_runs(const jasper_dupmap *r, const jasper_dup_run **runs, uint64_t *n);
+int jasper_dupmap_seconds(const jasper_dupmap *r, double *index, double *scan);   /* device time, HIP events */
+int jasper_dupmap_retried(const jasper_dupmap *r);
+void jasper_dupmap_free(jasper_dupmap *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

@@ -2,7 +2,7 @@
 sentinel files and log lines; the Jellyfish + per-batch python processes are replaced by the HBM table and the GPU
 polisher.  Lines are cited as src/jasper.sh:N.
 
-    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants]
+    python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants]
                             [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]
                             [--repair [--repair-rounds N]]
                             [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
@@ -107,6 +107,8 @@ class Options:
         self.copies = False
         self.peak = None             # --peak: the read count of a single-copy k-mer (default: from the histogram)
         self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
+        self.dups = False            # --dups: which other place holds the second copy of what the assembly holds twice (_dups)
+        self.dups_min_run = None     # --dups-min-run: shortest run the BED files list (default: k)
         self.variants = False
         self.indels = False
         self.indel_mixed = False
@@ -177,6 +179,10 @@ def parse_args(argv):
             o.peak = nxt; i += 1
         elif key == "--copies-min-run":
             o.copies_min_run = nxt; i += 1
+        elif key == "--dups":                                          # extension: every two-copy window paired with its other copy (_spectra_copies, _dups)
+            o.dups = True
+        elif key == "--dups-min-run":
+            o.dups_min_run = nxt; i += 1
         elif key == "--variants":                                      # extension: heterozygous and unpolished substitution sites (_variants)
             o.variants = True
         elif key == "--indels":                                        # extension: insertions and deletions the reads hold against the contigs (_indels)
@@ -1163,15 +1169,38 @@ def copies_peak(given, histo, thresh):
     return peak
 
 
+def dups_flags(dups, peak, min_run):
+    """--dups, --peak and --dups-min-run as given (None or text) -> (peak or None, min_run or None); exits on --dups-min-run without
+    --dups and on anything but integers >= 1"""
+    if not dups:
+        if min_run is not None:
+            error_exit("--dups-min-run is an option of the duplication map: give --dups as well")
+        return None, None
+    try:
+        m = None if min_run is None else int(min_run)
+        if m is not None and m < 1:
+            raise ValueError
+    except ValueError:
+        error_exit("--dups-min-run takes an integer of at least 1")
+    return copies_flags(peak, None)[0], m
+
+
+def scan_dups(table, asm, contigs, thre, peak):
+    """the duplication map of whole contigs [(name token, sequence)] -> (names, lengths, DupMap); `asm` is counted from exactly them"""
+    from . import report
+    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.dup_map(asm, [s for _, s in contigs], thre, peak)
+
+
 def scan_copies(table, asm, contigs, thre, peak):
     """the copy-number scan of whole contigs [(name token, sequence)] -> (names, lengths, CopyReport)"""
     from . import report
     return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.copy_report(asm, [s for _, s in contigs], thre, peak)
 
 
-def _spectra_copies(o, table, histo_file):
-    """--spectra and --copies (extensions, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each counted
-    into a second table -- ONCE per stage, it serves both -- while the read table is still in HBM.
+def _spectra_copies(o, table, histo_file, dups_out=None):
+    """--spectra, --copies and --dups (extensions, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each
+    counted into a second table -- ONCE per stage, it serves all of them -- while the read table is still in HBM.  --dups: the
+    contigs mapped here, while that table exists, into dups_out (peak, min_run, scans); its files and log lines are _dups', later.
     --spectra: the two tables joined into `$QUERY_FN.spectra_cn.{before,after}.tsv` and `$QUERY_FN.completeness.tsv`
     (jasper_amd/spectra.py).  --copies: the contigs scanned densely against both tables into `$QUERY_FN.copies.tsv` and
     `$QUERY_FN.copies.{before,after}.bed` (jasper_amd/copies.py).  The threshold is the polisher's (threshold.txt)."""
@@ -1184,6 +1213,13 @@ def _spectra_copies(o, table, histo_file):
         with open(histo_file) as f:
             peak = copies_peak(given, copies.histogram_from_rows(ln.split() for ln in f if ln.split()), thresh)
         min_run = k if min_run is None else min_run
+    if o.dups:
+        dgiven, dmin = dups_flags(True, o.peak, o.dups_min_run)
+        dpeak = peak
+        if dpeak is None:
+            with open(histo_file) as f:
+                dpeak = copies_peak(dgiven, copies.histogram_from_rows(ln.split() for ln in f if ln.split()), thresh)
+        dups_out.update(peak=dpeak, min_run=k if dmin is None else dmin, scans=[])
     rows, secs, scans = [], [], []
     for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta")):
         contigs = read_assembly(path)
@@ -1196,6 +1232,8 @@ def _spectra_copies(o, table, histo_file):
                 secs.append(spec.seconds)
             if o.copies:
                 scans.append(scan_copies(table, asm, contigs, thresh, peak))
+            if o.dups:
+                dups_out["scans"].append(scan_dups(table, asm, contigs, thresh, dups_out["peak"]))
         finally:
             asm.close()
     if o.spectra:
@@ -1215,6 +1253,27 @@ def _spectra_copies(o, table, histo_file):
                                                                            copies.stage_log_text(cnt1a, len(copies.listed(rep1.runs, min_run)))))
         if _timing_on():
             sys.stderr.write("[copies] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
+
+
+def _dups(o, table, state):
+    """--dups (an extension, no counterpart in src/jasper.sh): the files and log lines of the duplication maps that _spectra_copies
+    made of the input assembly and of the polished FASTA: `$QUERY_FN.dups.tsv`, `$QUERY_FN.dups.{before,after}.bed` and
+    `$QUERY_FN.dups.pairs.tsv` (jasper_amd/dups.py)."""
+    from . import copies, dups, report
+    qfn, k, peak, min_run = o.query_fn, table.k, state["peak"], state["min_run"]
+    (names, len0, map0), (names1, len1, map1) = state["scans"]
+    rows0, rows1 = dups.extended(map0.counts, names, map0.runs), dups.extended(map1.counts, names1, map1.runs)
+    len1a, rows1a = report.align(names, names1, len1, rows1)
+    dups.write_atomic(qfn + ".dups.tsv", dups.dups_tsv_text(peak, names, [("before", len0, rows0), ("after", len1a, rows1a)]))
+    dups.write_atomic(qfn + ".dups.before.bed", dups.bed_text(k, peak, names, map0.runs, min_run))
+    dups.write_atomic(qfn + ".dups.after.bed", dups.bed_text(k, peak, names1, map1.runs, min_run))
+    dups.write_atomic(qfn + ".dups.pairs.tsv", dups.pairs_tsv_text(peak, [("before", names, map0.runs), ("after", names1, map1.runs)]))
+    if not o.copies:
+        log(copies.peak_log_text(peak, o.peak is not None).replace("Copy-number scan", "Duplication map", 1))
+    log("Duplication map: before polishing %s; after polishing %s" % (dups.stage_log_text(rows0, len(dups.listed(map0.runs, min_run))),
+                                                                      dups.stage_log_text(rows1a, len(dups.listed(map1.runs, min_run)))))
+    if _timing_on():
+        sys.stderr.write("[dups] device seconds (index, scan): before %.6f %.6f after %.6f %.6f\n" % (map0.seconds + map1.seconds))
 
 
 def jf_k(path):
@@ -1637,6 +1696,7 @@ def run(argv):
     ranks = _Ranks(*_init_multi(o))
     if o.copies:
         copies_flags(o.peak, o.copies_min_run)      # (a bad value ends the run before it starts, not after the polishing)
+    dups_flags(o.dups, o.peak, o.dups_min_run)
     if o.indels:
         indel_flags(o.indel_max_len)
     indel_mixed_flag(o.indel_mixed, o.indels)
@@ -1737,11 +1797,17 @@ def run(argv):
             return [(n, ln, cs.report) for n, ln, cs in (scans["before"], scans["after"])] if o.compound else _report_stages(o, table)
         ranks.together((lambda: _report(o, table, stages())) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
         _timing("k-mer report")
+    dup_state = {}
     if o.spectra or o.copies:
         # as for --report: rank 0 alone, its sweeps and scans go through every owner's shard of the attached table
-        ranks.together((lambda: _spectra_copies(o, table, histo_file)) if ranks.is0 else (lambda: None),
+        ranks.together((lambda: _spectra_copies(o, table, histo_file, dup_state)) if ranks.is0 else (lambda: None),
                        "Writing the k-mer spectrum failed" if not o.copies else "Writing the copy-number scan failed")
         _timing("k-mer spectrum" if not o.copies else "k-mer spectrum + copy-number scan" if o.spectra else "copy-number scan")
+    elif o.dups:
+        # as for --report: rank 0 alone, through every owner's shard of the attached table (unmeasured over RCCL, like everything
+        # multi-GPU here); the maps are made here, while the assembly's table exists, and written after the other extensions (_dups)
+        ranks.together((lambda: _spectra_copies(o, table, histo_file, dup_state)) if ranks.is0 else (lambda: None), "The duplication map failed")
+        _timing("duplication map")
     if o.indels:
         # as for --report: rank 0 alone, through every owner's shard of the attached table; one scan per stage serves --variants too
         ranks.together((lambda: _indels(o, table)) if ranks.is0 else (lambda: None), "Writing the indel scan failed")
@@ -1757,6 +1823,8 @@ def run(argv):
         # (unmeasured over RCCL, like everything multi-GPU here)
         ranks.together((lambda: _hapmers(o, table, hap)) if ranks.is0 else (lambda: None), "Writing the hap-mer scan failed")
         _timing("hap-mer scan")
+    if o.dups:
+        ranks.together((lambda: _dups(o, table, dup_state)) if ranks.is0 else (lambda: None), "Writing the duplication map failed")
     if o.repair:
         # as for --report: rank 0 alone, through every owner's shard of the attached table (unmeasured over RCCL, like everything
         # multi-GPU here); after every other extension, so that their files are what they are without it

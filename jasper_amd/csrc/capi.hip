@@ -14,6 +14,7 @@
 #include "indels.hpp"
 #include "compound.hpp"
 #include "repair.hpp"
+#include "dups.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -52,6 +53,9 @@ static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record
 
 struct jasper_copyrep {
     CopyOut r;
+};
+struct jasper_dupmap {
+    DupOut r;
 };
 struct jasper_hapscan {
     HapOut r;
@@ -840,6 +844,32 @@ int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, u
 double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
 int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
 void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
+
+// ---- duplication map (dups.hip) ----
+static_assert(offsetof(jasper_dup_run, mate_start) == offsetof(DupRun, mate_start) && offsetof(jasper_dup_run, n_deficit) == offsetof(DupRun, n_deficit) &&
+                  offsetof(jasper_dup_run, mate_seq) == offsetof(DupRun, mate_seq) && offsetof(jasper_dup_run, strand) == offsetof(DupRun, strand),
+              "jasper_dup_run is DupRun");
+int jasper_dup_map(jasper_table *reads, jasper_table *assembly, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, uint32_t peak,
+                   jasper_dupmap **out) {
+    return scan_call(host_args(n_seqs, seqs, lens), reads && assembly, n_seqs, out,
+                     [&](jasper_dupmap &r) { return dup_map_host(reads->t, assembly->t, n_seqs, seqs, lens, thre, peak, r.r, g_err); });
+}
+int jasper_dup_map_device(jasper_table *reads, jasper_table *assembly, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, uint32_t peak,
+                          jasper_dupmap **out) {
+    return scan_call(offsets, reads && assembly, n_seqs, out,
+                     [&](jasper_dupmap &r) { return dup_map_device(reads->t, assembly->t, n_seqs, (const uint8_t *)d_text, offsets, thre, peak, r.r, g_err); });
+}
+int jasper_dupmap_num_seqs(const jasper_dupmap *r) { return r ? (int)(r->r.counts.size() / 7) : 0; }
+int jasper_dupmap_counts(const jasper_dupmap *r, int seq, uint64_t out7[7]) { return counts_out<7>(r ? &r->r.counts : nullptr, seq, out7); }
+int jasper_dupmap_runs(const jasper_dupmap *r, const jasper_dup_run **runs, uint64_t *n) { return records_out(r ? &r->r.runs : nullptr, runs, n); }
+int jasper_dupmap_seconds(const jasper_dupmap *r, double *index, double *scan) {
+    if (!r) { g_err = "bad argument"; return JASPER_ERR; }
+    if (index) *index = r->r.index_seconds;
+    if (scan) *scan = r->r.seconds;
+    return JASPER_OK;
+}
+int jasper_dupmap_retried(const jasper_dupmap *r) { return r ? r->r.retried : 0; }
+void jasper_dupmap_free(jasper_dupmap *r) { delete r; }
 
 // ---- trio hap-mer scan and census (hapmers.hip) ----
 int jasper_hapmer_scan(jasper_table *mat, jasper_table *pat, jasper_table *child, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre_mat,

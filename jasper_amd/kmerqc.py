@@ -1,7 +1,8 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
-                                [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
+                                [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants]
+                                [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
                                 [--compound [--compound-max-len N]]
                                 [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
                                  [--phase-short-range D] [--phase-max-switches S]]
@@ -26,6 +27,15 @@ and serves --spectra too), and two more files are written (jasper_amd/copies.py)
     PREFIX.copies.bed        one line per run of excess or deficit windows of at least --copies-min-run (default k) windows
 
 --peak is the read count of a single-copy k-mer; the default is the highest bin of the histogram at or above the threshold.
+
+With --dups every window whose k-mer the assembly holds exactly twice is paired with the place of the other copy
+(KmerTable.dup_map; the assembly's table is the one --spectra and --copies use, --peak as for --copies), and three more files are
+written (jasper_amd/dups.py):
+
+    PREFIX.dups.tsv          per contig one row of stage `asm`: two-copy, deficit, multi and unplaced windows, the copies the reads
+                             support, the contig that holds most of the mates; then contig `*`
+    PREFIX.dups.bed          one line per colinear run of two-copy windows of at least --dups-min-run (default k) windows, with its mate
+    PREFIX.dups.pairs.tsv    one row per (contig, mate, strand) with a run of any length
 
 With --variants the contigs are also scanned for positions where the reads hold a solid single-base alternative
 (KmerTable.variant_scan), and two more files are written (jasper_amd/variants.py); the threshold must be at least 1:
@@ -75,17 +85,17 @@ PREFIX defaults to the assembly's file name.  Nothing is polished and no other f
 import os
 import sys
 
-from . import cli, compound, copies, hapmers, hetclusters, indels, polisher, report, spectra, variants
+from . import cli, compound, copies, dups, hapmers, hetclusters, indels, polisher, report, spectra, variants
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None, hapmers=False,
+    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, dups=False, dups_min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None, hapmers=False,
              mat=None, mat_jf=None, pat=None, pat_jf=None, mat_threshold=None, pat_threshold=None, phase_short_range=None, phase_max_switches=None)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
-            "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run",
+            "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run", "--dups-min-run": "dups_min_run",
             "--indel-max-len": "indel_max_len", "--het-cluster-max-len": "het_cluster_max_len", "--compound-max-len": "compound_max_len"}
     keys.update(cli.HAPMER_VALUE_FLAGS)
     i = 0
@@ -94,7 +104,7 @@ def parse_args(argv):
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound", "--hapmers"):
+        if key in ("--spectra", "--copies", "--dups", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound", "--hapmers"):
             o[key[2:].replace("-", "_")] = True
             i += 1
             continue
@@ -120,6 +130,7 @@ def run(argv):
     except ValueError:
         cli.error_exit("-k, --threshold and --device take non-negative integers (k at least 1)")
     peak, min_run = cli.copies_flags(a["peak"], a["min_run"]) if a["copies"] else (None, None)
+    dpeak, dmin_run = cli.dups_flags(a["dups"], a["peak"], a["dups_min_run"])
     if a["variants"] and given is not None and given < 1:
         cli.error_exit("--variants needs a threshold of at least 1; --threshold %d was given" % given)
     max_len = cli.indel_flags(a["indel_max_len"]) if a["indels"] else None
@@ -155,6 +166,9 @@ def run(argv):
     if a["copies"]:
         peak = cli.copies_peak(peak, copies.histogram_from_rows(table.histo_rows()), given)
         min_run = k if min_run is None else min_run
+    if a["dups"]:
+        dpeak = cli.copies_peak(dpeak, copies.histogram_from_rows(table.histo_rows()), given)
+        dmin_run = k if dmin_run is None else dmin_run
     contigs = cli.read_assembly(a["asm"])
     cscan = None
     if a["compound"]:
@@ -162,12 +176,13 @@ def run(argv):
         rep = cscan.report
     else:
         names, lengths, rep = cli.scan_contigs(table, contigs, given)
-    spec = crep = hres = None
-    if a["spectra"] or a["copies"] or hap is not None:
+    spec = crep = hres = dmap = None
+    if a["spectra"] or a["copies"] or a["dups"] or hap is not None:
         asm = cli.assembly_table(table, contigs)          # counted once, it serves all of them
         try:
             spec = cli.assembly_spectrum(table, contigs, asm) if a["spectra"] else None
             crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
+            dmap = cli.scan_dups(table, asm, contigs, given, dpeak)[2] if a["dups"] else None
             if hap is not None:
                 if given < 1:
                     cli.error_exit("--hapmers needs a threshold of at least 1; the histogram gave %d: give --threshold" % given)
@@ -233,6 +248,14 @@ def run(argv):
         cli.log("Compound scan: %s in %s.compound.vcf" % (compound.stage_log_text(cscan.counts), prefix))
         if cli._timing_on():
             sys.stderr.write("[compound] search device seconds: %.6f; lookups %d\n" % (cscan.search_seconds, cscan.lookups))
+    if dmap is not None:
+        rows = dups.extended(dmap.counts, names, dmap.runs)
+        dups.write_atomic(prefix + ".dups.tsv", dups.dups_tsv_text(dpeak, names, [("asm", lengths, rows)]))
+        dups.write_atomic(prefix + ".dups.bed", dups.bed_text(k, dpeak, names, dmap.runs, dmin_run))
+        dups.write_atomic(prefix + ".dups.pairs.tsv", dups.pairs_tsv_text(dpeak, [("asm", names, dmap.runs)]))
+        cli.log("Duplication map: peak %d; %s in %s.dups.bed" % (dpeak, dups.stage_log_text(rows, len(dups.listed(dmap.runs, dmin_run))), prefix))
+        if cli._timing_on():
+            sys.stderr.write("[dups] device seconds: index %.6f scan %.6f\n" % dmap.seconds)
     return 0
 
 

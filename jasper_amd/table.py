@@ -161,6 +161,32 @@ class CopyReport:
         return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"]), int(r["sum_asm"])) for r in self.runs]
 
 
+DUPRUN_DTYPE = [("start", "<i8"), ("mate_start", "<i8"), ("n_kmers", "<u8"), ("sum_reads", "<u8"), ("n_deficit", "<u8"), ("seq", "<u4"), ("mate_seq", "<u4"),
+                ("strand", "<u4"), ("pad", "<u4")]
+
+
+class DupMap:
+    """duplication map of a set of sequences against the reads' table and the assembly's (include/jasper_hip.h: jasper_dup_map):
+    `counts[i]` = (windows, valid, two_copy, deficit, multi, unplaced, sum_reads) of sequence i, `runs` = numpy structured array
+    (DUPRUN_DTYPE) of the maximal colinear runs of two-copy windows ordered by (seq, start), each with the sequence and the leftmost
+    window of its mate stretch and the strand (0 = `+`, 1 = `-`), `seconds` = (device time of the index pass, of the scan).  The
+    files made from it: jasper_amd/dups.py."""
+
+    def __init__(self, counts, runs, seconds, retried):
+        self.counts = counts
+        self.runs = runs
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, DupMap) and self.counts == other.counts and self.runs.tobytes() == other.runs.tobytes()
+
+    def run_tuples(self):
+        """[(seq, start, n_kmers, mate_seq, mate_start, strand, sum_reads, n_deficit)]"""
+        return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["mate_seq"]), int(r["mate_start"]), int(r["strand"]), int(r["sum_reads"]),
+                 int(r["n_deficit"])) for r in self.runs]
+
+
 HAPRUN_DTYPE = [("start", "<i8"), ("n_kmers", "<u8"), ("seq", "<u4"), ("kind", "<u4")]
 HAP_KINDS = {1: "mat", 2: "pat"}
 
@@ -856,6 +882,39 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_copyrep_free(res)
+
+    # ---- duplication map (an extension: no counterpart in the reference) ----------------------------------
+    def dup_map(self, assembly_table, seqs, thre, peak):
+        """this table as the reads' counts, `assembly_table` the assembly's (a whole KmerTable of the same k on the same device,
+        counted from exactly `seqs`): every window whose k-mer the assembly holds exactly twice paired with the place of the other
+        copy, as per-sequence counters and the maximal colinear runs of such pairs; `thre` and `peak` as for copy_report ->
+        DupMap; neither table is modified"""
+        ah = self._assembly_handle(assembly_table, "dup_map")
+        n, cs, lens = _seq_args(seqs)
+        res = C.c_void_p()
+        rc = self._L.jasper_dup_map(self._h, ah, n, cs, lens, int(thre), _peak32(peak), C.byref(res))
+        return self._wrap_dupmap(rc, res)
+
+    def dup_map_device(self, assembly_table, d_text, offsets, thre, peak):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        ah = self._assembly_handle(assembly_table, "dup_map_device")
+        n, ptr, offs = _text_args(d_text, offsets)
+        res = C.c_void_p()
+        rc = self._L.jasper_dup_map_device(self._h, ah, n, ptr, offs, int(thre), _peak32(peak), C.byref(res))
+        return self._wrap_dupmap(rc, res)
+
+    def _wrap_dupmap(self, rc, res):
+        try:
+            check(rc)
+            counts = _counts(self._L.jasper_dupmap_num_seqs, self._L.jasper_dupmap_counts, res, 7)
+            runs = _records(self._L.jasper_dupmap_runs, res, _lib.DupRun, DUPRUN_DTYPE)
+            index, scan = C.c_double(0), C.c_double(0)
+            check(self._L.jasper_dupmap_seconds(res, C.byref(index), C.byref(scan)))
+            return DupMap(counts, runs, (index.value, scan.value), bool(self._L.jasper_dupmap_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_dupmap_free(res)
 
     # ---- trio hap-mer scan and census (an extension: no counterpart in the reference) ----------------------
     @staticmethod
