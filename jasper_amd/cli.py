@@ -21,7 +21,9 @@ import os
 import re
 import sys
 
-from . import polisher, qv
+from . import extensions, polisher, qv
+from .extensions import (compound_flags, copies_flags, copies_peak, dups_flags, hapmer_flags, het_cluster_flags, indel_flags,      # noqa: F401 -- the
+                         indel_mixed_flag, repair_flags, run_repair, scan_compound, scan_variants)                                # extensions' own checks and scans
 from .table import KmerTable
 
 MAX_BATCH_SIZE = 25000000  # :9
@@ -102,31 +104,7 @@ class Options:
         self.jf_db = None
         self.verbose = False
         self.device = 0
-        self.report = False
-        self.spectra = False
-        self.copies = False
-        self.peak = None             # --peak: the read count of a single-copy k-mer (default: from the histogram)
-        self.copies_min_run = None   # --copies-min-run: shortest run the BED files list (default: k)
-        self.dups = False            # --dups: which other place holds the second copy of what the assembly holds twice (_dups)
-        self.dups_min_run = None     # --dups-min-run: shortest run the BED files list (default: k)
-        self.variants = False
-        self.indels = False
-        self.indel_mixed = False
-        self.indel_max_len = None    # --indel-max-len: longest insertion / deletion the indel scan tries (default 4, at most 16)
-        self.het_clusters = False
-        self.het_cluster_max_len = None   # --het-cluster-max-len: longest replacement the het-cluster search lists (default 64, at most 64)
-        self.compound = False
-        self.compound_max_len = None # --compound-max-len: longest replacement the compound scan searches (default 64, at most 64)
-        self.repair = False          # --repair: apply the scans' error records to the polished contigs, in rounds (_repair)
-        self.repair_rounds = None    # --repair-rounds: at most this many rounds of scan, select and apply (default 3, at most 8)
-        self.hapmers = False         # --hapmers: trio hap-mer markers, phase blocks and switch errors (_hapmers)
-        self.mat = self.mat_jf = self.pat = self.pat_jf = None       # the parents' read files or Jellyfish databases
-        self.mat_threshold = self.pat_threshold = None               # default: from each parent's histogram
-        self.phase_short_range = self.phase_max_switches = None      # defaults: hapmers.SHORT_RANGE, hapmers.MAX_SWITCHES
-
-
-HAPMER_VALUE_FLAGS = {"--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat", "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold",
-                      "--pat-threshold": "pat_threshold", "--phase-short-range": "phase_short_range", "--phase-max-switches": "phase_max_switches"}
+        vars(self).update(extensions.flag_defaults())      # report, spectra, copies, peak, ...: one attribute per extension flag
 
 
 def parse_args(argv):
@@ -169,44 +147,10 @@ def parse_args(argv):
             o.device = int(nxt); i += 1
         elif key == "--gpus":                                          # extension: handled by main() (one process per GPU)
             i += 1
-        elif key == "--report":                                        # extension: per-contig k-mer QV and unreliable-k-mer tracks (_report)
-            o.report = True
-        elif key == "--spectra":                                       # extension: copy-number k-mer spectrum and completeness (_spectra_copies)
-            o.spectra = True
-        elif key == "--copies":                                        # extension: where the assembly is collapsed or duplicated (_spectra_copies)
-            o.copies = True
-        elif key == "--peak":
-            o.peak = nxt; i += 1
-        elif key == "--copies-min-run":
-            o.copies_min_run = nxt; i += 1
-        elif key == "--dups":                                          # extension: every two-copy window paired with its other copy (_spectra_copies, _dups)
-            o.dups = True
-        elif key == "--dups-min-run":
-            o.dups_min_run = nxt; i += 1
-        elif key == "--variants":                                      # extension: heterozygous and unpolished substitution sites (_variants)
-            o.variants = True
-        elif key == "--indels":                                        # extension: insertions and deletions the reads hold against the contigs (_indels)
-            o.indels = True
-        elif key == "--indel-mixed":                                   # extension: the indel scan also lists insertions of mixed bases
-            o.indel_mixed = True
-        elif key == "--indel-max-len":
-            o.indel_max_len = nxt; i += 1
-        elif key == "--het-clusters":                                  # extension: the indel scan also lists clusters of het differences less than k apart
-            o.het_clusters = True
-        elif key == "--het-cluster-max-len":
-            o.het_cluster_max_len = nxt; i += 1
-        elif key == "--compound":                                      # extension: what the reads hold for clusters of differences (_compound)
-            o.compound = True
-        elif key == "--compound-max-len":
-            o.compound_max_len = nxt; i += 1
-        elif key == "--repair":                                        # extension: the scans' error records applied to the polished contigs (_repair)
-            o.repair = True
-        elif key == "--repair-rounds":
-            o.repair_rounds = nxt; i += 1
-        elif key == "--hapmers":                                       # extension: parental markers, phase blocks and switch errors (_hapmers)
-            o.hapmers = True
-        elif key in HAPMER_VALUE_FLAGS:
-            setattr(o, HAPMER_VALUE_FLAGS[key], nxt); i += 1
+        elif key in extensions.BOOL_FLAGS:                             # extensions: what each flag asks for is said in extensions.py
+            setattr(o, extensions.flag_attr(key), True)
+        elif key in extensions.VALUE_FLAGS:
+            setattr(o, extensions.VALUE_FLAGS[key], nxt); i += 1
         else:
             print("Unknown option %s" % key)
             sys.exit(1)
@@ -1087,580 +1031,17 @@ def _qv_block(passes, kmer):
             os.remove(p)
 
 
-def scan_contigs(table, contigs, thre):
-    """the dense k-mer report of whole contigs [(name token, sequence)] -> (names, lengths, KmerReport)"""
-    from . import report
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.kmer_report([s for _, s in contigs], thre)
-
-
-def _report_stages(o, table):
-    """the two dense scans of --report: ((names, lengths, KmerReport) of the input assembly, ... of the polished FASTA).  The threshold
-    is the one the polisher used (threshold.txt)."""
-    thresh = int(open("threshold.txt").read().split()[0])
-    return scan_contigs(table, read_assembly(o.query), thresh), scan_contigs(table, read_assembly(o.query_fn + ".polished.fasta"), thresh)
-
-
-def _report(o, table, stages):
-    """--report (an extension, no counterpart in src/jasper.sh): two dense scans through the table while it is still in HBM -- the
-    input assembly's contigs and the polished contigs, WHOLE contigs read back from the two FASTA files, so the windows that span
-    two chunk records are there -- into `$QUERY_FN.kmer_qv.tsv` and `$QUERY_FN.unreliable.{before,after}.bed` (jasper_amd/report.py).
-    k is the table's (a -j database decides it).  `stages` are the two scans: _report_stages, or with --compound the reports that its
-    scans hold (_compound_scans), so that each stage is still ONE dense scan."""
-    from . import report
-    qfn, k = o.query_fn, table.k
-    (names, len0, rep0), (names1, len1, rep1) = stages
-    len1a, cnt1a = report.align(names, names1, len1, rep1.counts)
-    report.write_atomic(qfn + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("before", len0, rep0.counts), ("after", len1a, cnt1a)]))
-    report.write_atomic(qfn + ".unreliable.before.bed", report.bed_text(k, names, rep0.runs))
-    report.write_atomic(qfn + ".unreliable.after.bed", report.bed_text(k, names1, rep1.runs))
-    for stage, counts in (("Before", rep0.counts), ("After", cnt1a)):
-        _, v, u, a = report.totals(counts)
-        log("%s Polishing: dense k-mer QV = %s (unreliable k-mers), %s (absent k-mers)" % (stage, report.qv_text(u, v, k), report.qv_text(a, v, k)))
-    if _timing_on():
-        sys.stderr.write("[report] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
-
-
-def assembly_table(table, contigs):
-    """the contigs [(name token, sequence)] counted into a second table of their own (sized from their length; the sequences
-    joined by a separator byte, so no k-mer spans two contigs) on `table`'s device -> KmerTable, the caller closes it"""
-    from .table import KmerTable
-    seqs = [s for _, s in contigs]
-    asm = KmerTable(table.k, min_slots=max(1 << 16, int(1.25 * sum(len(s) for s in seqs))), device=table.device)
-    try:
-        asm.count_bases("N".join(seqs))
-    except BaseException:
-        asm.close()
-        raise
-    return asm
-
-
-def assembly_spectrum(table, contigs, asm=None):
-    """the contigs' table (assembly_table; `asm` when the caller has it already and keeps it) joined on the GPU with `table`, the
-    reads' -> KmerSpectrum"""
-    if asm is not None:
-        return table.spectrum(asm)
-    asm = assembly_table(table, contigs)
-    try:
-        return table.spectrum(asm)
-    finally:
-        asm.close()
-
-
-def copies_flags(peak, min_run):
-    """--peak and --copies-min-run as given (None or text) -> (peak or None, min_run or None); exits on anything but integers >= 1"""
-    try:
-        p = None if peak is None else int(peak)
-        m = None if min_run is None else int(min_run)
-        if (p is not None and not 1 <= p <= 0xFFFFFFFF) or (m is not None and m < 1):
-            raise ValueError
-    except ValueError:
-        error_exit("--peak and --copies-min-run take integers of at least 1")
-    return p, m
-
-
-def copies_peak(given, histo, thresh):
-    """the single-copy read count: --peak, or the histogram's (copies.peak_from_histogram); exits when there is neither"""
-    from . import copies
-    if given is not None:
-        return given
-    peak = copies.peak_from_histogram(histo, thresh)
-    if peak is None:
-        error_exit("The k-mer histogram has no peak at or above the threshold %d. Please give the read count of a single-copy k-mer with --peak." % thresh)
-    return peak
-
-
-def dups_flags(dups, peak, min_run):
-    """--dups, --peak and --dups-min-run as given (None or text) -> (peak or None, min_run or None); exits on --dups-min-run without
-    --dups and on anything but integers >= 1"""
-    if not dups:
-        if min_run is not None:
-            error_exit("--dups-min-run is an option of the duplication map: give --dups as well")
-        return None, None
-    try:
-        m = None if min_run is None else int(min_run)
-        if m is not None and m < 1:
-            raise ValueError
-    except ValueError:
-        error_exit("--dups-min-run takes an integer of at least 1")
-    return copies_flags(peak, None)[0], m
-
-
-def scan_dups(table, asm, contigs, thre, peak):
-    """the duplication map of whole contigs [(name token, sequence)] -> (names, lengths, DupMap); `asm` is counted from exactly them"""
-    from . import report
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.dup_map(asm, [s for _, s in contigs], thre, peak)
-
-
-def scan_copies(table, asm, contigs, thre, peak):
-    """the copy-number scan of whole contigs [(name token, sequence)] -> (names, lengths, CopyReport)"""
-    from . import report
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.copy_report(asm, [s for _, s in contigs], thre, peak)
-
-
-def _spectra_copies(o, table, histo_file, dups_out=None):
-    """--spectra, --copies and --dups (extensions, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each
-    counted into a second table -- ONCE per stage, it serves all of them -- while the read table is still in HBM.  --dups: the
-    contigs mapped here, while that table exists, into dups_out (peak, min_run, scans); its files and log lines are _dups', later.
-    --spectra: the two tables joined into `$QUERY_FN.spectra_cn.{before,after}.tsv` and `$QUERY_FN.completeness.tsv`
-    (jasper_amd/spectra.py).  --copies: the contigs scanned densely against both tables into `$QUERY_FN.copies.tsv` and
-    `$QUERY_FN.copies.{before,after}.bed` (jasper_amd/copies.py).  The threshold is the polisher's (threshold.txt)."""
-    from . import copies, report, spectra
-    qfn, k = o.query_fn, table.k
-    thresh = int(open("threshold.txt").read().split()[0])
-    peak = min_run = None
-    if o.copies:
-        given, min_run = copies_flags(o.peak, o.copies_min_run)
+def _extensions(ranks, o, table, histo_file, hap):
+    """the extensions of a run (extensions.driver_steps), after the reference's own stages, while the table is still in HBM.  Rank 0
+    alone works; the other ranks wait for the outcome of every step here, and at the barrier that precedes detach."""
+    def histo_rows():
         with open(histo_file) as f:
-            peak = copies_peak(given, copies.histogram_from_rows(ln.split() for ln in f if ln.split()), thresh)
-        min_run = k if min_run is None else min_run
-    if o.dups:
-        dgiven, dmin = dups_flags(True, o.peak, o.dups_min_run)
-        dpeak = peak
-        if dpeak is None:
-            with open(histo_file) as f:
-                dpeak = copies_peak(dgiven, copies.histogram_from_rows(ln.split() for ln in f if ln.split()), thresh)
-        dups_out.update(peak=dpeak, min_run=k if dmin is None else dmin, scans=[])
-    rows, secs, scans = [], [], []
-    for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta")):
-        contigs = read_assembly(path)
-        asm = assembly_table(table, contigs)
-        try:
-            if o.spectra:
-                spec = assembly_spectrum(table, contigs, asm)
-                spectra.write_atomic("%s.spectra_cn.%s.tsv" % (qfn, stage), spectra.spectra_cn_text(spec))
-                rows.append(spectra.completeness_row(stage, spec, thresh))
-                secs.append(spec.seconds)
-            if o.copies:
-                scans.append(scan_copies(table, asm, contigs, thresh, peak))
-            if o.dups:
-                dups_out["scans"].append(scan_dups(table, asm, contigs, thresh, dups_out["peak"]))
-        finally:
-            asm.close()
-    if o.spectra:
-        spectra.write_atomic(qfn + ".completeness.tsv", spectra.completeness_text(k, rows))
-        for stage, row in zip(("Before", "After"), rows):
-            log("%s Polishing: %s" % (stage, spectra.log_text(row)))
-        if _timing_on():
-            sys.stderr.write("[spectra] device seconds: before %.6f after %.6f\n" % tuple(secs))
-    if o.copies:
-        (names, len0, rep0), (names1, len1, rep1) = scans
-        len1a, cnt1a = report.align(names, names1, len1, rep1.counts)
-        copies.write_atomic(qfn + ".copies.tsv", copies.copies_tsv_text(peak, names, [("before", len0, rep0.counts), ("after", len1a, cnt1a)]))
-        copies.write_atomic(qfn + ".copies.before.bed", copies.bed_text(k, peak, names, rep0.runs, min_run))
-        copies.write_atomic(qfn + ".copies.after.bed", copies.bed_text(k, peak, names1, rep1.runs, min_run))
-        log(copies.peak_log_text(peak, o.peak is not None))
-        log("Copy-number scan: before polishing %s; after polishing %s" % (copies.stage_log_text(rep0.counts, len(copies.listed(rep0.runs, min_run))),
-                                                                           copies.stage_log_text(cnt1a, len(copies.listed(rep1.runs, min_run)))))
-        if _timing_on():
-            sys.stderr.write("[copies] device seconds: before %.6f after %.6f\n" % (rep0.seconds, rep1.seconds))
-
-
-def _dups(o, table, state):
-    """--dups (an extension, no counterpart in src/jasper.sh): the files and log lines of the duplication maps that _spectra_copies
-    made of the input assembly and of the polished FASTA: `$QUERY_FN.dups.tsv`, `$QUERY_FN.dups.{before,after}.bed` and
-    `$QUERY_FN.dups.pairs.tsv` (jasper_amd/dups.py)."""
-    from . import copies, dups, report
-    qfn, k, peak, min_run = o.query_fn, table.k, state["peak"], state["min_run"]
-    (names, len0, map0), (names1, len1, map1) = state["scans"]
-    rows0, rows1 = dups.extended(map0.counts, names, map0.runs), dups.extended(map1.counts, names1, map1.runs)
-    len1a, rows1a = report.align(names, names1, len1, rows1)
-    dups.write_atomic(qfn + ".dups.tsv", dups.dups_tsv_text(peak, names, [("before", len0, rows0), ("after", len1a, rows1a)]))
-    dups.write_atomic(qfn + ".dups.before.bed", dups.bed_text(k, peak, names, map0.runs, min_run))
-    dups.write_atomic(qfn + ".dups.after.bed", dups.bed_text(k, peak, names1, map1.runs, min_run))
-    dups.write_atomic(qfn + ".dups.pairs.tsv", dups.pairs_tsv_text(peak, [("before", names, map0.runs), ("after", names1, map1.runs)]))
-    if not o.copies:
-        log(copies.peak_log_text(peak, o.peak is not None).replace("Copy-number scan", "Duplication map", 1))
-    log("Duplication map: before polishing %s; after polishing %s" % (dups.stage_log_text(rows0, len(dups.listed(map0.runs, min_run))),
-                                                                      dups.stage_log_text(rows1a, len(dups.listed(map1.runs, min_run)))))
-    if _timing_on():
-        sys.stderr.write("[dups] device seconds (index, scan): before %.6f %.6f after %.6f %.6f\n" % (map0.seconds + map1.seconds))
-
-
-def jf_k(path):
-    """k of a Jellyfish binary/sorted database, from its header alone (nothing is loaded); None when there is no such header"""
-    import json
-    try:
-        with open(path, "rb") as f:
-            hlen = int(f.read(9))
-            return int(json.loads(f.read(hlen).rstrip(b"\0").decode())["key_len"]) // 2
-    except (OSError, ValueError, KeyError, TypeError):
-        return None
-
-
-def hapmer_flags(o, k, run_jf=None):
-    """the --hapmers options of `o` (attributes hapmers, mat, mat_jf, pat, pat_jf, mat_threshold, pat_threshold, phase_short_range,
-    phase_max_switches; None or text) checked before anything is counted -> None without --hapmers, else a dict of mat / pat = (read
-    files or None, database or None), thre_mat / thre_pat (int or None = from the parent's histogram), short_range, max_switches.
-    k = the run's -k, run_jf = the run's own database when it has one (its header decides the run's k).  Exits on a parental option
-    without --hapmers, a missing or doubly given parent, a parental database of another k, and anything but integers >= 1."""
-    from . import hapmers
-    given = [f for f, a in sorted(HAPMER_VALUE_FLAGS.items()) if getattr(o, a) is not None]
-    if not o.hapmers:
-        if given:
-            error_exit("%s is an option of the hap-mer scan: give --hapmers as well" % given[0])
-        return None
-    out = {}
-    for who, files, jf in (("mat", o.mat, o.mat_jf), ("pat", o.pat, o.pat_jf)):
-        if (files is None) == (jf is None):
-            error_exit("--hapmers needs both parents: exactly one of --%s (read files) and --%s-jf (Jellyfish database) must be given" % (who, who))
-        if files is not None and (not files.split() or not all(_nonempty(fn) for fn in files.split())):
-            error_exit("--%s: a read file does not exist or is empty" % who)
-        if jf is not None and not _nonempty(jf):
-            error_exit("--%s-jf: %s does not exist or is empty" % (who, jf))
-        out[who] = (files.split() if files is not None else None, jf)
-    try:
-        vals = {}
-        for name, text in (("thre_mat", o.mat_threshold), ("thre_pat", o.pat_threshold), ("short_range", o.phase_short_range), ("max_switches", o.phase_max_switches)):
-            vals[name] = None if text is None else int(text)
-            if vals[name] is not None and vals[name] < 1:
-                raise ValueError
-        if any(vals[n] is not None and vals[n] > 0xFFFFFFFF for n in ("thre_mat", "thre_pat")):
-            raise ValueError
-    except ValueError:
-        error_exit("--mat-threshold, --pat-threshold, --phase-short-range and --phase-max-switches take integers of at least 1")
-    out.update(vals)
-    out["short_range"] = hapmers.SHORT_RANGE if out["short_range"] is None else out["short_range"]
-    out["max_switches"] = hapmers.MAX_SWITCHES if out["max_switches"] is None else out["max_switches"]
-    run_k = k
-    if run_jf is not None and jf_k(run_jf) is not None:
-        run_k = jf_k(run_jf)
-    for who in ("mat", "pat"):
-        jf = out[who][1]
-        if jf is not None:
-            pk = jf_k(jf)
-            if pk is None:
-                error_exit(_jf_failed(jf))
-            if pk != run_k:
-                error_exit("--%s-jf: the database's k is %d, the run's is %d; the parents must be counted with the run's k" % (who, pk, run_k))
-    return out
-
-
-def parent_table(who, files, jf, k, device):
-    """one parent's reads counted into a whole table on `device`, or its database loaded -> KmerTable, the caller closes it.  A table
-    that cannot be made -- unreadable input, or no room for it beside the other tables -- ends the run with a message that carries the
-    library's own: there is no fallback, and no parental table spread over several GPUs."""
-    from .table import KmerTable
-    try:
-        if jf is not None:
-            t = KmerTable.from_jf(jf, device=device)
-        else:
-            size = sum(os.stat(f).st_size for f in files) // 10
-            t = KmerTable(k, min_slots=max(1 << 20, int(1.25 * size)), device=device)
-            try:
-                t.count_files(files)
-            except BaseException:
-                t.close()
-                raise
-    except Exception as e:      # noqa: BLE001
-        error_exit("--hapmers: the %s table could not be made on GPU %d: %s (both parental tables are kept whole on that GPU beside the reads' table)" %
-                   ("maternal" if who == "mat" else "paternal", device, e))
-    if t.k != k:
-        t.close()
-        error_exit("--%s-jf: the database's k is %d, the run's is %d; the parents must be counted with the run's k" % (who, t.k, k))
-    return t
-
-
-def parent_threshold(who, table, given):
-    """--mat-threshold / --pat-threshold, or what the solid-k-mer rule derives from that parent's histogram; exits when it derives none"""
-    from . import polisher
-    if given is not None:
-        return given
-    txt, status = polisher.threshold_from_histo_rows(table.histo_rows())
-    if status != 0 or not txt.split() or int(txt.split()[0]) < 1:
-        error_exit("The %s reads' k-mer histogram gives no threshold. Please give one with --%s-threshold." % ("mother's" if who == "mat" else "father's", who))
-    return int(txt.split()[0])
-
-
-def open_parents(flags, k, device):
-    """both parental tables and their thresholds -> (mat, pat, thre_mat, thre_pat); the caller closes the tables"""
-    mat = parent_table("mat", flags["mat"][0], flags["mat"][1], k, device)
-    try:
-        pat = parent_table("pat", flags["pat"][0], flags["pat"][1], k, device)
-        try:
-            return mat, pat, parent_threshold("mat", mat, flags["thre_mat"]), parent_threshold("pat", pat, flags["thre_pat"])
-        except BaseException:
-            pat.close()
-            raise
-    except BaseException:
-        mat.close()
-        raise
-
-
-def scan_hapmers(table, mat, pat, contigs, thre_mat, thre_pat, thre_child, flags, asm=None):
-    """the hap-mer scan of whole contigs [(name token, sequence)] against the trio's tables and the census against the contigs' own
-    table (`asm` when the caller has it already and keeps it) -> (hapmers.Stage, HapmerCensus, HapmerScan)"""
-    from . import hapmers, report
-    seqs = [s for _, s in contigs]
-    scan = table.hapmer_scan(mat, pat, seqs, thre_mat, thre_pat, thre_child)
-    own = asm is None
-    if own:
-        asm = assembly_table(table, contigs)
-    try:
-        census = table.hapmer_census(mat, pat, asm, thre_mat, thre_pat, thre_child)
-    finally:
-        if own:
-            asm.close()
-    stage = hapmers.Stage(table.k, [report.contig_name(n) for n, _ in contigs], [len(s) for s in seqs], scan.counts, scan.runs, flags["short_range"], flags["max_switches"])
-    return stage, census, scan
-
-
-def _hapmers(o, table, flags):
-    """--hapmers (an extension, no counterpart in src/jasper.sh): the input assembly and the polished FASTA, each scanned against the
-    mother's, the father's and the reads' table while the latter is still in HBM, and each counted into a table of its own for the
-    census.  The parental tables are counted or loaded ONCE, whole, on this GPU, and closed afterwards.  Files: `$QUERY_FN.hapmers.tsv`,
-    `$QUERY_FN.hapmer_completeness.tsv`, `$QUERY_FN.hapmers.{before,after}.bed` and `$QUERY_FN.phased_blocks.{before,after}.bed`
-    (jasper_amd/hapmers.py).  The child threshold is the polisher's (threshold.txt).
-    Unlike kmerqc, where one assembly table serves --spectra, --copies and this, the driver counts the two texts AGAIN here when
-    --spectra or --copies has counted them already (_spectra_copies closes its tables before this stage runs): two more counts of an
-    assembly-sized text per run, small beside the parental read sets."""
-    from . import hapmers
-    qfn, k = o.query_fn, table.k
-    thresh = int(open("threshold.txt").read().split()[0])
-    mat, pat, tm, tp = open_parents(flags, k, table.device)
-    try:
-        done = [(stage,) + scan_hapmers(table, mat, pat, read_assembly(path), tm, tp, thresh, flags)
-                for stage, path in (("before", o.query), ("after", qfn + ".polished.fasta"))]
-    finally:
-        mat.close()
-        pat.close()
-    names = done[0][1].names
-    hapmers.write_atomic(qfn + ".hapmers.tsv", hapmers.hapmers_tsv_text(names, [(stage, st) for stage, st, _, _ in done]))
-    hapmers.write_atomic(qfn + ".hapmer_completeness.tsv", hapmers.completeness_text(k, tm, tp, thresh, [(stage, cen) for stage, _, cen, _ in done]))
-    for stage, st, _, _ in done:
-        hapmers.write_atomic("%s.hapmers.%s.bed" % (qfn, stage), hapmers.bed_text(k, st.names, st.runs))
-        hapmers.write_atomic("%s.phased_blocks.%s.bed" % (qfn, stage), hapmers.blocks_bed_text(st.names, st.blocks))
-    log("Hap-mer scan (thresholds mat %d pat %d child %d): before polishing %s; after polishing %s" %
-        (tm, tp, thresh, hapmers.stage_log_text(done[0][1], done[0][2]), hapmers.stage_log_text(done[1][1], done[1][2])))
-    if _timing_on():
-        sys.stderr.write("[hapmers] scan device seconds: before %.6f after %.6f; census device seconds: before %.6f after %.6f\n" %
-                         (done[0][3].seconds, done[1][3].seconds, done[0][2].seconds, done[1][2].seconds))
-
-
-def scan_variants(table, contigs, thre):
-    """the variant scan of whole contigs [(name token, sequence)] -> (names, lengths, VariantScan); exits on a threshold of 0, which
-    would call every alternative solid"""
-    from . import report
-    if thre < 1:
-        error_exit("--variants needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.variant_scan([s for _, s in contigs], thre)
-
-
-def _variants(o, table):
-    """--variants (an extension, no counterpart in src/jasper.sh): the input assembly's contigs and the polished contigs scanned
-    through the read table while it is still in HBM for positions where the reads hold a solid single-base alternative, into
-    `$QUERY_FN.variants.tsv` and `$QUERY_FN.variants.{before,after}.vcf` (jasper_amd/variants.py) -- `before` in the input's
-    coordinates, `after` in the polished FASTA's.  The threshold is the polisher's (threshold.txt)."""
-    from . import report, variants
-    qfn, k = o.query_fn, table.k
-    thresh = int(open("threshold.txt").read().split()[0])
-    names, len0, vs0 = scan_variants(table, read_assembly(o.query), thresh)
-    names1, len1, vs1 = scan_variants(table, read_assembly(qfn + ".polished.fasta"), thresh)
-    len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
-    variants.write_atomic(qfn + ".variants.tsv", variants.variants_tsv_text(names, [("before", len0, vs0.counts), ("after", len1a, cnt1a)]))
-    variants.write_atomic(qfn + ".variants.before.vcf", variants.vcf_text(k, thresh, names, len0, vs0.records))
-    variants.write_atomic(qfn + ".variants.after.vcf", variants.vcf_text(k, thresh, names1, len1, vs1.records))
-    log(variants.log_text(vs0.counts, cnt1a))
-    if _timing_on():
-        sys.stderr.write("[variants] device seconds: before %.6f after %.6f; candidates %d %d\n" % (vs0.seconds, vs1.seconds, vs0.candidates, vs1.candidates))
-
-
-INDEL_MAX_LEN_DEFAULT = 4
-
-
-def indel_flags(max_len):
-    """--indel-max-len as given (a string or None) -> the longest indel to try; exits on anything but an integer in 1..16"""
-    if max_len is None:
-        return INDEL_MAX_LEN_DEFAULT
-    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 16:
-        error_exit("--indel-max-len takes an integer from 1 to 16; it is %s" % max_len)
-    return int(max_len)
-
-
-def indel_mixed_flag(mixed, indels):
-    """--indel-mixed is a mode of --indels: alone it ends the run"""
-    if mixed and not indels:
-        error_exit("--indel-mixed needs --indels: it adds the insertions of mixed bases to the indel scan")
-
-
-HET_CLUSTER_MAX_LEN_DEFAULT = 64
-
-
-def het_cluster_flags(max_len, clusters=True, indels=True):
-    """--het-cluster-max-len as given (a string or None) -> the longest replacement to list; exits on anything but an integer in
-    1..64.  --het-clusters is a mode of --indels: alone it ends the run"""
-    if clusters and not indels:
-        error_exit("--het-clusters needs --indels: it adds the clusters of heterozygous differences less than k apart to the indel scan")
-    if max_len is None:
-        return HET_CLUSTER_MAX_LEN_DEFAULT
-    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 64:
-        error_exit("--het-cluster-max-len takes an integer from 1 to 64; it is %s" % max_len)
-    return int(max_len)
-
-
-def scan_indels(table, contigs, thre, max_len, mixed=False, clusters=0):
-    """the indel scan of whole contigs [(name token, sequence)] -> (names, lengths, IndelScan), whose .variants is what scan_variants
-    gives; exits on a threshold of 0, which would call every alternative solid"""
-    from . import report
-    if thre < 1:
-        error_exit("--indels needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    more = dict(mixed=True) if mixed else {}
-    if clusters:
-        more["clusters"] = clusters
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.indel_scan([s for _, s in contigs], thre, max_len, **more)
-
-
-def _indels(o, table):
-    """--indels (an extension, no counterpart in src/jasper.sh): the input assembly's contigs and the polished contigs scanned through
-    the read table while it is still in HBM for same-base insertions and for deletions that the reads hold, into
-    `$QUERY_FN.indels.tsv` and `$QUERY_FN.indels.{before,after}.vcf` (jasper_amd/indels.py) -- `before` in the input's coordinates,
-    `after` in the polished FASTA's.  The threshold is the polisher's (threshold.txt).  With --variants as well each stage is still
-    ONE scan: the variant files are written from its substitution half, byte for byte those of --variants alone."""
-    from . import indels, report, variants
-    qfn, k = o.query_fn, table.k
-    max_len = indel_flags(o.indel_max_len)
-    thresh = int(open("threshold.txt").read().split()[0])
-    asm0, asm1 = read_assembly(o.query), read_assembly(qfn + ".polished.fasta")
-    mixed = o.indel_mixed
-    clusters = het_cluster_flags(o.het_cluster_max_len) if o.het_clusters else 0
-    names, len0, is0 = scan_indels(table, asm0, thresh, max_len, mixed, clusters)
-    names1, len1, is1 = scan_indels(table, asm1, thresh, max_len, mixed, clusters)
-    if o.variants:
-        vs0, vs1 = is0.variants, is1.variants
-        len1a, cnt1a = report.align(names, names1, len1, vs1.counts)
-        variants.write_atomic(qfn + ".variants.tsv", variants.variants_tsv_text(names, [("before", len0, vs0.counts), ("after", len1a, cnt1a)]))
-        variants.write_atomic(qfn + ".variants.before.vcf", variants.vcf_text(k, thresh, names, len0, vs0.records))
-        variants.write_atomic(qfn + ".variants.after.vcf", variants.vcf_text(k, thresh, names1, len1, vs1.records))
-        log(variants.log_text(vs0.counts, cnt1a))
-    len1a, cnt1a = report.align(names, names1, len1, is1.counts)
-    if mixed:
-        mix1a = report.align(names, names1, len1, is1.mixed.counts)[1]
-        stages = [("before", len0, is0.counts, is0.mixed.counts), ("after", len1a, cnt1a, mix1a)]
-    else:
-        stages = [("before", len0, is0.counts), ("after", len1a, cnt1a)]
-    indels.write_atomic(qfn + ".indels.tsv", indels.indels_tsv_text(names, stages))
-    indels.write_atomic(qfn + ".indels.before.vcf", indels.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], is0.records,
-                                                                    is0.mixed.records if mixed else None))
-    indels.write_atomic(qfn + ".indels.after.vcf", indels.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], is1.records,
-                                                                   is1.mixed.records if mixed else None))
-    log(indels.log_text(is0.counts, cnt1a))
-    if mixed:
-        log(indels.mixed_log_text(is0.mixed.counts, mix1a))
-    if clusters:
-        from . import hetclusters
-        hc0, hc1 = is0.clusters, is1.clusters
-        hc1a = report.align(names, names1, len1, hc1.counts)[1]
-        hetclusters.write_atomic(qfn + ".het_clusters.tsv", hetclusters.het_clusters_tsv_text(names, [("before", len0, hc0.counts), ("after", len1a, hc1a)]))
-        hetclusters.write_atomic(qfn + ".het_clusters.before.vcf", hetclusters.vcf_text(k, thresh, clusters, names, len0, [s for _, s in asm0], hc0.records))
-        hetclusters.write_atomic(qfn + ".het_clusters.after.vcf", hetclusters.vcf_text(k, thresh, clusters, names1, len1, [s for _, s in asm1], hc1.records))
-        log(hetclusters.log_text(hc0.counts, hc1a))
-    if _timing_on():
-        sys.stderr.write("[indels] device seconds: before %.6f (check %.6f) after %.6f (check %.6f); candidates %d %d\n" %
-                         (is0.seconds, is0.check_seconds, is1.seconds, is1.check_seconds, is0.variants.candidates, is1.variants.candidates))
-        if mixed:
-            sys.stderr.write("[indels] mixed search device seconds: before %.6f after %.6f; lookups %d %d\n" %
-                             (is0.mixed.seconds, is1.mixed.seconds, is0.mixed.lookups, is1.mixed.lookups))
-        if clusters:
-            sys.stderr.write("[indels] het-cluster search device seconds: before %.6f after %.6f; lookups %d %d\n" %
-                             (is0.clusters.seconds, is1.clusters.seconds, is0.clusters.lookups, is1.clusters.lookups))
-
-
-COMPOUND_MAX_LEN_DEFAULT = 64
-
-
-def compound_flags(max_len):
-    """--compound-max-len as given (a string or None) -> the longest replacement to search; exits on anything but an integer in 1..64"""
-    if max_len is None:
-        return COMPOUND_MAX_LEN_DEFAULT
-    if not re.match(r"^[0-9]+$", str(max_len)) or not 1 <= int(max_len) <= 64:
-        error_exit("--compound-max-len takes an integer from 1 to 64; it is %s" % max_len)
-    return int(max_len)
-
-
-def scan_compound(table, contigs, thre, max_len):
-    """the compound scan of whole contigs [(name token, sequence)] -> (names, lengths, CompoundScan), whose .report is what
-    scan_contigs gives; exits on a threshold of 0, for which no k-mer is unreliable and every string solid"""
-    from . import report
-    if thre < 1:
-        error_exit("--compound needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    return [report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs], table.compound_scan([s for _, s in contigs], thre, max_len)
-
-
-def _compound_scans(o, table):
-    """the two compound scans of a run -- the input assembly's contigs and the polished contigs, through the read table while it is
-    still in HBM: what _compound writes its files from and, with --report, _report too"""
-    max_len = compound_flags(o.compound_max_len)
-    thresh = int(open("threshold.txt").read().split()[0])
-    asm0, asm1 = read_assembly(o.query), read_assembly(o.query_fn + ".polished.fasta")
-    return dict(thresh=thresh, max_len=max_len, asm0=asm0, asm1=asm1, before=scan_compound(table, asm0, thresh, max_len),
-                after=scan_compound(table, asm1, thresh, max_len))
-
-
-def _compound(o, table, scans):
-    """--compound (an extension, no counterpart in src/jasper.sh): for the runs of unreliable k-mers that clusters of differences
-    leave, what the reads hold in their place, into `$QUERY_FN.compound.tsv` and `$QUERY_FN.compound.{before,after}.vcf`
-    (jasper_amd/compound.py) -- `before` in the input's coordinates, `after` in the polished FASTA's.  The threshold is the
-    polisher's (threshold.txt)."""
-    from . import compound, report
-    qfn, k = o.query_fn, table.k
-    thresh, max_len, asm0, asm1 = scans["thresh"], scans["max_len"], scans["asm0"], scans["asm1"]
-    (names, len0, cs0), (names1, len1, cs1) = scans["before"], scans["after"]
-    len1a, cnt1a = report.align(names, names1, len1, cs1.counts)
-    compound.write_atomic(qfn + ".compound.tsv", compound.compound_tsv_text(names, [("before", len0, cs0.counts), ("after", len1a, cnt1a)]))
-    compound.write_atomic(qfn + ".compound.before.vcf", compound.vcf_text(k, thresh, max_len, names, len0, [s for _, s in asm0], cs0.records))
-    compound.write_atomic(qfn + ".compound.after.vcf", compound.vcf_text(k, thresh, max_len, names1, len1, [s for _, s in asm1], cs1.records))
-    log(compound.log_text(cs0.counts, cnt1a))
-    if _timing_on():
-        sys.stderr.write("[compound] search device seconds: before %.6f after %.6f; lookups %d %d\n" %
-                         (cs0.search_seconds, cs1.search_seconds, cs0.lookups, cs1.lookups))
-
-
-REPAIR_ROUNDS_DEFAULT = 3
-
-
-def repair_flags(repair, rounds):
-    """--repair and --repair-rounds as given (a string or None) -> the rounds to run, 0 without --repair; exits on --repair-rounds
-    without --repair and on anything but an integer in 1..8"""
-    if rounds is not None and not repair:
-        error_exit("--repair-rounds needs --repair")
-    if not repair:
-        return 0
-    if rounds is None:
-        return REPAIR_ROUNDS_DEFAULT
-    if not re.match(r"^[0-9]+$", str(rounds)) or not 1 <= int(rounds) <= 8:
-        error_exit("--repair-rounds takes an integer from 1 to 8; it is %s" % rounds)
-    return int(rounds)
-
-
-def run_repair(table, contigs, thre, indel_max_len, compound_max_len, rounds):
-    """the repair stage on whole contigs [(name token, sequence)] -> (names, lengths, Repair); exits on a threshold of 0, for which no
-    k-mer is unreliable and every string solid"""
-    from . import report
-    if thre < 1:
-        error_exit("--repair needs a threshold for unreliable kmers of at least 1; it is %d" % thre)
-    return ([report.contig_name(n) for n, _ in contigs], [len(s) for _, s in contigs],
-            table.repair([s for _, s in contigs], thre, indel_max_len, compound_max_len, rounds))
-
-
-def _repair(o, table):
-    """--repair (an extension, no counterpart in src/jasper.sh): the error records that the variant, indel and compound scans find on
-    the polished contigs applied to them on the GPU, in rounds, through the read table while it is still in HBM, into
-    `$QUERY_FN.repaired.fasta`, `$QUERY_FN.repairs.tsv` and `$QUERY_FN.repair.tsv` (jasper_amd/repair.py).  The polished FASTA is read,
-    not written.  The threshold is the polisher's (threshold.txt)."""
-    from . import repair
-    qfn, k = o.query_fn, table.k
-    rounds = repair_flags(o.repair, o.repair_rounds)
-    thresh = int(open("threshold.txt").read().split()[0])
-    asm1 = read_assembly(qfn + ".polished.fasta")
-    names, len1, rp = run_repair(table, asm1, thresh, indel_flags(o.indel_max_len), compound_flags(o.compound_max_len), rounds)
-    edits = rp.edit_tuples()
-    with open(qfn + ".polished.fasta", newline="") as f:
-        polished_text = f.read()
-    repair.write_atomic(qfn + ".repaired.fasta", repair.fasta_text(polished_text, rp.seqs))
-    repair.write_atomic(qfn + ".repairs.tsv", repair.repairs_tsv_text(names, repair.round_texts([s for _, s in asm1], edits), edits))
-    repair.write_atomic(qfn + ".repair.tsv", repair.repair_tsv_text(k, names, len1, [len(s) for s in rp.seqs], edits, rp.before.counts, rp.after.counts))
-    log(repair.log_text(k, rp.rounds, rp.before.counts, rp.after.counts))
-    if _timing_on():
-        sys.stderr.write("[repair] device seconds: stage %.6f apply kernel %.6f; rounds %d, edits %d\n" % (rp.seconds, rp.apply_seconds, len(rp.rounds), len(edits)))
+            return [ln.split() for ln in f if ln.split()]
+    run = extensions.Run(table, o.query_fn, {"before": o.query, "after": o.query_fn + ".polished.fasta"}, o, extensions.scan_flags(o), hap, histo_rows)
+    for work, failed, label in extensions.driver_steps(o, hap):
+        ranks.together((lambda: work(run)) if ranks.is0 else (lambda: None), failed)
+        if label:
+            _timing(label)
 
 
 def _init_multi(o):
@@ -1694,20 +1075,7 @@ def run(argv):
         sys.stderr.write("[timing-abs] run() entered at %.6f\n" % time.time())
     o = parse_args(argv)
     ranks = _Ranks(*_init_multi(o))
-    if o.copies:
-        copies_flags(o.peak, o.copies_min_run)      # (a bad value ends the run before it starts, not after the polishing)
-    dups_flags(o.dups, o.peak, o.dups_min_run)
-    if o.indels:
-        indel_flags(o.indel_max_len)
-    indel_mixed_flag(o.indel_mixed, o.indels)
-    if o.het_clusters:
-        het_cluster_flags(o.het_cluster_max_len, True, o.indels)
-    if o.compound:
-        compound_flags(o.compound_max_len)
-    if repair_flags(o.repair, o.repair_rounds):
-        indel_flags(o.indel_max_len)                # (--repair honours the two scans' lengths, with or without --indels and --compound)
-        compound_flags(o.compound_max_len)
-    hap = hapmer_flags(o, int(o.kmer) if re.match(r"^[0-9]+$", str(o.kmer)) else 0, o.jf_db)
+    hap = extensions.check_flags(o, int(o.kmer) if re.match(r"^[0-9]+$", str(o.kmer)) else 0, o.jf_db)["hap"]     # (a bad value ends the run before it starts)
     if not _nonempty(o.query):
         error_exit("The query file does not exist. Please supply a valid fasta file to be polished with -a option.")
     # The counting stage -- the start of the GPU runtime, the table's allocation and reads -> table: everything of src/jasper.sh:177
@@ -1784,52 +1152,7 @@ def run(argv):
         _join(ranks, o, job, in_job, join_writer, batch_size, passes - 1, contigs)
     if ranks.is0:
         _qv_block(passes, kmer)                                                         # :235-257
-    scans = {}
-    if o.compound:
-        # as for --report: rank 0 alone, through every owner's shard of the attached table.  The scans come first because their dense half
-        # is the report's; the files and the log line are written after the other extensions' (_compound)
-        ranks.together((lambda: scans.update(_compound_scans(o, table))) if ranks.is0 else (lambda: None), "The compound scan failed")
-        _timing("compound scan")
-    if o.report:
-        # rank 0 alone scans, through the attached owner-sharded table; the other ranks wait for its outcome here and at the barrier
-        # that precedes detach (unmeasured over RCCL, like everything multi-GPU here)
-        def stages():
-            return [(n, ln, cs.report) for n, ln, cs in (scans["before"], scans["after"])] if o.compound else _report_stages(o, table)
-        ranks.together((lambda: _report(o, table, stages())) if ranks.is0 else (lambda: None), "Writing the k-mer report failed")
-        _timing("k-mer report")
-    dup_state = {}
-    if o.spectra or o.copies:
-        # as for --report: rank 0 alone, its sweeps and scans go through every owner's shard of the attached table
-        ranks.together((lambda: _spectra_copies(o, table, histo_file, dup_state)) if ranks.is0 else (lambda: None),
-                       "Writing the k-mer spectrum failed" if not o.copies else "Writing the copy-number scan failed")
-        _timing("k-mer spectrum" if not o.copies else "k-mer spectrum + copy-number scan" if o.spectra else "copy-number scan")
-    elif o.dups:
-        # as for --report: rank 0 alone, through every owner's shard of the attached table (unmeasured over RCCL, like everything
-        # multi-GPU here); the maps are made here, while the assembly's table exists, and written after the other extensions (_dups)
-        ranks.together((lambda: _spectra_copies(o, table, histo_file, dup_state)) if ranks.is0 else (lambda: None), "The duplication map failed")
-        _timing("duplication map")
-    if o.indels:
-        # as for --report: rank 0 alone, through every owner's shard of the attached table; one scan per stage serves --variants too
-        ranks.together((lambda: _indels(o, table)) if ranks.is0 else (lambda: None), "Writing the indel scan failed")
-        _timing("variant + indel scan" if o.variants else "indel scan")
-    elif o.variants:
-        # as for --report: rank 0 alone, through every owner's shard of the attached table
-        ranks.together((lambda: _variants(o, table)) if ranks.is0 else (lambda: None), "Writing the variant scan failed")
-        _timing("variant scan")
-    if o.compound:
-        ranks.together((lambda: _compound(o, table, scans)) if ranks.is0 else (lambda: None), "Writing the compound scan failed")
-    if hap is not None:
-        # as for --report: rank 0 alone, the child's table through every owner's shard, both parental tables whole on rank 0's GPU
-        # (unmeasured over RCCL, like everything multi-GPU here)
-        ranks.together((lambda: _hapmers(o, table, hap)) if ranks.is0 else (lambda: None), "Writing the hap-mer scan failed")
-        _timing("hap-mer scan")
-    if o.dups:
-        ranks.together((lambda: _dups(o, table, dup_state)) if ranks.is0 else (lambda: None), "Writing the duplication map failed")
-    if o.repair:
-        # as for --report: rank 0 alone, through every owner's shard of the attached table (unmeasured over RCCL, like everything
-        # multi-GPU here); after every other extension, so that their files are what they are without it
-        ranks.together((lambda: _repair(o, table)) if ranks.is0 else (lambda: None), "The repair stage failed")
-        _timing("repair")
+    _extensions(ranks, o, table, histo_file, hap)
     _timing("join + QV")
     if jf_writer is not None:
         _jf_written(jf_writer, table, o, kmer)
@@ -1971,4 +1294,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    from jasper_amd.cli import main as _main       # (under its own name: the one copy of this module, which extensions.py looks up)
+    _main()

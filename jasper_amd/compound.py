@@ -16,34 +16,28 @@ half of the indel scan (--indels --het-clusters, jasper_amd/hetclusters.py), del
 
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, vcf_preamble, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 from .table import compound_string
 
 TSV_HEADER = "#contig\tstage\tlength\tsites\tbridged\trecords\tlong\tcomplex\n"
 ZERO = (0, 0, 0, 0, 0)
+KIND_TEXT = "error: only the alternative is solid in the reads; the contig's own k-mers there are unreliable"
 
 
 def _row(name, stage, length, c):
-    return "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % ((name, stage, length) + tuple(c))
+    return "%s\t%s" % (name, stage) + "\t%d" * (1 + len(c)) % ((length,) + tuple(c)) + "\n"
 
 
 def totals(counts):
     """column sums of the (sites, bridged, records, long, complex) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(5))
+    return column_sums(counts, 5)
 
 
 def compound_tsv_text(names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and five counters, or None for a contig
     that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
     contig `*` with the sums."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, _row, ZERO, totals)
 
 
 def _rec_fields(r):
@@ -55,34 +49,36 @@ def _rec_fields(r):
     return int(seq), int(pos), int(rlen), int(ln), y if isinstance(y, str) else bytes(y).decode("latin-1"), int(rmin), int(amin)
 
 
-def vcf_lines(seqs, records):
-    """[(seq, POS, len, ALT, REF, INFO)] sorted by (contig, POS, LEN, ALT): POS = a + 1, REF = the contig's R bytes as they stand"""
+def _by_len_alt(seq, pos1, rlen, ln, alt):
+    return seq, pos1, ln, alt
+
+
+def vcf_lines(seqs, records, kind="error", order=_by_len_alt):
+    """[(seq, POS, ALT, REF, INFO)] of the replacements, here and in jasper_amd/hetclusters.py, sorted by order(seq, POS, RLEN, LEN, ALT) --
+    here (contig, POS, LEN, ALT): POS = a + 1, REF = the contig's R bytes as they stand"""
     out = []
     for seq, pos, rlen, ln, y, rmin, amin in (_rec_fields(r) for r in records):
         s = seqs[seq]
         ref = s[pos:pos + rlen]
         ref = ref if isinstance(ref, str) else bytes(ref).decode("latin-1")
-        out.append((seq, pos + 1, ln, y, ref, "KIND=error;TYPE=%s;RLEN=%d;LEN=%d;RC=%d;AC=%d" % ("mnp" if rlen == ln else "complex", rlen, ln, rmin, amin)))
+        out.append((order(seq, pos + 1, rlen, ln, y), ref, "KIND=%s;TYPE=%s;RLEN=%d;LEN=%d;RC=%d;AC=%d" % (kind, "mnp" if rlen == ln else "complex", rlen, ln, rmin, amin)))
     out.sort()
-    return out
+    return [(key[0], key[1], key[-1], ref, info) for key, ref, info in out]
 
 
-def vcf_text(k, thre, max_len, names, lengths, seqs, records):
+def vcf_text(k, thre, max_len, names, lengths, seqs, records, scan="compound scan", kind="error", kind_text=KIND_TEXT, order=_by_len_alt):
     """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record ordered by (contig, POS, LEN, ALT)
     whatever order they come in: name, POS, ., REF, ALT, ., ., KIND=error;TYPE=mnp|complex;RLEN=R;LEN=t;RC=ref_min;AC=alt_min.
-    seqs[i] = contig i's sequence: REF is read from it.  Both alleles are non-empty, so there is no anchor base."""
-    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd compound scan, k=%d, threshold=%d, max_len=%d\n" % (k, thre, max_len)]
-    for name, ln in zip(names, lengths):
-        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
-    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="error: only the alternative is solid in the reads; the contig\'s own k-mers there are '
-               'unreliable">\n')
-    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="mnp: ALT is as long as REF; complex: the lengths differ">\n')
-    out.append('##INFO=<ID=RLEN,Number=1,Type=Integer,Description="bytes of the contig that are replaced">\n')
-    out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="bases the reads hold in their place">\n')
-    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
-    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
-    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
-    for seq, pos1, _ln, alt, ref, info in vcf_lines(seqs, records):
+    seqs[i] = contig i's sequence: REF is read from it.  Both alleles are non-empty, so there is no anchor base.
+    scan, kind, kind_text and order: what jasper_amd/hetclusters.py writes its own file with."""
+    out = vcf_preamble("%s, k=%d, threshold=%d, max_len=%d" % (scan, k, thre, max_len), names, lengths, [
+        ("KIND", "String", kind_text),
+        ("TYPE", "String", "mnp: ALT is as long as REF; complex: the lengths differ"),
+        ("RLEN", "Integer", "bytes of the contig that are replaced"),
+        ("LEN", "Integer", "bases the reads hold in their place"),
+        ("RC", "Integer", "smallest read count of the contig's k-mers that span the site"),
+        ("AC", "Integer", "smallest read count of the k-mers of the alternative")])
+    for seq, pos1, alt, ref, info in vcf_lines(seqs, records, kind, order):
         out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], pos1, ref, alt, info))
     return "".join(out)
 

@@ -9,7 +9,7 @@ haplotig, or thin support), and the maximal runs of either class as a BED track.
 
 Nothing here touches the GPU: the functions take names, lengths, counters and runs.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\twindows\tvalid\texcess\tdeficit\tsum_reads\tsum_asm\tdepth\tpeak\n"
 KINDS = {1: "excess", 2: "deficit"}
@@ -51,21 +51,14 @@ def _row(name, stage, length, c, peak):
 
 def totals(counts):
     """column sums of the (windows, valid, excess, deficit, sum_reads, sum_asm) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(6))
+    return column_sums(counts, 6)
 
 
 def copies_tsv_text(peak, names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and six counters, or None for a contig
     that stage does not have (a row of zeros and NA).  Per contig in the order of `names` one row per stage, then one row per
     stage for contig `*` with the sums."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO, peak))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts), peak))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, lambda name, stage, length, c: _row(name, stage, length, c, peak), ZERO, totals)
 
 
 def _run_fields(r):

@@ -9,7 +9,7 @@ say.
 
 Nothing here touches the GPU: the functions take names, lengths, counters and runs.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\twindows\tvalid\ttwo_copy\tdeficit\tmulti\tunplaced\tread_copies\tbest_mate\tbest_windows\tbest_fraction\n"
 PAIRS_HEADER = "#stage\tcontig\tmate\tstrand\truns\twindows\tdeficit\tread_copies\n"
@@ -58,8 +58,7 @@ def extended(counts, names, runs):
 
 def totals(rows):
     """column sums of the seven counters and of best_windows over the contigs that have any (None = contig missing)"""
-    have = [r for r in rows if r is not None]
-    return tuple(sum(r[i] for r in have) for i in range(7)) + (".", sum(r[8] for r in have))
+    return column_sums(rows, 7) + (".", sum(r[8] for r in rows if r is not None))
 
 
 def _row(name, stage, length, r, peak):
@@ -72,14 +71,7 @@ def dups_tsv_text(peak, names, stages):
     """stages: [(stage name, lengths, rows)], rows[i] = extended() of contig i, or None for a contig that stage does not have (a row
     of zeros, NA and `.`).  Per contig in the order of `names` one row per stage, then one row per stage for contig `*` with the
     sums (best_mate `.`, best_windows the sum of the contigs')."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, rows in stages:
-            r = rows[i]
-            out.append(_row(name, stage, lengths[i] if r is not None else 0, r if r is not None else ZERO, peak))
-    for stage, lengths, rows in stages:
-        out.append(_row("*", stage, sum(ln for ln, r in zip(lengths, rows) if r is not None), totals(rows), peak))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, lambda name, stage, length, r: _row(name, stage, length, r, peak), ZERO, totals)
 
 
 def bed_text(k, peak, names, runs, min_run=1):

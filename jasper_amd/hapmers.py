@@ -11,7 +11,7 @@ The block rule is this project's own (it is not Merqury's), stated in full in ph
 
 Nothing here touches the GPU: the functions take names, lengths, counters and runs.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\twindows\tvalid\tmat\tpat\tmarkers\tblocks\tblock_n50\tswitch_markers\tswitch_kmers\tswitch_rate\n"
 COMPLETENESS_HEADER = "#stage\thap\tk\tparent_threshold\tchild_threshold\thapmers\tfound\tcompleteness\toccurrences\n"
@@ -133,11 +133,11 @@ class Stage:
 
 def totals(counts):
     """column sums of the (windows, valid, mat, pat) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
+    return column_sums(counts, 4)
 
 
-def _row(name, stage, length, c, markers, blocks):
-    w, v, m, p = c
+def _row(name, stage, length, r):
+    (w, v, m, p), markers, blocks = r
     nm, nb, n50, sm, sk, own = contig_stats(len(markers), blocks)
     return "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\n" % (name, stage, length, w, v, m, p, nm, nb, n50, sm, sk, switch_rate_text(nm, own, sk))
 
@@ -145,16 +145,12 @@ def _row(name, stage, length, c, markers, blocks):
 def hapmers_tsv_text(names, stages):
     """stages: [(stage name, Stage)].  Per contig in the order of `names` one row per stage (zeros and NA for a contig that stage does
     not have), then one row per stage for contig `*`: the sums, the N50 over all blocks and the switch rate over all of them."""
-    al = [(stage, s.aligned(names)) for stage, s in stages]
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, (lengths, counts, markers, blocks) in al:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO, markers[i] or [], blocks[i] or []))
-    for stage, (lengths, counts, markers, blocks) in al:
-        have = [i for i, c in enumerate(counts) if c is not None]
-        out.append(_row("*", stage, sum(lengths[i] for i in have), totals(counts), [m for i in have for m in markers[i]], [b for i in have for b in blocks[i]]))
-    return "".join(out)
+    rows = []                                    # a contig's row: (counts, markers, blocks)
+    for stage, s in stages:
+        lengths, counts, markers, blocks = s.aligned(names)
+        rows.append((stage, lengths, [None if c is None else (c, markers[i], blocks[i]) for i, c in enumerate(counts)]))
+    return stage_table_text(TSV_HEADER, names, rows, _row, (ZERO, [], []),
+                            lambda rs: (totals([r and r[0] for r in rs]), [m for r in rs if r for m in r[1]], [b for r in rs if r for b in r[2]]))
 
 
 def bed_text(k, names, runs):

@@ -16,66 +16,40 @@ variant scan's and a pure insertion or deletion the indel scan's, and nothing lo
 
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
 """
-from .compound import _rec_fields
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from . import compound
+from .report import align, column_sums, contig_name, stage_table_text, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\tsearched\tsites\trecords\tcomplex\n"
 ZERO = (0, 0, 0, 0)
 
 
-def _row(name, stage, length, c):
-    return "%s\t%s\t%d\t%d\t%d\t%d\t%d\n" % ((name, stage, length) + tuple(c))
-
-
 def totals(counts):
     """column sums of the (searched, sites, records, complex) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
+    return column_sums(counts, 4)
 
 
 def het_clusters_tsv_text(names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and four counters, or None for a contig
     that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
     contig `*` with the sums."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, compound._row, ZERO, totals)
+
+
+def _by_rlen_len_alt(seq, pos1, rlen, ln, alt):
+    return seq, pos1, rlen, ln, alt
 
 
 def vcf_lines(seqs, records):
-    """[(seq, POS, RLEN, LEN, ALT, REF, INFO)] sorted by (contig, POS, RLEN, LEN, ALT): POS = p + 1, REF = the contig's R bytes as they
-    stand"""
-    out = []
-    for seq, pos, rlen, ln, y, rmin, amin in (_rec_fields(r) for r in records):
-        s = seqs[seq]
-        ref = s[pos:pos + rlen]
-        ref = ref if isinstance(ref, str) else bytes(ref).decode("latin-1")
-        out.append((seq, pos + 1, rlen, ln, y, ref, "KIND=het;TYPE=%s;RLEN=%d;LEN=%d;RC=%d;AC=%d" % ("mnp" if rlen == ln else "complex", rlen, ln, rmin, amin)))
-    out.sort()
-    return out
+    """[(seq, POS, ALT, REF, INFO)] sorted by (contig, POS, RLEN, LEN, ALT): POS = p + 1, REF = the contig's R bytes as they stand"""
+    return compound.vcf_lines(seqs, records, "het", _by_rlen_len_alt)
 
 
 def vcf_text(k, thre, max_len, names, lengths, seqs, records):
     """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record ordered by (contig, POS, RLEN, LEN,
     ALT) whatever order they come in: name, POS, ., REF, ALT, ., ., KIND=het;TYPE=mnp|complex;RLEN=R;LEN=t;RC=ref_min;AC=alt_min.
     seqs[i] = contig i's sequence: REF is read from it.  Both alleles are non-empty, so there is no anchor base."""
-    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd het-cluster scan, k=%d, threshold=%d, max_len=%d\n" % (k, thre, max_len)]
-    for name, ln in zip(names, lengths):
-        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
-    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="het: the contig\'s sequence and the alternative are both solid in the reads">\n')
-    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="mnp: ALT is as long as REF; complex: the lengths differ">\n')
-    out.append('##INFO=<ID=RLEN,Number=1,Type=Integer,Description="bytes of the contig that are replaced">\n')
-    out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="bases the reads hold in their place">\n')
-    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
-    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
-    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
-    for seq, pos1, _rlen, _ln, alt, ref, info in vcf_lines(seqs, records):
-        out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], pos1, ref, alt, info))
-    return "".join(out)
+    return compound.vcf_text(k, thre, max_len, names, lengths, seqs, records, "het-cluster scan", "het",
+                             "het: the contig's sequence and the alternative are both solid in the reads", _by_rlen_len_alt)
 
 
 def stage_log_text(counts):

@@ -16,7 +16,7 @@ k apart hide each other (the het-cluster half of the scan lists those where both
 The scan reports every indel at its right-most position; the VCF writer moves it to the left-most one (`left_align`), as VCF asks.
 Nothing here touches the GPU: the functions take names, lengths, sequences, counters and records.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, vcf_preamble, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\tins_het\tins_error\tdel_het\tdel_error\n"
 KINDS = {1: "het", 2: "error"}
@@ -34,12 +34,12 @@ def _row(name, stage, length, c):
 
 def totals(counts):
     """column sums of the (ins_het, ins_error, del_het, del_error) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
+    return column_sums(counts, 4)
 
 
 def mixed_totals(mcounts):
     """column sums of the (mixed_het, mixed_error, complex) of the contigs that have any"""
-    return tuple(sum(c[i] for c in mcounts if c is not None) for i in range(3))
+    return column_sums(mcounts, 3)
 
 
 def _more(c3):
@@ -51,21 +51,13 @@ def indels_tsv_text(names, stages):
     that stage does not have (a row of zeros).  Per contig in the order of `names` one row per stage, then one row per stage for
     contig `*` with the sums.  Stages of the mixed scan are (stage name, lengths, counts, mixed counts): every row, the header
     included, then ends in the three columns mixed_het, mixed_error, complex."""
-    mixed = any(len(st) > 3 for st in stages)
-    stages = [tuple(st) + (None,) * (4 - len(st)) for st in stages]
-    out = [TSV_HEADER[:-1] + MIXED_COLUMNS + "\n" if mixed else TSV_HEADER]
-
-    def row(name, stage, length, c, m):
-        return _row(name, stage, length, c)[:-1] + _more(m) if mixed else _row(name, stage, length, c)
-
-    for i, name in enumerate(names):
-        for stage, lengths, counts, mc in stages:
-            c = counts[i]
-            m = mc[i] if mc is not None and c is not None and mc[i] is not None else ZERO3
-            out.append(row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO, m))
-    for stage, lengths, counts, mc in stages:
-        out.append(row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts), mixed_totals(mc) if mc is not None else ZERO3))
-    return "".join(out)
+    if not any(len(st) > 3 for st in stages):
+        return stage_table_text(TSV_HEADER, names, stages, _row, ZERO, totals)
+    paired = []                                  # a contig's row: (counts, mixed counts -- zeros where a stage has none)
+    for stage, lengths, counts, mc in (tuple(st) + (None,) * (4 - len(st)) for st in stages):
+        paired.append((stage, lengths, [None if c is None else (c, mc[i] if mc is not None and mc[i] is not None else ZERO3) for i, c in enumerate(counts)]))
+    return stage_table_text(TSV_HEADER[:-1] + MIXED_COLUMNS + "\n", names, paired, lambda name, stage, length, r: _row(name, stage, length, r[0])[:-1] + _more(r[1]),
+                            (ZERO, ZERO3), lambda rows: (totals([r and r[0] for r in rows]), mixed_totals([r and r[1] for r in rows])))
 
 
 def _letter(v):
@@ -150,17 +142,12 @@ def vcf_text(k, thre, max_len, names, lengths, seqs, records, mixed_records=None
     read from it).  mixed_records (not None: the scan had its mixed half) are the insertions of mixed bases: `TYPE=ins` lines in the
     same order, REF = the anchor, ALT = the anchor and the inserted string."""
     mixed = mixed_records is not None
-    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd indel scan, k=%d, threshold=%d, max_len=%d%s\n" % (k, thre, max_len, ", mixed" if mixed else "")]
-    for name, ln in zip(names, lengths):
-        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
-    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="het: the contig\'s sequence and the alternative are both solid in the reads; '
-               'error: only the alternative is">\n')
-    out.append('##INFO=<ID=TYPE,Number=1,Type=String,Description="ins: the reads hold LEN more %s; del: the reads lack LEN bytes">\n' %
-               ("bases" if mixed else "copies of one base"))
-    out.append('##INFO=<ID=LEN,Number=1,Type=Integer,Description="length of the insertion or deletion">\n')
-    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the contig\'s k-mers that span the site">\n')
-    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of the k-mers of the alternative">\n')
-    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+    out = vcf_preamble("indel scan, k=%d, threshold=%d, max_len=%d%s" % (k, thre, max_len, ", mixed" if mixed else ""), names, lengths, [
+        ("KIND", "String", "het: the contig's sequence and the alternative are both solid in the reads; error: only the alternative is"),
+        ("TYPE", "String", "ins: the reads hold LEN more %s; del: the reads lack LEN bytes" % ("bases" if mixed else "copies of one base")),
+        ("LEN", "Integer", "length of the insertion or deletion"),
+        ("RC", "Integer", "smallest read count of the contig's k-mers that span the site"),
+        ("AC", "Integer", "smallest read count of the k-mers of the alternative")])
     for seq, q, _typ, _ln, alt, ref, info in vcf_lines(names, seqs, records, mixed_records if mixed else ()):
         out.append("%s\t%d\t.\t%s\t%s\t.\t.\t%s\n" % (names[seq], q, ref, alt, info))
     return "".join(out)

@@ -81,31 +81,35 @@ threshold defaults to what that parent's histogram gives; the child's is the run
     PREFIX.hapmer_completeness.tsv   two rows (mat, pat): hap-mers, how many the assembly holds, completeness, occurrences
 
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
+
+The flags, the scans, the files and the log lines are the driver's, described once for both in jasper_amd/extensions.py; here the list
+of stages is the single stage `asm`, so no file name carries a stage.
 """
 import os
 import sys
 
-from . import cli, compound, copies, dups, hapmers, hetclusters, indels, polisher, report, spectra, variants
+from . import cli, extensions, polisher
 from .table import KmerTable
 
 USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
+NOT_HERE = ("--report", "--repair", "--repair-rounds")      # of the extension flags: the report is always written, nothing is repaired
 
 
 def parse_args(argv):
-    o = dict(asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0, spectra=False, copies=False, peak=None, min_run=None, dups=False, dups_min_run=None, variants=False, indels=False, indel_max_len=None, indel_mixed=False, het_clusters=False, het_cluster_max_len=None, compound=False, compound_max_len=None, hapmers=False,
-             mat=None, mat_jf=None, pat=None, pat_jf=None, mat_threshold=None, pat_threshold=None, phase_short_range=None, phase_max_switches=None)
+    o = dict(extensions.flag_defaults(), asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0)
     keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
-            "--threshold": "threshold", "-o": "prefix", "--device": "device", "--peak": "peak", "--copies-min-run": "min_run", "--dups-min-run": "dups_min_run",
-            "--indel-max-len": "indel_max_len", "--het-cluster-max-len": "het_cluster_max_len", "--compound-max-len": "compound_max_len"}
-    keys.update(cli.HAPMER_VALUE_FLAGS)
+            "--threshold": "threshold", "-o": "prefix", "--device": "device"}
+    keys.update((f, a) for f, a in extensions.VALUE_FLAGS.items() if f not in NOT_HERE)
+    keys["--copies-min-run"] = "min_run"        # (the name it has always had in this result; run() hands it on as copies_min_run)
+    o["min_run"] = o.pop("copies_min_run")
     i = 0
     while i < len(argv):
         key = argv[i]
         if key in ("-h", "--help"):
             print(USAGE)
             sys.exit(0)
-        if key in ("--spectra", "--copies", "--dups", "--variants", "--indels", "--indel-mixed", "--het-clusters", "--compound", "--hapmers"):
-            o[key[2:].replace("-", "_")] = True
+        if key in extensions.BOOL_FLAGS and key not in NOT_HERE:
+            o[extensions.flag_attr(key)] = True
             i += 1
             continue
         if key not in keys or i + 1 >= len(argv):
@@ -129,133 +133,65 @@ def run(argv):
             raise ValueError
     except ValueError:
         cli.error_exit("-k, --threshold and --device take non-negative integers (k at least 1)")
-    peak, min_run = cli.copies_flags(a["peak"], a["min_run"]) if a["copies"] else (None, None)
-    dpeak, dmin_run = cli.dups_flags(a["dups"], a["peak"], a["dups_min_run"])
-    if a["variants"] and given is not None and given < 1:
-        cli.error_exit("--variants needs a threshold of at least 1; --threshold %d was given" % given)
-    max_len = cli.indel_flags(a["indel_max_len"]) if a["indels"] else None
-    cli.indel_mixed_flag(a["indel_mixed"], a["indels"])
-    clusters = cli.het_cluster_flags(a["het_cluster_max_len"], True, a["indels"]) if a["het_clusters"] else 0
-    if a["indels"] and given is not None and given < 1:
-        cli.error_exit("--indels needs a threshold of at least 1; --threshold %d was given" % given)
-    comp_len = cli.compound_flags(a["compound_max_len"]) if a["compound"] else None
-    if a["compound"] and given is not None and given < 1:
-        cli.error_exit("--compound needs a threshold of at least 1; --threshold %d was given" % given)
-    hap = cli.hapmer_flags(type("HapmerOptions", (), a), k, a["jf"])
-    if hap is not None and given is not None and given < 1:
-        cli.error_exit("--hapmers needs a threshold of at least 1; --threshold %d was given" % given)
+    o = type("KmerqcOptions", (), dict(a, copies_min_run=a["min_run"]))
+    f = extensions.check_flags(o, k, a["jf"], given)
+    hap = f["hap"]
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
         except Exception as e:      # noqa: BLE001
             cli.error_exit(cli._jf_failed(a["jf"]) + " (%s)" % e)
     else:
-        o = cli.Options()
-        o.reads = a["reads"]
-        reads = cli._reads(o)
-        size = sum(os.stat(f).st_size for f in reads) // 10                        # (the `-s` of src/jasper.sh:82)
+        opts = cli.Options()
+        opts.reads = a["reads"]
+        reads = cli._reads(opts)
+        size = sum(os.stat(fn).st_size for fn in reads) // 10                        # (the `-s` of src/jasper.sh:82)
         table = KmerTable(k, min_slots=max(1 << 20, int(1.25 * size)), device=device)
         table.count_files(reads)
-    k = table.k
     if given is None:
         txt, status = polisher.threshold_from_histo_rows(table.histo_rows())    # src/jellyfish.py, as cli._threshold applies it
         if status != 0 or not txt.split():
             cli.error_exit("Local min of kmer counts is smaller than 4. The input read data is not suitable; give --threshold.")
         given = int(txt.split()[0])
     cli.log("Lower threshold for unreliable kmers is %d" % given)
-    if a["copies"]:
-        peak = cli.copies_peak(peak, copies.histogram_from_rows(table.histo_rows()), given)
-        min_run = k if min_run is None else min_run
-    if a["dups"]:
-        dpeak = cli.copies_peak(dpeak, copies.histogram_from_rows(table.histo_rows()), given)
-        dmin_run = k if dmin_run is None else dmin_run
-    contigs = cli.read_assembly(a["asm"])
-    cscan = None
-    if a["compound"]:
-        names, lengths, cscan = cli.scan_compound(table, contigs, given, comp_len)      # (its dense scan is the report's)
+    prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
+    run = extensions.Run(table, prefix, {"asm": a["asm"]}, o, f, hap, table.histo_rows, given)
+    run.derive_peaks()
+    text = run.text("asm")
+    # every scan first, then the table goes, then the files
+    if o.compound:
+        cscan = extensions.scan_compound(table, text.contigs, given, f["compound_max_len"])[2]      # (its dense scan is the report's)
         rep = cscan.report
     else:
-        names, lengths, rep = cli.scan_contigs(table, contigs, given)
-    spec = crep = hres = dmap = None
-    if a["spectra"] or a["copies"] or a["dups"] or hap is not None:
-        asm = cli.assembly_table(table, contigs)          # counted once, it serves all of them
-        try:
-            spec = cli.assembly_spectrum(table, contigs, asm) if a["spectra"] else None
-            crep = cli.scan_copies(table, asm, contigs, given, peak)[2] if a["copies"] else None
-            dmap = cli.scan_dups(table, asm, contigs, given, dpeak)[2] if a["dups"] else None
-            if hap is not None:
-                if given < 1:
-                    cli.error_exit("--hapmers needs a threshold of at least 1; the histogram gave %d: give --threshold" % given)
-                mat, pat, tm, tp = cli.open_parents(hap, k, table.device)
-                try:
-                    hres = (tm, tp) + cli.scan_hapmers(table, mat, pat, contigs, tm, tp, given, hap, asm)
-                finally:
-                    mat.close()
-                    pat.close()
-        finally:
-            asm.close()
-    iscan = cli.scan_indels(table, contigs, given, max_len, a["indel_mixed"], clusters)[2] if a["indels"] else None
-    vscan = (iscan.variants if iscan is not None else cli.scan_variants(table, contigs, given)[2]) if a["variants"] else None
+        rep = table.kmer_report(text.seqs, given)
+
+    def trio(text, asm):
+        if given < 1:
+            cli.error_exit("--hapmers needs a threshold of at least 1; the histogram gave %d: give --threshold" % given)
+        return extensions.with_parents(run, lambda parents: extensions.hapmers_scan(run, text, parents, asm))
+
+    own = {}
+    if o.spectra or o.copies or o.dups or hap is not None:
+        own = run.asm_scans("asm", trio if hap is not None else None)          # the assembly's table: counted once, it serves all of them
+    iscan = extensions.scan_indels(table, text.contigs, given, f["indel_max_len"], o.indel_mixed, f["clusters"])[2] if o.indels else None
+    vscan = extensions.scan_variants(table, text.contigs, given)[2] if o.variants and iscan is None else None
     table.close()
-    prefix = a["prefix"] if a["prefix"] is not None else os.path.basename(a["asm"])
-    report.write_atomic(prefix + ".kmer_qv.tsv", report.qv_tsv_text(k, names, [("asm", lengths, rep.counts)]))
-    report.write_atomic(prefix + ".unreliable.bed", report.bed_text(k, names, rep.runs))
-    _, v, u, ab = report.totals(rep.counts)
-    cli.log("Dense k-mer QV = %s (unreliable k-mers), %s (absent k-mers); %d runs in %s.unreliable.bed" %
-            (report.qv_text(u, v, k), report.qv_text(ab, v, k), len(rep.runs), prefix))
-    if spec is not None:
-        row = spectra.completeness_row("asm", spec, given)
-        spectra.write_atomic(prefix + ".spectra_cn.tsv", spectra.spectra_cn_text(spec))
-        spectra.write_atomic(prefix + ".completeness.tsv", spectra.completeness_text(k, [row]))
-        cli.log("Assembly: %s" % spectra.log_text(row))
-    if crep is not None:
-        copies.write_atomic(prefix + ".copies.tsv", copies.copies_tsv_text(peak, names, [("asm", lengths, crep.counts)]))
-        copies.write_atomic(prefix + ".copies.bed", copies.bed_text(k, peak, names, crep.runs, min_run))
-        cli.log("Copy-number scan: peak %d; %s in %s.copies.bed" % (peak, copies.stage_log_text(crep.counts, len(copies.listed(crep.runs, min_run))), prefix))
-    if hres is not None:
-        tm, tp, hstage, census, hscan = hres
-        hapmers.write_atomic(prefix + ".hapmers.tsv", hapmers.hapmers_tsv_text(names, [("asm", hstage)]))
-        hapmers.write_atomic(prefix + ".hapmers.bed", hapmers.bed_text(k, names, hscan.runs))
-        hapmers.write_atomic(prefix + ".phased_blocks.bed", hapmers.blocks_bed_text(names, hstage.blocks))
-        hapmers.write_atomic(prefix + ".hapmer_completeness.tsv", hapmers.completeness_text(k, tm, tp, given, [("asm", census)]))
-        cli.log("Hap-mer scan (thresholds mat %d pat %d child %d): %s in %s.hapmers.bed" % (tm, tp, given, hapmers.stage_log_text(hstage, census), prefix))
-        if cli._timing_on():
-            sys.stderr.write("[hapmers] scan device seconds: %.6f; census device seconds: %.6f\n" % (hscan.seconds, census.seconds))
-    if vscan is not None:
-        variants.write_atomic(prefix + ".variants.tsv", variants.variants_tsv_text(names, [("asm", lengths, vscan.counts)]))
-        variants.write_atomic(prefix + ".variants.vcf", variants.vcf_text(k, given, names, lengths, vscan.records))
-        cli.log("Variant scan: %s in %s.variants.vcf" % (variants.stage_log_text(vscan.counts), prefix))
+    extensions.report_files(run, [("asm", text, rep)])
+    if o.spectra:
+        extensions.spectrum_file(run, "asm", own["spectra"][2])
+        extensions.spectra_files(run, [own["spectra"]])
+    if o.copies:
+        extensions.copies_files(run, [own["copies"]])
+    if hap is not None:
+        extensions.hapmers_files(run, [own["hapmers"]])
     if iscan is not None:
-        mixed = iscan.mixed
-        indels.write_atomic(prefix + ".indels.tsv", indels.indels_tsv_text(names, [("asm", lengths, iscan.counts) + ((mixed.counts,) if mixed is not None else ())]))
-        indels.write_atomic(prefix + ".indels.vcf", indels.vcf_text(k, given, max_len, names, lengths, [s for _, s in contigs], iscan.records,
-                                                                    mixed.records if mixed is not None else None))
-        cli.log("Indel scan: %s in %s.indels.vcf" % (indels.stage_log_text(iscan.counts), prefix))
-        if mixed is not None:
-            cli.log("Mixed insertions: %s in %s.indels.vcf" % (indels.mixed_stage_log_text(mixed.counts), prefix))
-            if cli._timing_on():
-                sys.stderr.write("[indels] mixed search device seconds: %.6f; lookups %d\n" % (mixed.seconds, mixed.lookups))
-        hc = iscan.clusters
-        if hc is not None:
-            hetclusters.write_atomic(prefix + ".het_clusters.tsv", hetclusters.het_clusters_tsv_text(names, [("asm", lengths, hc.counts)]))
-            hetclusters.write_atomic(prefix + ".het_clusters.vcf", hetclusters.vcf_text(k, given, clusters, names, lengths, [s for _, s in contigs], hc.records))
-            cli.log("Het clusters: %s in %s.het_clusters.vcf" % (hetclusters.stage_log_text(hc.counts), prefix))
-            if cli._timing_on():
-                sys.stderr.write("[indels] het-cluster search device seconds: %.6f; lookups %d\n" % (hc.seconds, hc.lookups))
-    if cscan is not None:
-        compound.write_atomic(prefix + ".compound.tsv", compound.compound_tsv_text(names, [("asm", lengths, cscan.counts)]))
-        compound.write_atomic(prefix + ".compound.vcf", compound.vcf_text(k, given, comp_len, names, lengths, [s for _, s in contigs], cscan.records))
-        cli.log("Compound scan: %s in %s.compound.vcf" % (compound.stage_log_text(cscan.counts), prefix))
-        if cli._timing_on():
-            sys.stderr.write("[compound] search device seconds: %.6f; lookups %d\n" % (cscan.search_seconds, cscan.lookups))
-    if dmap is not None:
-        rows = dups.extended(dmap.counts, names, dmap.runs)
-        dups.write_atomic(prefix + ".dups.tsv", dups.dups_tsv_text(dpeak, names, [("asm", lengths, rows)]))
-        dups.write_atomic(prefix + ".dups.bed", dups.bed_text(k, dpeak, names, dmap.runs, dmin_run))
-        dups.write_atomic(prefix + ".dups.pairs.tsv", dups.pairs_tsv_text(dpeak, [("asm", names, dmap.runs)]))
-        cli.log("Duplication map: peak %d; %s in %s.dups.bed" % (dpeak, dups.stage_log_text(rows, len(dups.listed(dmap.runs, dmin_run))), prefix))
-        if cli._timing_on():
-            sys.stderr.write("[dups] device seconds: index %.6f scan %.6f\n" % dmap.seconds)
+        extensions.indels_files(run, [("asm", text, iscan)])        # (the variant files too, from its substitution half)
+    elif o.variants:
+        extensions.variants_files(run, [("asm", text, vscan)])
+    if o.compound:
+        extensions.compound_files(run, [("asm", text, cscan)])
+    if o.dups:
+        extensions.dups_files(run, [own["dups"]])
     return 0
 
 

@@ -36,23 +36,45 @@ def _row(name, stage, length, c, k):
     return "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%s\t%s\n" % (name, stage, length, w, v, u, a, qv_text(u, v, k), qv_text(a, v, k))
 
 
+def column_sums(rows, width):
+    """the sums of the first `width` columns over the contigs that have a row (None = contig missing)"""
+    return tuple(sum(r[i] for r in rows if r is not None) for i in range(width))
+
+
+def stage_table_text(header, names, stages, row, zero, sums):
+    """the table that every scan writes.  stages: [(stage name, lengths, rows)], lengths[i] / rows[i] = contig i's length and counters,
+    or None for a contig that stage does not have (length 0 and the row `zero`).  Per contig in the order of `names` one line per
+    stage, then one line per stage for contig `*` with sums(rows); row(name, stage, length, r) makes a line."""
+    out = [header]
+    for i, name in enumerate(names):
+        for stage, lengths, rows in stages:
+            r = rows[i]
+            out.append(row(name, stage, lengths[i] if r is not None else 0, r if r is not None else zero))
+    for stage, lengths, rows in stages:
+        out.append(row("*", stage, sum(ln for ln, r in zip(lengths, rows) if r is not None), sums(rows)))
+    return "".join(out)
+
+
+def vcf_preamble(source, names, lengths, infos):
+    """the lines of a VCFv4.2 file before its records: `##source=jasper_amd <source>`, one `##contig` line per contig in the order of
+    `names`, one `##INFO` line per (ID, Type, Description) of `infos` (Number=1 each) and the column line"""
+    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd %s\n" % source]
+    out += ["##contig=<ID=%s,length=%d>\n" % (name, ln) for name, ln in zip(names, lengths)]
+    out += ['##INFO=<ID=%s,Number=1,Type=%s,Description="%s">\n' % info for info in infos]
+    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+    return out
+
+
 def totals(counts):
     """column sums of the (windows, valid, unreliable, absent) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(4))
+    return column_sums(counts, 4)
 
 
 def qv_tsv_text(k, names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and (windows, valid, unreliable,
     absent), or None for a contig that stage does not have (a row of zeros and NA).  Per contig in the order of `names` one row
     per stage, then one row per stage for contig `*` with the sums."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else (0, 0, 0, 0), k))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts), k))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, lambda name, stage, length, c: _row(name, stage, length, c, k), (0, 0, 0, 0), totals)
 
 
 def bed_text(k, names, runs):

@@ -12,7 +12,7 @@ covers one of them holds the other allele of the other; insertions and deletions
 
 Nothing here touches the GPU: the functions take names, lengths, counters and records.
 """
-from .report import align, contig_name, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
+from .report import align, column_sums, contig_name, stage_table_text, vcf_preamble, write_atomic  # noqa: F401  (every file of this module is written through write_atomic)
 
 TSV_HEADER = "#contig\tstage\tlength\tevaluated\thet\terror\thet_per_kb\n"
 KINDS = {1: "het", 2: "error"}
@@ -33,21 +33,14 @@ def _row(name, stage, length, c):
 
 def totals(counts):
     """column sums of the (evaluated, het, error) of the contigs that have any (None = contig missing)"""
-    return tuple(sum(c[i] for c in counts if c is not None) for i in range(3))
+    return column_sums(counts, 3)
 
 
 def variants_tsv_text(names, stages):
     """stages: [(stage name, lengths, counts)], lengths[i] / counts[i] = contig i's length and three counters, or None for a contig
     that stage does not have (a row of zeros and NA).  Per contig in the order of `names` one row per stage, then one row per
     stage for contig `*` with the sums."""
-    out = [TSV_HEADER]
-    for i, name in enumerate(names):
-        for stage, lengths, counts in stages:
-            c = counts[i]
-            out.append(_row(name, stage, lengths[i] if c is not None else 0, c if c is not None else ZERO))
-    for stage, lengths, counts in stages:
-        out.append(_row("*", stage, sum(ln for ln, c in zip(lengths, counts) if c is not None), totals(counts)))
-    return "".join(out)
+    return stage_table_text(TSV_HEADER, names, stages, _row, ZERO, totals)
 
 
 def _letter(v):
@@ -65,14 +58,10 @@ def _rec_fields(r):
 def vcf_text(k, thre, names, lengths, records):
     """VCFv4.2: one `##contig` line per contig in the order of `names`, then one line per record, sorted by (seq, pos, alt) whatever
     order they come in: name, pos + 1 (VCF positions are 1-based), ., REF, ALT, ., ., KIND=het|error;RC=ref_min;AC=alt_min"""
-    out = ["##fileformat=VCFv4.2\n", "##source=jasper_amd variant scan, k=%d, threshold=%d\n" % (k, thre)]
-    for name, ln in zip(names, lengths):
-        out.append("##contig=<ID=%s,length=%d>\n" % (name, ln))
-    out.append('##INFO=<ID=KIND,Number=1,Type=String,Description="het: the contig\'s base and the alternative are both solid in the reads; '
-               'error: only the alternative is">\n')
-    out.append('##INFO=<ID=RC,Number=1,Type=Integer,Description="smallest read count of the k k-mers that cover the position, with the contig\'s base">\n')
-    out.append('##INFO=<ID=AC,Number=1,Type=Integer,Description="smallest read count of those k-mers with the alternative base">\n')
-    out.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+    out = vcf_preamble("variant scan, k=%d, threshold=%d" % (k, thre), names, lengths, [
+        ("KIND", "String", "het: the contig's base and the alternative are both solid in the reads; error: only the alternative is"),
+        ("RC", "Integer", "smallest read count of the k k-mers that cover the position, with the contig's base"),
+        ("AC", "Integer", "smallest read count of those k-mers with the alternative base")])
     for seq, pos, ref, alt, rmin, amin, kind in sorted(_rec_fields(r) for r in records):
         out.append("%s\t%d\t.\t%s\t%s\t.\t.\tKIND=%s;RC=%d;AC=%d\n" % (names[seq], pos + 1, ref, alt, KINDS[kind], rmin, amin))
     return "".join(out)
