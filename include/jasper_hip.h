@@ -245,6 +245,11 @@ int jasper_result_lookups(const jasper_result *r, uint64_t *n);
 double jasper_result_seconds(const jasper_result *r);         /* device time of the passes (HIP events) */
 /* how the batch was parallelised: segments walked over all passes, chunks redone unsegmented after a failed speculation */
 int jasper_result_segments(const jasper_result *r, uint64_t *n_segments, uint64_t *n_respeculated);
+/* where a pass may cut a chunk of a table of this k into segments (no GPU call; tests restate the rule from these):
+ * out5 = TMIN (least distance between sync points, and from the last one to the chunk end), CMIN (least distance between a
+ * clean-zone boundary and its neighbours), CLEAN_CELL (one boundary candidate per this many positions), W (clean windows
+ * required left of a sync point), M (text a segment keeps right of the next sync point) */
+int jasper_polish_cut_geometry(int k, int64_t out5[5]);
 /* 1 if the batch had to be repeated with larger internal buffers (results are the same either way) */
 int jasper_result_retried(const jasper_result *r);
 void jasper_result_free(jasper_result *r);

@@ -179,6 +179,7 @@ SYMBOLS = {
     "jasper_result_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "jasper_result_seconds": (C.c_double, [_P]),
     "jasper_result_segments": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jasper_polish_cut_geometry": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
     "jasper_result_retried": (C.c_int, [_P]),
     "jasper_result_free": (None, [_P]),
     "jasper_kmer_report": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),

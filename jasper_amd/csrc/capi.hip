@@ -799,6 +799,12 @@ int jasper_result_qv_chunk(const jasper_result *r, int chunk, int64_t out4[4]) {
     for (int i = 0; i < 4; ++i) out4[i] = r->qv_chunk[4 * (size_t)chunk + i];
     return JASPER_OK;
 }
+int jasper_polish_cut_geometry(int k, int64_t out5[5]) {
+    if (k < 1 || k > 64 || !out5) { g_err = "jasper_polish_cut_geometry: k must be 1 .. 64"; return JASPER_ERR; }
+    const CutGeometry g = cut_geometry(k);
+    out5[0] = g.tmin; out5[1] = g.cmin; out5[2] = g.clean_cell; out5[3] = g.w; out5[4] = g.m;
+    return JASPER_OK;
+}
 int jasper_result_retried(const jasper_result *r) { return r ? r->retried : 0; }
 void jasper_result_free(jasper_result *r) {
     if (r && r->owner && r->owner->pending == r) r->owner->pending = nullptr;

@@ -138,6 +138,15 @@ struct ScanChunk {
     uint32_t n_cells;
 };
 constexpr int64_t CLEAN_CELL = 65536;
+// where a pass may cut a chunk (polish_host.hip: build_segments; jasper_polish_cut_geometry reports the same numbers)
+struct CutGeometry {
+    int64_t tmin;        // minimum distance between sync points, and from the last one to the chunk end
+    int64_t cmin;        // minimum distance between a clean-zone boundary and its neighbours
+    int64_t clean_cell;  // one clean-zone boundary candidate per this many positions
+    int64_t w;           // clean windows required left of a sync point = text a segment re-reads left of its boundary
+    int64_t m;           // text kept right of the next sync point
+};
+inline CutGeometry cut_geometry(int k) { return CutGeometry{1024, 32768, CLEAN_CELL, 4ll * k, 3ll * k}; }
 // pass 0: dense scan (counts stay in LDS) + classes + sync-point candidates of every chunk
 void launch_scan_batch(const TableDev &T, const ScanChunk *d_chunks, int n_chunks, int k, uint32_t solid, hipStream_t stream);
 // later passes: classes were carried over by the stitch; recompute the 64-window tiles next to changed text, then candidates

@@ -42,10 +42,23 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
     const int64_t RM = roomy ? 8 : 1;
     const bool tight = !roomy && getenv("JASPER_POLISH_TIGHT") != nullptr;   // tests: make the first attempt run out of room
     const int k = T.k;
-    const int64_t W = 4ll * k;        // clean window required left of a sync point
-    const int64_t M = 3ll * k;        // text kept right of the next sync point
-    const int64_t TMIN = 1024;        // minimum distance between sync points
-    const int64_t CMIN = 32768;       // minimum distance between a clean-zone boundary and its neighbours
+    const CutGeometry geo = cut_geometry(k);
+    const int64_t W = geo.w, M = geo.m, TMIN = geo.tmin, CMIN = geo.cmin;
+    // tests: chunks (lane-local indices, or "all") treated in every pass as if their speculation had failed
+    const char *const test_redo = getenv("JASPER_POLISH_TEST_REDO");
+    // tests: the redo finds no spare room behind the good segments and redoes every chunk unsegmented
+    const bool test_redo_noroom = getenv("JASPER_POLISH_TEST_REDO_NOROOM") != nullptr;
+    std::vector<char> forced;         // per chunk: JASPER_POLISH_TEST_REDO lists it
+    if (test_redo && *test_redo) {
+        forced.assign((size_t)std::max(n_chunks, 0), (char)(strcmp(test_redo, "all") == 0));
+        for (const char *p = test_redo; *p && !forced.empty() && strcmp(test_redo, "all") != 0;) {
+            char *e = nullptr;
+            const long c = strtol(p, &e, 10);
+            if (e == p) break;
+            if (c >= 0 && c < n_chunks) forced[(size_t)c] = 1;
+            p = *e == ',' ? e + 1 : e;
+        }
+    }
     HIPCHK(hipSetDevice(T.device));
     const int ws_base = lane ? Table::WS_LANE0 + (lane - 1) * Table::WS_POLISH_MAX : 0, pin_base = lane * Table::PIN_PER_LANE;
     R.seqs.assign(n_chunks, std::string());
@@ -200,6 +213,8 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
     HIPCHK(hipEventRecord(ev0, st));
 
     std::vector<SegDev> segs;
+    std::vector<int64_t> idx_base;                  // the host's own bookkeeping (rare path).  These four and `segs` go up with asynchronous
+    std::vector<uint32_t> seq_base, rec_off, aux_off;   // copies: they live across passes, so also across a `break` out of the pass loop
     std::vector<ScanChunk> sc(n_chunks);            // lives across passes: the async H2D copy reads it after the call returns
     int64_t *const d_count = b_cells.as<int64_t>(), *const d_cells = d_count + 2, *const d_cands = d_cells + cell_items;
     std::vector<int64_t> all_cands(cand_items);     // every chunk's sync-point candidates, fetched with one copy per pass
@@ -371,10 +386,8 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
         // ---- 3. + 4. the bookkeeping per chunk came back as summaries.  Anything out of the ordinary -- a segment that ran out of
         //         room, the reference's own IndexError, a speculation that failed -- takes the host's own bookkeeping (below),
         //         on the whole segment table; so does the debug output, which wants every segment's counters.
-        bool ordinary = !getenv("JASPER_POLISH_DEBUG") && !getenv("JASPER_POLISH_HOST_BOOKKEEPING");      // (the second: tests take the rare path every time)
+        bool ordinary = !getenv("JASPER_POLISH_DEBUG") && !getenv("JASPER_POLISH_HOST_BOOKKEEPING") && forced.empty();   // (the second and third: tests take the rare path every time)
         for (int c = 0; c < n_chunks && ordinary; ++c) ordinary = sum_p[c].bad_seg < 0 && !sum_p[c].spec_fail;
-        std::vector<int64_t> idx_base;
-        std::vector<uint32_t> seq_base, rec_off, aux_off;
         std::vector<int64_t> newlen(n_chunks, 0), shift(n_chunks, 0);
         std::vector<uint32_t> seqc(n_chunks, 0);
         size_t nrec_pass = 0, naux_pass = 0;
@@ -400,6 +413,8 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
         bool any_failed = false;
         for (const SegDev &S : segs)
             if (S.spec_fail && S.status == PS_OK) { failed[S.chunk] = 1; any_failed = true; }
+        for (size_t c = 0; c < forced.size(); ++c)
+            if (forced[c]) { failed[c] = 1; any_failed = true; }
         if (any_failed) {
             std::vector<int> redo;
             for (int c = 0; c < n_chunks; ++c) if (failed[c]) redo.push_back(c);
@@ -422,7 +437,7 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
                 S.edits = b_segedit.as<EditRec>() + r2; r2 += S.rec_cap;
                 S.aux = b_segaux.as<uint8_t>() + a2;   a2 += al256(S.aux_cap);
             }
-            if (t2 > seg_text_bound || r2 > seg_rec_bound || a2 > seg_aux_bound) {
+            if (test_redo_noroom || t2 > seg_text_bound || r2 > seg_rec_bound || a2 > seg_aux_bound) {
                 // not enough spare room: fall back to redoing EVERYTHING unsegmented (always fits)
                 segs.assign((size_t)max_segs, SegDev{});
                 size_t nall = 0;
@@ -546,10 +561,12 @@ static int run_polish_lane(Table &T, const int lane, hipStream_t st, int n_chunk
                           carry ? (uint8_t *const *)ptrFlags : nullptr, st);
         HIPCHK(hipGetLastError());
         for (int c = 0; c < n_chunks; ++c) len[c] = newlen[c];
-        // The host's own bookkeeping went up from vectors of THIS iteration (segs, idx_base, seq_base, rec_off, aux_off: ordinary host
-        // memory): an asynchronous copy may read its source when the stream gets to it, not when it is issued -- the vectors must
-        // outlive that.  (Round 5: without this wait a chunk whose speculation had failed now and then came back with the records
-        // or the text of freed memory: 1 run in ~1 000 of one fuzz case, on some boxes.)  The rare path can afford the wait.
+        // A precaution.  The host's own bookkeeping went up from ordinary host memory (segs, idx_base, seq_base, rec_off, aux_off): an
+        // asynchronous copy may read its source when the stream gets to it, not when it is issued, so the vectors must not change or
+        // go before that.  The wait was added in round 5, when four of them were vectors of the iteration and it was what kept them
+        // alive; now all five live across passes and the next pass waits for the stream before it touches them.  Round 5's open
+        // observation (seed 995395 differing from the oracle now and then) is NOT established to have come from
+        // here.  The rare path can afford the wait; tests/test_gpu_polish_paths.py takes this path in every pass.
         if (!ordinary) HIPCHK(jk_stream_wait(st));
         // the text just written is read next; the next pass writes into the arena that is free (never into the caller's buffer)
         std::swap(hIn, hOut);

@@ -1181,6 +1181,13 @@ class KmerTable:
         runs = _records(self._L.jasper_report_runs, res, _lib.KmerRun, KMERRUN_DTYPE)
         return KmerReport(counts, runs, self._L.jasper_report_seconds(res), bool(self._L.jasper_report_retried(res)))
 
+    @staticmethod
+    def polish_cut_geometry(k):
+        """{TMIN, CMIN, CLEAN_CELL, W, M} of the polisher's segment cuts for this k (tests restate the cut rule from these)"""
+        out = (C.c_int64 * 5)()
+        check(_lib.lib().jasper_polish_cut_geometry(int(k), out))
+        return dict(zip(("TMIN", "CMIN", "CLEAN_CELL", "W", "M"), (int(v) for v in out)))
+
     def _wrap_result(self, rc, res, n, want_str):
         try:
             check(rc)
