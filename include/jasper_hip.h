@@ -827,6 +827,103 @@ int jasper_dupmap_seconds(const jasper_dupmap *r, double *index, double *scan); 
 int jasper_dupmap_retried(const jasper_dupmap *r);
 void jasper_dupmap_free(jasper_dupmap *r);
 
+/* Gap scan: WHAT the reads hold in place of a scaffold gap, or of a run of unreliable k-mers too long for jasper_compound_scan.
+ *
+ * What it replaces: nothing -- an EXTENSION (a Sealer-style closure).  A window that holds a non-base byte has no k-mer, so an N run is
+ * invisible to every scan above; and jasper_compound_scan counts a run that replaces more than 64 bytes as `long` and stops.  This scan
+ * walks the solid k-mers of the reads from the left flank of such a place until they rejoin its right flank, for up to 4096 bases.
+ * For a sequence s of n bytes (case folded; a BASE is one of ACGT), the table's k >= 2, thre >= 1, 0 <= max_len <= JASPER_GAP_MAX_LEN =
+ * 4096 and max_trim >= 0 (anything else is JASPER_ERR with a message that names the argument, even with nothing to scan); cnt() = the
+ * table's count of a canonical k-mer, clamped to 2^32-1 as jasper_lookup clamps; FRONT = JASPER_GAP_FRONT = 64, MAXREC =
+ * JASPER_GAP_MAX_RECORDS = 16.  Window w (0 <= w <= n-k) is VALID when its k bytes are bases and SOLID when it is valid and cnt >= thre.
+ *   sites          a STRETCH is a maximal run [u0, u1] of windows that are not solid, invalid or unreliable.  Its kind is GAP when it
+ *                  holds at least one invalid window, and RUN when it holds none and u1 - u0 + 2 - k > JASPER_GAP_RUN_MIN = 64 -- exactly
+ *                  what jasper_compound_scan calls long at its default; the 64 is fixed.  Other stretches are no sites, and RUN sites
+ *                  exist only when long_runs is set.  For a site a = u0 + k - 1, q = u1 + 1, F = s[a-k+1 .. a) = the last k - 1 bases of
+ *                  the solid window before the stretch, G = s[q .. q+k-1) = the first k - 1 of the solid window after it, and the R =
+ *                  q - a bytes s[a .. q) are what a fill replaces.  So N runs with fewer than k bases between them are one site, and
+ *                  an unreliable run that touches a gap is part of its site (a dirty contig end).
+ *   a site is      EDGE when u0 = 0 or u1 = n-k (no solid window on that side; its trims are 0); else RAGGED when trim_left or
+ *                  trim_right exceeds max_trim -- trim_left = (first non-base byte of the stretch) - a, trim_right = q - (last
+ *                  non-base byte + 1), both 0 for kind RUN; else SEARCHED.  ref_min = the smallest cnt over the stretch's valid
+ *                  windows, 0 when it has none.
+ *   the search     per searched site, S_0 = {empty string}.  At level t = 0, 1, 2, .. in this order:
+ *                  1 rejoin  every y in S_t whose windows t .. t+k-2 of F + y + G (the k - 1 that hold a base of G) are all solid is a
+ *                            record of level t.  If the site's records so far plus this level's exceed MAXREC, the level lists none of
+ *                            them, the site is COMPLEX and the search ends (levels = t).
+ *                  2 close   every y with t >= k - 1 whose last k - 1 bases equal G leaves S_t: it is a record followed by the whole
+ *                            right flank, and what follows it is the sequence.
+ *                  3 stop    t = max_len: the search ends, LIMIT if S_t is not empty, else DEAD.  S_t empty: DEAD.  (levels = t)
+ *                  4 extend  S_(t+1) = { yz : y in S_t, z in ACGT, cnt(the last k bases of F + yz) >= thre }.  |S_(t+1)| > FRONT: the site
+ *                            is COMPLEX, records of lengths <= t stay; S_(t+1) empty: DEAD.  In both cases levels = t + 1, the level
+ *                            that could not be formed.
+ *   record         {seq, pos = a, ref_len = R, len = t, y, alt_min}; alt_min = the minimum of cnt over all t + k - 1 windows of
+ *                  F + y + G.  y is len upper-case letters at bases_off of the result's byte pool.  Ordered by (seq, pos, len, y), and
+ *                  the pool holds the strings in that order.
+ *   per sequence   nine counters: sites, searched, bridged (at least one record), unique (exactly one record and not complex),
+ *                  records, edge, ragged, limit, complex
+ * The rule is one of sets, not of a search order: sites, records and bytes are identical on every call.  The table is not modified.
+ *
+ * Limits: the walk is over EXACT k-mers of the reads (a gap whose true sequence has a read-coverage hole stays open); a het bubble
+ * inside a gap multiplies the front, and both alleles are records (such a site is not unique); the closing rule ends a tandem
+ * expansion at k - 1 bases -- inside (ACG)x40 at k = 21 the lengths 0, 3, .., 18 are listed and the search ends dead; there are no
+ * negative gaps (contig ends that overlap are not joined); at most MAXREC fills of one site are listed.
+ *
+ * On the device jasper_kmer_report's scan runs unchanged; one more dense kernel lists the runs of invalid windows (no table probe);
+ * the host makes the sites; one more kernel searches them, one wave each, and keeps the strings in a per-wave log in global memory
+ * (64 bytes a level), not in registers.  With no site to search nothing of the search is allocated or launched.
+ *   jasper_gap_scan, _device        as jasper_kmer_report / _device, with max_len, max_trim and long_runs (0 / 1)
+ *   jasper_gap_search, _device      the search alone on a caller's sites: a, q, seq and ref_min of each entry are read, the rest is
+ *                                   ignored.  They must be in (seq, a) order, no two at one place, with k-1 <= a <= q <= n-(k-1);
+ *                                   anything else is JASPER_ERR and launches nothing.  A site whose flanks are not all bases comes back
+ *                                   SKIPPED; kind is 0, the trims are 0 and ref_min is the caller's.  The result has no report.
+ *   jasper_gapscan_counts           out9 of one sequence, in the order above
+ *   jasper_gapscan_sites, _records  the site list, ordered by (seq, a), and the record list (owned by the result)
+ *   jasper_gapscan_bases            the byte pool the records' bases_off point into (owned by the result)
+ *   jasper_gapscan_report           the report of the same input, owned by the result (do not free it)
+ *   jasper_gapscan_seconds          device time (HIP events) of the search kernel (*search), of the invalid-window scan (*runs) and of
+ *                                   both and the dense report (*total)
+ *   jasper_gapscan_lookups          table lookups the search made;  jasper_gapscan_retried: it was repeated with larger lists
+ *   jasper_gap_front, _max_records, _max_len    the constants as the library was built */
+#define JASPER_GAP_FRONT 64
+#define JASPER_GAP_MAX_RECORDS 16
+#define JASPER_GAP_MAX_LEN 4096
+#define JASPER_GAP_RUN_MIN 64
+enum { JASPER_GAP_KIND_EXPLICIT = 0, JASPER_GAP_KIND_GAP = 1, JASPER_GAP_KIND_RUN = 2 };
+enum { JASPER_GAP_DEAD = 1, JASPER_GAP_LIMIT = 2, JASPER_GAP_COMPLEX = 3, JASPER_GAP_EDGE = 4, JASPER_GAP_RAGGED = 5, JASPER_GAP_SKIPPED = 6 };
+typedef struct jasper_gapscan jasper_gapscan;
+typedef struct jasper_gap_site {
+    int64_t a, q;
+    uint32_t seq, ref_min, n_records, levels /* the t at which the search ended */, trim_left, trim_right;
+    uint8_t kind /* JASPER_GAP_KIND_* */, status /* JASPER_GAP_DEAD .. */, pad[6] /* 0 */;
+} jasper_gap_site; /* 48 B */
+typedef struct jasper_gap_fill {
+    int64_t pos;
+    uint64_t bases_off; /* y = len letters from here in jasper_gapscan_bases */
+    uint32_t seq, ref_len, len, alt_min;
+} jasper_gap_fill; /* 32 B */
+int jasper_gap_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, int64_t max_trim, int long_runs,
+                    jasper_gapscan **out);
+int jasper_gap_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, int64_t max_trim, int long_runs,
+                           jasper_gapscan **out);
+int jasper_gap_search(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, const jasper_gap_site *sites, uint64_t n_sites,
+                      jasper_gapscan **out);
+int jasper_gap_search_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, const jasper_gap_site *sites,
+                             uint64_t n_sites, jasper_gapscan **out);
+int jasper_gapscan_num_seqs(const jasper_gapscan *r);
+int jasper_gapscan_counts(const jasper_gapscan *r, int seq, uint64_t out9[9]);   /* sites, searched, bridged, unique, records, edge, ragged, limit, complex */
+int jasper_gapscan_sites(const jasper_gapscan *r, const jasper_gap_site **sites, uint64_t *n);
+int jasper_gapscan_records(const jasper_gapscan *r, const jasper_gap_fill **recs, uint64_t *n);
+int jasper_gapscan_bases(const jasper_gapscan *r, const char **bases, uint64_t *n);
+const jasper_report *jasper_gapscan_report(const jasper_gapscan *r);
+int jasper_gapscan_seconds(const jasper_gapscan *r, double *search, double *runs, double *total);
+int jasper_gapscan_lookups(const jasper_gapscan *r, uint64_t *n);
+int jasper_gapscan_retried(const jasper_gapscan *r);
+int jasper_gap_front(void);
+int jasper_gap_max_records(void);
+int jasper_gap_max_len(void);
+void jasper_gapscan_free(jasper_gapscan *r);
+
 /* The assembly side of src/jasper.sh, natively and by several host threads (no GPU call except jasper_asm_polish):
  *   jasper_asm_open          the assembly FASTA read once into ONE host arena (line ends taken out, contigs back to back).  Returns 1
  *                            (not an error, *out = NULL) for anything but the ordinary file -- '\r', a first byte that is not '>',

@@ -108,6 +108,21 @@ class RepairRound(C.Structure):
 
 assert C.sizeof(RepairRound) == 48
 
+
+class GapSite(C.Structure):
+    _fields_ = [("a", C.c_int64), ("q", C.c_int64), ("seq", C.c_uint32), ("ref_min", C.c_uint32), ("n_records", C.c_uint32), ("levels", C.c_uint32),
+                ("trim_left", C.c_uint32), ("trim_right", C.c_uint32), ("kind", C.c_uint8), ("status", C.c_uint8), ("pad", C.c_uint8 * 6)]
+
+
+assert C.sizeof(GapSite) == 48
+
+
+class GapFill(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("bases_off", C.c_uint64), ("seq", C.c_uint32), ("ref_len", C.c_uint32), ("len", C.c_uint32), ("alt_min", C.c_uint32)]
+
+
+assert C.sizeof(GapFill) == 32
+
 # every symbol include/jasper_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -277,6 +292,23 @@ SYMBOLS = {
     "jasper_repaired_after": (_P, [_P]),
     "jasper_repaired_seconds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "jasper_repaired_free": (None, [_P]),
+    "jasper_gap_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int64, C.c_int, C.POINTER(_P)]),
+    "jasper_gap_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, C.c_int64, C.c_int, C.POINTER(_P)]),
+    "jasper_gap_search": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int, _P, C.c_uint64, C.POINTER(_P)]),
+    "jasper_gap_search_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_int, _P, C.c_uint64, C.POINTER(_P)]),
+    "jasper_gapscan_num_seqs": (C.c_int, [_P]),
+    "jasper_gapscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_gapscan_sites": (C.c_int, [_P, C.POINTER(C.POINTER(GapSite)), C.POINTER(C.c_uint64)]),
+    "jasper_gapscan_records": (C.c_int, [_P, C.POINTER(C.POINTER(GapFill)), C.POINTER(C.c_uint64)]),
+    "jasper_gapscan_bases": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "jasper_gapscan_report": (_P, [_P]),
+    "jasper_gapscan_seconds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "jasper_gapscan_lookups": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_gapscan_retried": (C.c_int, [_P]),
+    "jasper_gap_front": (C.c_int, []),
+    "jasper_gap_max_records": (C.c_int, []),
+    "jasper_gap_max_len": (C.c_int, []),
+    "jasper_gapscan_free": (None, [_P]),
     "jasper_asm_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "jasper_asm_close": (None, [_P]),
     "jasper_asm_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -4,6 +4,7 @@ polisher.  Lines are cited as src/jasper.sh:N.
 
     python -m jasper_amd.cli -r 'R1.fq R2.fq' -a asm.fa -k 37 -t 16 -p 2 [--gpus N] [--report] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants]
                             [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]]
+                            [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs] [--gaps-fill]]
                             [--repair [--repair-rounds N]]
                             [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
                              [--phase-short-range D] [--phase-max-switches S]]
@@ -22,7 +23,7 @@ import re
 import sys
 
 from . import extensions, polisher, qv
-from .extensions import (compound_flags, copies_flags, copies_peak, dups_flags, hapmer_flags, het_cluster_flags, indel_flags,      # noqa: F401 -- the
+from .extensions import (compound_flags, copies_flags, copies_peak, dups_flags, gap_flags, scan_gaps, hapmer_flags, het_cluster_flags, indel_flags,      # noqa: F401 -- the
                          indel_mixed_flag, repair_flags, run_repair, scan_compound, scan_variants)                                # extensions' own checks and scans
 from .table import KmerTable
 

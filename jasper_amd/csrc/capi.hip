@@ -15,6 +15,7 @@
 #include "compound.hpp"
 #include "repair.hpp"
 #include "dups.hpp"
+#include "gaps.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cmath>
@@ -73,6 +74,10 @@ struct jasper_report {
 struct jasper_compscan {
     CompoundOut r;
     jasper_report rep;                   // the report of the same call, written by the scan itself: what jasper_compscan_report hands out
+};
+struct jasper_gapscan {
+    GapOut r;
+    jasper_report rep;                   // the report of the same call (empty after jasper_gap_search): what jasper_gapscan_report hands out
 };
 struct jasper_repaired {
     RepairOut r;
@@ -1063,5 +1068,68 @@ int jasper_repaired_seconds(const jasper_repaired *r, double *apply, double *tot
     return JASPER_OK;
 }
 void jasper_repaired_free(jasper_repaired *r) { delete r; }
+
+// ---- gap scan (gaps.hip) ----
+static_assert(offsetof(jasper_gap_site, q) == offsetof(GapSite, q) && offsetof(jasper_gap_site, seq) == offsetof(GapSite, seq) &&
+                  offsetof(jasper_gap_site, ref_min) == offsetof(GapSite, ref_min) && offsetof(jasper_gap_site, n_records) == offsetof(GapSite, n_records) &&
+                  offsetof(jasper_gap_site, levels) == offsetof(GapSite, levels) && offsetof(jasper_gap_site, trim_left) == offsetof(GapSite, trim_left) &&
+                  offsetof(jasper_gap_site, trim_right) == offsetof(GapSite, trim_right) && offsetof(jasper_gap_site, kind) == offsetof(GapSite, kind) &&
+                  offsetof(jasper_gap_site, status) == offsetof(GapSite, status),
+              "jasper_gap_site is GapSite");
+static_assert(offsetof(jasper_gap_fill, bases_off) == offsetof(GapFill, bases_off) && offsetof(jasper_gap_fill, seq) == offsetof(GapFill, seq) &&
+                  offsetof(jasper_gap_fill, ref_len) == offsetof(GapFill, ref_len) && offsetof(jasper_gap_fill, len) == offsetof(GapFill, len) &&
+                  offsetof(jasper_gap_fill, alt_min) == offsetof(GapFill, alt_min),
+              "jasper_gap_fill is GapFill");
+static_assert(sizeof(jasper_gap_site) == 48 && sizeof(jasper_gap_fill) == 32, "jasper_gap_site is 48 bytes, jasper_gap_fill 32");
+static_assert(JASPER_GAP_FRONT == GAP_FRONT && JASPER_GAP_MAX_RECORDS == GAP_MAX_RECORDS && JASPER_GAP_MAX_LEN == GAP_MAX_LEN && JASPER_GAP_RUN_MIN == GAP_RUN_MIN &&
+                  JASPER_GAP_SKIPPED == GAP_SKIPPED && JASPER_GAP_KIND_RUN == GAP_KIND_RUN,
+              "the header's constants are the kernel's");
+int jasper_gap_scan(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, int64_t max_trim, int long_runs,
+                    jasper_gapscan **out) {
+    return scan_call(host_args(n_seqs, seqs, lens), t, n_seqs, out,
+                     [&](jasper_gapscan &r) { return gap_scan_host(t->t, n_seqs, seqs, lens, thre, max_len, max_trim, long_runs != 0, r.rep.r, r.r, g_err); });
+}
+int jasper_gap_scan_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, int64_t max_trim, int long_runs,
+                           jasper_gapscan **out) {
+    return scan_call(offsets, t, n_seqs, out, [&](jasper_gapscan &r) {
+        return gap_scan_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, max_trim, long_runs != 0, r.rep.r, r.r, g_err);
+    });
+}
+int jasper_gap_search(jasper_table *t, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, int max_len, const jasper_gap_site *sites, uint64_t n_sites,
+                      jasper_gapscan **out) {
+    return scan_call(host_args(n_seqs, seqs, lens), t, n_seqs, out, [&](jasper_gapscan &r) {
+        return gap_search_host(t->t, n_seqs, seqs, lens, thre, max_len, reinterpret_cast<const GapSite *>(sites), n_sites, r.r, g_err);
+    });
+}
+int jasper_gap_search_device(jasper_table *t, int n_seqs, const void *d_text, const int64_t *offsets, uint32_t thre, int max_len, const jasper_gap_site *sites,
+                             uint64_t n_sites, jasper_gapscan **out) {
+    return scan_call(offsets, t, n_seqs, out, [&](jasper_gapscan &r) {
+        return gap_search_device(t->t, n_seqs, (const uint8_t *)d_text, offsets, thre, max_len, reinterpret_cast<const GapSite *>(sites), n_sites, r.r, g_err);
+    });
+}
+int jasper_gapscan_num_seqs(const jasper_gapscan *r) { return r ? (int)(r->r.counts.size() / GAP_COUNTS) : 0; }
+int jasper_gapscan_counts(const jasper_gapscan *r, int seq, uint64_t out9[9]) { return counts_out<GAP_COUNTS>(r ? &r->r.counts : nullptr, seq, out9); }
+int jasper_gapscan_sites(const jasper_gapscan *r, const jasper_gap_site **sites, uint64_t *n) { return records_out(r ? &r->r.sites : nullptr, sites, n); }
+int jasper_gapscan_records(const jasper_gapscan *r, const jasper_gap_fill **recs, uint64_t *n) { return records_out(r ? &r->r.fills : nullptr, recs, n); }
+int jasper_gapscan_bases(const jasper_gapscan *r, const char **bases, uint64_t *n) {
+    if (!r || !bases || !n) { g_err = "bad argument"; return JASPER_ERR; }
+    *bases = r->r.pool.data();
+    *n = r->r.pool.size();
+    return JASPER_OK;
+}
+const jasper_report *jasper_gapscan_report(const jasper_gapscan *r) { return r ? &r->rep : nullptr; }
+int jasper_gapscan_seconds(const jasper_gapscan *r, double *search, double *runs, double *total) {
+    if (!r) { g_err = "bad argument"; return JASPER_ERR; }
+    if (search) *search = r->r.search_seconds;
+    if (runs) *runs = r->r.runs_seconds;
+    if (total) *total = r->r.seconds;
+    return JASPER_OK;
+}
+int jasper_gapscan_lookups(const jasper_gapscan *r, uint64_t *n) { return word_out(r ? &r->r.lookups : nullptr, n); }
+int jasper_gapscan_retried(const jasper_gapscan *r) { return r ? r->r.retried : 0; }
+int jasper_gap_front(void) { return GAP_FRONT; }
+int jasper_gap_max_records(void) { return GAP_MAX_RECORDS; }
+int jasper_gap_max_len(void) { return GAP_MAX_LEN; }
+void jasper_gapscan_free(jasper_gapscan *r) { delete r; }
 
 }  // extern "C"

@@ -26,6 +26,9 @@ BOOL_FLAGS = (
     "--indel-mixed",     # the indel scan also lists insertions of mixed bases
     "--het-clusters",    # the indel scan also lists clusters of het differences less than k apart
     "--compound",        # what the reads hold for clusters of differences (compound_files)
+    "--gaps",            # what the reads hold in place of N gaps and of long runs of unreliable k-mers (gaps_files)
+    "--gap-long-runs",   # the gap scan also searches the runs the compound scan counts as long
+    "--gaps-fill",       # the driver writes the polished FASTA with the unique fills applied
     "--repair",          # the scans' error records applied to the polished contigs, in rounds (repair_files)
     "--hapmers",         # trio: parental markers, phase blocks and switch errors (hapmers_files)
 )
@@ -39,6 +42,8 @@ VALUE_FLAGS = dict({
     "--indel-max-len": "indel_max_len",               # longest insertion / deletion the indel scan tries (default 4, at most 16)
     "--het-cluster-max-len": "het_cluster_max_len",   # longest replacement the het-cluster search lists (default 64, at most 64)
     "--compound-max-len": "compound_max_len",         # longest replacement the compound scan searches (default 64, at most 64)
+    "--gap-max-len": "gap_max_len",                   # longest fill the gap scan searches (default 1000, from 0 to 4096)
+    "--gap-max-trim": "gap_max_trim",                 # most unreliable bases between a flank and the gap (default k, from 0 to 1000)
     "--repair-rounds": "repair_rounds",               # at most this many rounds of scan, select and apply (default 3, at most 8)
 }, **HAPMER_VALUE_FLAGS)
 
@@ -112,13 +117,18 @@ def dups_flags(dups, peak, min_run):
     return copies_flags(peak, None)[0], m
 
 
-def _length_flag(flag, given, default, most):
-    """a length as given (a string or None) -> int; exits on anything but an integer in 1..most"""
+def _range_flag(flag, given, default, least, most):
+    """a number as given (a string or None) -> int; exits on anything but an integer in least..most"""
     if given is None:
         return default
-    if not re.match(r"^[0-9]+$", str(given)) or not 1 <= int(given) <= most:
-        error_exit("%s takes an integer from 1 to %d; it is %s" % (flag, most, given))
+    if not re.match(r"^[0-9]+$", str(given)) or not least <= int(given) <= most:
+        error_exit("%s takes an integer from %d to %d; it is %s" % (flag, least, most, given))
     return int(given)
+
+
+def _length_flag(flag, given, default, most):
+    """a length as given (a string or None) -> int; exits on anything but an integer in 1..most"""
+    return _range_flag(flag, given, default, 1, most)
 
 
 INDEL_MAX_LEN_DEFAULT = 4
@@ -149,6 +159,21 @@ def het_cluster_flags(max_len, clusters=True, indels=True):
 def compound_flags(max_len):
     """--compound-max-len as given (a string or None) -> the longest replacement to search; exits on anything but an integer in 1..64"""
     return _length_flag("--compound-max-len", max_len, COMPOUND_MAX_LEN_DEFAULT, 64)
+
+
+GAP_MAX_LEN_DEFAULT = 1000
+
+
+def gap_flags(gaps, max_len, max_trim, long_runs=False, fill=False):
+    """--gaps, --gap-max-len and --gap-max-trim as given (a string or None), --gap-long-runs and --gaps-fill -> (max_len, max_trim or None
+    = k), (None, None) without --gaps; exits on one of the four options without --gaps and on anything but integers in 0..4096 and
+    0..1000"""
+    if not gaps:
+        for flag, on in (("--gap-max-len", max_len is not None), ("--gap-max-trim", max_trim is not None), ("--gap-long-runs", long_runs), ("--gaps-fill", fill)):
+            if on:
+                error_exit("%s is an option of the gap scan: give --gaps as well" % flag)
+        return None, None
+    return _range_flag("--gap-max-len", max_len, GAP_MAX_LEN_DEFAULT, 0, 4096), _range_flag("--gap-max-trim", max_trim, None, 0, 1000)
 
 
 def repair_flags(repair, rounds):
@@ -227,7 +252,7 @@ def _needs_threshold(flag, given):
 def scan_flags(o, given=None):
     """the flags of every extension but the hap-mer scan, checked in the one order both drivers keep (a bad value ends the run before it
     starts, not after the polishing) -> dict of peak, copies_min_run, dups_peak, dups_min_run (None: to be derived), indel_max_len,
-    clusters (0: no het-cluster search), compound_max_len, rounds (0: no repair), repair_lens.  given: kmerqc's --threshold."""
+    clusters (0: no het-cluster search), compound_max_len, gap_max_len, gap_max_trim (None: k), rounds (0: no repair), repair_lens.  given: kmerqc's --threshold."""
     f = {}
     f["peak"], f["copies_min_run"] = copies_flags(o.peak, o.copies_min_run) if o.copies else (None, None)
     f["dups_peak"], f["dups_min_run"] = dups_flags(o.dups, o.peak, o.dups_min_run)
@@ -241,6 +266,9 @@ def scan_flags(o, given=None):
     f["compound_max_len"] = compound_flags(o.compound_max_len) if o.compound else None
     if o.compound:
         _needs_threshold("compound", given)
+    f["gap_max_len"], f["gap_max_trim"] = gap_flags(o.gaps, o.gap_max_len, o.gap_max_trim, o.gap_long_runs, o.gaps_fill)
+    if o.gaps:
+        _needs_threshold("gaps", given)
     f["rounds"] = repair_flags(o.repair, o.repair_rounds)
     if f["rounds"]:     # (--repair honours the two scans' lengths, with or without --indels and --compound)
         f["repair_lens"] = indel_flags(o.indel_max_len), compound_flags(o.compound_max_len)
@@ -400,6 +428,14 @@ def scan_compound(table, contigs, thre, max_len):
     return names, lengths, table.compound_scan(seqs, thre, max_len)
 
 
+def scan_gaps(table, contigs, thre, max_len, max_trim=None, long_runs=False):
+    """the gap scan of whole contigs [(name token, sequence)] -> (names, lengths, GapScan), whose .report is the dense k-mer report of
+    the same contigs; exits on a threshold of 0"""
+    _solid_threshold("gaps", thre)
+    names, lengths, seqs = _whole_contigs(contigs)
+    return names, lengths, table.gap_scan(seqs, thre, max_len, max_trim, long_runs)
+
+
 def run_repair(table, contigs, thre, indel_max_len, compound_max_len, rounds):
     """the repair stage on whole contigs [(name token, sequence)] -> (names, lengths, Repair); exits on a threshold of 0"""
     _solid_threshold("repair", thre)
@@ -410,7 +446,7 @@ def run_repair(table, contigs, thre, indel_max_len, compound_max_len, rounds):
 def report_files(run, done):
     """--report (the driver; kmerqc always): the dense scan of WHOLE contigs, so the windows that span two chunk records are there, into
     `PREFIX.kmer_qv.tsv` and `PREFIX.unreliable[.before|.after].bed` (jasper_amd/report.py).  done: [(stage, Text, KmerReport)] -- with
-    --compound the reports that its scans hold, so that each stage is still ONE dense scan."""
+    --compound, or else --gaps, the reports that its scans hold, so that each stage is still ONE dense scan."""
     from . import report
     k, names = run.k, done[0][1].names
     table = aligned(done)
@@ -540,6 +576,28 @@ def compound_files(run, done):
     device_line("[compound] search device seconds: %s; lookups %s" % (per_stage(done, "%.6f", lambda cs: cs.search_seconds), " ".join("%d" % cs.lookups for _, _, cs in done)))
 
 
+def gaps_files(run, done):
+    """--gaps: for the N gaps (with --gap-long-runs also the long runs of unreliable k-mers) the strings of the reads' solid k-mers that
+    lead from the left flank to the right one, into `PREFIX.gaps.tsv`, `PREFIX.gaps[.before|.after].bed` and
+    `PREFIX.gapfills[.before|.after].tsv` (jasper_amd/gaps.py), each stage in its own text's coordinates; with --gaps-fill (the driver)
+    `PREFIX.gapfilled.fasta`, the polished FASTA with the unique fills of stage `after` applied.  done: [(stage, Text, GapScan)]"""
+    from . import gaps
+    table = aligned(done)
+    gaps.write_atomic(run.name("gaps", "tsv"), gaps.gaps_tsv_text(done[0][1].names, table))
+    for stage, text, gs in done:
+        recs = gs.record_tuples()
+        gaps.write_atomic(run.name("gaps", "bed", stage), gaps.bed_text(text.names, gs.sites, recs))
+        gaps.write_atomic(run.name("gapfills", "tsv", stage), gaps.fills_tsv_text(text.names, recs))
+    if run.o.gaps_fill:
+        from . import repair
+        stage, text, gs = done[-1]
+        with open(run.paths[stage], newline="") as f:
+            polished_text = f.read()
+        gaps.write_atomic(run.name("gapfilled", "fasta"), repair.fasta_text(polished_text, gaps.fill_sequences(text.seqs, gs.sites, gs.record_tuples())))
+    stages_log(run, "Gap scan", [gaps.stage_log_text(counts) for _, _, counts in table], run.name("gaps", "bed"))
+    device_line("[gaps] search device seconds: %s; lookups %s" % (per_stage(done, "%.6f", lambda gs: gs.search_seconds), " ".join("%d" % gs.lookups for _, _, gs in done)))
+
+
 def parent_table(who, files, jf, k, device):
     """one parent's reads counted into a whole table on `device`, or its database loaded -> KmerTable, the caller closes it.  A table
     that cannot be made -- unreadable input, or no room for it beside the other tables -- ends the run with a message that carries the
@@ -657,9 +715,19 @@ def driver_steps(o, hap):
     def compound_scans(run):        # first, because their dense half is the report's; the files come after the other extensions'
         run.done["compound"] = run.scanned(lambda text: scan_compound(run.table, text.contigs, run.thresh, run.f["compound_max_len"])[2])
 
+    def gap_scans(run):             # before the report when their dense half serves it (no --compound)
+        if "gaps" not in run.done:
+            run.done["gaps"] = run.scanned(lambda text: scan_gaps(run.table, text.contigs, run.thresh, run.f["gap_max_len"], run.f["gap_max_trim"], o.gap_long_runs)[2])
+
     def report(run):
-        report_files(run, [(stage, text, cs.report) for stage, text, cs in run.done["compound"]] if o.compound else
+        if o.gaps and not o.compound:
+            gap_scans(run)
+        report_files(run, [(stage, text, cs.report) for stage, text, cs in run.done["compound" if o.compound else "gaps"]] if o.compound or o.gaps else
                      run.scanned(lambda text: run.table.kmer_report(text.seqs, run.thresh)))
+
+    def gaps(run):
+        gap_scans(run)
+        gaps_files(run, run.done["gaps"])
 
     def asm_scans(run):             # --dups: the maps are made here, while the text's own table exists, and written after the other extensions
         run.derive_peaks()
@@ -708,6 +776,8 @@ def driver_steps(o, hap):
         steps.append((variants, "Writing the variant scan failed", "variant scan"))
     if o.compound:
         steps.append((lambda run: compound_files(run, run.done["compound"]), "Writing the compound scan failed", None))
+    if o.gaps:
+        steps.append((gaps, "The gap scan failed", "gap scan"))
     if hap is not None:
         steps.append((hapmers, "Writing the hap-mer scan failed", "hap-mer scan"))
     if o.dups:

@@ -3,7 +3,7 @@
     python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
                                 [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants]
                                 [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
-                                [--compound [--compound-max-len N]]
+                                [--compound [--compound-max-len N]] [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs]]
                                 [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N]
                                  [--phase-short-range D] [--phase-max-switches S]]
 
@@ -69,6 +69,17 @@ With --compound the runs of unreliable k-mers that two or more differences less 
     PREFIX.compound.tsv      per contig one row of stage `asm`: sites, bridged, records, long, complex; then contig `*`
     PREFIX.compound.vcf      VCFv4.2, one line per replacement: KIND=error;TYPE=mnp|complex;RLEN=..;LEN=..
 
+With --gaps the N gaps of the contigs -- which no other scan sees, because a window that holds a non-base byte has no k-mer -- and,
+with --gap-long-runs, the runs of unreliable k-mers that --compound counts as long are searched for the strings of the reads' solid
+k-mers that lead from the last solid window before them to the first one after them, up to --gap-max-len bases (default 1000, from 0
+to 4096; KmerTable.gap_scan, whose dense scan is the report's: without --compound still one per run); unreliable k-mers that touch a gap
+belong to its site, up to --gap-max-trim bases (default k, from 0 to 1000) on either side.  Three more files are written
+(jasper_amd/gaps.py); the threshold must be at least 1.  No assembly is written here: --gaps-fill is the driver's.
+
+    PREFIX.gaps.tsv          per contig one row of stage `asm`: sites, searched, bridged, unique, records, edge, ragged, limit, complex; then contig `*`
+    PREFIX.gaps.bed          one line per site: contig a q kind status n_records trim_left trim_right fill_len alt_min
+    PREFIX.gapfills.tsv      one line per record: contig pos ref_len len ref_min alt_min fill
+
 With --hapmers the reads are the CHILD's of a trio: the mother's and the father's reads are counted into two more tables (or their
 databases loaded: --mat-jf / --pat-jf, of the run's k), the contigs are scanned against all three (KmerTable.hapmer_scan) for the
 k-mers that only one parent holds, the markers are made into phase blocks, and the parents' hap-mers are counted against the
@@ -91,8 +102,8 @@ import sys
 from . import cli, extensions, polisher
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
-NOT_HERE = ("--report", "--repair", "--repair-rounds")      # of the extension flags: the report is always written, nothing is repaired
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
+NOT_HERE = ("--report", "--repair", "--repair-rounds", "--gaps-fill")      # of the extension flags: the report is always written, nothing is repaired, no assembly is written
 
 
 def parse_args(argv):
@@ -162,8 +173,9 @@ def run(argv):
     if o.compound:
         cscan = extensions.scan_compound(table, text.contigs, given, f["compound_max_len"])[2]      # (its dense scan is the report's)
         rep = cscan.report
-    else:
-        rep = table.kmer_report(text.seqs, given)
+    gscan = extensions.scan_gaps(table, text.contigs, given, f["gap_max_len"], f["gap_max_trim"], o.gap_long_runs)[2] if o.gaps else None
+    if not o.compound:
+        rep = gscan.report if o.gaps else table.kmer_report(text.seqs, given)      # (without --compound the gap scan's dense scan is the report's)
 
     def trio(text, asm):
         if given < 1:
@@ -190,6 +202,8 @@ def run(argv):
         extensions.variants_files(run, [("asm", text, vscan)])
     if o.compound:
         extensions.compound_files(run, [("asm", text, cscan)])
+    if o.gaps:
+        extensions.gaps_files(run, [("asm", text, gscan)])
     if o.dups:
         extensions.dups_files(run, [own["dups"]])
     return 0

@@ -371,6 +371,65 @@ class HetClusters:
                 for r in self.records]
 
 
+GAP_SITE_DTYPE = [("a", "<i8"), ("q", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("n_records", "<u4"), ("levels", "<u4"), ("trim_left", "<u4"), ("trim_right", "<u4"),
+                  ("kind", "u1"), ("status", "u1"), ("pad", "u1", (6,))]
+GAP_FILL_DTYPE = [("pos", "<i8"), ("bases_off", "<u8"), ("seq", "<u4"), ("ref_len", "<u4"), ("len", "<u4"), ("alt_min", "<u4")]
+GAP_KINDS = {0: "explicit", 1: "gap", 2: "run"}
+GAP_STATUS = {1: "dead", 2: "limit", 3: "complex", 4: "edge", 5: "ragged", 6: "skipped"}
+
+
+def make_gap_sites(sites):
+    """[(seq, a, q)] or [(seq, a, q, ref_min)] -> structured array (GAP_SITE_DTYPE) as KmerTable.gap_search takes it"""
+    import numpy as np
+    arr = np.zeros(len(sites), dtype=GAP_SITE_DTYPE)
+    for i, s in enumerate(sites):
+        arr[i]["seq"], arr[i]["a"], arr[i]["q"] = s[0], s[1], s[2]
+        arr[i]["ref_min"] = s[3] if len(s) > 3 else 0
+    return arr
+
+
+class GapScan:
+    """gap scan of a set of sequences against the reads' table (include/jasper_hip.h: jasper_gap_scan): `counts[i]` = (sites, searched,
+    bridged, unique, records, edge, ragged, limit, complex) of sequence i, `sites` = numpy structured array (GAP_SITE_DTYPE) ordered by
+    (seq, a), `records` = numpy structured array (GAP_FILL_DTYPE) of the fills the reads hold, ordered by (seq, pos, len, y), whose
+    bases are `bases[bases_off : bases_off + len]`, `report` = the KmerReport of the same input (None after gap_search), `seconds` =
+    device time of the dense scans and the search, `search_seconds` = of the search kernel alone, `runs_seconds` = of the
+    invalid-window scan, `lookups` = table lookups the search made, `retried` = it was repeated with larger lists.  The files made
+    from it: jasper_amd/gaps.py."""
+
+    def __init__(self, counts, sites, records, bases, report, seconds, search_seconds, runs_seconds, lookups, retried):
+        self.counts = counts
+        self.sites = sites
+        self.records = records
+        self.bases = bases
+        self.report = report
+        self.seconds = seconds
+        self.search_seconds = search_seconds
+        self.runs_seconds = runs_seconds
+        self.lookups = lookups
+        self.retried = retried
+
+    def __eq__(self, other):
+        return (isinstance(other, GapScan) and self.counts == other.counts and self.sites.tobytes() == other.sites.tobytes()
+                and self.records.tobytes() == other.records.tobytes() and self.bases == other.bases and self.report == other.report)
+
+    def fill(self, r):
+        """y of a record"""
+        return self.bases[int(r["bases_off"]):int(r["bases_off"]) + int(r["len"])].decode("latin-1")
+
+    def record_tuples(self):
+        """[(seq, pos, ref_len, len, y, ref_min, alt_min)], y = the fill, ref_min = its site's"""
+        rmin = {(int(s["seq"]), int(s["a"])): int(s["ref_min"]) for s in self.sites}
+        return [(int(r["seq"]), int(r["pos"]), int(r["ref_len"]), int(r["len"]), self.fill(r), rmin[(int(r["seq"]), int(r["pos"]))], int(r["alt_min"]))
+                for r in self.records]
+
+    def site_tuples(self):
+        """[(seq, a, q, kind, status, n_records, levels, trim_left, trim_right, ref_min)], kind = 'gap' | 'run' | 'explicit', status = 'dead' |
+        'limit' | 'complex' | 'edge' | 'ragged' | 'skipped'"""
+        return [(int(s["seq"]), int(s["a"]), int(s["q"]), GAP_KINDS[int(s["kind"])], GAP_STATUS[int(s["status"])], int(s["n_records"]), int(s["levels"]),
+                 int(s["trim_left"]), int(s["trim_right"]), int(s["ref_min"])) for s in self.sites]
+
+
 EDIT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref_len", "<u4"), ("bases", "<u8", (2,)), ("len", "<u2"), ("source", "u1"),
               ("round", "u1"), ("pad", "u1", (4,))]
 EDIT_SOURCES = {1: "sub", 2: "ins", 3: "del", 4: "mixed", 5: "compound"}
@@ -1059,6 +1118,69 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_compscan_free(res)
+
+    # ---- gap scan (an extension: what the reads hold in place of scaffold gaps and long runs of unreliable k-mers) ------
+    def gap_scan(self, seqs, thre, max_len=1000, max_trim=None, long_runs=False):
+        """the fills of up to max_len (0..4096) bases that the reads hold for the N gaps of the sequences and, with long_runs, for the
+        runs of unreliable k-mers that replace more than 64 bytes, and the kmer_report of the same input (thre >= 1, k >= 2; max_trim =
+        the most unreliable bases between a flank and the gap, None: k) -> GapScan; the table is not modified"""
+        n, cs, lens = _seq_args(seqs)
+        res = C.c_void_p()
+        rc = self._L.jasper_gap_scan(self._h, n, cs, lens, _thre32(thre), int(max_len), int(self.k if max_trim is None else max_trim), int(bool(long_runs)), C.byref(res))
+        return self._wrap_gapscan(rc, res, True)
+
+    def gap_scan_device(self, d_text, offsets, thre, max_len=1000, max_trim=None, long_runs=False):
+        """the same for sequences already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the
+        sequences back to back, offsets the n+1 boundaries"""
+        n, ptr, offs = _text_args(d_text, offsets)
+        res = C.c_void_p()
+        rc = self._L.jasper_gap_scan_device(self._h, n, ptr, offs, _thre32(thre), int(max_len), int(self.k if max_trim is None else max_trim), int(bool(long_runs)),
+                                            C.byref(res))
+        return self._wrap_gapscan(rc, res, True)
+
+    def gap_search(self, seqs, thre, max_len, sites):
+        """the search alone on the caller's sites: a structured array (GAP_SITE_DTYPE; see make_gap_sites) or [(seq, a, q[, ref_min])] in
+        (seq, a) order with k-1 <= a <= q <= n-(k-1); anything else raises and launches nothing -> GapScan without a report"""
+        import numpy as np
+        n, cs, lens = _seq_args(seqs)
+        arr = np.ascontiguousarray(sites if hasattr(sites, "dtype") else make_gap_sites(sites), dtype=GAP_SITE_DTYPE)
+        res = C.c_void_p()
+        rc = self._L.jasper_gap_search(self._h, n, cs, lens, _thre32(thre), int(max_len), C.c_void_p(arr.ctypes.data if len(arr) else None), len(arr), C.byref(res))
+        return self._wrap_gapscan(rc, res, False)
+
+    @staticmethod
+    def gap_front():
+        """the most strings of one length the gap search keeps (a wider level makes the site complex)"""
+        return int(_lib.lib().jasper_gap_front())
+
+    @staticmethod
+    def gap_max_records():
+        """the most fills of one site the gap search lists (more make the site complex)"""
+        return int(_lib.lib().jasper_gap_max_records())
+
+    @staticmethod
+    def gap_max_len():
+        """the longest fill the gap search can be asked for"""
+        return int(_lib.lib().jasper_gap_max_len())
+
+    def _wrap_gapscan(self, rc, res, with_report):
+        try:
+            check(rc)
+            counts = _counts(self._L.jasper_gapscan_num_seqs, self._L.jasper_gapscan_counts, res, 9)
+            sites = _records(self._L.jasper_gapscan_sites, res, _lib.GapSite, GAP_SITE_DTYPE)
+            recs = _records(self._L.jasper_gapscan_records, res, _lib.GapFill, GAP_FILL_DTYPE)
+            bp, bn = C.c_void_p(), C.c_uint64(0)
+            check(self._L.jasper_gapscan_bases(res, C.byref(bp), C.byref(bn)))
+            bases = C.string_at(bp, bn.value) if bn.value else b""
+            nl = C.c_uint64(0)
+            check(self._L.jasper_gapscan_lookups(res, C.byref(nl)))
+            search, runs, total = C.c_double(0), C.c_double(0), C.c_double(0)
+            check(self._L.jasper_gapscan_seconds(res, C.byref(search), C.byref(runs), C.byref(total)))
+            rep = self._read_report(C.c_void_p(self._L.jasper_gapscan_report(res))) if with_report else None      # (owned by res: read, not freed)
+            return GapScan(counts, sites, recs, bases, rep, total.value, search.value, runs.value, int(nl.value), bool(self._L.jasper_gapscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_gapscan_free(res)
 
     # ---- repair (an extension: the scans' error records applied to the text on the GPU, in rounds) ------------
     def repair(self, seqs, thre, indel_max_len=4, compound_max_len=64, rounds=3):
