@@ -6,49 +6,29 @@
 // of the sequence leave when no window that holds one of them is solid.  The host picks those runs (R <= max_len: a site; longer ones are
 // counted), uploads them as plain (seq, a, q, ref_min) tuples and launches
 //
-//   compound_search_kernel   one wave per site, four per block, grid-stride.  F = the k - 1 bases before a and G = the k - 1 bases from q
-//                            on are loaded once (lane l byte l of each), checked -- in bounds, all bases; wave-uniform -- and made two
-//                            wave-uniform 128-bit words.  Then a bounded breadth-first search over the replacement y, as
-//                            indels_mixed_kernel does it but with y of up to 64 bases: the frontier S_t is at most
-//                            COMPOUND_FRONT = 64 prefixes, one per lane -- y as 2-bit codes in 128 bits, first base in the highest
-//                            pair, so that lane order is lexicographic order -- with the minimum over its t windows.
-//                              extend   (prefix, z) on lane 4 * prefix + z, sixteen prefixes a round: the last k bases of F + y + z,
+//   compound_search_kernel   one wave per site, four per block, grid-stride: a front search on the shared pieces of front_search.hpp
+//                            (DESIGN 4.8.1).  F = the k - 1 bases before a and G = the k - 1 bases from q on are two wave-uniform
+//                            128-bit words (front_flanks; a flank out of bounds or with a non-base: no search).  The frontier S_t is
+//                            at most COMPOUND_FRONT = 64 prefixes of the replacement y, one per lane -- y of up to 64 bases as 2-bit
+//                            codes in 128 bits, first base in the highest pair, so that lane order is lexicographic order -- with
+//                            the minimum over its t windows.  The kernel's own part of each shared step:
+//                              extend   (front_extend, front_handover) the child's newest window is the last k bases of F + y + z:
 //                                       ((F << 2t) | yz) & mask(2k) while t < k and yz & mask(2k) from t >= k on (F << 2t is formed
-//                                       only for t < k <= 64, so no shift reaches 128 bits).  The ballot of a round is in (prefix, z)
-//                                       order, so a child's place is a popcount; it moves through a per-wave LDS strip of 64 x (16 + 4)
-//                                       bytes.  More than 64 children: the site is complex, counted once, and the wave stops there.
-//                              rejoin   window t of F + y + G, the first that holds a base of G: lane i for its own prefix, from W =
-//                                       the last k - 1 bases of F + y (y alone from t >= k - 1 on).  Then, in a wave-uniform loop over
-//                                       the prefixes that passed, W is read from its lane and lane j cuts window t + 1 + j out of W and
-//                                       G by two 128-bit shifts  (k - 2 lookups)
-//                            The records of a level (at most 64, lane i its own) take one returning cursor add; a level writes all its
-//                            records or none.  Level 1 of a site with R = 1 is searched but not listed: it is the variant scan's.
+//                                       only for t < k <= 64, so no shift reaches 128 bits).  The strip is 64 x (16 + 4) bytes per
+//                                       wave.  More than 64 children: the site is complex, counted once, and the wave stops there.
+//                              rejoin   (front_window0, front_rejoin with front_window) from W = the last k - 1 bases of F + y (y
+//                                       alone from t >= k - 1 on)
+//                              records  (front_reserve) lane i its own.  Level 1 of a site with R = 1 is searched but not listed: it
+//                                       is the variant scan's.
 //
 // The record list starts at sites + 4096 entries; a search that found more has counted them and is repeated once with exactly that room
-// (run_counted, scan_tile.hpp).  The dense scan is not repeated.
+// (search_stage and run_counted, scan_tile.hpp).  The dense scan is not repeated.
 #include "compound.hpp"
-#include "scan_tile.hpp"
+#include "front_search.hpp"
 
 namespace jk {
 
 enum { CC_LOOKUPS = 1, CC_COMPLEX = 2 };                                 // control words 1 and 2: table lookups made; complex sites
-
-__device__ __forceinline__ uint32_t cp_count(const TableDev &R, u128 fwd, int k) {
-    const u128 rc = revcomp(fwd, k);
-    return clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
-}
-__device__ __forceinline__ uint32_t cp_min(uint32_t a, uint32_t b) { return b < a ? b : a; }
-__device__ __forceinline__ uint64_t cp_or64(uint64_t v) {      // OR over the wave, in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint64_t cp_readlane64(uint64_t v, int l) {      // l wave-uniform
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-__device__ __forceinline__ uint64_t cp_first64(uint64_t v) {      // a value all lanes hold, as a scalar
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 
 __global__ __launch_bounds__(256) void compound_search_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, uint32_t n_seqs, TableDev R, uint32_t thre,
                                                               int max_len, const CompoundSite *__restrict__ sites, uint64_t nsites, Compound *__restrict__ out,
@@ -60,7 +40,6 @@ __global__ __launch_bounds__(256) void compound_search_kernel(const uint8_t *__r
     uint32_t *strip_mn = s_mn[threadIdx.x >> 6];
     const int k = R.k;
     const u128 kmask = maskbits(2 * k), fmask = maskbits(2 * (k - 1));
-    const unsigned long long below = (1ull << lane) - 1ull;
     const uint64_t nwv = (uint64_t)gridDim.x * 4;
     unsigned long long nlook = 0, ncomplex = 0;         // (wave-uniform)
     for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < nsites; i += nwv) {
@@ -68,41 +47,28 @@ __global__ __launch_bounds__(256) void compound_search_kernel(const uint8_t *__r
         if (S.seq >= n_seqs) continue;                  // (wave-uniform, like every check here; the host writes no such site)
         const int64_t o0 = offs[S.seq];
         const int64_t n = offs[S.seq + 1] - o0;
-        const uint8_t *__restrict__ txt = text + o0;
         const int64_t RL = S.q - S.a;
         if (S.a < k - 1 || RL < 1 || RL > max_len || S.q > n - (k - 1)) continue;      // F and G lie inside the sequence
-        int cf = 0, cg = 0;
-        if (lane < k - 1) {
-            cf = code(txt[S.a - (k - 1) + lane]);
-            cg = code(txt[S.q + lane]);
-        }
-        if (__ballot(cf < 0 || cg < 0)) continue;       // ... and are bases
-        const unsigned sh = lane < k - 1 ? 2u * (unsigned)(k - 2 - lane) : 0u;      // base l of F and of G: bit pair k - 2 - l
-        const u128 f1 = lane < k - 1 ? shl(mk(0, (uint64_t)cf), sh) : mk(0, 0), g1 = lane < k - 1 ? shl(mk(0, (uint64_t)cg), sh) : mk(0, 0);
-        const u128 F = mk(cp_first64(cp_or64(f1.hi)), cp_first64(cp_or64(f1.lo))), G = mk(cp_first64(cp_or64(g1.hi)), cp_first64(cp_or64(g1.lo)));
+        const Flanks FG = front_flanks(text + o0, S.a, S.q, k);
+        if (!FG.bases) continue;                        // ... and are bases
+        const u128 F = FG.F, G = FG.G;
         // level 0: S_0 = {empty}
         u128 y = mk(0, 0);                              // lane i < nf: prefix i, first base in the highest pair ...
         uint32_t mn = 0xFFFFFFFFu;                      // ... and the minimum over its windows
         int nf = 1;
         for (int t = 1; t <= max_len; ++t) {
-            // extend S_(t-1) to S_t: sixteen prefixes a round, (prefix, z) on lane 4 * prefix + z
+            // extend S_(t-1) to S_t: the last k bases of F + y + z
             const u128 Fs = t < k ? shl(F, 2 * t) : mk(0, 0);      // from t >= k on the newest window is y's alone (and 2t may be 128)
-            int tot = 0;
-            for (int r0 = 0; r0 < nf; r0 += 16) {
-                const int src = r0 + (lane >> 2);       // <= 63
-                const u128 ny = bor(shl(mk(__shfl(y.hi, src), __shfl(y.lo, src)), 2), mk(0, (uint64_t)(lane & 3)));      // (t - 1 <= 63 bases: nothing is lost)
-                const uint32_t pm = (uint32_t)__shfl(mn, src);
-                uint32_t c = 0;
-                if (src < nf) c = cp_count(R, band(bor(Fs, ny), kmask), k);
-                const bool ok = src < nf && c >= thre;
-                const unsigned long long B = __ballot(ok);
-                const int at = tot + __popcll(B & below);
-                if (ok && at < COMPOUND_FRONT) {
+            const int tot = front_extend(
+                R, thre, y, mn, nf, COMPOUND_FRONT,
+                [=](int, u128 parent) {
+                    const u128 ny = bor(shl(parent, 2), mk(0, (uint64_t)(lane & 3)));      // (t - 1 <= 63 bases: nothing is lost)
+                    return FrontChild<u128>{ny, band(bor(Fs, ny), kmask), true, true};
+                },
+                [&](int at, int, u128 ny, uint32_t m) {
                     strip_y[at] = make_ulonglong2(ny.lo, ny.hi);
-                    strip_mn[at] = cp_min(pm, c);
-                }
-                tot += __popcll(B);
-            }
+                    strip_mn[at] = m;
+                });
             nlook += 4u * (unsigned)nf;
             if (tot > COMPOUND_FRONT) {                 // complex: nothing of length >= t is listed here
                 ++ncomplex;
@@ -110,52 +76,25 @@ __global__ __launch_bounds__(256) void compound_search_kernel(const uint8_t *__r
                 break;
             }
             if (tot == 0) break;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (lane < tot) {
-                const ulonglong2 v = strip_y[lane];
+            front_handover(tot, [&](int l) {
+                const ulonglong2 v = strip_y[l];
                 y = mk(v.y, v.x);
-                mn = strip_mn[lane];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+                mn = strip_mn[l];
+            });
             nf = tot;
             if (RL == 1 && t == 1) continue;            // a single substitution: the variant scan's
             // rejoin: window t, lane i for prefix i
             const bool act = lane < nf;
             const u128 W = t >= k - 1 ? band(y, fmask) : band(bor(Fs, y), fmask);      // the last k - 1 bases of F + y  (t < k - 1: Fs = F << 2t)
             uint32_t a = 0xFFFFFFFFu;
-            if (act) a = cp_count(R, band(bor(shl(W, 2), shr(G, 2 * (k - 2))), kmask), k);
+            if (act) a = canon_count(R, front_window0(W, G, k, kmask), k);
             nlook += (unsigned)nf;
-            a = cp_min(a, mn);
-            const unsigned long long P = __ballot(act && a >= thre);
-            unsigned long long recm = 0;                // (wave-uniform) bit i: prefix i is a record
-            uint32_t my_amin = a;
-            if (k > 2) {
-                for (unsigned long long p = P; p; p &= p - 1ull) {
-                    const int j = (int)__builtin_ctzll(p);
-                    const u128 Wj = mk(cp_readlane64(W.hi, j), cp_readlane64(W.lo, j));
-                    const uint32_t aj = (uint32_t)__builtin_amdgcn_readlane((int)a, j);
-                    uint32_t b = 0xFFFFFFFFu;
-                    if (lane < k - 2)                   // window t + 1 + lane: the last k - 2 - lane bases of W, then lane + 2 bases of G
-                        b = cp_count(R, band(bor(shl(Wj, 2 * (lane + 2)), shr(G, 2 * (k - 3 - lane))), kmask), k);
-                    nlook += (unsigned)(k - 2);
-                    b = cp_min(wave_min32(b), aj);
-                    if (b >= thre) {
-                        recm |= 1ull << j;
-                        if (lane == j) my_amin = b;
-                    }
-                }
-            } else {
-                recm = P;
-            }
+            a = min32(a, mn);
+            uint32_t my_amin;
+            const unsigned long long recm = front_rejoin(R, thre, __ballot(act && a >= thre), a, nlook, my_amin, [&](int j) { return front_window(readlane128(W, j), G, k, kmask); });
             if (recm) {
-                unsigned long long base = 0;
-                const unsigned total = __popcll(recm);
-                if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
-                base = __shfl(base, 0);
-                if (base + total <= cap && ((recm >> lane) & 1ull)) {      // (a level writes all its records or none)
+                const unsigned long long at = front_reserve(recm, &ctl[SC_CURSOR], cap);
+                if (at != FRONT_NONE) {
                     const u128 rv = shr(mk(revpairs64(y.lo), revpairs64(y.hi)), 128 - 2 * t);      // base i in bits 2i, 2i + 1
                     Compound v;
                     v.pos = S.a;
@@ -167,7 +106,7 @@ __global__ __launch_bounds__(256) void compound_search_kernel(const uint8_t *__r
                     v.bases[1] = rv.hi;
                     v.len = (uint16_t)t;
                     for (int z = 0; z < 6; ++z) v.pad[z] = 0;
-                    out[base + __popcll(recm & below)] = v;
+                    out[at] = v;
                 }
             }
         }
@@ -210,37 +149,27 @@ int compound_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int6
     if (nsites == 0) return 0;                          // nothing of the search is allocated or launched
     hipStream_t st = T.stream;
     const int W = Table::WS_COMPOUND;
-    const size_t words = SC_WORDS + (size_t)n_seqs;     // the control words, then the complex sites per sequence
     CompoundSite *d_sites = (CompoundSite *)T.workspace(W, nsites * sizeof(CompoundSite), err);
     int64_t *d_offs = (int64_t *)T.workspace(W + 1, ((size_t)n_seqs + 1) * sizeof(int64_t), err);
-    unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 3, words * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
-    if (!d_sites || !d_offs || !d_ctl) return -1;
+    if (!d_sites || !d_offs) return -1;
     HIPCHK(hipMemcpyAsync(d_sites, sites.data(), nsites * sizeof(CompoundSite), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_offs, offsets, ((size_t)n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    Compound *d_rec = nullptr;
-    auto search = [&](unsigned long long cap) {
-        d_rec = (Compound *)T.workspace(W + 2, cap * sizeof(Compound), err);
-        if (!d_rec) return -1;
-        hipLaunchKernelGGL(compound_search_kernel, dim3((unsigned)std::min<uint64_t>((nsites + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, d_offs, (uint32_t)n_seqs, T.d, thre,
-                           max_len, d_sites, nsites, d_rec, cap, d_ctl, d_ctl + SC_WORDS);
-        return 0;
-    };
-    if (run_counted(st, d_ctl, words, d_ctl, nsites + 4096, "compound scan: the number of records changed between two searches", ctl, out.search_seconds, out.retried, err,
-                    search))
+    unsigned long long ctl[SC_WORDS] = {0, 0, 0, 0};
+    std::vector<unsigned long long> cplx;               // after the control words: the complex sites per sequence
+    const int sums[1] = {CC_COMPLEX};
+    if (search_stage(T, W + 3, n_seqs, 1, sums, nsites + 4096, "compound scan: the number of records changed between two searches",
+                     "compound scan: the complex sites per sequence do not add up", ctl, out.recs, cplx, out.search_seconds, out.retried, err,
+                     [&](unsigned long long cap, unsigned long long *d_ctl, unsigned long long *d_per) {
+                         Compound *d_rec = (Compound *)T.workspace(W + 2, cap * sizeof(Compound), err);
+                         if (d_rec)
+                             hipLaunchKernelGGL(compound_search_kernel, dim3((unsigned)std::min<uint64_t>((nsites + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, d_offs,
+                                                (uint32_t)n_seqs, T.d, thre, max_len, d_sites, nsites, d_rec, cap, d_ctl, d_per);
+                         return d_rec;
+                     }))
         return -1;
     out.seconds += out.search_seconds;
     out.lookups = ctl[CC_LOOKUPS];
-    out.recs.resize(ctl[SC_CURSOR]);
-    std::vector<unsigned long long> cplx((size_t)n_seqs);
-    if (!out.recs.empty()) HIPCHK(hipMemcpyAsync(out.recs.data(), d_rec, out.recs.size() * sizeof(Compound), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(cplx.data(), d_ctl + SC_WORDS, cplx.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(jk_stream_wait(st));
-    unsigned long long sum = 0;
-    for (size_t i = 0; i < cplx.size(); ++i) {
-        out.counts[5 * i + 4] = cplx[i];
-        sum += cplx[i];
-    }
-    if (sum != ctl[CC_COMPLEX]) { err = "compound scan: the complex sites per sequence do not add up"; return -1; }
+    for (size_t i = 0; i < cplx.size(); ++i) out.counts[5 * i + 4] = cplx[i];
     for (const Compound &v : out.recs) {                // a record the kernel cannot have written is refused
         const auto s = std::lower_bound(sites.begin(), sites.end(), v, [](const CompoundSite &a, const Compound &b) { return a.seq != b.seq ? a.seq < b.seq : a.a < b.pos; });
         bool ok = s != sites.end() && s->seq == v.seq && s->a == v.pos && (int64_t)v.ref_len == s->q - s->a && v.len >= 1 && (int)v.len <= max_len;

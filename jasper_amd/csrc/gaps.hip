@@ -10,35 +10,33 @@
 // The host makes the sites from the two run lists (gaps_host.hpp: stretches, kinds, a and q, the trims, edge and ragged), uploads them
 // as they are and launches
 //
-//   gap_search_kernel    one wave per site, four per block, grid-stride, at most 1024 waves.  F = the k - 1 bases before a and G = the
-//                        k - 1 bases from q on are loaded and checked as compound_search_kernel does.  Then the bounded breadth-first
-//                        search of jasper_gap_scan, level t = 0, 1, ..: the frontier S_t is at most GAP_FRONT = 64 strings, one per
-//                        lane, but a lane keeps of its string y only W = the last k - 1 bases of F + y (128 bits) and the minimum over
-//                        its windows.  The string itself is in the wave's LOG in global memory: row t - 1 holds 64 bytes, byte s =
-//                        (the slot of S_(t-1) that slot s of S_t extends) << 2 | the base it adds.
-//                          rejoin   window t of F + y + G, lane i for its own string, from W and G's first base; then, per string that
-//                                   passed, lane j cuts window t + 1 + j out of W and G  (k - 2 lookups), as the compound search does.
-//                                   A record's y is read out of the log by its own lane, t rows back, and written as letters into the
-//                                   byte pool; the records and the bytes of a level take one returning cursor add each, and a level
-//                                   writes all of both or nothing.  More than GAP_MAX_RECORDS at a site: complex.
+//   gap_search_kernel    one wave per site, four per block, grid-stride, at most 1024 waves: a front search on the shared pieces of
+//                        front_search.hpp.  F and G are front_flanks' (a non-base: the site is skipped).  Level t = 0,
+//                        1, ..: the frontier S_t is at most GAP_FRONT = 64 strings, one per lane, but a lane keeps of its string y only
+//                        W = the last k - 1 bases of F + y (128 bits) and the minimum over its windows.  The string itself is in the
+//                        wave's LOG in global memory: row t - 1 holds 64 bytes, byte s = (the slot of S_(t-1) that slot s of S_t
+//                        extends) << 2 | the base it adds.  The kernel's own part of each step:
+//                          rejoin   (front_window0, front_rejoin with front_window) from W as it is.  A record's y is read out of the
+//                                   log by its own lane, t rows back, and written as letters into the byte pool; the records and the
+//                                   bytes of a level are front_reserve's two lists: all of both or nothing.  More than
+//                                   GAP_MAX_RECORDS at a site: complex.
 //                          close    t >= k - 1 and W == G: the string ends here (it is a record followed by the whole right flank).
-//                          extend   (string, z) on lane 4 * string + z, sixteen strings a round: the k-mer is W << 2 | z whatever t is,
-//                                   since W always holds k - 1 bases.  A child's place is a popcount of the round's ballot; W, the
-//                                   minimum and the log byte move through a per-wave LDS strip, and the new row is stored by the lanes
-//                                   that take the children over, 64 bytes side by side.
+//                          extend   (front_extend) strings that are closed have no children; the k-mer is W << 2 | z whatever t is,
+//                                   since W always holds k - 1 bases.  W, the minimum and the log byte move through the strip, and
+//                                   front_handover's lanes store the new row, 64 bytes side by side.
 //                        Visibility of the log: a row is read only by lanes of the wave that stored it, later in program order.  The
 //                        vector memory operations of one wave to global memory are performed in the order they were issued, and a CU's
 //                        L1 serves the wave's loads behind its own write-through stores, so no cache has to be written back or dropped:
-//                        a release / acquire fence pair of WAVEFRONT scope around the hand-over keeps the compiler from moving the
-//                        loads above the stores, which is all that is needed (the form compound.hip uses for its LDS strip).  Nothing
+//                        the release / acquire fence pairs of WAVEFRONT scope of front_handover keep the compiler from moving the
+//                        loads above the stores, which is all that is needed.  Nothing
 //                        is handed between waves, and a later launch starts with clean caches.
 //                        Every loop is bounded: levels <= max_len, rounds <= 4, the walk back <= t.  No spin; the only atomics are the
 //                        cursor and counter adds.
 //
 // The record list starts at sites + 4096 entries and the byte pool at 2048 bytes per site to search + 16384; a search that wanted more of either has
-// counted both and is repeated once with exactly that room (counted_twice, beside run_counted's rule).  The dense scans are not repeated.
+// counted both and is repeated once with exactly that room (run_counted with its second list, scan_tile.hpp).  The dense scans are not repeated.
 #include "gaps.hpp"
-#include "scan_tile.hpp"
+#include "front_search.hpp"
 
 namespace jk {
 
@@ -103,23 +101,6 @@ __global__ __launch_bounds__(RP_THREADS) void gap_runs_kernel(const uint8_t *__r
     }
 }
 
-__device__ __forceinline__ uint32_t gp_count(const TableDev &R, u128 fwd, int k) {
-    const u128 rc = revcomp(fwd, k);
-    return clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
-}
-__device__ __forceinline__ uint32_t gp_min(uint32_t a, uint32_t b) { return b < a ? b : a; }
-__device__ __forceinline__ uint64_t gp_or64(uint64_t v) {      // OR over the wave, in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ uint64_t gp_readlane64(uint64_t v, int l) {      // l wave-uniform
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-__device__ __forceinline__ uint64_t gp_first64(uint64_t v) {      // a value all lanes hold, as a scalar
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
 // log: gridDim.x * 4 waves x max_len rows x GAP_FRONT bytes.  out has room for cap records and pool for pool_cap bytes.
 __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, uint32_t n_seqs, TableDev R, uint32_t thre,
                                                          int max_len, GapSite *sites, uint64_t nsites, uint8_t *log, GapFill *__restrict__ out, unsigned long long cap,
@@ -133,7 +114,6 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
     uint8_t *strip_b = s_b[threadIdx.x >> 6];
     const int k = R.k;
     const u128 kmask = maskbits(2 * k), fmask = maskbits(2 * (k - 1));
-    const unsigned long long below = (1ull << lane) - 1ull;
     const uint64_t nwv = (uint64_t)gridDim.x * 4, wv = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     uint8_t *mylog = log + wv * (uint64_t)max_len * GAP_FRONT;
     unsigned long long nlook = 0;                       // (wave-uniform)
@@ -142,22 +122,15 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
         if (S.status >= GAP_EDGE || S.seq >= n_seqs) continue;      // (wave-uniform, like every check here) the host's own verdicts stay
         const int64_t o0 = offs[S.seq];
         const int64_t n = offs[S.seq + 1] - o0;
-        const uint8_t *__restrict__ txt = text + o0;
         const int64_t RL = S.q - S.a;
         if (S.a < k - 1 || RL < 0 || S.q > n - (k - 1)) continue;      // F and G lie inside the sequence (the host writes no other site)
-        int cf = 0, cg = 0;
-        if (lane < k - 1) {
-            cf = code(txt[S.a - (k - 1) + lane]);
-            cg = code(txt[S.q + lane]);
-        }
+        const Flanks FG = front_flanks(text + o0, S.a, S.q, k);
         uint32_t status = GAP_NONE, nrec = 0;
         int t = 0;
-        if (__ballot(cf < 0 || cg < 0)) {
+        if (!FG.bases) {
             status = GAP_SKIPPED;                       // ... and are bases
         } else {
-            const unsigned sh = lane < k - 1 ? 2u * (unsigned)(k - 2 - lane) : 0u;      // base l of F and of G: bit pair k - 2 - l
-            const u128 f1 = lane < k - 1 ? shl(mk(0, (uint64_t)cf), sh) : mk(0, 0), g1 = lane < k - 1 ? shl(mk(0, (uint64_t)cg), sh) : mk(0, 0);
-            const u128 F = mk(gp_first64(gp_or64(f1.hi)), gp_first64(gp_or64(f1.lo))), G = mk(gp_first64(gp_or64(g1.hi)), gp_first64(gp_or64(g1.lo)));
+            const u128 F = FG.F, G = FG.G;
             // level 0: S_0 = {empty}
             u128 W = F;                                 // lane i < nf: the last k - 1 bases of F + (string i) ...
             uint32_t mn = 0xFFFFFFFFu;                  // ... the minimum over its windows ...
@@ -166,30 +139,11 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
             for (;; ++t) {                              // (t <= max_len: the stop check)
                 // rejoin: window t, lane i for string i
                 uint32_t a = 0xFFFFFFFFu;
-                if (alive) a = gp_count(R, band(bor(shl(W, 2), shr(G, 2 * (k - 2))), kmask), k);
+                if (alive) a = canon_count(R, front_window0(W, G, k, kmask), k);
                 nlook += (unsigned)__popcll(__ballot(alive));
-                a = gp_min(a, mn);
-                const unsigned long long P = __ballot(alive && a >= thre);
-                unsigned long long recm = 0;            // (wave-uniform) bit i: string i is a record
-                uint32_t my_amin = a;
-                if (k > 2) {
-                    for (unsigned long long p = P; p; p &= p - 1ull) {
-                        const int j = (int)__builtin_ctzll(p);
-                        const u128 Wj = mk(gp_readlane64(W.hi, j), gp_readlane64(W.lo, j));
-                        const uint32_t aj = (uint32_t)__builtin_amdgcn_readlane((int)a, j);
-                        uint32_t b = 0xFFFFFFFFu;
-                        if (lane < k - 2)               // window t + 1 + lane: the last k - 2 - lane bases of W, then lane + 2 bases of G
-                            b = gp_count(R, band(bor(shl(Wj, 2 * (lane + 2)), shr(G, 2 * (k - 3 - lane))), kmask), k);
-                        nlook += (unsigned)(k - 2);
-                        b = gp_min(wave_min32(b), aj);
-                        if (b >= thre) {
-                            recm |= 1ull << j;
-                            if (lane == j) my_amin = b;
-                        }
-                    }
-                } else {
-                    recm = P;
-                }
+                a = min32(a, mn);
+                uint32_t my_amin;
+                const unsigned long long recm = front_rejoin(R, thre, __ballot(alive && a >= thre), a, nlook, my_amin, [&](int j) { return front_window(readlane128(W, j), G, k, kmask); });
                 if (recm) {
                     const unsigned total = __popcll(recm);
                     if (nrec + total > (uint32_t)GAP_MAX_RECORDS) {      // the level lists none of them
@@ -197,16 +151,9 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
                         break;
                     }
                     nrec += total;
-                    unsigned long long base = 0, bbase = 0;
-                    if (lane == 0) {
-                        base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
-                        bbase = atomicAdd(&ctl[GC_BYTES], (unsigned long long)total * (unsigned)t);
-                    }
-                    base = __shfl(base, 0);
-                    bbase = __shfl(bbase, 0);
-                    if (base + total <= cap && bbase + (unsigned long long)total * (unsigned)t <= pool_cap && ((recm >> lane) & 1ull)) {      // (all of the level or nothing)
-                        const unsigned mine = __popcll(recm & below);
-                        const unsigned long long off = bbase + (unsigned long long)mine * (unsigned)t;
+                    unsigned long long off;             // the records and their t bytes each: all of the level in both lists or nothing
+                    const unsigned long long at = front_reserve(recm, &ctl[SC_CURSOR], cap, &ctl[GC_BYTES], (unsigned)t, pool_cap, &off);
+                    if (at != FRONT_NONE) {
                         int slot = lane;                // y, last base first: t rows back through the log (slot <= 63; rows 0 .. t - 1 < max_len)
                         for (int r = t; r >= 1; --r) {
                             const uint32_t b = mylog[(uint64_t)(r - 1) * GAP_FRONT + slot];
@@ -220,7 +167,7 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
                         v.ref_len = (uint32_t)RL;
                         v.len = (uint32_t)t;
                         v.alt_min = my_amin;
-                        out[base + mine] = v;
+                        out[at] = v;
                     }
                 }
                 // close: the string holds the whole right flank
@@ -236,45 +183,30 @@ __global__ __launch_bounds__(256) void gap_search_kernel(const uint8_t *__restri
                     break;
                 }
                 // extend S_t to S_(t+1): sixteen strings a round, (string, z) on lane 4 * string + z
-                int tot = 0;
-                for (int r0 = 0; r0 < nf; r0 += 16) {
-                    const int src = r0 + (lane >> 2);   // <= 63
-                    const u128 nw = band(bor(shl(mk(__shfl(W.hi, src), __shfl(W.lo, src)), 2), mk(0, (uint64_t)(lane & 3))), kmask);      // the k-mer: W holds k - 1 bases
-                    const uint32_t pm = (uint32_t)__shfl(mn, src);
-                    const bool from = __shfl((int)alive, src) != 0 && src < nf;
-                    uint32_t c = 0;
-                    if (from) c = gp_count(R, nw, k);
-                    const bool ok = from && c >= thre;
-                    const unsigned long long B = __ballot(ok);
-                    const int at = tot + __popcll(B & below);
-                    if (ok && at < GAP_FRONT) {
-                        const u128 w1 = band(nw, fmask);
+                const int tot = front_extend(
+                    R, thre, W, mn, nf, GAP_FRONT,
+                    [=](int src, u128 parent) {      // (by value: capturing `alive` by reference costs two VGPRs)
+                        const u128 nw = band(bor(shl(parent, 2), mk(0, (uint64_t)(lane & 3))), kmask);      // the k-mer: W holds k - 1 bases
+                        return FrontChild<u128>{band(nw, fmask), nw, __shfl((int)alive, src) != 0, true};
+                    },
+                    [&](int at, int src, u128 w1, uint32_t m) {
                         strip_w[at] = make_ulonglong2(w1.lo, w1.hi);
-                        strip_mn[at] = gp_min(pm, c);
+                        strip_mn[at] = m;
                         strip_b[at] = (uint8_t)((src << 2) | (lane & 3));
-                    }
-                    tot += __popcll(B);
-                }
+                    });
                 nlook += 4u * (unsigned)nalive;
                 if (tot > GAP_FRONT || tot == 0) {      // level t + 1 cannot be formed: complex, or nothing is left
                     status = tot ? GAP_COMPLEX : GAP_DEAD;
                     ++t;
                     break;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 alive = lane < tot;
-                if (alive) {
-                    const ulonglong2 v = strip_w[lane];
+                front_handover(tot, [&](int l) {        // the row is read by whichever lane lists a record later on
+                    const ulonglong2 v = strip_w[l];
                     W = mk(v.y, v.x);
-                    mn = strip_mn[lane];
-                    mylog[(uint64_t)t * GAP_FRONT + lane] = strip_b[lane];      // row t = level t + 1  (t < max_len)
-                }
-                // the strip may be written again, and the row is read by whichever lane lists a record later on
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    mn = strip_mn[l];
+                    mylog[(uint64_t)t * GAP_FRONT + l] = strip_b[l];      // row t = level t + 1  (t < max_len)
+                });
                 nf = tot;
             }
         }
@@ -293,31 +225,6 @@ static int gap_check_args(const Table &T, uint32_t thre, int max_len, int64_t ma
     if (max_len < 0 || max_len > GAP_MAX_LEN) { err = "gap scan: max_len must be in 0..4096"; return -1; }
     if (max_trim < 0) { err = "gap scan: max_trim must be at least 0"; return -1; }
     return 0;
-}
-
-// run_counted's rule for a kernel that appends to TWO lists: launch(cap, pool_cap) sizes both and launches on st; the kernel adds what it
-// WANTED to ctl[SC_CURSOR] (records) and ctl[GC_BYTES] (pool bytes) and writes nothing of a level that does not fit both.  If more of
-// either was wanted, it is repeated once with exactly that room; more still is an error.
-template <class Launch>
-static int counted_twice(hipStream_t st, unsigned long long *d_ctl, unsigned long long cap, unsigned long long pool_cap, unsigned long long (&ctl)[SC_WORDS], double &seconds,
-                         int &retried, std::string &err, Launch &&launch) {
-    Events ev;
-    if (ev.create(err)) return -1;
-    for (int attempt = 0;; ++attempt) {
-        HIPCHK(hipMemsetAsync(d_ctl, 0, SC_WORDS * sizeof(unsigned long long), st));
-        HIPCHK(hipEventRecord(ev.e[0], st));
-        if (launch(cap, pool_cap)) return -1;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.e[1], st));
-        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        if (ev.add_seconds(seconds, err)) return -1;
-        if (ctl[SC_CURSOR] <= cap && ctl[GC_BYTES] <= pool_cap) return 0;
-        if (attempt) { err = "gap scan: the number of records or of their bases changed between two searches"; return -1; }
-        cap = std::max(cap, ctl[SC_CURSOR]);            // the kernel counted what it could not write: exactly this much room is needed
-        pool_cap = std::max(pool_cap, ctl[GC_BYTES]);
-        retried = 1;
-    }
 }
 
 // the search on out.sites (in (seq, a) order; the host's verdicts edge and ragged are in), then the checks, the order and the counters
@@ -340,7 +247,8 @@ static int gap_search_sites(Table &T, int n_seqs, const uint8_t *d_text, const i
         HIPCHK(hipMemcpyAsync(d_offs, offsets, ((size_t)n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         GapFill *d_rec = nullptr;
         uint8_t *d_pool = nullptr;
-        auto search = [&](unsigned long long cap, unsigned long long pool_cap) {
+        unsigned long long pool_cap = 2048 * nsearch + 16384;
+        auto search = [&](unsigned long long cap) {
             d_rec = (GapFill *)T.workspace(W + 4, cap * sizeof(GapFill), err);
             d_pool = (uint8_t *)T.workspace(W + 5, pool_cap, err);
             if (!d_rec || !d_pool) return -1;
@@ -348,7 +256,9 @@ static int gap_search_sites(Table &T, int n_seqs, const uint8_t *d_text, const i
                                pool_cap, d_ctl);
             return 0;
         };
-        if (counted_twice(st, d_ctl, nsites + 4096, 2048 * nsearch + 16384, ctl, out.search_seconds, out.retried, err, search)) return -1;
+        if (run_counted(st, d_ctl, SC_WORDS, d_ctl, nsites + 4096, "gap scan: the number of records or of their bases changed between two searches", ctl, out.search_seconds,
+                        out.retried, err, search, GC_BYTES, &pool_cap))
+            return -1;
         out.seconds += out.search_seconds;
         out.lookups = ctl[GC_LOOKUPS];
         out.fills.resize(ctl[SC_CURSOR]);

@@ -26,21 +26,20 @@
 //                         the minima of bit b and writes its record.  Places are reserved with one returning cursor add per wave, and a
 //                         wave writes all its records or none.
 //
-//   indels_mixed_kernel   (only when the caller asks for mixed insertions) one wave per candidate (p, x): a bounded breadth-first search
-//                         over the inserted string y, y[0] == x.  The frontier S_t -- the prefixes of length t all of whose windows of
-//                         F + y are solid -- is at most INDEL_FRONT = 64 prefixes, one per lane: y as 2-bit codes in a word (first base
-//                         in the highest pair, so that lane order is lexicographic order) and the minimum over its t windows.
+//   indels_mixed_kernel   (only when the caller asks for mixed insertions) one wave per candidate (p, x): a front search on the shared
+//                         pieces of front_search.hpp over the inserted string y, y[0] == x.  The frontier S_t -- the
+//                         prefixes of length t all of whose windows of F + y are solid -- is at most INDEL_FRONT = 64 prefixes, one per
+//                         lane: y as 2-bit codes in a word (first base in the highest pair, so that lane order is lexicographic order)
+//                         and the minimum over its t windows.  The kernel's own part of each shared step:
 //                           rejoin   per level: window t of F + y + s[p ..], the first that holds s[p], lane i for its own prefix
-//                                    (128-bit arithmetic on F's k-mer, one lookup per prefix that is not x^t); then, in a wave-uniform
-//                                    loop over the prefixes that passed, windows t+1 .. k+t-2 cut out of the planes with y put in
-//                                    (pl_ins_y), lane j owning window t + 1 + j  (k - 2 lookups)
+//                                    (128-bit arithmetic on F's k-mer, one lookup per prefix that is not x^t); then front_rejoin with
+//                                    windows t+1 .. k+t-2 cut out of the planes with y put in (pl_ins_y)
 //                           ref      windows 0 .. k-2 of s, once per candidate and only when something passed
-//                           extend   (prefix, z) spread over four lanes each, sixteen prefixes a round: the last k bases of F + y + z.
-//                                    The ballot of a round is in (parent, z) order already, so a child's place is a popcount; it moves
-//                                    through a per-wave LDS strip of 64 x 8 bytes.  More than 64 children: the site is complex, counted
-//                                    once, and the wave stops there.  Four lookups per prefix.
-//                         The records of a level (at most 64, lane i its own) take one returning cursor add; a level writes all its
-//                         records or none.  Same-base strings x^t stay in the frontier but are never written: they are the check's.
+//                           records  (front_reserve) lane i its own.  Same-base strings x^t stay in the frontier but are never
+//                                    written: they are the check's.
+//                           extend   (front_extend, front_handover) the child's newest window is the last k bases of F + y + z; the
+//                                    strip is 64 x 8 bytes per wave.  More than 64 children: the site is complex, counted once, and the
+//                                    wave stops there.  Four lookups per prefix.
 //
 //   het_cluster_kernel    (only when the caller asks for het clusters, cluster_len = N > 0) one wave per candidate (p, x): the replacements
 //                         of s[p .. p+R) by a string y, y[0] == x, R and |y| up to N, where the sequence and the replacement are both
@@ -51,24 +50,24 @@
 //                                    windows are not all solid leaves: R_max = 0, the compound scan's.  A prefix minimum over both rounds
 //                                    puts ref_min(R) on lane R - 1, and the ballot of ref_min(R) >= thre is R_max (wave-uniform).
 //                           lane R-1 keeps CW = the k - 1 bases before p + R (closure) and G = the k - 1 bases from p + R on (rejoin).
-//                         Then the breadth-first search of indels_mixed_kernel with y in 128 bits as in compound_search_kernel (first
-//                         base in the highest pair; the shift boundaries t < k, t >= k - 1 and t = 64 are those documented there), per
-//                         level t:
+//                         Then a front search (front_search.hpp) with y in 128 bits (first base in the highest pair; the shift
+//                         boundaries t < k, t >= k - 1 and t = 64 are those compound.hip documents), per level t:
 //                           closure  per prefix, W = the last k - 1 bases of F + y against every lane's CW: one 128-bit compare, one ballot
-//                           extend   (prefix, z) on lane 4 * prefix + z, sixteen prefixes a round.  Every prefix is looked up, the closed
-//                                    ones too: the four answers are window t of F + y + G_R for the R with s[p+R] == z, so lane i keeps its
-//                                    prefix's 4-bit solid mask.  Children of the prefixes that are not closed go through the LDS strip.
+//                           extend   (front_extend, front_handover) every prefix is looked up, the closed ones too: the four answers are
+//                                    window t of F + y + G_R for the R with s[p+R] == z, so lane i keeps its prefix's 4-bit solid mask
+//                                    from the round's ballot.  Only children of prefixes that are not closed enter the strip.
 //                           rejoin   per prefix, lane R - 1: normal form and one bit of that mask (no lookup); the R that survive look up
 //                                    windows t+1 .. t+3 one after the other, each lane its own, leaving at the first that fails -- every
 //                                    one of them cuts the field to a quarter in ordinary sequence; what is left runs all k - 1 windows
-//                                    t .. t+k-2 lane-parallel with a wave minimum, in a wave-uniform loop.
-//                         The records of a prefix (at most 64, lane R - 1 its own) take one returning cursor add; a prefix writes all
-//                         its records or none.
+//                                    t .. t+k-2 lane-parallel with a wave minimum, in a wave-uniform loop.  (Per prefix and per R: not
+//                                    the shape of front_rejoin, which is per level.)
+//                         The records of a prefix (at most 64, lane R - 1 its own) are front_reserve's: all of them or none.
 //
 // The record list starts at candidates + 4096 entries; a check that found more has counted them and is repeated once with exactly that
-// room (run_counted, scan_tile.hpp: the dense scans' repeat, here around the check).  The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
+// room (run_counted, scan_tile.hpp: the dense scans' repeat, here around the check; the two searches' host stage is search_stage there).
+// The scan is not repeated.  The substitution check (variants_check_kernel rewrites the candidates in place) runs afterwards.
 #include "indels.hpp"
-#include "scan_tile.hpp"
+#include "front_search.hpp"
 
 namespace jk {
 
@@ -134,11 +133,6 @@ __device__ __forceinline__ u128 id_kmer(Plane lo, Plane hi, int s, int k) {
     return mk(id_spread((uint32_t)(r0 >> 32)) | (id_spread((uint32_t)(r1 >> 32)) << 1), id_spread((uint32_t)r0) | (id_spread((uint32_t)r1) << 1));
 }
 
-__device__ __forceinline__ uint32_t id_count(const TableDev &R, u128 fwd, int k) {
-    const u128 rc = revcomp(fwd, k);
-    return clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
-}
-
 __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int max_len,
                                                            const Variant *__restrict__ cand, uint64_t ncand, Indel *__restrict__ out, unsigned long long cap,
                                                            unsigned long long *__restrict__ ctl) {
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
         }
         // prefix: windows j < max_len of F + x x x ..
         uint32_t cnt = 0xFFFFFFFFu;
-        if (lane < max_len) cnt = id_count(R, id_kmer(pl_prefix(clo, fm, x & 1), pl_prefix(chi, fm, x & 2), lane, k), k);
+        if (lane < max_len) cnt = canon_count(R, id_kmer(pl_prefix(clo, fm, x & 1), pl_prefix(chi, fm, x & 2), lane, k), k);
         nlook += (unsigned)max_len;
         const unsigned long long fail = __ballot(lane < max_len && cnt < thre);
         const int Lp = fail ? (int)__builtin_ctzll(fail) : max_len;      // ins(.., L) can pass for L <= Lp only
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
         uint32_t my_amin = 0, my_rmin = 0;              // lane b: the minima of hypothesis bit b
         for (int L = 1; L <= Lp; ++L) {
             uint32_t a = 0xFFFFFFFFu;
-            if (lane < k - 1) a = id_count(R, id_kmer(pl_ins(clo, fm, k, L, x & 1), pl_ins(chi, fm, k, L, x & 2), L + lane, k), k);
+            if (lane < k - 1) a = canon_count(R, id_kmer(pl_ins(clo, fm, k, L, x & 1), pl_ins(chi, fm, k, L, x & 2), L + lane, k), k);
             nlook += (unsigned)(k - 1);
             a = wave_min32(a);
             const uint32_t pl = __shfl(pm, L - 1);
@@ -200,7 +194,7 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
                 if (!((dels >> L) & 1u)) continue;
                 uint32_t a = 0xFFFFFFFFu;
                 if (k > 2) {
-                    if (lane < k - 2) a = id_count(R, id_kmer(pl_del(clo, fm, L), pl_del(chi, fm, L), 1 + lane, k), k);
+                    if (lane < k - 2) a = canon_count(R, id_kmer(pl_del(clo, fm, L), pl_del(chi, fm, L), 1 + lane, k), k);
                     nlook += (unsigned)(k - 2);
                     a = wave_min32(a);
                 }
@@ -216,8 +210,8 @@ __global__ __launch_bounds__(256) void indels_check_kernel(const uint8_t *__rest
         const int Ld = (pass >> 16) ? 32 - __clz(pass >> 16) : 0;        // the largest deletion that passed
         const int jmax = Ld ? k + Ld - 2 : k - 2;                         // <= 78
         uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;                      // windows lane and lane + 64
-        if (lane <= jmax) ra = id_count(R, id_kmer(clo, chi, lane, k), k);
-        if (lane + 64 <= jmax) rb = id_count(R, id_kmer(clo, chi, lane + 64, k), k);
+        if (lane <= jmax) ra = canon_count(R, id_kmer(clo, chi, lane, k), k);
+        if (lane + 64 <= jmax) rb = canon_count(R, id_kmer(clo, chi, lane + 64, k), k);
         nlook += (unsigned)(jmax + 1);
         if (pass & 0xFFFFu) {
             const uint32_t r = wave_min32(lane <= k - 2 ? ra : 0xFFFFFFFFu);
@@ -274,7 +268,6 @@ __device__ __forceinline__ Plane pl_ins_y(Plane t, unsigned long long m, int k, 
     u.b |= ybit >> (64 - (k - 1));                      // (1 <= k - 1 <= 63)
     return u;
 }
-__device__ __forceinline__ uint32_t id_min(uint32_t a, uint32_t b) { return b < a ? b : a; }
 
 __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int max_len,
                                                            const Variant *__restrict__ cand, uint64_t ncand, MixedIns *__restrict__ out, unsigned long long cap,
@@ -285,7 +278,6 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
     const int k = R.k;
     const int CL = 2 * k - 2;                           // context bytes: at most 126
     const u128 kmask = maskbits(2 * k);
-    const unsigned long long below = (1ull << lane) - 1ull;
     const uint64_t nwv = (uint64_t)gridDim.x * 4;
     unsigned long long nlook = 0, ncomplex = 0;         // (wave-uniform)
     for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ncand; i += nwv) {
@@ -310,7 +302,7 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
         // level 1: S_1 = {x}
         uint32_t yk = (uint32_t)x, mn = 0xFFFFFFFFu;    // lane i < nf: prefix i, first base in the highest pair, and the minimum over its windows
         int nf = 1;
-        if (lane == 0) mn = id_count(R, band(bor(shl(F, 2), mk(0, (uint64_t)x)), kmask), k);
+        if (lane == 0) mn = canon_count(R, band(bor(shl(F, 2), mk(0, (uint64_t)x)), kmask), k);
         nlook += 1;
         if ((uint32_t)__shfl(mn, 0) < thre) continue;
         bool have_ref = false;
@@ -323,44 +315,27 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
             uint32_t a = 0xFFFFFFFFu;
             if (act) {
                 const u128 w = band(bor(shl(F, 2 * t), mk(0, yk)), kmask);      // the last k bases of F + y
-                a = id_count(R, band(bor(shl(w, 2), mk(0, (uint64_t)refc)), kmask), k);
+                a = canon_count(R, band(bor(shl(w, 2), mk(0, (uint64_t)refc)), kmask), k);
             }
             nlook += (unsigned)__popcll(actm);
-            a = id_min(a, mn);
-            const unsigned long long P = __ballot(act && a >= thre);
-            unsigned long long recm = 0;                // (wave-uniform) bit i: prefix i is a record
-            uint32_t my_amin = a;
-            if (k > 2) {
-                for (unsigned long long q = P; q; q &= q - 1ull) {
-                    const int j = (int)__builtin_ctzll(q);
-                    const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)yk, j), aj = (uint32_t)__builtin_amdgcn_readlane((int)a, j);
-                    const unsigned long long rv = brev64((unsigned long long)yj) >> (64 - 2 * t);      // base b: its high bit at 2b, its low bit at 2b + 1
-                    const unsigned long long yhi = id_squeeze((uint32_t)rv), ylo = id_squeeze((uint32_t)(rv >> 1));
-                    uint32_t b = 0xFFFFFFFFu;
-                    if (lane < k - 2) b = id_count(R, id_kmer(pl_ins_y(clo, fm, k, t, ylo), pl_ins_y(chi, fm, k, t, yhi), t + 1 + lane, k), k);
-                    nlook += (unsigned)(k - 2);
-                    b = id_min(wave_min32(b), aj);
-                    if (b >= thre) {
-                        recm |= 1ull << j;
-                        if (lane == j) my_amin = b;
-                    }
-                }
-            } else {
-                recm = P;
-            }
+            a = min32(a, mn);
+            uint32_t my_amin;
+            const unsigned long long recm = front_rejoin(R, thre, __ballot(act && a >= thre), a, nlook, my_amin, [&](int j) {      // windows t+1 .. k+t-2 of the planes with y put in
+                const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)yk, j);
+                const unsigned long long rv = brev64((unsigned long long)yj) >> (64 - 2 * t);      // base b: its high bit at 2b, its low bit at 2b + 1
+                const unsigned long long yhi = id_squeeze((uint32_t)rv), ylo = id_squeeze((uint32_t)(rv >> 1));
+                return id_kmer(pl_ins_y(clo, fm, k, t, ylo), pl_ins_y(chi, fm, k, t, yhi), t + 1 + lane, k);
+            });
             if (recm) {
                 if (!have_ref) {                        // windows 0 .. k-2 of s, once
                     uint32_t r = 0xFFFFFFFFu;
-                    if (lane < k - 1) r = id_count(R, id_kmer(clo, chi, lane, k), k);
+                    if (lane < k - 1) r = canon_count(R, id_kmer(clo, chi, lane, k), k);
                     nlook += (unsigned)(k - 1);
                     rmin = wave_min32(r);
                     have_ref = true;
                 }
-                unsigned long long base = 0;
-                const unsigned total = __popcll(recm);
-                if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
-                base = __shfl(base, 0);
-                if (base + total <= cap && ((recm >> lane) & 1ull)) {      // (a level writes all its records or none)
+                const unsigned long long at = front_reserve(recm, &ctl[SC_CURSOR], cap);
+                if (at != FRONT_NONE) {
                     MixedIns v;
                     v.pos = p;
                     v.seq = seq;
@@ -370,23 +345,18 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
                     v.len = (uint16_t)t;
                     v.kind = rmin >= thre ? VK_HET : VK_ERROR;
                     for (int q = 0; q < 5; ++q) v.pad[q] = 0;
-                    out[base + __popcll(recm & below)] = v;
+                    out[at] = v;
                 }
             }
             if (t >= max_len) break;
-            // extend: sixteen prefixes a round, (prefix, z) on lane 4 * prefix + z
-            int tot = 0;
-            for (int r0 = 0; r0 < nf; r0 += 16) {
-                const int src = r0 + (lane >> 2);       // <= 63
-                const uint32_t ny = ((uint32_t)__shfl(yk, src) << 2) | (uint32_t)(lane & 3), pm = (uint32_t)__shfl(mn, src);
-                uint32_t c = 0;
-                if (src < nf) c = id_count(R, band(bor(shl(F, 2 * (t + 1)), mk(0, ny)), kmask), k);
-                const bool ok = src < nf && c >= thre;
-                const unsigned long long B = __ballot(ok);
-                const int at = tot + __popcll(B & below);
-                if (ok && at < INDEL_FRONT) strip[at] = make_uint2(ny, id_min(pm, c));
-                tot += __popcll(B);
-            }
+            // extend: the last k bases of F + y + z
+            const int tot = front_extend(
+                R, thre, yk, mn, nf, INDEL_FRONT,
+                [=](int, uint32_t parent) {
+                    const uint32_t ny = (parent << 2) | (uint32_t)(lane & 3);
+                    return FrontChild<uint32_t>{ny, band(bor(shl(F, 2 * (t + 1)), mk(0, ny)), kmask), true, true};
+                },
+                [&](int at, int, uint32_t ny, uint32_t m) { strip[at] = make_uint2(ny, m); });
             nlook += 4u * (unsigned)nf;
             if (tot > INDEL_FRONT) {                    // complex: nothing of length > t is reported here
                 ++ncomplex;
@@ -394,16 +364,11 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
                 break;
             }
             if (tot == 0) break;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (lane < tot) {
-                const uint2 v = strip[lane];
+            front_handover(tot, [&](int l) {
+                const uint2 v = strip[l];
                 yk = v.x;
                 mn = v.y;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            });
             nf = tot;
         }
     }
@@ -413,11 +378,6 @@ __global__ __launch_bounds__(256) void indels_mixed_kernel(const uint8_t *__rest
 
 // ---- het clusters ----------------------------------------------------------------------------------------------------------------------
 enum { HC_LOOKUPS = 1, HC_COMPLEX = 2, HC_SEARCHED = 3 };                // control words 1 .. 3: table lookups made; complex and searched candidates
-
-__device__ __forceinline__ uint64_t hc_readlane64(uint64_t v, int l) {      // l wave-uniform
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-__device__ __forceinline__ u128 hc_readlane128(u128 v, int l) { return mk(hc_readlane64(v.hi, l), hc_readlane64(v.lo, l)); }
 
 __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ offs, TableDev R, uint32_t thre, int N,
                                                           const Variant *__restrict__ cand, uint64_t ncand, HetCluster *__restrict__ out, unsigned long long cap,
@@ -430,7 +390,6 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
     const int k = R.k;
     const int CL = 2 * k - 2 + N;                       // context bytes: at most 190
     const u128 kmask = maskbits(2 * k), fmask = maskbits(2 * (k - 1));
-    const unsigned long long below = (1ull << lane) - 1ull;
     const uint64_t nwv = (uint64_t)gridDim.x * 4;
     unsigned long long nlook = 0, ncomplex = 0, nsearched = 0;      // (wave-uniform)
     for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < ncand; i += nwv) {
@@ -456,15 +415,15 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
         // ref: windows 0 .. k+Rev-2 of s, lane j and, past 64, lane j - 64
         const int jmax = k + Rev - 2;                   // <= 126
         uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;
-        if (lane <= jmax) ra = id_count(R, id_kmer(clo, chi, lane, k), k);
+        if (lane <= jmax) ra = canon_count(R, id_kmer(clo, chi, lane, k), k);
         nlook += (unsigned)(jmax < 63 ? jmax + 1 : 64);
         const uint32_t pma = wave_prefix_min32<64>(ra);
         if ((uint32_t)__shfl(pma, k - 1) < thre) continue;      // R_max = 0: the sequence's own k-mers are unreliable here
         if (jmax >= 64) {
-            if (lane + 64 <= jmax) rb = id_count(R, id_kmer(clo, chi, lane + 64, k), k);
+            if (lane + 64 <= jmax) rb = canon_count(R, id_kmer(clo, chi, lane + 64, k), k);
             nlook += (unsigned)(jmax - 63);
         }
-        const uint32_t pmb = id_min(wave_prefix_min32<64>(rb), (uint32_t)__shfl(pma, 63));
+        const uint32_t pmb = min32(wave_prefix_min32<64>(rb), (uint32_t)__shfl(pma, 63));
         const int ri = lane + k - 1;                    // lane R - 1: ref_min(R) is the prefix minimum at window k + R - 2
         const uint32_t va = (uint32_t)__shfl(pma, ri & 63), vb = (uint32_t)__shfl(pmb, ri & 63);
         const uint32_t rmin = ri < 64 ? va : vb;
@@ -484,7 +443,7 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
         u128 y = mk(0, (uint64_t)x);                    // lane i < nf: prefix i, first base in the highest pair ...
         uint32_t mn = 0xFFFFFFFFu;                      // ... and the minimum over its windows
         int nf = 1;
-        if (lane == 0) mn = id_count(R, band(bor(shl(F, 2), y), kmask), k);
+        if (lane == 0) mn = canon_count(R, band(bor(shl(F, 2), y), kmask), k);
         nlook += 1;
         if ((uint32_t)__shfl(mn, 0) < thre) continue;
         for (int t = 1; t <= N; ++t) {
@@ -492,41 +451,35 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
             // closure: a prefix that has been back on the sequence for k - 1 bases is not extended
             unsigned long long closedm = 0;             // (wave-uniform) bit i: prefix i is closed
             for (int i2 = 0; i2 < nf; ++i2) {
-                const u128 Wi = hc_readlane128(W, i2);
+                const u128 Wi = readlane128(W, i2);
                 if (__ballot(lane < Rmax && eq(Wi, CW))) closedm |= 1ull << i2;
             }
             // extend: sixteen prefixes a round, (prefix, z) on lane 4 * prefix + z; lane i keeps the solid mask of prefix i
             const u128 Fs = t + 1 < k ? shl(F, 2 * (t + 1)) : mk(0, 0);      // from t + 1 >= k on the newest window is yz's alone
             unsigned solid = 0;
-            int tot = 0;
-            for (int r0 = 0; r0 < nf; r0 += 16) {
-                const int src = r0 + (lane >> 2);       // <= 63
-                const u128 ny = bor(shl(mk(__shfl(y.hi, src), __shfl(y.lo, src)), 2), mk(0, (uint64_t)(lane & 3)));      // (at t = 64 the first base is lost: no child then)
-                const uint32_t pm = (uint32_t)__shfl(mn, src);
-                uint32_t c = 0;
-                if (src < nf) c = id_count(R, band(bor(Fs, ny), kmask), k);
-                const bool ok = src < nf && c >= thre;
-                const unsigned long long B = __ballot(ok);
-                if (lane >= r0 && lane < r0 + 16) solid = (unsigned)(B >> (4 * (lane - r0))) & 15u;
-                const bool child = ok && t < N && !((closedm >> src) & 1ull);
-                const unsigned long long C = __ballot(child);
-                const int at = tot + __popcll(C & below);
-                if (child && at < INDEL_FRONT) {
+            const int tot = front_extend(
+                R, thre, y, mn, nf, INDEL_FRONT,
+                [=](int src, u128 parent) {
+                    const u128 ny = bor(shl(parent, 2), mk(0, (uint64_t)(lane & 3)));      // (at t = 64 the first base is lost: no child then)
+                    return FrontChild<u128>{ny, band(bor(Fs, ny), kmask), true, t < N && !((closedm >> src) & 1ull)};
+                },
+                [&](int at, int, u128 ny, uint32_t m) {
                     strip_y[at] = make_ulonglong2(ny.lo, ny.hi);
-                    strip_mn[at] = id_min(pm, c);
-                }
-                tot += __popcll(C);
-            }
+                    strip_mn[at] = m;
+                },
+                [&](int r0, unsigned long long B) {
+                    if (lane >= r0 && lane < r0 + 16) solid = (unsigned)(B >> (4 * (lane - r0))) & 15u;
+                });
             nlook += 4u * (unsigned)nf;
             // rejoin: the records of level t, prefix by prefix, lane R - 1 for its own R
             for (int i2 = 0; i2 < nf; ++i2) {
-                const u128 yi = hc_readlane128(y, i2), Wi = hc_readlane128(W, i2);
+                const u128 yi = readlane128(y, i2), Wi = readlane128(W, i2);
                 const unsigned sol = (unsigned)__builtin_amdgcn_readlane((int)solid, i2);
                 const uint32_t mni = (uint32_t)__builtin_amdgcn_readlane((int)mn, i2);
                 bool alive = lane < Rmax && ((sol >> nb) & 1u) && ((unsigned)yi.lo & 3u) != lastref && !(t == 1 && lane == 0);
                 unsigned long long am = __ballot(alive);
                 for (int j = 1; j <= 3 && j <= k - 2 && am; ++j) {      // windows t + 1 .. t + 3, each lane its own
-                    if (alive) alive = id_count(R, band(bor(shl(Wi, 2 * (j + 1)), shr(G, 2 * (k - 2 - j))), kmask), k) >= thre;
+                    if (alive) alive = canon_count(R, band(bor(shl(Wi, 2 * (j + 1)), shr(G, 2 * (k - 2 - j))), kmask), k) >= thre;
                     nlook += (unsigned)__popcll(am);
                     am = __ballot(alive);
                 }
@@ -534,23 +487,20 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
                 uint32_t my_amin = 0;
                 for (unsigned long long q = am; q; q &= q - 1ull) {
                     const int r = (int)__builtin_ctzll(q);
-                    const u128 Gr = hc_readlane128(G, r);
+                    const u128 Gr = readlane128(G, r);
                     uint32_t b = 0xFFFFFFFFu;
                     if (lane < k - 1)                   // window t + lane: the last k - 1 - lane bases of W, then lane + 1 bases of G
-                        b = id_count(R, band(bor(shl(Wi, 2 * (lane + 1)), shr(Gr, 2 * (k - 2 - lane))), kmask), k);
+                        b = canon_count(R, band(bor(shl(Wi, 2 * (lane + 1)), shr(Gr, 2 * (k - 2 - lane))), kmask), k);
                     nlook += (unsigned)(k - 1);
-                    b = id_min(wave_min32(b), mni);
+                    b = min32(wave_min32(b), mni);
                     if (b >= thre) {
                         recm |= 1ull << r;
                         if (lane == r) my_amin = b;
                     }
                 }
                 if (recm) {
-                    unsigned long long base = 0;
-                    const unsigned total = __popcll(recm);
-                    if (lane == 0) base = atomicAdd(&ctl[SC_CURSOR], (unsigned long long)total);
-                    base = __shfl(base, 0);
-                    if (base + total <= cap && ((recm >> lane) & 1ull)) {      // (a prefix writes all its records or none)
+                    const unsigned long long at = front_reserve(recm, &ctl[SC_CURSOR], cap);      // (a prefix writes all its records or none)
+                    if (at != FRONT_NONE) {
                         const u128 rv = shr(mk(revpairs64(yi.lo), revpairs64(yi.hi)), 128 - 2 * t);      // base i in bits 2i, 2i + 1
                         HetCluster v;
                         v.pos = p;
@@ -562,7 +512,7 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
                         v.bases[1] = rv.hi;
                         v.len = (uint16_t)t;
                         for (int z = 0; z < 6; ++z) v.pad[z] = 0;
-                        out[base + __popcll(recm & below)] = v;
+                        out[at] = v;
                     }
                 }
             }
@@ -572,16 +522,11 @@ __global__ __launch_bounds__(256) void het_cluster_kernel(const uint8_t *__restr
                 break;
             }
             if (tot == 0) break;                        // (also t == N: no child is placed then)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (lane < tot) {
-                const ulonglong2 v = strip_y[lane];
+            front_handover(tot, [&](int l) {
+                const ulonglong2 v = strip_y[l];
                 y = mk(v.y, v.x);
-                mn = strip_mn[lane];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+                mn = strip_mn[l];
+            });
             nf = tot;
         }
     }
@@ -635,65 +580,45 @@ int indel_scan_device(Table &T, int n_seqs, const uint8_t *d_text, const int64_t
         if (!out.recs.empty()) HIPCHK(hipMemcpyAsync(out.recs.data(), d_rec, out.recs.size() * sizeof(Indel), hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
     }
-    std::vector<unsigned long long> cplx;
+    const unsigned search_grid = (unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16);
     if (ncand && mixed) {
         const int W = Table::WS_MIXED;
-        const size_t words = SC_WORDS + (size_t)n_seqs;      // the control words, then the complex sites per sequence
-        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 1, words * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
-        if (!d_ctl) return -1;
-        MixedIns *d_rec = nullptr;
-        auto search = [&](unsigned long long cap) {
-            d_rec = (MixedIns *)T.workspace(W, cap * sizeof(MixedIns), err);
-            if (!d_rec) return -1;
-            hipLaunchKernelGGL(indels_mixed_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, max_len,
-                               S.d_cand, ncand, d_rec, cap, d_ctl, d_ctl + SC_WORDS);
-            return 0;
-        };
-        if (run_counted(st, d_ctl, words, d_ctl, ncand + 4096, "indel scan: the number of mixed insertions changed between two searches", ctl, out.mixed_seconds,
-                        out.mixed_retried, err, search))
+        unsigned long long ctl[SC_WORDS] = {0, 0, 0, 0};
+        std::vector<unsigned long long> cplx;           // after the control words: the complex sites per sequence
+        const int sums[1] = {MC_COMPLEX};
+        if (search_stage(T, W + 1, n_seqs, 1, sums, ncand + 4096, "indel scan: the number of mixed insertions changed between two searches",
+                         "indel scan: the complex sites per sequence do not add up", ctl, out.mixed_recs, cplx, out.mixed_seconds, out.mixed_retried, err,
+                         [&](unsigned long long cap, unsigned long long *d_ctl, unsigned long long *d_per) {
+                             MixedIns *d_rec = (MixedIns *)T.workspace(W, cap * sizeof(MixedIns), err);
+                             if (d_rec)
+                                 hipLaunchKernelGGL(indels_mixed_kernel, dim3(search_grid), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, max_len, S.d_cand, ncand, d_rec, cap,
+                                                    d_ctl, d_per);
+                             return d_rec;
+                         }))
             return -1;
         out.mixed_lookups = ctl[MC_LOOKUPS];
-        out.mixed_recs.resize(ctl[SC_CURSOR]);
-        cplx.resize((size_t)n_seqs);
-        if (!out.mixed_recs.empty()) HIPCHK(hipMemcpyAsync(out.mixed_recs.data(), d_rec, out.mixed_recs.size() * sizeof(MixedIns), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cplx.data(), d_ctl + SC_WORDS, cplx.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        unsigned long long sum = 0;
-        for (size_t i = 0; i < cplx.size(); ++i) {
-            out.mixed_counts[3 * i + 2] = cplx[i];
-            sum += cplx[i];
-        }
-        if (sum != ctl[MC_COMPLEX]) { err = "indel scan: the complex sites per sequence do not add up"; return -1; }
+        for (size_t i = 0; i < cplx.size(); ++i) out.mixed_counts[3 * i + 2] = cplx[i];
     }
     if (ncand && cluster_len) {
         const int W = Table::WS_CLUSTERS;
-        const size_t words = SC_WORDS + 2 * (size_t)n_seqs;      // the control words, then per sequence the searched and the complex candidates
-        unsigned long long *d_ctl = (unsigned long long *)T.workspace(W + 1, words * sizeof(unsigned long long), err), ctl[SC_WORDS] = {0, 0, 0, 0};
-        if (!d_ctl) return -1;
-        HetCluster *d_rec = nullptr;
-        auto search = [&](unsigned long long cap) {
-            d_rec = (HetCluster *)T.workspace(W, cap * sizeof(HetCluster), err);
-            if (!d_rec) return -1;
-            hipLaunchKernelGGL(het_cluster_kernel, dim3((unsigned)std::min<uint64_t>((ncand + 3) / 4, 256 * 16)), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, cluster_len,
-                               S.d_cand, ncand, d_rec, cap, d_ctl, d_ctl + SC_WORDS);
-            return 0;
-        };
-        if (run_counted(st, d_ctl, words, d_ctl, ncand + 4096, "indel scan: the number of het clusters changed between two searches", ctl, out.cluster_seconds,
-                        out.cluster_retried, err, search))
+        unsigned long long ctl[SC_WORDS] = {0, 0, 0, 0};
+        std::vector<unsigned long long> per;            // after the control words: per sequence the searched and the complex candidates
+        const int sums[2] = {HC_SEARCHED, HC_COMPLEX};
+        if (search_stage(T, W + 1, n_seqs, 2, sums, ncand + 4096, "indel scan: the number of het clusters changed between two searches",
+                         "indel scan: the searched and complex candidates per sequence do not add up", ctl, out.cluster_recs, per, out.cluster_seconds, out.cluster_retried, err,
+                         [&](unsigned long long cap, unsigned long long *d_ctl, unsigned long long *d_per) {
+                             HetCluster *d_rec = (HetCluster *)T.workspace(W, cap * sizeof(HetCluster), err);
+                             if (d_rec)
+                                 hipLaunchKernelGGL(het_cluster_kernel, dim3(search_grid), dim3(256), 0, st, d_text, S.d_offs, T.d, thre, cluster_len, S.d_cand, ncand, d_rec,
+                                                    cap, d_ctl, d_per);
+                             return d_rec;
+                         }))
             return -1;
         out.cluster_lookups = ctl[HC_LOOKUPS];
-        out.cluster_recs.resize(ctl[SC_CURSOR]);
-        std::vector<unsigned long long> per(2 * (size_t)n_seqs);
-        if (!out.cluster_recs.empty())
-            HIPCHK(hipMemcpyAsync(out.cluster_recs.data(), d_rec, out.cluster_recs.size() * sizeof(HetCluster), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(per.data(), d_ctl + SC_WORDS, per.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(jk_stream_wait(st));
-        unsigned long long nsearched = 0, ncomplex = 0;
         for (size_t i = 0; i < (size_t)n_seqs; ++i) {
-            nsearched += out.cluster_counts[4 * i] = per[2 * i];
-            ncomplex += out.cluster_counts[4 * i + 3] = per[2 * i + 1];
+            out.cluster_counts[4 * i] = per[2 * i];
+            out.cluster_counts[4 * i + 3] = per[2 * i + 1];
         }
-        if (nsearched != ctl[HC_SEARCHED] || ncomplex != ctl[HC_COMPLEX]) { err = "indel scan: the searched and complex candidates per sequence do not add up"; return -1; }
         if (het_cluster_finish(out.cluster_recs, n_seqs, cluster_len, out.cluster_counts, err)) return -1;
     }
     if (variant_check_stage(T, n_seqs, d_text, thre, "indel scan", S, out.var, err)) return -1;

@@ -25,7 +25,10 @@
 // Host side: pack_host_text (sequences in host memory -> one device text), settle (the tables of a scan zeroed and ordered before one
 // stream), build_tiles / upload_tiles, run_counted (launch, read the control words, repeat once with exactly the counted room), stitch_runs,
 // and run_scan, the whole host stage of a run scan around the caller's one kernel launch.  The workspace base stays the caller's: each scan
-// has its own slots.
+// has its own slots.  search_stage is the same for the front searches (front_search.hpp): control and per-sequence words, run_counted, the
+// downloads and the add-up check around the caller's one kernel launch.
+// Wave helpers, once: wave_incl_scan, wave_sum, wave_min32, wave_prefix_min32, min32, wave_or64, readlane64 / 128, readfirstlane64, and
+// canon_count, a forward k-mer's count in a table.
 #pragma once
 #include "report.hpp"
 #include <algorithm>
@@ -70,6 +73,25 @@ __device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
         v = u < v ? u : v;
     }
     return v;
+}
+
+__device__ __forceinline__ uint32_t min32(uint32_t a, uint32_t b) { return b < a ? b : a; }
+__device__ __forceinline__ uint64_t wave_or64(uint64_t v) {              // OR over the wave, in every lane
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {      // l wave-uniform
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+__device__ __forceinline__ u128 readlane128(u128 v, int l) { return mk(readlane64(v.hi, l), readlane64(v.lo, l)); }
+__device__ __forceinline__ uint64_t readfirstlane64(uint64_t v) {        // a value all lanes hold, as a scalar
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+// the table's count of the canonical form of the forward k-mer fwd, clamped to 32 bits
+__device__ __forceinline__ uint32_t canon_count(const TableDev &R, u128 fwd, int k) {
+    const u128 rc = revcomp(fwd, k);
+    return clamp32(table_get(R, mix(lt(rc, fwd) ? rc : fwd, R.B)));
 }
 
 template <int N> __device__ __forceinline__ uint32_t wave_prefix_min32(uint32_t v) {      // lane j < N: the minimum over lanes 0 .. j
@@ -268,9 +290,11 @@ int launch_heads(hipStream_t st, const ScanTile *d_tiles, const TileRuns *d_tout
 // it WANTED to write to d_ctl[SC_CURSOR] and writes nothing that does not fit.  Zeroes d_zero[0 .. zero_words) (the control words are in
 // there) before each launch, adds the kernel's event time to `seconds`, and leaves the control words in ctl.  If more was wanted than
 // `cap`, it is repeated once with exactly that room (`retried`); more still is the error `changed`.
+// A kernel that appends to TWO lists counts the second one in control word word2 and writes nothing that does not fit both; *cap2 is the
+// second list's room, which launch reads where it sizes that list.  More wanted of either: repeated once with exactly that room for both.
 template <class Launch>
 int run_counted(hipStream_t st, unsigned long long *d_zero, size_t zero_words, const unsigned long long *d_ctl, unsigned long long cap, const std::string &changed,
-                unsigned long long (&ctl)[SC_WORDS], double &seconds, int &retried, std::string &err, Launch &&launch) {
+                unsigned long long (&ctl)[SC_WORDS], double &seconds, int &retried, std::string &err, Launch &&launch, int word2 = 0, unsigned long long *cap2 = nullptr) {
     Events ev;
     if (ev.create(err)) return -1;
     for (int attempt = 0;; ++attempt) {
@@ -282,11 +306,42 @@ int run_counted(hipStream_t st, unsigned long long *d_zero, size_t zero_words, c
         HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
         if (ev.add_seconds(seconds, err)) return -1;
-        if (ctl[SC_CURSOR] <= cap) return 0;
+        if (ctl[SC_CURSOR] <= cap && (!cap2 || ctl[word2] <= *cap2)) return 0;
         if (attempt) { err = changed; return -1; }
-        cap = ctl[SC_CURSOR];            // the kernel counted what it could not write: exactly this much room is needed
+        cap = std::max(cap, ctl[SC_CURSOR]);            // the kernel counted what it could not write: exactly this much room is needed
+        if (cap2) *cap2 = std::max(*cap2, ctl[word2]);
         retried = 1;
     }
+}
+
+// The host stage of a front search on T's stream, after the caller has uploaded its sites: the control words and `per_seq` words per
+// sequence after them live in workspace slot ctl_slot and are zeroed before each launch.  launch(cap, d_ctl, d_per) sizes the caller's
+// record list for cap records, launches its kernel and returns the list (null: err is set); run_counted repeats it once if more were
+// found.  Leaves the control words in ctl, the records in recs and the per-sequence words in per, all downloaded and waited for, and
+// checks that column c of the per-sequence words adds up to control word sum_words[c] (`no_sum` if not).  `seconds` is the kernel's event
+// time, both attempts if it was repeated.
+template <class Rec, class Launch>
+int search_stage(Table &T, int ctl_slot, int n_seqs, int per_seq, const int *sum_words, unsigned long long cap, const char *changed, const char *no_sum,
+                 unsigned long long (&ctl)[SC_WORDS], std::vector<Rec> &recs, std::vector<unsigned long long> &per, double &seconds, int &retried, std::string &err,
+                 Launch &&launch) {
+    hipStream_t st = T.stream;
+    const size_t words = SC_WORDS + (size_t)per_seq * (size_t)n_seqs;
+    unsigned long long *d_ctl = (unsigned long long *)T.workspace(ctl_slot, words * sizeof(unsigned long long), err);
+    if (!d_ctl) return -1;
+    const Rec *d_rec = nullptr;
+    if (run_counted(st, d_ctl, words, d_ctl, cap, changed, ctl, seconds, retried, err, [&](unsigned long long room) { return (d_rec = launch(room, d_ctl, d_ctl + SC_WORDS)) ? 0 : -1; }))
+        return -1;
+    recs.resize(ctl[SC_CURSOR]);
+    per.resize(words - SC_WORDS);
+    if (!recs.empty()) HIPCHK(hipMemcpyAsync(recs.data(), d_rec, recs.size() * sizeof(Rec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(per.data(), d_ctl + SC_WORDS, per.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(jk_stream_wait(st));
+    for (int c = 0; c < per_seq; ++c) {
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < (size_t)n_seqs; ++i) sum += per[(size_t)per_seq * i + c];
+        if (sum != ctl[sum_words[c]]) { err = no_sum; return -1; }
+    }
+    return 0;
 }
 
 // The nparts > 0 partial runs of a run scan made into final runs (workspace slot out_slot of T) and queued for download into `runs`; the
