@@ -1,5 +1,6 @@
 """Planted polishing workloads whose position classes are known by construction, and a restatement of the polisher's cut rule
-(jasper_amd/csrc/polish.hip: find_sync_batch_kernel, find_clean_batch_kernel; polish_host.hip: build_segments).  No GPU use.
+(jasper_amd/csrc/polish.hip: find_sync_batch_kernel, find_clean_batch_kernel; polish_plan.hpp: plan_cuts, which
+tests/test_polish_plan_host.py holds against this restatement).  No GPU use.
 
 The workload.  A random truth without a repeated canonical k-mer; error-free reads: pieces of the truth, C times each, 'N'
 between them.  A window that a piece covers has count C (solid), any other count 0, and no window is OTHER (no count is 50
@@ -141,7 +142,7 @@ def clean_cells(cls, k, cell):
 
 
 def cuts(cls, length, k, geo):
-    """build_segments: [(position, chained)] of one chunk of `length` bases in one pass; its segments are one more"""
+    """plan_cuts: [(position, chained)] of one chunk of `length` bases in one pass; its segments are one more"""
     TMIN, CMIN = geo["TMIN"], geo["CMIN"]
     nwin = length - k + 1
     assert len(cls) == max(0, nwin)
