@@ -24,10 +24,13 @@
 // and the polisher do not know which path filled the table.  HBM traffic per k-mer: 1 B base + 8 B x 2 (part1 list)
 // + 8 B x 2 (part2 list) + the table once in, once out -- all of it streaming.
 //
-// Host side: Table::partition_geometry sizes the lists (PartGeom, table.hpp), Table::launch_count_partitioned puts a piece's
-// passes on the stream, the xchg_* entry points do the same for the exchange between GPUs (each begins with xchg_begin).  Every
-// pass has one place that picks the kernel instance -- launch_part1, launch_part2, launch_region_insert -- and every instance
-// is launched through launch_big_lds, which raises its dynamic-LDS limit the first time.
+// Host side: the arithmetic is in count_plan.hpp, plain C++ that a CPU test reaches -- partition_geometry sizes the lists
+// (PartGeom), xchg_geometry does so for the exchange between GPUs, piece_buffers, region_insert_launch and part2_instance size a
+// piece's buffers and launches; none of them reads the environment (CountOptions::from_env, below, does, whenever a geometry
+// is derived).  Here Table::launch_count_partitioned puts a piece's passes on the stream and the xchg_* entry points do the same
+// for the exchange (each begins with xchg_begin).  Every pass has one place that picks the kernel instance -- launch_part1,
+// launch_part2, launch_region_insert -- and every instance is launched through launch_big_lds, which raises its dynamic-LDS
+// limit the first time.
 #include "table.hpp"
 #include <algorithm>
 #include <cmath>
@@ -52,14 +55,10 @@ namespace jk {
 // for the prefetch of the next tile, although nothing in the workgroup reads those bytes back.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-constexpr int PT_THREADS = 1024;
-constexpr int PT_GROUP = 16;
-constexpr int PT_TILE = PT_THREADS * PT_GROUP;   // 16384 records per block iteration
+// (PT_THREADS, PT_GROUP, PT_TILE, PT_MAXBUCKETS, RG_MAXBITS and the other constants the geometry is made from: count_plan.hpp)
 constexpr int PT_HALO = 4;
-constexpr int PT_MAXBUCKETS = 2048;              // p1, p2 <= 11
-constexpr int RG_MAXBITS = 12;                   // region = 4096 slots: 48 KB of LDS in region_insert_kernel, three workgroups per CU (8192 for the largest tables)
 
-// (PartGeom, the geometry of the two list levels: table.hpp)
+// (PartGeom, the geometry of the two list levels: count_plan.hpp)
 // level-1 list of bucket b = slices  out1[(b * nblk1 + g) * cap1 ...], filled counts cnt1[g * 2^p1 + b]  (slice-major: a wave's 64
 // fill-count atomics in part1 -- lane = bucket -- are then 256 contiguous bytes, four requests to the memory side instead of 8 x nblk1)
 // region list of region r  = slices  out2[(r * nblk2 + x) * cap2 ...],   filled counts cnt2[r * nblk2 + x]
@@ -724,7 +723,7 @@ __global__ __launch_bounds__(256) void transpose_counts_kernel(const unsigned in
 // The list kernels keep their stages in dynamic LDS beyond the default limit: every instance has the limit raised once per
 // process, the first time it is launched (an instance that missed its own line failed only at run time, on the shape that
 // reached it).
-constexpr int BIG_LDS = 160 * 1024;    // the whole LDS of a CU
+// (BIG_LDS, the whole LDS of a CU: count_plan.hpp)
 template <auto KERNEL, typename... Args>
 static hipError_t launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
     static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
@@ -941,7 +940,7 @@ constexpr size_t P2_LDS = (size_t)PT_TILE * 8 + (size_t)(3 * PT_MAXBUCKETS + 1 +
 // <512, 10>: up to 512 lists (tables of 2^30 .. 2^32 slots, and every shard of the larger configurations): the carry alone is
 // 64 KB, next to an 80-KB stage (10 rows; 8 rows: 12.1-12.4 ms against 11.7 on the 140 Mb workload); a round brings a list 16 records on average, i.e. about one line leaves per list and round and
 // nearly every record passes through the carry (LDS traffic, which this kernel has to spare).
-constexpr int P2F_LINE = 16;           // records per 128-byte line
+// (P2F_LINE, records per 128-byte line: count_plan.hpp)
 // per list and round: stage record i leaves to gbase + 8 i if i < lim, else waits in carry slot i + cadd
 struct P2Meta { uint64_t gbase; uint32_t lim; int32_t cadd; };
 __device__ __forceinline__ u128 rec_hash(uint64_t b1, uint64_t r, int recbits) { return hash_of(b1, r, recbits); }
@@ -1190,8 +1189,7 @@ __global__ __launch_bounds__(PT_THREADS, 4) void part2f_kernel(const REC *__rest
     }
 }
 
-constexpr int LDS_HBINS = 1024;        // histogram bins kept in LDS by region_insert_kernel (higher multiplicities are rare: global atomics)
-constexpr int LI_MAXSL = 64;           // slices per region an owner reads (region_insert_kernel<., XCHG>)
+// (LDS_HBINS, LI_MAXSL: count_plan.hpp)
 // ---- final: region lists -> LDS image of the region -> table ---------------------------------------------------------------------
 // One workgroup per region of R = 2^rbits slots (R <= 4096 here: 48 KB of LDS, three workgroups of 512 threads per CU, so that
 // one's record loads and image write-out overlap another's insert loop).  The LDS image keeps the tag (8 bytes, the table's own
@@ -1701,62 +1699,26 @@ __global__ __launch_bounds__(256) void import3h_kernel(const unsigned long long 
     if ((threadIdx.x & 63) == 0 && fresh) atomicAdd(&T.stats[ST_DISTINCT], fresh);
 }
 
-static uint32_t list_cap(double avg) { return (uint32_t)std::min<double>(4.0e9, avg * 1.25 + 8.0 * std::sqrt(avg) + 64.0); }
-
-// can this piece take the partitioned path, and with which geometry?
-bool Table::partition_geometry(uint64_t piece_bases, PartGeom &G) const {
-    if (getenv("JASPER_COUNT_DIRECT")) return false;
-    if (piece_bases < (8u << 20)) return false;          // small pieces: the direct kernel is already latency-hidden
-    const int B = d.B, s = d.s;
-    // 8-byte records hold the hash below the p1 <= 10 bucket bits: keys of up to 74 bits (k <= 37).  Longer keys travel as
-    // 16-byte records (part1w_kernel, part2f_kernel<., ., ., Rec16>, region_insert_kernel<., ., Rec16>): half the records per LDS round.
-    const bool rec16 = B > 74;
-    if (rec16 && getenv("JASPER_COUNT_NO_REC16")) return false;
-    if (d.ext && !rec16) return false;                    // (a tiny table for short keys: its images would need the second word for 8-byte records)
-    if (d.ext && getenv("JASPER_COUNT_NO_WIDE")) return false;
-    const int need_p1 = rec16 ? std::min(10, s - 12) : (B > 64 ? B - 64 : 0);
-    // regions of 2^12 slots (three region_insert workgroups per CU); 2^13 only where the two list levels cannot split finer
-    int p1 = 0, p2 = 0;
-    bool ok = false;
-    // (first choice: at most 512 lists per bucket, which part2f_kernel writes in whole lines)
-    // (a wide table's image is 20 bytes per slot: regions of 2^11)
-    const int rg0 = d.ext ? RG_MAXBITS - 1 : RG_MAXBITS;
-    for (int maxp2 = 9; maxp2 <= (rec16 ? 9 : 11) && !ok; maxp2 += 2)
-    for (int rg = rg0; rg <= rg0 + 1 && !ok; ++rg) {
-        p1 = std::max(need_p1, (s - rg + 1) / 2);
-        if (p1 < 1) p1 = 1;
-        if (p1 > 10 || p1 > s - 8 || p1 < 1) continue;    // (a table too small to be worth it)
-        p2 = s - rg - p1;
-        if (p2 < 0) p2 = 0;
-        ok = p2 <= maxp2;
-    }
-    if (!ok) return false;
-    G.p1 = p1; G.p2 = p2; G.rbits = s - p1 - p2; G.recbits = B - p1;
-    // one 1024-thread block (159 KB of LDS) per CU; the blocks of an XCD (b, b + 8, ...) share their slices (part1_kernel)
-    const uint64_t tile1 = (uint64_t)PT_TILE;
-    const uint64_t ntiles = (piece_bases + tile1 - 1) / tile1;
-    uint64_t grid1 = piece_bases / ((uint64_t)(1u << p1) * 512);
-    grid1 = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(grid1, ntiles), 256));
+// what the environment switches say, for the geometry functions of count_plan.hpp: read whenever a geometry is derived or a
+// piece is sized (tests flip the switches in-process between calls), the two tuning experiments once per process.  Not quite
+// the moments of the code this replaced: every call reads every switch (JASPER_EXPERIMENT_PIECE also where a geometry is derived,
+// the exchange's switches also where a piece is sized); the two tuning experiments are fixed at the first call of this function,
+// before at the first geometry that got past its refusals; and launch_part2 looks at JASPER_EXPERIMENT_OLDP2 for every geometry,
+// before only where the whole-line kernel would do.  Nothing in the tree sets a switch between two such moments.
+CountOptions CountOptions::from_env() {
+    CountOptions o;
+    o.direct = getenv("JASPER_COUNT_DIRECT") != nullptr;
+    o.no_rec16 = getenv("JASPER_COUNT_NO_REC16") != nullptr;
+    o.no_wide = getenv("JASPER_COUNT_NO_WIDE") != nullptr;
     static const int ngrp_exp = getenv("JASPER_EXPERIMENT_NGRP") ? atoi(getenv("JASPER_EXPERIMENT_NGRP")) : 0;     // tuning experiments only
-    // (measured, 47 Mb workload, round 4's kernel with the fill counts slice-major: 2 to 16 slices per list 4.0-4.1 ms, 32 slices 4.2,
-    //  ONE slice 5.3 -- 256 blocks adding to each count; with the counts bucket-major a wave's 64 atomics were 8 x nblk1 requests
-    //  to the memory side, which alone took 4.4 ms at 2 slices and more at 8.  8 slices: part2f's 16 waves find slices of their own)
-    const uint64_t nblk1 = std::min<uint64_t>(grid1, ngrp_exp > 0 ? (uint64_t)ngrp_exp : 8);
-    G.grid1 = (uint32_t)grid1;
-    G.nblk1 = (uint32_t)nblk1;
-    // (a slice takes the tiles of ceil(grid1 / nblk1) blocks of ceil(ntiles / grid1) tiles each)
-    const uint64_t tiles_per_slice = ((grid1 + nblk1 - 1) / nblk1) * ((ntiles + grid1 - 1) / grid1);
-    // (a level-1 slice holds half a million records and more: 10 % above the BASES that can fall into it -- records are ~3/4 of the
-    //  bases -- is slack for a bucket with a very frequent k-mer; what does not fit is deferred.  Device memory that has been used
-    //  before is cleared when it is allocated again, ~28 ms per GB on some boxes: every GB of slack shows in a first call.)
-    const double avg1 = (double)std::min<uint64_t>(piece_bases, tiles_per_slice * tile1) / (double)(1u << p1);
-    G.cap1 = avg1 >= 65536.0 ? (uint32_t)std::min<double>(4.0e9, avg1 * 1.10 + 8.0 * std::sqrt(avg1) + 64.0) : list_cap(avg1);
-    // one slice per region list: part2 runs one 1024-thread block per CU, and 2^p1 >= 256 buckets already fill the chip;
-    // region_insert_kernel then reads a region's records as one contiguous list
     static const int nblk2_exp = getenv("JASPER_EXPERIMENT_NBLK2") ? atoi(getenv("JASPER_EXPERIMENT_NBLK2")) : 0;   // tuning experiments only
-    G.nblk2 = p2 ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nblk1, nblk2_exp > 0 ? nblk2_exp : ((1u << p1) >= 256 ? 1 : 8))) : 1;
-    G.cap2 = p2 ? (list_cap((double)piece_bases / ((double)(1ull << (p1 + p2)) * (double)G.nblk2)) + 15u) & ~15u : 0;      // whole 128-byte lines (part2f_kernel)
-    return true;
+    o.ngrp = ngrp_exp;
+    o.nblk2 = nblk2_exp;
+    o.xchg_rb13 = getenv("JASPER_EXPERIMENT_XCHG_RB13") != nullptr;
+    o.xchg_rb12 = getenv("JASPER_EXPERIMENT_XCHG_RB12") != nullptr;
+    if (const char *e = getenv("JASPER_XCHG_TEST_MAXLISTS")) o.xchg_max_lists = std::max(2, atoi(e));
+    if (const char *e = getenv("JASPER_EXPERIMENT_PIECE")) { o.piece_set = true; o.piece = strtoull(e, nullptr, 10); }   // tuning experiments only
+    return o;
 }
 
 // second pass, one place for one GPU and for a sender of the exchange: every level-1 bucket -> nown x 2^p2 lists (nown = 1: one
@@ -1772,22 +1734,19 @@ static hipError_t launch_part2f(hipStream_t stream, dim3 grid, P2Args P, const u
 static int launch_part2(hipStream_t stream, const TableDev &d, const PartGeom &G, uint32_t nown, bool by_owner, const uint64_t *out1, const unsigned int *cnt1, uint64_t *out2,
                         unsigned int *cnt2, const DeferList &D, std::string &err) {
     const dim3 grid(G.nblk2, std::min<uint32_t>(1u << G.p1, 2048));
-    const uint64_t nlists = (uint64_t)nown << G.p2;            // per bucket
-    const bool rec16 = G.recbits > 64;
-    const bool lines = nlists <= 512 && G.cap2 % P2F_LINE == 0;
-    if (rec16 && !lines) { err = "count: no list geometry for 16-byte records"; return -1; }
     P2Args P;
     P.p1 = G.p1; P.p2 = G.p2; P.recbits = G.recbits; P.nblk1 = G.nblk1; P.nblk2 = G.nblk2; P.cap1 = G.cap1; P.cap2 = G.cap2; P.stats = d.stats; P.nown = nown;
     P.vper = 0;                                                // (launch_part2f: from the instance's piece)
-    if (rec16) HIPCHK((launch_part2f<512, 4, false, Rec16>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
-    else if (lines && !getenv("JASPER_EXPERIMENT_OLDP2")) {
-        // (the sender's split in whole lines, like the single-GPU pass)
-        if (by_owner) HIPCHK((launch_part2f<512, 10, true, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
-        else if (nlists <= 128) HIPCHK((launch_part2f<128, 12, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
-        else HIPCHK((launch_part2f<512, 10, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D)));
+    switch (part2_instance(G, nown, by_owner, getenv("JASPER_EXPERIMENT_OLDP2") != nullptr)) {
+    case Part2Kind::none: err = "count: no list geometry for 16-byte records"; return -1;
+    case Part2Kind::rec16_lines: HIPCHK((launch_part2f<512, 4, false, Rec16>(stream, grid, P, out1, cnt1, out2, cnt2, D))); break;
+    // (the sender's split in whole lines, like the single-GPU pass)
+    case Part2Kind::owner_lines: HIPCHK((launch_part2f<512, 10, true, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D))); break;
+    case Part2Kind::lines128: HIPCHK((launch_part2f<128, 12, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D))); break;
+    case Part2Kind::lines512: HIPCHK((launch_part2f<512, 10, false, uint64_t>(stream, grid, P, out1, cnt1, out2, cnt2, D))); break;
+    case Part2Kind::general_owner: HIPCHK(launch_big_lds<part2_kernel<true>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, nown, 0)); break;
+    case Part2Kind::general: HIPCHK(launch_big_lds<part2_kernel<false>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, 1u, 0)); break;
     }
-    else if (by_owner) HIPCHK(launch_big_lds<part2_kernel<true>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, nown, 0));
-    else HIPCHK(launch_big_lds<part2_kernel<false>>(grid, dim3(PT_THREADS), P2_LDS, stream, out1, cnt1, d, G, out2, cnt2, D.e, D.n, D.cap, 1u, 0));
     return 0;
 }
 
@@ -1797,12 +1756,10 @@ static int launch_part2(hipStream_t stream, const TableDev &d, const PartGeom &G
 // (cbits, fbits: region_insert_kernel).
 static hipError_t launch_region_insert(hipStream_t stream, const TableDev &d, const PartGeom &G, uint32_t nregions, const void *lists, const unsigned int *lcnt, uint32_t lcap,
                                        uint32_t nsl, const DeferList &D, unsigned long long *histo, bool fresh, bool xchg, uint32_t nsrc, int cbits, int fbits) {
-    const size_t R = (size_t)1 << G.rbits;
     const bool rec16 = G.recbits > 64;
-    // (a wide table's image: tag, second word and count per slot, no histogram bins)
-    const size_t lds = xchg ? R * 16 + LDS_HBINS * 4 + (LI_MAXSL + 1) * 4 : d.ext ? R * (fresh ? 20 : 24) : R * (fresh ? 12 : 16) + (histo ? LDS_HBINS * 4 : 0);
-    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, BIG_LDS / lds));
-    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>(nregions, 256 * per_cu * 4));
+    const RegionLaunch L = region_insert_launch(G.rbits, nregions, d.ext != nullptr, fresh, histo != nullptr, xchg);
+    const size_t lds = L.lds;
+    const uint32_t nblk = L.blocks;
 #define JK_RI_LAUNCH(REC, KERNEL, ...) \
     launch_big_lds<KERNEL>(dim3(nblk), dim3(RI_TH), lds, stream, reinterpret_cast<const REC *>(lists), lcnt, lcap, nsl, d, G, nregions, D.e, D.n, D.cap, ##__VA_ARGS__)
     if (xchg) return fresh ? JK_RI_LAUNCH(uint64_t, (region_insert_kernel<true, true>), histo, nsrc, cbits, fbits)
@@ -1817,10 +1774,10 @@ static hipError_t launch_region_insert(hipStream_t stream, const TableDev &d, co
 }
 
 int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const PartGeom &G, std::string &err) {
-    const uint32_t nb1 = 1u << G.p1, nregions = 1u << (G.p1 + G.p2);
-    const uint64_t deferred_cap = std::max<uint64_t>(1u << 16, len / 48);      // (24 bytes each; a piece that needs more abandons itself: part_decide_kernel)
-    const size_t n_cnt1 = (size_t)nb1 * G.nblk1, n_cnt2 = G.p2 ? (size_t)nregions * G.nblk2 : n_cnt1;      // (one level: the counts once more, bucket-major)
-    const size_t RB = G.recbits > 64 ? 16 : 8;
+    const PieceBuffers PB = piece_buffers(G, len);
+    const uint32_t nb1 = PB.nb1, nregions = PB.nregions;
+    const uint64_t deferred_cap = PB.deferred_cap;
+    const size_t n_cnt1 = PB.n_cnt1, n_cnt2 = PB.n_cnt2, RB = PB.rec_bytes;
     uint64_t *out1 = (uint64_t *)workspace(WS_COUNT + 0, n_cnt1 * G.cap1 * RB, err);
     uint64_t *out2 = G.p2 ? (uint64_t *)workspace(WS_COUNT + 1, n_cnt2 * G.cap2 * RB, err) : nullptr;
     unsigned int *cur = (unsigned int *)workspace(WS_COUNT + 2, (n_cnt1 + n_cnt2 + 4) * 4, err);
@@ -1857,10 +1814,8 @@ int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64
     if (d.ext) histo_request = false;                      // (a wide table's histogram is read from the table afterwards)
     unsigned long long *histo = histo_request ? d_histo : nullptr;
     if (histo) HIPCHK(hipMemsetAsync(histo, 0, HISTO_WORDS * sizeof(unsigned long long), stream));
-    // A table that is logically empty is not read: the images start from zeros and every slot is written (a lazily cleared table
-    // is never zeroed in HBM).  Its LDS image counts in 32 bits -- a piece below 2^32 bases cannot overflow them.
-    const bool empty_tbl = slots_dirty || histo != nullptr;
-    const bool fresh32 = empty_tbl && len < (1ull << 32);
+    // a table that is logically empty is not read (piece_fresh32)
+    const bool fresh32 = piece_fresh32(slots_dirty || histo != nullptr, len);
     if (slots_dirty && !fresh32) { if (materialize(err)) return -1; }
     HIPCHK(launch_region_insert(stream, d, G, nregions, lists, lcnt, lcap, nsl, D, histo, fresh32, false, 1u, 0, 0));
     HIPCHK(hipEventRecord(ev_stage_t[3], stream));
@@ -1894,55 +1849,13 @@ int Table::launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64
 //                                  what owner o is to get is one contiguous block of the send buffers (records + slice counts)
 //   the caller    one all_to_all of the blocks (8 B per k-mer occurrence + slack), dist.count_sharded
 //   every owner   xchg_insert      region_insert<., XCHG> straight into its shard, fused histogram, deferred records
-// All ranks must derive the same geometry: from the shard geometry (one for all owners), the number of owners, piece_max =
-// the longest piece any rank scans in this round, and records_max = the most records any rank's scan produced (0: not known,
-// piece_max stands in).  The slack of the send lists is what travels, so they are sized from the records actually there, not
-// with the 1.25x of the local lists: mean + 6 sigma, where a list's fill is a sum over the distinct keys hashed into it of
-// their multiplicities in this sender's reads -- variance = mean x (1 + multiplicity).  The multiplicity is estimated from the
-// table the caller sized for the keys (about a third full): records / (keys all shards were sized for).  A list that still
-// overflows (a k-mer far more frequent than the rest, or a table sized far too large) spends the deferred list, as everywhere.
-static uint32_t xchg_cap(double avg, double mult) { return (uint32_t)std::min<double>(4.0e9, avg + 6.0 * std::sqrt(avg * (1.0 + mult)) + 16.0); }
-// G: what the senders and the wire use (G.p2 = the second-level bits the SENDER resolves); p2b: second-level bits left to the
-// owner -- a bucket can be split 2048 ways in one pass, and the senders also split by owner, so for very large shards (2^32
-// slots on 8 GPUs) the owner runs one more split pass over what it received (part2_kernel<false, MIN>) before its insert.
-static int xchg_max_lists() { const char *e = getenv("JASPER_XCHG_TEST_MAXLISTS"); return e ? std::max(2, atoi(e)) : PT_MAXBUCKETS; }   // (tests: force the extra pass on small tables)
-// (returns p2b, or -1: no geometry)
-static int xchg_geometry(const Table &t, uint64_t piece_max, uint64_t records_max, uint32_t nown, PartGeom &G) {
-    if (nown < 2 || nown > MAX_SHARDS) return -1;
-    // (a feed's last batch may be small: the lists are then laid out as for the smallest piece the passes are tuned for)
-    piece_max = std::max<uint64_t>(piece_max, 8u << 20);
-    if (!t.partition_geometry(piece_max, G)) return -1;
-    if (G.recbits > 64) return -1;                        // (keys of more than 74 bits: per-GPU tables and the entry exchange instead)
-    // the senders split by (owner, second-level bits): more than 512 lists per bucket would leave the whole-line kernel, so the
-    // owners take regions of 8192 slots instead of 4096 where that is what it takes -- for up to four owners, whose lists travel
-    // deduplicated (dist.dedupe_pays).  Beyond that the lists travel as they are, and an owner inserting 10^9 raw records into
-    // 8192-slot regions (one workgroup per CU) takes 8.6 ms against 5.7 into 4096-slot ones, which the general split kernel's
-    // 5.7 ms against 4.6 does not eat up (role-play at 8 ranks, profiles/round5/exchange_roleplay_model.txt: 15.7 against 17.3 ms
-    // of kernels per rank).  JASPER_EXPERIMENT_XCHG_RB12 / _RB13 force one or the other.
-    const bool rb13 = getenv("JASPER_EXPERIMENT_XCHG_RB13") ? true : getenv("JASPER_EXPERIMENT_XCHG_RB12") ? false : nown <= 4;
-    if (((uint64_t)nown << G.p2) > 512 && ((uint64_t)nown << (G.p2 - 1)) <= 512 && G.p2 > 0 && G.rbits == RG_MAXBITS && rb13) { --G.p2; ++G.rbits; }
-    int p2b = 0;
-    while (((uint64_t)nown << (G.p2 - p2b)) > (uint64_t)xchg_max_lists() && p2b < G.p2) ++p2b;
-    if (((uint64_t)nown << (G.p2 - p2b)) > (uint64_t)PT_MAXBUCKETS) return -1;
-    G.p2 -= p2b;
-    const uint32_t nb1 = 1u << G.p1;
-    G.nblk2 = nb1 >= 256 ? 1u : std::min<uint32_t>(G.nblk1, 8u);
-    if (nown * G.nblk2 > (uint32_t)LI_MAXSL) return -1;
-    const double lists = (double)nb1 * (double)((uint64_t)nown << G.p2) * (double)G.nblk2;
-    if (records_max) {
-        const double rec = (double)std::min(records_max, piece_max);
-        const double keys = std::max(1.0, std::min(rec, 0.35 * (double)t.nslots * (double)nown));
-        G.cap2 = xchg_cap(rec / lists, rec / keys);
-    } else G.cap2 = list_cap((double)piece_max / lists);
-    G.cap2 = (G.cap2 + 15u) & ~15u;                       // whole 128-byte lines (part2f_kernel<., ., OWN>)
-    return p2b;
-}
+// All ranks must derive the same geometry: count_plan.hpp, xchg_geometry (the sizing of the send lists is explained there).
 // how the entry points below begin: this table's device, the geometry all ranks agree on and -- lists1: for the sender's passes --
 // the level-1 lists in the workspace (the scan fills them, the partition reads them: same sizes, nothing is reallocated)
 struct XchgCall { PartGeom G; int p2b; size_t n_cnt1; uint64_t *out1; unsigned int *cnt1; };
 static int xchg_begin(Table &t, uint64_t piece_max, uint64_t records_max, uint32_t nown, bool lists1, XchgCall &X, std::string &err) {
     HIPCHK(hipSetDevice(t.device));
-    X.p2b = xchg_geometry(t, piece_max, records_max, nown, X.G);
+    X.p2b = xchg_geometry(t.shape(), piece_max, records_max, nown, CountOptions::from_env(), X.G);
     if (X.p2b < 0) { err = "count exchange: no geometry for this table / piece size"; return -1; }
     X.n_cnt1 = ((size_t)1 << X.G.p1) * X.G.nblk1;
     X.out1 = lists1 ? (uint64_t *)t.workspace(Table::WS_COUNT + 0, X.n_cnt1 * X.G.cap1 * 8, err) : nullptr;
@@ -1953,13 +1866,9 @@ static int xchg_begin(Table &t, uint64_t piece_max, uint64_t records_max, uint32
 int Table::xchg_plan(uint64_t piece_max, uint64_t records_max, uint32_t nown, uint64_t out[8], std::string &err) {
     (void)err;
     PartGeom G;
-    const int p2b = xchg_geometry(*this, piece_max, records_max, nown, G);
+    const int p2b = xchg_geometry(shape(), piece_max, records_max, nown, CountOptions::from_env(), G);
     if (p2b < 0) return 1;
-    const uint64_t lists_per_owner = (uint64_t)1 << (G.p1 + G.p2);
-    out[0] = lists_per_owner * G.nblk2 * G.cap2;               // records (8 B) per owner block
-    out[1] = lists_per_owner * G.nblk2;                        // slice counts (4 B) per owner block
-    out[2] = std::max<uint64_t>(1u << 16, piece_max / 16);     // deferred entries (24 B) a rank may produce
-    out[3] = (uint64_t)G.p1; out[4] = (uint64_t)G.p2 | ((uint64_t)p2b << 8); out[5] = (uint64_t)G.rbits; out[6] = G.nblk2; out[7] = G.cap2;
+    xchg_plan_words(G, p2b, piece_max, out);
     return 0;
 }
 
@@ -1985,14 +1894,9 @@ int Table::xchg_scan(const uint8_t *d_bases, uint64_t n, uint64_t pos, uint64_t 
         return 0;
     }
     if (end - pos > piece_max) { err = "count exchange: piece longer than the agreed maximum"; return -1; }
-    const uint64_t halo = (uint64_t)(k - 1);
-    const uint64_t misalign = reinterpret_cast<uintptr_t>(d_bases) & 15;
-    uint64_t start = pos >= halo ? pos - halo : 0;
-    const uint64_t a = (start + misalign) & 15;
-    start = start >= a ? start - a : 0;
-    const uint64_t len = end - start, emit_from = pos - start;
-    const uint64_t ntiles = (len + (uint64_t)PT_TILE - 1) / (uint64_t)PT_TILE;
-    HIPCHK(launch_part1(stream, k, d_bases + start, len, ntiles, emit_from, d, X.G, X.out1, X.cnt1, D));
+    const PieceWindow W = piece_window(pos, end, (uint64_t)(k - 1), reinterpret_cast<uintptr_t>(d_bases) & 15);
+    const uint64_t ntiles = (W.len + (uint64_t)PT_TILE - 1) / (uint64_t)PT_TILE;
+    HIPCHK(launch_part1(stream, k, d_bases + W.start, W.len, ntiles, W.emit_from, d, X.G, X.out1, X.cnt1, D));
     HIPCHK(hipEventRecord(ev_stage_t[1], stream));
     if (read_stats(err)) return -1;                            // (waits for the kernel)
     if (records) *records = h_stats[ST_OCCURRENCES] - occ_before;
@@ -2149,7 +2053,6 @@ int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piec
     PartGeom G = X.G;
     const int p2b = X.p2b;
     if (read_stats(err)) return -1;
-    const uint32_t nregions = 1u << (G.p1 + G.p2 + p2b);
     const bool empty = h_stats[ST_DISTINCT] == 0;
     histo_cached = false;
     unsigned long long *histo = whole_input && empty ? d_histo : nullptr;
@@ -2157,7 +2060,7 @@ int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piec
     // (a table that is logically empty is not read: the images start from zeros and every slot is written)
     const bool fresh = slots_dirty || histo != nullptr;
     // this rank's own deferred list lives in the caller's buffer; the kernel's own overflow (probe beyond the halo) goes to a list of its own
-    const uint64_t own_cap = std::max<uint64_t>(1u << 16, piece_max / 16);
+    const uint64_t own_cap = xchg_defer_cap(piece_max);
     unsigned long long *defer = (unsigned long long *)workspace(WS_COUNT + 3, own_cap * 24 + 64, err);
     if (!defer) return -2;
     DeferList D;
@@ -2171,15 +2074,11 @@ int Table::xchg_insert(const void *d_recv, const void *d_recv_cnt, uint64_t piec
     const void *lists = d_recv;
     const unsigned int *lcnt = (const unsigned int *)d_recv_cnt;
     uint32_t lcap = G.cap2, nsl = nown * G.nblk2;
-    PartGeom GI = G;                                           // what lds_insert sees: all second-level bits resolved
-    GI.p2 = G.p2 + p2b;
+    const OwnerSplit OS = xchg_owner_split(G, p2b, nown, records_max);
+    const uint32_t nregions = OS.nregions;
+    const PartGeom &GI = OS.GI, &G2 = OS.G2;                   // what region_insert sees; the extra split pass
     if (p2b) {
-        // the senders resolved only G.p2 of the second-level bits: one more split pass here, over what arrived.  Its buckets are
-        // the received lists (2^(p1 + G.p2) of them, nown * nblk2 slices each), its record bits the ones below those lists' bits
-        PartGeom G2 = G;
-        G2.p1 = G.p1 + G.p2; G2.p2 = p2b; G2.recbits = G.recbits - G.p2;
-        G2.nblk1 = nown * G.nblk2; G2.cap1 = G.cap2; G2.nblk2 = 1;
-        G2.cap2 = list_cap((double)std::max<uint64_t>(records_max, 1) / (double)nregions);
+        // the senders resolved only G.p2 of the second-level bits: one more split pass here, over what arrived
         uint64_t *out2 = (uint64_t *)workspace(WS_XCHG + 1, (size_t)nregions * G2.cap2 * 8, err);
         unsigned int *cnt2 = (unsigned int *)workspace(WS_XCHG + 2, ((size_t)nregions + 4) * 4, err);
         if (!out2 || !cnt2) return -2;

@@ -854,7 +854,7 @@ int Table::after_batch(std::string &err) {
         if (h_stats[ST_FATAL]) { err = "k-mer table overflow (spill buffer exhausted): pass a larger size hint"; return -2; }
         const uint64_t spilled = h_stats[ST_SPILL];
         if (getenv("JASPER_COUNT_DEBUG") && spilled) fprintf(stderr, "[count] after_batch: %llu spilled insertions\n", (unsigned long long)spilled);
-        const bool too_full = (double)h_stats[ST_DISTINCT] > grow_at * (double)nslots && d.s < d.B;
+        const bool too_full = table_too_full(h_stats[ST_DISTINCT], grow_at, nslots, d.s, d.B);
         if (!spilled && !too_full) return 0;
         if (round == 8) break;
         std::vector<unsigned long long> sp;
@@ -863,8 +863,7 @@ int Table::after_batch(std::string &err) {
             HIPCHK(hipMemcpy(sp.data(), d.spill, sp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             HIPCHK(hipMemsetAsync(d.stats + ST_SPILL, 0, sizeof(unsigned long long), stream));
         }
-        int ns = d.s + 1;
-        while ((double)h_stats[ST_DISTINCT] > 0.5 * grow_at * (double)(1ull << ns) && ns < d.B) ++ns;
+        const int ns = grow_target(h_stats[ST_DISTINCT], grow_at, d.s, d.B);
         if (d.s >= d.B && spilled) { err = "k-mer table cannot grow further"; return -2; }
         if (grow(ns, err)) return -1;
         if (spilled) {
@@ -882,21 +881,17 @@ int Table::after_batch(std::string &err) {
 }
 
 int Table::ensure_capacity(uint64_t upcoming_kmers, std::string &err) {
-    // keep the worst case (every upcoming k-mer new) under 3/4 full so probe runs stay far below MAXPROBE
+    // keep the worst case (every upcoming k-mer new) under 3/4 full (count_plan.hpp: capacity_target)
     if (read_stats(err)) return -1;
-    int ns = d.s;
-    while ((double)(h_stats[ST_DISTINCT] + upcoming_kmers) > 0.75 * (double)(1ull << ns) && ns < d.B) ++ns;
+    const int ns = capacity_target(h_stats[ST_DISTINCT], upcoming_kmers, d.s, d.B);
     if (ns != d.s) return grow(ns, err);
     return 0;
 }
 
 int Table::launch_count(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, std::string &err) {
     PartGeom geom;
-    // the partitioned path streams the whole table once per piece: worth it only for pieces that are large relative
-    // to the table (host-staged 64 MiB pieces stay on the direct kernel and are PCIe-bound anyway)
-    // break-even measured on MI355X: direct ~18 Gk-mers/s; partitioned ~55 Gk-mers/s for the two list passes plus one
-    // streaming pass over the table (32 B/slot, 16 B/slot when the table is still lazily cleared)
-    if (!part_off && len >= (slots_dirty ? nslots / 6 : nslots / 4)) {
+    // the list passes only for pieces that are large relative to the table (count_plan.hpp)
+    if (!part_off && piece_worth_partitioning(len, nslots, slots_dirty)) {
         if (partition_geometry(len, geom)) {
             ++count_partitioned_launches;
             return launch_count_partitioned(d_piece, len, emit_from, geom, err);
@@ -916,137 +911,161 @@ int Table::launch_count(const uint8_t *d_piece, uint64_t len, uint64_t emit_from
     return 0;
 }
 
-// bases already in HBM. Processed in launches of at most nslots/4 bases so that the load factor is re-checked
-// (and the table grown) between launches. A piece starts k-1 bases early, rounded down to 16 bytes so the
-// kernel keeps its 16-byte vector loads; emit_from keeps every window counted exactly once.
-int Table::count_device(const uint8_t *d_bases, uint64_t n, std::string &err, uint64_t first_new) {
-    HIPCHK(hipSetDevice(device));
-    if (read_stats(err)) return -1;
-    histo_cached = false;
-    const uint64_t halo = (uint64_t)(k - 1);
-    const uint64_t misalign = reinterpret_cast<uintptr_t>(d_bases) & 15;
-    uint64_t pos = std::min(first_new, n);
-    // Before anything has been measured, the caller's size hint plays the role of `jellyfish count -s`: the expected
-    // number of distinct k-mers of this input.  hint / bases is then the expected share of new keys per k-mer; it is
-    // only trusted for sizing the pieces (x1.5 below) -- an input that is less repetitive than promised still ends up
-    // in the spill / deferred lists and a grown table, or in a clean error, never in wrong counts.
-    bool have_ratio = false;
-    if (size_hint > 0 && n > (1u << 24) && h_stats[ST_DISTINCT] == 0 && h_stats[ST_OCCURRENCES] == 0) {
-        dup_ratio = std::min(1.0, (double)size_hint / (double)n);
-        have_ratio = dup_ratio < 0.6;
-    }
-    const bool started_empty = h_stats[ST_DISTINCT] == 0 && h_stats[ST_OCCURRENCES] == 0;
+// One call of count_device: bases already in HBM, counted piece by piece so that the load factor is re-checked (and the table
+// grown) between launches.  Where a piece begins and ends, what it is expected to bring and whether the histogram can be fused
+// into it is t.pieces' business (count_plan.hpp: PiecePlan); the steps here put it on the stream and settle it.
+namespace {
+struct CountCall {
+    Table &t;
+    const uint8_t *d_bases;
+    uint64_t n, first_new;
+    std::string &err;
+    uint64_t pos = 0;
     size_t mem_have = 0;
-    {   // partition lists need ~20 bytes of workspace per base
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            mem_have = free_b;
-            for (int w = WS_COUNT; w < WS_COUNT + 4; ++w) mem_have += ws[w].bytes;
-        }
-    }
-    const bool dbg = getenv("JASPER_COUNT_DEBUG") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_call = now_ms();
-    if (dbg) fprintf(stderr, "[count] call start: %llu bases\n", (unsigned long long)n);
-    while (pos < n) {
-        // a launch may add at most as many new keys as keep the table under 3/4 full in the worst case (every
-        // base a new k-mer); h_stats holds the distinct count of the last check
-        const uint64_t room = (uint64_t)(0.75 * (double)nslots) > h_stats[ST_DISTINCT] ? (uint64_t)(0.75 * (double)nslots) - h_stats[ST_DISTINCT] : 0;
-        uint64_t piece = std::max<uint64_t>(room, 1u << 20);
-        // after the first piece the measured share of NEW keys per k-mer (x1.5 safety) replaces the worst case "every base
-        // a new key"; the spill list / deferred list / growth still catch a piece that turns out less repetitive
-        if ((pos > 0 || have_ratio) && dup_ratio < 0.6) piece = std::max<uint64_t>(piece, (uint64_t)((double)room / std::max(0.05, 1.5 * dup_ratio)));
-        if (mem_have) piece = std::min<uint64_t>(piece, std::max<uint64_t>(mem_have / 28, 1u << 20));
-        piece = std::min<uint64_t>(piece, 1ull << 33);   // (positions are 64-bit throughout; slice counters are 32-bit but per slice)
-        // do not leave a small tail for a separate launch (the 1.5x safety factor covers a quarter more)
-        if ((pos > 0 || have_ratio) && dup_ratio < 0.6 && n - pos <= piece + piece / 4 && n - pos <= (1ull << 33)) piece = n - pos;
-        // the caller's own promise (size hint = expected distinct k-mers of this input) fits the free room: one piece
-        if (have_ratio && pos == 0 && (double)n * dup_ratio <= (double)room && n <= (1ull << 33) && (!mem_have || n <= mem_have / 28)) piece = n;
-        if (const char *e = getenv("JASPER_EXPERIMENT_PIECE")) piece = strtoull(e, nullptr, 10);   // tuning experiments only
-        {   // make room up front for the new keys this piece is expected to bring (worst case for the first piece)
-            const uint64_t todo = std::min<uint64_t>(piece, n - pos);
-            // (the share of new keys only falls as coverage accumulates, so the last piece's ratio is already an upper
-            // estimate; spill list, deferred list and growth after the piece remain the safety net)
-            const uint64_t expect = (pos > 0 || have_ratio) && dup_ratio < 0.6 ? (uint64_t)((double)todo * std::min(1.0, dup_ratio)) : todo;
-            if (expect > room && !getenv("JASPER_EXPERIMENT_PIECE")) {
-                if (ensure_capacity(expect, err)) return -1;
+    bool dbg = false;
+    double t_call = 0, t_l0 = 0, t_l1 = 0;
+    Piece piece{};
+    uint64_t pos_piece = 0, distinct_before = 0, occ_before = 0;
+    bool fused_histo = false;
+
+    static double now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+    // the table's statistics, the caller's size hint, the memory the lists may take
+    int begin() {
+        HIPCHK(hipSetDevice(t.device));
+        if (t.read_stats(err)) return -1;
+        t.histo_cached = false;
+        pos = std::min(first_new, n);
+        t.pieces.begin(t.size_hint, n, t.h_stats[ST_DISTINCT], t.h_stats[ST_OCCURRENCES]);
+        {   // partition lists need ~20 bytes of workspace per base
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+                mem_have = free_b;
+                for (int w = Table::WS_COUNT; w < Table::WS_COUNT + 4; ++w) mem_have += t.ws[w].bytes;
             }
         }
-        uint64_t start = pos >= halo ? pos - halo : 0;
-        // round the start down so that (d_bases + start) is 16-byte aligned
-        const uint64_t a = (start + misalign) & 15;
-        start = start >= a ? start - a : 0;
-        const uint64_t end = std::min<uint64_t>(n, pos + piece);
-        const uint64_t distinct_before = h_stats[ST_DISTINCT], occ_before = h_stats[ST_OCCURRENCES];
-        const double t_l0 = dbg ? now_ms() : 0;
+        dbg = getenv("JASPER_COUNT_DEBUG") != nullptr;
+        t_call = now_ms();
+        if (dbg) fprintf(stderr, "[count] call start: %llu bases\n", (unsigned long long)n);
+        return 0;
+    }
+    // (h_stats holds the distinct count of the last check)
+    void next_piece() {
+        piece = t.pieces.next(pos, n, first_new, t.h_stats[ST_DISTINCT], t.nslots, mem_have, (uint64_t)(t.k - 1), reinterpret_cast<uintptr_t>(d_bases) & 15, CountOptions::from_env());
+    }
+    // room up front for the new keys this piece is expected to bring
+    int make_room() { return piece.needs_room && t.ensure_capacity(piece.expect_new, err) ? -1 : 0; }
+    int launch() {
+        distinct_before = t.h_stats[ST_DISTINCT];
+        occ_before = t.h_stats[ST_OCCURRENCES];
+        t_l0 = dbg ? now_ms() : 0;
         if (dbg) fprintf(stderr, "[count] host: %.2f ms since call start (sizing, capacity)\n", t_l0 - t_call);
-        histo_request = started_empty && pos == 0 && first_new == 0 && end == n && h_stats[ST_DISTINCT] == 0;   // one piece, whole input, empty table
-        histo_cached = false;
-        const int lrc = launch_count(d_bases + start, end - start, pos - start, err);
-        const bool fused_histo = histo_request;      // still set only if the partitioned path took the request
-        histo_request = false;
+        t.histo_request = piece.histo_request && t.h_stats[ST_DISTINCT] == 0;   // one piece, whole input, empty table
+        t.histo_cached = false;
+        const int lrc = t.launch_count(d_bases + piece.start, piece.end - piece.start, piece.emit_from, err);
+        fused_histo = t.histo_request;      // still set only if the partitioned path took the request
+        t.histo_request = false;
         if (lrc) return -1;
-        const double t_l1 = dbg ? now_ms() : 0;
-        const uint64_t pos_piece = pos;
-        pos = end;
-        int rc = after_batch(err);
-        histo_cached = rc == 0 && fused_histo;
-        if (rc == -2 && count_path == 1 && part_defer_header) {
-            unsigned long long abandoned = 0;
-            HIPCHK(hipMemcpy(&abandoned, part_defer_header + 1, 8, hipMemcpyDeviceToHost));
+        t_l1 = dbg ? now_ms() : 0;
+        pos_piece = pos;
+        pos = piece.end;
+        return 0;
+    }
+    // spilled insertions, growth; the fused histogram holds if nothing went wrong
+    int settle() {
+        const int rc = t.after_batch(err);
+        t.histo_cached = rc == 0 && fused_histo;
+        return rc;
+    }
+    // did the piece that failed abandon itself before it wrote to the table (count_part.hip: part_decide_kernel)?
+    int piece_abandoned(bool &yes) {
+        yes = false;
+        if (t.count_path != 1 || !t.part_defer_header) return 0;
+        unsigned long long abandoned = 0;
+        HIPCHK(hipMemcpy(&abandoned, t.part_defer_header + 1, 8, hipMemcpyDeviceToHost));
+        yes = abandoned != 0;
+        return 0;
+    }
+    // One k-mer (or a few) so frequent that its region list overflowed beyond the deferred list: the piece stopped before
+    // it wrote to the table.  Counted again, like everything after it, by the direct kernel -- the k-mer's atomics
+    // queue up on one address there, but they all arrive.
+    int fall_back_to_direct() {
+        if (dbg) {
+            float m1 = 0, m2 = 0;
+            (void)hipEventElapsedTime(&m1, t.ev_stage_t[0], t.ev_stage_t[1]);
+            (void)hipEventElapsedTime(&m2, t.ev_stage_t[1], t.ev_stage_t[2]);
+            fprintf(stderr, "[count] partitioned piece abandoned (lists overflowed the deferred list; its partition passes took %.2f + %.2f ms): direct kernel from here on\n", m1, m2);
+        }
+        err.clear();
+        t.part_off = true;
+        t.part_stage_pending = false;
+        t.slots_dirty = t.part_slots_dirty_before;
+        const unsigned long long zero = 0, occ = occ_before;
+        HIPCHK(hipMemcpy(t.d.stats + ST_FATAL, &zero, 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t.d.stats + ST_OCCURRENCES, &occ, 8, hipMemcpyHostToDevice));
+        if (t.read_stats(err)) return -1;
+        pos = pos_piece;
+        return 0;
+    }
+    // The size hint promised a more repetitive input than this one: the piece sized from it overflowed the table.
+    // Nothing else was in the table when this call started, so start over with worst-case piece sizes.
+    int restart_worst_case() {
+        if (dbg) fprintf(stderr, "[count] size hint too small for this input: restarting with worst-case sizing\n");
+        err.clear();
+        if (t.clear(err)) return -1;
+        if (t.read_stats(err)) return -1;
+        if (t.grow(std::min(t.d.B, t.d.s + 2), err)) return -1;
+        t.pieces.restart_worst_case();
+        pos = std::min(first_new, n);
+        return 0;
+    }
+    // the measured share of new keys, the stages' and the kernels' time
+    int account() {
+        if (t.h_stats[ST_OCCURRENCES] > occ_before) t.pieces.observe(t.h_stats[ST_DISTINCT] - distinct_before, t.h_stats[ST_OCCURRENCES] - occ_before);
+        if (t.part_stage_pending) {
+            for (int i = 0; i < t.part_stage_n; ++i) { float m = 0; if (hipEventElapsedTime(&m, t.ev_stage_t[i], t.ev_stage_t[i + 1]) == hipSuccess) t.part_stage_ms[i] += m; }
+            t.part_stage_pending = false;
+        }
+        if (dbg)
+            fprintf(stderr, "[count] piece done: pos %llu / %llu, distinct %llu, slots 2^%d, dup_ratio %.3f, stage ms so far %.2f %.2f %.2f %.2f %.2f\n",
+                    (unsigned long long)pos, (unsigned long long)n, (unsigned long long)t.h_stats[ST_DISTINCT], t.d.s, t.pieces.dup_ratio,
+                    t.part_stage_ms[0], t.part_stage_ms[1], t.part_stage_ms[2], t.part_stage_ms[3], t.part_stage_ms[4]);
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, t.ev_k0, t.ev_k1));
+        t.count_kernel_ms += ms;
+        t.count_launches += 1;
+        return 0;
+    }
+
+    int run() {
+        if (begin()) return -1;
+        while (pos < n) {
+            next_piece();
+            if (make_room()) return -1;
+            if (launch()) return -1;
+            const int rc = settle();
+            bool abandoned = false;
+            if (rc == -2 && piece_abandoned(abandoned)) return -1;
             if (abandoned) {
-                // One k-mer (or a few) so frequent that its region list overflowed beyond the deferred list: the piece stopped before
-                // it wrote to the table.  Counted again, like everything after it, by the direct kernel -- the k-mer's atomics
-                // queue up on one address there, but they all arrive.
-                if (dbg) {
-                    float m1 = 0, m2 = 0;
-                    (void)hipEventElapsedTime(&m1, ev_stage_t[0], ev_stage_t[1]);
-                    (void)hipEventElapsedTime(&m2, ev_stage_t[1], ev_stage_t[2]);
-                    fprintf(stderr, "[count] partitioned piece abandoned (lists overflowed the deferred list; its partition passes took %.2f + %.2f ms): direct kernel from here on\n", m1, m2);
-                }
-                err.clear();
-                part_off = true;
-                part_stage_pending = false;
-                slots_dirty = part_slots_dirty_before;
-                const unsigned long long zero = 0, occ = occ_before;
-                HIPCHK(hipMemcpy(d.stats + ST_FATAL, &zero, 8, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(d.stats + ST_OCCURRENCES, &occ, 8, hipMemcpyHostToDevice));
-                if (read_stats(err)) return -1;
-                pos = pos_piece;
+                if (fall_back_to_direct()) return -1;
                 continue;
             }
+            if (dbg) fprintf(stderr, "[count] host: launch calls %.2f ms, wait + after_batch %.2f ms\n", t_l1 - t_l0, now_ms() - t_l1);
+            if (rc == -2 && t.pieces.have_ratio && t.pieces.started_empty) {
+                if (restart_worst_case()) return -1;
+                continue;
+            }
+            if (rc) return rc;
+            if (account()) return -1;
         }
-        if (dbg) fprintf(stderr, "[count] host: launch calls %.2f ms, wait + after_batch %.2f ms\n", t_l1 - t_l0, now_ms() - t_l1);
-        if (rc == -2 && have_ratio && started_empty) {
-            // The size hint promised a more repetitive input than this one: the piece sized from it overflowed the table.
-            // Nothing else was in the table when this call started, so start over with worst-case piece sizes.
-            if (dbg) fprintf(stderr, "[count] size hint too small for this input: restarting with worst-case sizing\n");
-            err.clear();
-            if (clear(err)) return -1;
-            if (read_stats(err)) return -1;
-            if (grow(std::min(d.B, d.s + 2), err)) return -1;
-            have_ratio = false;
-            dup_ratio = 1.0;
-            pos = std::min(first_new, n);
-            continue;
-        }
-        if (rc) return rc;
-        if (h_stats[ST_OCCURRENCES] > occ_before)
-            dup_ratio = (double)(h_stats[ST_DISTINCT] - distinct_before) / (double)(h_stats[ST_OCCURRENCES] - occ_before);
-        if (part_stage_pending) {
-            for (int i = 0; i < part_stage_n; ++i) { float m = 0; if (hipEventElapsedTime(&m, ev_stage_t[i], ev_stage_t[i + 1]) == hipSuccess) part_stage_ms[i] += m; }
-            part_stage_pending = false;
-        }
-        if (getenv("JASPER_COUNT_DEBUG"))
-            fprintf(stderr, "[count] piece done: pos %llu / %llu, distinct %llu, slots 2^%d, dup_ratio %.3f, stage ms so far %.2f %.2f %.2f %.2f %.2f\n",
-                    (unsigned long long)pos, (unsigned long long)n, (unsigned long long)h_stats[ST_DISTINCT], d.s, dup_ratio,
-                    part_stage_ms[0], part_stage_ms[1], part_stage_ms[2], part_stage_ms[3], part_stage_ms[4]);
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_k0, ev_k1));
-        count_kernel_ms += ms;
-        count_launches += 1;
+        return 0;
     }
-    return 0;
+};
+}  // namespace
+
+int Table::count_device(const uint8_t *d_bases, uint64_t n, std::string &err, uint64_t first_new) {
+    CountCall call{*this, d_bases, n, first_new, err};
+    return call.run();
 }
 
 // bases in host memory: double-buffered pinned staging; the copy of piece i+1 overlaps the kernel of piece i
@@ -1105,7 +1124,7 @@ int Table::count_host(const char *bases, uint64_t n, std::string &err) {
         const uint64_t piece = std::min<uint64_t>(stage_bytes - halo, n - pos);
         // the load factor is only re-checked (a stream sync) when the worst case could pass 3/4: between checks the
         // host copy of piece i+1 into pinned memory overlaps the PCIe copy and the kernel of piece i
-        if ((double)(h_stats[ST_DISTINCT] + pending + piece) > 0.75 * (double)nslots) {
+        if (worst_case_passes_load(h_stats[ST_DISTINCT], pending, piece, nslots)) {
             int rc = after_batch(err);
             if (rc) return rc;
             pending = 0;

@@ -6,6 +6,7 @@
 //   JF::include/jellyfish/binary_dumper.hpp:148-199                   (query: exact count or 0)
 //   JF::sub_commands/histo_main.cc:34-44                              (histogram)
 #pragma once
+#include "count_plan.hpp"
 #include "kmer.hpp"
 #include <atomic>
 #include <functional>
@@ -20,7 +21,7 @@ extern std::atomic<int> g_cancel;
 
 
 // what kernels receive (by value)
-constexpr uint32_t MAX_SHARDS = 8;   // the GPUs of one node
+// (MAX_SHARDS, the GPUs of one node: count_plan.hpp)
 struct TableDev {
     unsigned long long *slots;  // 2 words per slot: tag, count
     uint64_t mask;              // nslots - 1
@@ -288,15 +289,7 @@ __device__ __forceinline__ u128 encode_padded(int k, long n, Get get) {
     return m;
 }
 
-// geometry of the two list levels of the partitioned counting path (count_part.hip); its kernels take it by value
-struct PartGeom {
-    int p1, p2, rbits;       // p1 + p2 + rbits == s
-    int recbits;             // 2k - p1  (<= 64): bits kept in a record
-    uint32_t nblk1;          // slices per level-1 list: the part1 blocks b, b + nblk1, b + 2 nblk1, ... append to slice b % nblk1 of every list
-    uint32_t grid1;          // part1 blocks
-    uint32_t nblk2;          // part2 blocks per level-1 bucket: every one owns a slice of each of the bucket's region lists
-    uint32_t cap1, cap2;     // slice capacities (records)
-};
+// (PartGeom, the geometry of the two list levels of the partitioned counting path: count_plan.hpp)
 
 // ---- host side ----------------------------------------------------------------------------------
 struct Table {
@@ -319,7 +312,8 @@ struct Table {
     void reset_timing() { count_kernel_ms = 0; count_launches = 0; count_partitioned_launches = 0; for (double &m : part_stage_ms) m = 0; }
     int launch_count(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, std::string &err);
     // partitioned (atomic-free) path, count_part.hip
-    bool partition_geometry(uint64_t piece_bases, PartGeom &G) const;
+    TableShape shape() const { return {k, d.B, d.s, d.ext != nullptr, nslots}; }
+    bool partition_geometry(uint64_t piece_bases, PartGeom &G) const { return jk::partition_geometry(shape(), piece_bases, CountOptions::from_env(), G); }
     int launch_count_partitioned(const uint8_t *d_piece, uint64_t len, uint64_t emit_from, const PartGeom &G, std::string &err);
     uint64_t count_partitioned_launches = 0;
     static constexpr int N_STAGES = 8;
@@ -342,7 +336,7 @@ struct Table {
     static constexpr int HISTO_WORDS = 10002 + 6;
     unsigned long long *d_histo = nullptr;
     bool histo_cached = false, histo_request = false;
-    double dup_ratio = 1.0;   // new distinct keys per k-mer of the last piece (sizes the next piece)
+    PiecePlan pieces;         // how count_device cuts a call into pieces (count_plan.hpp); its dup_ratio is carried from call to call
     uint64_t size_hint = 0;   // caller's expected number of distinct k-mers (`jellyfish count -s`); 0 = none given
     // grow-only device workspace reused by the polisher across calls (hipMalloc of GBs costs far more than the kernels)
     struct WsBuf { void *p = nullptr; size_t bytes = 0; };
