@@ -409,6 +409,35 @@ void jasper_hapscan_free(jasper_hapscan *r);
 int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *child, jasper_table *assembly, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,
                          uint64_t out6[6] /* mat: hapmers, found, occurrences; then pat */, double *device_seconds);
 
+/* Trio read binning: per READ of the child, how many of its windows hold a k-mer that only the mother's reads have and how many hold one
+ * that only the father's have -- what TrioCanu-style binning sorts the child's reads by.  The tables are the scan's mat (M) and pat (P)
+ * above: whole tables of the same k on the same device, different handles; thre_mat and thre_pat are each at least 1.  No table is
+ * modified.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  It is the hap-mer scan without a child table, laid
+ * out for reads: jasper_hapmer_scan of the same reads gives the same two numbers (counters 2 and 3 of a sequence), but its work is cut per
+ * sequence, in tiles a read of 150 bases fills to 3 %, and it takes a pointer per read.  Here the text is FLAT and the work is cut over it.
+ *
+ * Input.  n_reads reads packed back to back, no separator bytes: read i = text[offsets[i] .. offsets[i+1]); offsets is a host array of
+ * n_reads+1 entries, non-decreasing, offsets[0] >= 0 (bytes before offsets[0] and from offsets[n_reads] on are not read).  For the tables' k:
+ *   window                 k consecutive bytes of ONE read: read i has max(0, len_i - k + 1) of them.  No window spans two reads
+ *   valid                  iff all its k bytes are ACGTacgt (case folded)
+ *   m, p                   the counts of its canonical k-mer in M and P, each clamped to 2^32-1
+ *   out_mat[i]             the valid windows of read i with m >= thre_mat and p == 0
+ *   out_pat[i]             the valid windows of read i with p >= thre_pat and m == 0
+ * Reads shorter than k (empty ones too, several in a row too) are legal and give zeros; n_reads == 0 is legal and writes nothing.  The
+ * result is the same on every call.  out_mat and out_pat are host arrays of n_reads words.  device_seconds (may be NULL): device time of
+ * the start-bit pass and the scan kernel, HIP events.  The kernels run on the mother's stream.
+ *   jasper_read_bins         the text in host memory (text[offsets[0] .. offsets[n_reads]) is uploaded)
+ *   jasper_read_bins_device  the text in HBM on the tables' device, at any alignment; offsets still a host array
+ * Limits (the index arithmetic's): at most 2^31-1 reads and 2^43 text bytes per call, at most 2^32-1 windows per read.
+ * JASPER_ERR with a message that names the cause: a different k, different devices, the same handle twice, an attached (owner-sharded)
+ * table, a threshold of 0, offsets that decrease or start below 0, a NULL text with offsets[n_reads] > offsets[0], input beyond the limits. */
+int jasper_read_bins(jasper_table *mat, jasper_table *pat, int64_t n_reads, const char *text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat,
+                     uint32_t *out_mat, uint32_t *out_pat, double *device_seconds);
+int jasper_read_bins_device(jasper_table *mat, jasper_table *pat, int64_t n_reads, const void *d_text, const int64_t *offsets /* host */, uint32_t thre_mat,
+                            uint32_t thre_pat, uint32_t *out_mat, uint32_t *out_pat, double *device_seconds);
+
 /* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
  * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
  * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.

@@ -10,6 +10,7 @@
 #include "spectra.hpp"
 #include "copies.hpp"
 #include "hapmers.hpp"
+#include "readbins.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
 #include "compound.hpp"
@@ -907,6 +908,18 @@ int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *chi
     return hapmer_census(mat->t, pat->t, child ? &child->t : nullptr, assembly ? &assembly->t : nullptr, thre_mat, thre_pat, thre_child, out6, device_seconds, g_err)
                ? JASPER_ERR
                : JASPER_OK;
+}
+
+// ---- trio read binning (readbins.hip) ----
+int jasper_read_bins(jasper_table *mat, jasper_table *pat, int64_t n_reads, const char *text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t *out_mat,
+                     uint32_t *out_pat, double *device_seconds) {
+    if (!mat || !pat) { g_err = "bad argument"; return JASPER_ERR; }
+    return read_bins_host(mat->t, pat->t, n_reads, text, offsets, thre_mat, thre_pat, out_mat, out_pat, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_read_bins_device(jasper_table *mat, jasper_table *pat, int64_t n_reads, const void *d_text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat,
+                            uint32_t *out_mat, uint32_t *out_pat, double *device_seconds) {
+    if (!mat || !pat) { g_err = "bad argument"; return JASPER_ERR; }
+    return read_bins_device(mat->t, pat->t, n_reads, (const uint8_t *)d_text, offsets, thre_mat, thre_pat, out_mat, out_pat, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
 }
 
 // ---- variant scan (variants.hip) ----

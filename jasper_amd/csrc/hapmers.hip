@@ -194,8 +194,7 @@ __global__ __launch_bounds__(SP_THREADS) void hapmer_census_kernel(TableDev M, T
     if (threadIdx.x < 3 && s_sum[threadIdx.x]) atomicAdd(&out[threadIdx.x], s_sum[threadIdx.x]);
 }
 
-namespace {
-// what: "hap-mer scan" or "hap-mer census".  R and A may be null.
+// what: "hap-mer scan", "hap-mer census" or "read bins" (readbins.hip).  R and A may be null.
 int check_trio(const char *what, Table &M, Table &P, Table *R, Table *A, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child, std::string &err) {
     const std::string w(what);
     Table *all[4] = {&M, &P, R, A};
@@ -218,6 +217,7 @@ int check_trio(const char *what, Table &M, Table &P, Table *R, Table *A, uint32_
     if (thre_child < 1) { err = w + ": the child threshold must be at least 1 (it is 0)"; return -1; }
     return 0;
 }
+namespace {
 unsigned census_grid(uint64_t nslots) {                // as the spectrum's sweeps: fills the chip, the rest is grid-stride
     uint64_t b = (nslots + (uint64_t)SP_THREADS * SP_BATCH - 1) / ((uint64_t)SP_THREADS * SP_BATCH);
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(b, 1), 256 * 8);

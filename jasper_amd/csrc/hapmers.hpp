@@ -38,4 +38,9 @@ int hapmer_scan_host(Table &M, Table &P, Table *R, int n_seqs, const char *const
 // out6 = hapmers, found, occurrences of the mother's hap-mers, then of the father's; R and A may be null
 int hapmer_census(Table &M, Table &P, Table *R, Table *A, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child, uint64_t out6[6], double *seconds, std::string &err);
 
+// The checks every trio call makes before it touches a table: one k, one device, no handle twice, M, P and A whole tables, thresholds of at
+// least 1.  `what` starts the message.  (Hidden: the library's list of exported symbols stays what it was.)
+__attribute__((visibility("hidden"))) int check_trio(const char *what, Table &M, Table &P, Table *R, Table *A, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,
+                                                     std::string &err);
+
 }  // namespace jk

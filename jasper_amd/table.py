@@ -224,6 +224,20 @@ class HapmerCensus:
         return isinstance(other, HapmerCensus) and self.mat == other.mat and self.pat == other.pat
 
 
+class ReadBins:
+    """trio read binning of a batch of reads (include/jasper_hip.h: jasper_read_bins): `mat[i]` / `pat[i]` = the windows of read i whose
+    k-mer only the mother's / only the father's reads hold (np.uint32[n]), `seconds` = device time of the kernels.  The rule that makes
+    bins of them and the files: jasper_amd/triobin.py."""
+
+    def __init__(self, mat, pat, seconds):
+        self.mat = mat
+        self.pat = pat
+        self.seconds = seconds
+
+    def __eq__(self, other):
+        return isinstance(other, ReadBins) and self.mat.tobytes() == other.mat.tobytes() and self.pat.tobytes() == other.pat.tobytes()
+
+
 VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
 VARIANT_KINDS = {1: "het", 2: "error"}
 
@@ -1036,6 +1050,67 @@ class KmerTable:
         check(mat._L.jasper_hapmer_census(mh, ph, ch, ah, _thre32(thre_mat), _thre32(thre_pat), _thre32(thre_child), out, C.byref(secs)))
         v = [int(x) for x in out]
         return HapmerCensus(tuple(v[:3]), tuple(v[3:]), secs.value)
+
+    # ---- trio read binning (an extension: the hap-mer scan's probes over a packed batch of reads) ----------
+    @staticmethod
+    def _packed_reads(reads):
+        """reads as one flat buffer and its boundaries: a list of bytes / str, or a pair (buffer, offsets) with the buffer bytes or
+        np.uint8 and the offsets n+1 integers -> (bytes-like or np.uint8 array, np.int64[n+1], contiguous)"""
+        import numpy as np
+        if isinstance(reads, tuple) and len(reads) == 2 and not isinstance(reads[1], (bytes, str)):
+            buf, offs = reads
+            if isinstance(buf, str):
+                buf = buf.encode("latin-1")
+            if not isinstance(buf, bytes):
+                buf = np.ascontiguousarray(buf)
+                if buf.dtype != np.uint8 or buf.ndim != 1:
+                    raise TypeError("read_bins: the buffer must be bytes or a one-dimensional np.uint8 array")
+            offs = np.ascontiguousarray(offs, dtype=np.int64)
+            if offs.ndim != 1 or len(offs) < 1:
+                raise ValueError("read_bins: offsets must hold n+1 boundaries")
+            if len(offs) > 1 and (int(offs[0]) < 0 or int(offs[-1]) > len(buf)):
+                raise ValueError("read_bins: offsets reach outside the buffer")
+            return buf, offs
+        bs = [s.encode("latin-1") if isinstance(s, str) else (s if isinstance(s, bytes) else bytes(s)) for s in reads]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=offs[1:])
+        return b"".join(bs), offs
+
+    @staticmethod
+    def _read_bins_call(fn, mat, pat, text_ptr, offs, thre_mat, thre_pat, what):
+        import numpy as np
+        mh, ph = KmerTable._parent_handle(mat, "maternal", what), KmerTable._parent_handle(pat, "paternal", what)
+        n = len(offs) - 1
+        om, op = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        secs = C.c_double(0)
+        check(fn(mh, ph, n, text_ptr, C.c_void_p(offs.ctypes.data), _thre32(thre_mat), _thre32(thre_pat), C.c_void_p(om.ctypes.data), C.c_void_p(op.ctypes.data),
+                 C.byref(secs)))
+        return ReadBins(om, op, secs.value)
+
+    @staticmethod
+    def read_bins(mat, pat, reads, thre_mat, thre_pat):
+        """`mat` / `pat` the mother's and the father's whole KmerTables (one k, one device): per read the windows whose k-mer is solid
+        in one parent (count >= its threshold) and absent from the other -> ReadBins.  reads: a list of bytes / str, or a pair
+        (buffer, offsets) of the reads back to back (bytes or np.uint8) and their n+1 boundaries (np.int64).  No table is modified"""
+        import numpy as np
+        buf, offs = KmerTable._packed_reads(reads)
+        ptr = C.c_char_p(buf) if isinstance(buf, bytes) else C.c_void_p(buf.ctypes.data)
+        if isinstance(buf, np.ndarray) and buf.size == 0:
+            ptr = None
+        return KmerTable._read_bins_call(mat._L.jasper_read_bins if isinstance(mat, KmerTable) else None, mat, pat, ptr, offs, thre_mat, thre_pat, "read_bins")
+
+    @staticmethod
+    def read_bins_device(mat, pat, d_text, offsets, thre_mat, thre_pat):
+        """the same for reads already in HBM: d_text is a device pointer (int) or an object with .data_ptr() holding the reads back to
+        back, offsets the n+1 boundaries (host)"""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("read_bins_device: offsets must hold n+1 boundaries")
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        return KmerTable._read_bins_call(mat._L.jasper_read_bins_device if isinstance(mat, KmerTable) else None, mat, pat, C.c_void_p(ptr), offs, thre_mat, thre_pat,
+                                         "read_bins_device")
 
     # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
     def variant_scan(self, seqs, thre):

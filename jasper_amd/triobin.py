@@ -1,0 +1,442 @@
+"""Trio read binning: the child's reads sorted into maternal, paternal and unknown by the parental hap-mers they carry.
+
+    python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
+                                 [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
+                                 [--batch-bases N] [-o PREFIX] [--device D]
+
+An extension (the reference has no such tool), and the cure for what `--hapmers` only shows: a polisher that repairs toward the reads'
+solid k-mers can move a het site of a phased assembly onto the other haplotype, which hapmers.tsv lists as switches in its `after` row.
+TrioCanu-style binning prevents it: each haplotype is polished with the reads that belong to it.
+
+    python -m jasper_amd.triobin -r 'child.fq' --mat 'mat.fq' --pat 'pat.fq' --write-reads -o trio
+    jasper.sh -a hap1.fa -r 'trio.mat.child.fq trio.unknown.child.fq' ...
+    jasper.sh -a hap2.fa -r 'trio.pat.child.fq trio.unknown.child.fq' ...
+
+The parents.  The mother's and the father's reads are counted into two whole tables on one GPU, or their Jellyfish databases are loaded
+(--mat-jf / --pat-jf; a database's header decides k, and both parents must have one k).  A marker (hap-mer) is a k-mer that is solid in
+one parent -- count >= that parent's threshold, --mat-threshold / --pat-threshold or what its histogram gives -- and has count 0 in the
+other.  M_total and P_total are how many of them each parent has (KmerTable.hapmer_census_parents); when either is 0 the run ends with
+exit status 1.  All of this is extensions.open_parents, with the messages of `--hapmers`.
+
+The reads.  The child's files are read on the host: FASTQ in four-line records or FASTA with one or more sequence lines, line ends LF or
+CRLF, plain or .gz.  A read's sequence is its sequence lines without line ends, bytes as they stand (lower case counts as upper case, any
+other byte has no k-mer).  The sequences go to the GPU packed back to back in batches of at most --batch-bases bytes (default 256 Mi; a
+batch holds at least one read), where KmerTable.read_bins counts per read the windows whose k-mer is a maternal marker (m) and those whose
+k-mer is a paternal one (p).  A malformed record ends the run with exit status 1 and a message that names the file and the record.  The
+tool's wall time is this reader's; the kernel's share is what JASPER_AMD_TIMING=1 prints.
+
+The rule.  A template's m and p are its read's counts; with --paired they are the sums over its two mates.
+
+    m + p < --min-markers (default 1, at least 1)    unknown
+    otherwise  m * P_total > p * M_total             mat
+    otherwise  m * P_total < p * M_total             pat
+    otherwise  (equal)                               unknown
+
+The comparison is exact integer arithmetic: no floating point, and products beyond 2^64 stay exact.
+
+--paired: the files are R1 R2 [R1 R2 ...], record i of each file of a pair is one template.  An odd number of files ends the run before
+anything is counted, pair files with different record counts end it when that is found; neither leaves an output file.
+
+The files (each written as .tmp, then renamed; the read files renamed only when the run has succeeded):
+
+    PREFIX.readbins.tsv         #file bin reads bases mat_markers pat_markers: per input file in the order given three rows (mat, pat,
+                                unknown), then three rows for file `*` with the sums.  bases = sequence bytes of the bin's reads; the marker
+                                columns sum m and p of the bin's reads, each read's own counts, not its template's
+    PREFIX.readbins.reads.tsv   with --per-read: #file record name length mat pat bin, one line per read in input order; record is 0-based
+                                within its file, name the first token of the header line without @ / >
+    PREFIX.<bin>.<basename>     with --write-reads: for each of the three bins and each input file (its base name without a final .gz)
+                                that file's records of that bin, byte for byte as they stand in the decompressed input, in input order --
+                                the mates of a pair stay in step across R1 and R2, and the three files of an input hold each of its
+                                records exactly once.  Written by a second pass over the input with the bins in memory.  Two inputs with
+                                one base name end the run before anything is counted.  No .gz is written.
+
+PREFIX defaults to the first read file's name.  The log gives k, both thresholds and where they came from, M_total and P_total, then
+reads and bases per bin with their shares.  One GPU; parental tables that do not fit whole on it are an error.
+"""
+import gzip
+import os
+import sys
+from collections import namedtuple
+
+from . import cli, extensions
+from .report import write_atomic
+
+USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
+         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--batch-bases N] [-o PREFIX] [--device D]")
+BINS = ("mat", "pat", "unknown")
+MAT, PAT, UNKNOWN = 0, 1, 2
+BATCH_BASES_DEFAULT = 256 << 20
+BATCH_BASES_MOST = 1 << 40          # (the kernel takes 2^43 text bytes per call)
+CHUNK = 16 << 20                    # file bytes parsed at a time
+BOOL_FLAGS = ("--paired", "--per-read", "--write-reads")
+VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
+               "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases"}
+
+
+class Malformed(Exception):
+    """a record that is no FASTQ / FASTA record: (file, 0-based record, what is wrong with it)"""
+
+    def __init__(self, path, record, what):
+        Exception.__init__(self, "%s: record %d is malformed: %s" % (path, record, what))
+
+
+# what a file's reader hands on at a time: `buf` (np.uint8) holds whole records, record i is buf[rec_start[i]:rec_end[i]] and its header
+# line ends (without its line end) at head_end[i]; seq = the records' sequences back to back, lens their lengths
+Chunk = namedtuple("Chunk", "buf rec_start rec_end head_end seq lens")
+
+
+def _lines(buf, eof):
+    """(starts, ends) of the complete lines of buf: ends[i] is where line i's LF is; at the end of the file a last line without LF counts"""
+    import numpy as np
+    nl = np.flatnonzero(buf == 10)
+    if eof and len(buf) and (len(nl) == 0 or nl[-1] != len(buf) - 1):
+        nl = np.append(nl, len(buf))
+    ls = np.empty(len(nl), dtype=np.int64)
+    if len(nl):
+        ls[0] = 0
+        ls[1:] = nl[:-1] + 1
+    return ls, nl
+
+
+def _without_cr(buf, ls, le):
+    """line ends moved before a CR that stands right before the LF"""
+    import numpy as np
+    return le - ((le > ls) & (buf[np.maximum(le - 1, 0)] == 13))
+
+
+def _fastq_chunk(buf, eof, path, nrec, want_seq):
+    import numpy as np
+    ls, nl = _lines(buf, eof)
+    n = len(nl) // 4
+    if eof and len(nl) % 4:
+        raise Malformed(path, nrec + n, "the file ends inside it")
+    if n == 0:
+        return 0, None
+    ls, nl = ls[:4 * n], nl[:4 * n]
+    le = _without_cr(buf, ls, nl)
+    bad = (buf[ls[0::4]] != 64) | (buf[ls[2::4]] != 43) | (le[3::4] - ls[3::4] != le[1::4] - ls[1::4])
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        what = "its first line does not begin with @" if buf[ls[4 * i]] != 64 else "its third line does not begin with +" if buf[ls[4 * i + 2]] != 43 else \
+            "its quality line is not as long as its sequence"
+        raise Malformed(path, nrec + i, what)
+    rec_start, rec_end = ls[0::4], np.minimum(nl[3::4] + 1, len(buf))
+    used = int(rec_end[-1])
+    s, e = ls[1::4], le[1::4]
+    seq = None
+    if want_seq:
+        d = np.zeros(used + 1, dtype=np.int8)
+        some = e > s
+        d[s[some]] = 1
+        d[e[some]] = -1
+        seq = buf[:used][np.cumsum(d[:-1], dtype=np.int8).astype(bool)]
+    return used, Chunk(buf[:used], rec_start, rec_end, le[0::4], seq, e - s)
+
+
+def _fasta_chunk(buf, eof, path, nrec, want_seq):
+    import numpy as np
+    ls, nl = _lines(buf, eof)
+    heads = np.flatnonzero(buf[ls] == 62) if len(ls) else np.zeros(0, dtype=np.int64)
+    n = len(heads) - (0 if eof else 1)
+    if n <= 0:
+        return 0, None
+    rec_start = ls[heads[:n]]
+    rec_end = np.append(ls[heads[1:n]], len(buf) if n == len(heads) else ls[heads[n]])
+    used = int(rec_end[-1])
+    head_nl = nl[heads[:n]]
+    seq_start = np.minimum(head_nl + 1, used)
+    keep = np.repeat(np.arange(2 * n) % 2 == 1, np.stack([seq_start - rec_start, rec_end - seq_start], axis=1).ravel())      # header, sequence, header, ...
+    view = buf[:used]
+    cr = view == 13
+    cr[:-1] &= view[1:] == 10
+    cr[-1] &= eof and used == len(buf)      # (a CR that ends the file ends its line)
+    keep &= (view != 10) & ~cr
+    lens = np.add.reduceat(keep, rec_start - rec_start[0], dtype=np.int64)
+    return used, Chunk(view, rec_start, rec_end, _without_cr(buf, rec_start, head_nl), view[keep] if want_seq else None, lens)
+
+
+def chunks(path, want_seq=True):
+    """the records of one read file, CHUNK file bytes at a time -> Chunk; raises Malformed"""
+    import numpy as np
+    parse, carry, nrec = None, b"", 0
+    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+        while True:
+            block = f.read(CHUNK)
+            eof = not block
+            data = carry + block
+            if not data:
+                return
+            if parse is None:
+                if data[:1] not in (b"@", b">"):
+                    raise Malformed(path, 0, "the file begins with neither @ (FASTQ) nor > (FASTA)")
+                parse = _fastq_chunk if data[:1] == b"@" else _fasta_chunk
+            used, ch = parse(np.frombuffer(data, dtype=np.uint8), eof, path, nrec, want_seq)
+            if ch is not None:
+                nrec += len(ch.lens)
+                yield ch
+            carry = data[used:]
+            if eof:
+                return
+
+
+def names_of(ch):
+    """the records' names: the first token of the header line without its first byte"""
+    out = []
+    for a, b in zip(ch.rec_start.tolist(), ch.head_end.tolist()):
+        tok = ch.buf[a + 1:b].tobytes().split()
+        out.append(tok[0].decode("latin-1") if tok else "")
+    return out
+
+
+def bin_codes(m, p, m_total, p_total, min_markers):
+    """the rule, per template -> np.uint8 codes (MAT, PAT, UNKNOWN).  m, p: integer arrays; the products are Python integers"""
+    import numpy as np
+    out = np.full(len(m), UNKNOWN, dtype=np.uint8)
+    m64, p64 = np.asarray(m, dtype=np.uint64), np.asarray(p, dtype=np.uint64)
+    if len(out) == 0:
+        return out
+    if int(m64.max()) * p_total < 1 << 64 and int(p64.max()) * m_total < 1 << 64 and min_markers < 1 << 63:      # both products of every template fit 64 bits: still exact
+        a, b = m64 * np.uint64(p_total), p64 * np.uint64(m_total)
+        enough = m64 + p64 >= np.uint64(min_markers)
+        out[enough & (a > b)] = MAT
+        out[enough & (a < b)] = PAT
+        return out
+    for i in np.flatnonzero((m64 != 0) | (p64 != 0)).tolist():      # (m + p >= min_markers >= 1 needs one of them)
+        mi, pi = int(m64[i]), int(p64[i])
+        if mi + pi < min_markers:
+            continue
+        a, b = mi * p_total, pi * m_total
+        out[i] = MAT if a > b else PAT if a < b else UNKNOWN
+    return out
+
+
+class _Batcher:
+    """reads gathered into batches of at most `room` sequence bytes (at least one read) and counted: count(text, offsets) -> (m, p,
+    device seconds).  The counts come back in input order in self.m / self.p (lists of arrays)."""
+
+    def __init__(self, room, count):
+        self.room, self.count = room, count
+        self.seqs, self.lens, self.bases, self.reads = [], [], 0, 0
+        self.m, self.p, self.seconds, self.batches = [], [], 0.0, 0
+
+    def add(self, seq, lens):
+        import numpy as np
+        c = np.cumsum(lens)
+        done, base = 0, 0                               # reads and bytes of this call already placed
+        while done < len(lens):
+            take = max(0, int(np.searchsorted(c, base + self.room - self.bases, side="right")) - done)
+            if take == 0 and self.reads == 0:
+                take = 1
+            if take == 0:
+                self.flush()
+                continue
+            upto = int(c[done + take - 1])
+            self.seqs.append(seq[base:upto])
+            self.lens.append(lens[done:done + take])
+            self.bases += upto - base
+            self.reads += take
+            done, base = done + take, upto
+            if done < len(lens):
+                self.flush()
+
+    def flush(self):
+        import numpy as np
+        if self.reads == 0:
+            return
+        offs = np.zeros(self.reads + 1, dtype=np.int64)
+        np.cumsum(np.concatenate(self.lens), out=offs[1:])
+        m, p, secs = self.count(np.concatenate(self.seqs), offs)
+        self.m.append(m)
+        self.p.append(p)
+        self.seconds += secs
+        self.batches += 1
+        self.seqs, self.lens, self.bases, self.reads = [], [], 0, 0
+
+
+def out_basename(path):
+    b = os.path.basename(path)
+    return b[:-3] if b.endswith(".gz") else b
+
+
+def _share(a, b):
+    return "%.2f %%" % (100.0 * a / b) if b else "NA"
+
+
+def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT):
+    """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
+    cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds"""
+    import numpy as np
+    bat = _Batcher(batch_bases, count)
+    nrec, lens, names = [], [], []
+    try:
+        for fi, path in enumerate(paths):
+            fl, fn = [], []
+            for ch in chunks(path):
+                fl.append(ch.lens)
+                if per_read:
+                    fn += names_of(ch)
+                bat.add(ch.seq, ch.lens)
+            lens.append(np.concatenate(fl) if fl else np.zeros(0, dtype=np.int64))
+            nrec.append(len(lens[-1]))
+            names.append(fn)
+            if paired and fi % 2 == 1 and nrec[fi] != nrec[fi - 1]:
+                cli.error_exit("--paired: %s has %d records and %s has %d; the files of a pair must hold the same templates" % (paths[fi - 1], nrec[fi - 1], path, nrec[fi]))
+        bat.flush()
+    except Malformed as e:
+        cli.error_exit(str(e))
+    cuts = np.cumsum(nrec)[:-1]
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint32)      # noqa: E731
+    ms, ps = np.split(cat(bat.m), cuts), np.split(cat(bat.p), cuts)
+    bins = []
+    for fi in range(len(paths)):
+        if paired and fi % 2 == 1:
+            bins.append(bins[-1])
+        elif paired:
+            bins.append(bin_codes(ms[fi].astype(np.uint64) + ms[fi + 1], ps[fi].astype(np.uint64) + ps[fi + 1], m_total, p_total, min_markers))
+        else:
+            bins.append(bin_codes(ms[fi], ps[fi], m_total, p_total, min_markers))
+    # the table
+    text = "#file\tbin\treads\tbases\tmat_markers\tpat_markers\n"
+    total = np.zeros((3, 4), dtype=object)
+    for fi, path in enumerate(paths):
+        for b in range(3):
+            sel = bins[fi] == b
+            row = [int(sel.sum()), int(lens[fi][sel].sum()), int(ms[fi][sel].sum(dtype=np.uint64)), int(ps[fi][sel].sum(dtype=np.uint64))]
+            total[b] += row
+            text += "%s\t%s\t%d\t%d\t%d\t%d\n" % (path, BINS[b], row[0], row[1], row[2], row[3])
+    text += "".join("*\t%s\t%d\t%d\t%d\t%d\n" % ((BINS[b],) + tuple(int(v) for v in total[b])) for b in range(3))
+    made = []
+    try:
+        if write_reads:
+            _write_reads(paths, prefix, bins, nrec, made)
+        write_atomic(prefix + ".readbins.tsv", text)
+        if per_read:
+            with open(prefix + ".readbins.reads.tsv.tmp", "w") as f:
+                made.append(prefix + ".readbins.reads.tsv")
+                f.write("#file\trecord\tname\tlength\tmat\tpat\tbin\n")
+                for fi, path in enumerate(paths):
+                    f.writelines("%s\t%d\t%s\t%d\t%d\t%d\t%s\n" % (path, i, names[fi][i], lens[fi][i], ms[fi][i], ps[fi][i], BINS[bins[fi][i]]) for i in range(nrec[fi]))
+        for fn in made:
+            os.replace(fn + ".tmp", fn)
+        made = []
+    finally:
+        for fn in made:                                 # a run that has not succeeded leaves no read file behind
+            if os.path.exists(fn + ".tmp"):
+                os.remove(fn + ".tmp")
+    return [(int(total[b][0]), int(total[b][1])) for b in range(3)], bat.seconds
+
+
+def _write_reads(paths, prefix, bins, nrec, made):
+    """the second pass: every input's records into its three .tmp files; `made` gets the names they are to have"""
+    import numpy as np
+    for fi, path in enumerate(paths):
+        outs = ["%s.%s.%s" % (prefix, b, out_basename(path)) for b in BINS]
+        made += outs
+        files = [open(fn + ".tmp", "wb") for fn in outs]
+        try:
+            at = 0
+            try:
+                for ch in chunks(path, want_seq=False):
+                    n = len(ch.lens)
+                    if at + n > nrec[fi]:
+                        break
+                    size = ch.rec_end - ch.rec_start
+                    for b in range(3):
+                        ch.buf[np.repeat(bins[fi][at:at + n] == b, size)].tofile(files[b])
+                    at += n
+            except Malformed:
+                at = -1
+            if at != nrec[fi]:
+                cli.error_exit("--write-reads: %s changed between the two passes" % path)
+        finally:
+            for f in files:
+                f.close()
+
+
+def parse_args(argv):
+    o = dict.fromkeys(set(VALUE_FLAGS.values()))
+    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False)
+    i = 0
+    while i < len(argv):
+        key = argv[i]
+        if key in ("-h", "--help"):
+            print(USAGE)
+            sys.exit(0)
+        if key in BOOL_FLAGS:
+            o[extensions.flag_attr(key)] = True
+            i += 1
+            continue
+        if key not in VALUE_FLAGS or i + 1 >= len(argv):
+            print("Unknown option %s" % key)
+            sys.exit(1)
+        o[VALUE_FLAGS[key]] = argv[i + 1]
+        i += 2
+    return o
+
+
+def check_flags(a):
+    """everything that can be refused before a parent is opened -> (read files, k, device, the parents' flags, min_markers, batch_bases)"""
+    if a["reads"] is None:
+        cli.error_exit("No reads given. Please supply the child's read files with -r, separated by space and wrapped in one pair of quotation marks.")
+    opts = cli.Options()
+    opts.reads = a["reads"]
+    reads = cli._reads(opts)
+    if not reads:
+        cli.error_exit("No reads given. Please supply the child's read files with -r, separated by space and wrapped in one pair of quotation marks.")
+    k = extensions._range_flag("-k", a["k"], 37, 1, 64)
+    device = extensions._range_flag("--device", a["device"], 0, 0, 1023)
+    min_markers = extensions._range_flag("--min-markers", a["min_markers"], 1, 1, 1 << 33)
+    batch_bases = extensions._range_flag("--batch-bases", a["batch_bases"], BATCH_BASES_DEFAULT, 1, BATCH_BASES_MOST)
+    o = type("TriobinOptions", (), dict(a, hapmers=True, phase_short_range=None, phase_max_switches=None))
+    first_jf = a["mat_jf"] if a["mat_jf"] is not None else a["pat_jf"]
+    hap = extensions.hapmer_flags(o, k, first_jf)       # (a database's header decides k; both parents must have it)
+    if first_jf is not None:
+        k = extensions.jf_k(first_jf)
+    if a["paired"] and len(reads) % 2:
+        cli.error_exit("--paired takes the read files as R1 R2 [R1 R2 ...]; %d files were given" % len(reads))
+    if a["write_reads"]:
+        seen = {}
+        for fn in reads:
+            if out_basename(fn) in seen:
+                cli.error_exit("--write-reads: %s and %s would be written to the same files; give inputs with different base names" % (seen[out_basename(fn)], fn))
+            seen[out_basename(fn)] = fn
+    return reads, k, device, hap, min_markers, batch_bases
+
+
+def check_totals(m_total, p_total):
+    """a parent without a single hap-mer ends the run: the rule has nothing to weigh"""
+    if m_total == 0 or p_total == 0:
+        cli.error_exit("The %s no hap-mers at these thresholds: nothing tells the parents' reads apart." % (
+            "parents have" if m_total == p_total else "mother has" if m_total == 0 else "father has"))
+
+
+def run(argv):
+    from .table import KmerTable
+    a = parse_args(argv)
+    reads, k, device, hap, min_markers, batch_bases = check_flags(a)
+    prefix = a["prefix"] if a["prefix"] is not None else reads[0]
+    mat, pat, tm, tp = extensions.open_parents(hap, k, device)
+    try:
+        census = KmerTable.hapmer_census_parents(mat, pat, None, tm, tp)
+        m_total, p_total = census.mat[0], census.pat[0]
+        cli.log("Trio read binning with k = %d: maternal threshold %d (%s), paternal threshold %d (%s); %d maternal and %d paternal hap-mers" % (
+            k, tm, "given" if hap["thre_mat"] is not None else "from the histogram", tp, "given" if hap["thre_pat"] is not None else "from the histogram", m_total, p_total))
+        check_totals(m_total, p_total)
+
+        def count(text, offs):
+            r = KmerTable.read_bins(mat, pat, (text, offs), tm, tp)
+            return r.mat, r.pat, r.seconds
+
+        per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases)
+    finally:
+        mat.close()
+        pat.close()
+    n, bases = sum(r for r, _ in per_bin), sum(b for _, b in per_bin)
+    cli.log("Read bins: " + "; ".join("%s %d reads (%s), %d bases (%s)" % (BINS[b], per_bin[b][0], _share(per_bin[b][0], n), per_bin[b][1], _share(per_bin[b][1], bases))
+                                      for b in range(3)) + " in %s.readbins.tsv" % prefix)
+    extensions.device_line("[triobin] read_bins device seconds: %.6f; %s bases per second" % (seconds, "%.4g" % (bases / seconds) if seconds > 0 else "NA"))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(run(sys.argv[1:]))
