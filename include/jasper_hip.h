@@ -438,6 +438,34 @@ int jasper_read_bins(jasper_table *mat, jasper_table *pat, int64_t n_reads, cons
 int jasper_read_bins_device(jasper_table *mat, jasper_table *pat, int64_t n_reads, const void *d_text, const int64_t *offsets /* host */, uint32_t thre_mat,
                             uint32_t thre_pat, uint32_t *out_mat, uint32_t *out_pat, double *device_seconds);
 
+/* The same from the child's read FILES: a chunk of raw FASTQ / FASTA text is uploaded as it stands, kernels find its lines, verify the
+ * record shape, pack the sequences back to back and write the offsets, and the binning above runs on what they packed.  Only the small
+ * per-record arrays come back.  An EXTENSION like the binning; beside the read feed (jasper_read_feed_*), which marks a record's end in
+ * the base stream and hands out no offsets.  What it computes is what the host parser of jasper_amd/triobin.py computes for the same
+ * (text, eof):
+ *   line       ends at a line feed; with eof a last line without one counts.  A CR directly before a line's end (the line feed, or the
+ *              text's end with eof) is not part of the line; a CR anywhere else is a byte like any other
+ *   FASTQ      format 0.  A record is four lines, counted from the text's first byte, which the caller guarantees begins a record: line 4i
+ *              begins with @, line 4i+2 with +, lines 4i+1 and 4i+3 have equal lengths (a quality line may begin with @ or +).  Without
+ *              eof a trailing partial record is not used; with eof a line count that is no multiple of 4 is malformed
+ *   FASTA      format 1.  A line is a header iff it begins with >; a record is a header and every line up to the next header, its sequence
+ *              those lines' bytes without line ends (blank lines give nothing, a header alone is an empty read).  Without eof the last
+ *              record of the text is not used: its end is not known
+ *   used       the bytes whole records cover; n_records how many.  The caller passes text + used on with the next chunk
+ *   status     0 clean, 1 malformed with bad_record = the first record that fails a check, or n_records when the file ends inside a
+ *              record.  Malformed is no error (JASPER_OK); nothing is binned then and nothing can be fetched
+ *   device_seconds (may be NULL) two numbers, HIP events: [0] the index and pack kernels, [1] the start-bit pass and the scan kernel
+ * The results stay in mat's workspace until its next binning call of any kind.  jasper_read_text_fetch copies them out: rec_start[n_records
+ * + 1] (record i = text[rec_start[i] .. rec_start[i+1]), the last entry = used), head_end[n_records] (where the header line ends, before
+ * a CR), lens[n_records], out_mat / out_pat as jasper_read_bins gives them for the packed sequences, and, where out_seq is not NULL, those
+ * sequences (sum of lens bytes; for tests).  n_records must be what the call before returned: anything else is JASPER_ERR.
+ * Limits: n < 2^31 text bytes per call (more is JASPER_ERR before the text is looked at).  JASPER_ERR also for what jasper_read_bins
+ * refuses of the tables and thresholds, a format other than 0 / 1, a NULL text with n > 0. */
+int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text /* host */, int64_t n, int eof, int format, uint32_t thre_mat, uint32_t thre_pat,
+                          int64_t *used, int64_t *n_records, int *status, int64_t *bad_record, double *device_seconds /* [2] */);
+int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat,
+                           uint8_t *out_seq /* may be NULL */);
+
 /* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
  * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
  * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.

@@ -235,6 +235,9 @@ SYMBOLS = {
     "jasper_hapmer_census": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_read_bins": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(C.c_double)]),
     "jasper_read_bins_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(C.c_double)]),
+    "jasper_read_text_bins": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "jasper_read_text_fetch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "jasper_variant_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_variant_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_varscan_num_seqs": (C.c_int, [_P]),

@@ -11,6 +11,7 @@
 #include "copies.hpp"
 #include "hapmers.hpp"
 #include "readbins.hpp"
+#include "readtext.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
 #include "compound.hpp"
@@ -920,6 +921,16 @@ int jasper_read_bins_device(jasper_table *mat, jasper_table *pat, int64_t n_read
                             uint32_t *out_mat, uint32_t *out_pat, double *device_seconds) {
     if (!mat || !pat) { g_err = "bad argument"; return JASPER_ERR; }
     return read_bins_device(mat->t, pat->t, n_reads, (const uint8_t *)d_text, offsets, thre_mat, thre_pat, out_mat, out_pat, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+// ... from raw FASTQ / FASTA text (readtext.hip)
+int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text, int64_t n, int eof, int format, uint32_t thre_mat, uint32_t thre_pat, int64_t *used,
+                          int64_t *n_records, int *status, int64_t *bad_record, double *device_seconds) {
+    if (!mat || !pat) { g_err = "bad argument"; return JASPER_ERR; }
+    return read_text_bins(mat->t, pat->t, text, n, eof, format, thre_mat, thre_pat, used, n_records, status, bad_record, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat, uint8_t *out_seq) {
+    if (!mat) { g_err = "bad argument"; return JASPER_ERR; }
+    return read_text_fetch(mat->t, n_records, rec_start, head_end, lens, out_mat, out_pat, out_seq, g_err) ? JASPER_ERR : JASPER_OK;
 }
 
 // ---- variant scan (variants.hip) ----

@@ -17,7 +17,8 @@
 //                       and for each piece that holds a marker searches the offsets for the piece's read -- between the reads of the
 //                       tile's first and last byte, which two threads of the tile have searched for while the text was staged -- and
 //                       adds the piece's two sums to that read's counters: one atomic add per thread, read and class.
-// The host stage orders the two tables (settle), uploads the offsets, zeroes counters and bits, and times the two kernels by HIP events.
+// The host stage orders the two tables (settle), uploads the offsets, zeroes counters and bits, and times the two kernels by HIP events:
+// read_bins_core, which the read-text path (readtext.hip) calls with offsets its own kernels have left in HBM.
 #include "readbins.hpp"
 #include "hapmers.hpp"
 #include "scan_tile.hpp"
@@ -160,6 +161,45 @@ int check_reads(int64_t n_reads, const void *text, const int64_t *offsets, int k
 }
 }  // namespace
 
+// the core: settle, start bits, scan.  The offsets are in HBM already (d_offs_in: n_reads + 1 offsets and the two words of the stream's
+// span behind them), or on the host (h_offs, uploaded into the binning's own slot).  L = the stream's bytes; n_reads > 0.  The counters
+// stay in WS_READBINS + 1 (*d_cnt_out: mat[n_reads], then pat[n_reads]); ev times the kernels once the stream has been waited for.
+int read_bins_core(Table &M, Table &P, int64_t n_reads, const uint8_t *d_text, const int64_t *h_offs, const int64_t *d_offs_in, int64_t L, uint32_t thre_mat, uint32_t thre_pat,
+                   Events &ev, uint32_t **d_cnt_out, std::string &err) {
+    M.text_records = -1;                                // (the counters of a read-text call are about to be overwritten: readtext.hip)
+    const size_t n = (size_t)n_reads;
+    const uint64_t ntiles = L >= M.k ? ((uint64_t)(L - M.k + 1) + RP_TILE - 1) / RP_TILE : 0;
+    HIPCHK(hipSetDevice(M.device));
+    Table *others[1] = {&P};
+    Events order;
+    if (settle(M, others, 1, order, err)) return -1;
+    hipStream_t st = M.stream;
+    const size_t bit_words = (size_t)((L + 31) / 32) + 1;
+    int64_t *d_offs = h_offs ? (int64_t *)M.workspace(Table::WS_READBINS, (n + 3) * sizeof(int64_t), err) : const_cast<int64_t *>(d_offs_in);
+    uint32_t *d_cnt = (uint32_t *)M.workspace(Table::WS_READBINS + 1, 2 * n * sizeof(uint32_t), err);
+    uint32_t *d_bits = (uint32_t *)M.workspace(Table::WS_READBINS + 2, bit_words * sizeof(uint32_t), err);
+    if (!d_offs || !d_cnt || !d_bits) return -1;
+    if (h_offs) {
+        const int64_t span[2] = {h_offs[0], h_offs[n]};
+        HIPCHK(hipMemcpyAsync(d_offs, h_offs, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_offs + n + 1, span, sizeof span, hipMemcpyHostToDevice, st));
+    }
+    if (ev.create(err)) return -1;
+    HIPCHK(hipEventRecord(ev.e[0], st));
+    HIPCHK(hipMemsetAsync(d_cnt, 0, 2 * n * sizeof(uint32_t), st));
+    if (ntiles) {                                       // (no tile: no window anywhere, the counters are zeros)
+        HIPCHK(hipMemsetAsync(d_bits, 0, bit_words * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(read_starts_kernel, dim3((unsigned)std::min<uint64_t>((n + RS_THREADS - 1) / RS_THREADS, 256 * 8)), dim3(RS_THREADS), 0, st, d_offs, n_reads, d_bits);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(read_bins_kernel, dim3((unsigned)std::min<uint64_t>(ntiles, 256 * 8)), dim3(RP_THREADS), 0, st, d_text, d_offs, n_reads, d_bits, ntiles, M.d, P.d, thre_mat,
+                           thre_pat, d_cnt, d_cnt + n);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev.e[1], st));
+    *d_cnt_out = d_cnt;
+    return 0;
+}
+
 int read_bins_device(Table &M, Table &P, int64_t n_reads, const uint8_t *d_text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t *out_mat,
                      uint32_t *out_pat, double *seconds, std::string &err) {
     if (seconds) *seconds = 0;
@@ -168,36 +208,15 @@ int read_bins_device(Table &M, Table &P, int64_t n_reads, const uint8_t *d_text,
     if (check_reads(n_reads, d_text, offsets, M.k, out_mat, out_pat, L, err)) return -1;
     if (n_reads == 0) return 0;
     const size_t n = (size_t)n_reads;
-    const uint64_t ntiles = L >= M.k ? ((uint64_t)(L - M.k + 1) + RP_TILE - 1) / RP_TILE : 0;
-    if (ntiles == 0) {                                  // no window anywhere
+    if (L < M.k) {                                      // no window anywhere
         std::fill(out_mat, out_mat + n, 0u);
         std::fill(out_pat, out_pat + n, 0u);
         return 0;
     }
-    HIPCHK(hipSetDevice(M.device));
-    Table *others[1] = {&P};
-    Events order;
-    if (settle(M, others, 1, order, err)) return -1;
-    hipStream_t st = M.stream;
-    const size_t bit_words = (size_t)((L + 31) / 32) + 1;
-    int64_t *d_offs = (int64_t *)M.workspace(Table::WS_READBINS, (n + 3) * sizeof(int64_t), err);
-    uint32_t *d_cnt = (uint32_t *)M.workspace(Table::WS_READBINS + 1, 2 * n * sizeof(uint32_t), err);
-    uint32_t *d_bits = (uint32_t *)M.workspace(Table::WS_READBINS + 2, bit_words * sizeof(uint32_t), err);
-    if (!d_offs || !d_cnt || !d_bits) return -1;
-    const int64_t span[2] = {offsets[0], offsets[n]};
-    HIPCHK(hipMemcpyAsync(d_offs, offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_offs + n + 1, span, sizeof span, hipMemcpyHostToDevice, st));
     Events ev;
-    if (ev.create(err)) return -1;
-    HIPCHK(hipEventRecord(ev.e[0], st));
-    HIPCHK(hipMemsetAsync(d_cnt, 0, 2 * n * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(d_bits, 0, bit_words * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(read_starts_kernel, dim3((unsigned)std::min<uint64_t>((n + RS_THREADS - 1) / RS_THREADS, 256 * 8)), dim3(RS_THREADS), 0, st, d_offs, n_reads, d_bits);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(read_bins_kernel, dim3((unsigned)std::min<uint64_t>(ntiles, 256 * 8)), dim3(RP_THREADS), 0, st, d_text, d_offs, n_reads, d_bits, ntiles, M.d, P.d, thre_mat,
-                       thre_pat, d_cnt, d_cnt + n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.e[1], st));
+    uint32_t *d_cnt = nullptr;
+    if (read_bins_core(M, P, n_reads, d_text, offsets, nullptr, L, thre_mat, thre_pat, ev, &d_cnt, err)) return -1;
+    hipStream_t st = M.stream;
     HIPCHK(hipMemcpyAsync(out_mat, d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(out_pat, d_cnt + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(jk_stream_wait(st));

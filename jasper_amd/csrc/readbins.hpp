@@ -23,6 +23,13 @@ constexpr int64_t RB_MAX_READ_WINDOWS = 0xFFFFFFFFll;
 // host arrays of n_reads words.  seconds (may be null) = device time (HIP events) of the start-bit pass and the scan.
 int read_bins_device(Table &M, Table &P, int64_t n_reads, const uint8_t *d_text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t *out_mat,
                      uint32_t *out_pat, double *seconds, std::string &err);
+// what both run, and the read-text path on its packed sequences (readtext.hip): n_reads > 0 reads of L bytes in all whose offsets are
+// either a host array (h_offs: uploaded) or in HBM already (d_offs_in: the n_reads + 1 offsets, then {offsets[0], offsets[n_reads]}).
+// Nothing is checked and nothing is waited for: the counters stay on the device (*d_cnt_out: mat[n_reads], pat[n_reads]) and ev holds
+// the two events around the kernels.
+struct Events;
+int read_bins_core(Table &M, Table &P, int64_t n_reads, const uint8_t *d_text, const int64_t *h_offs, const int64_t *d_offs_in, int64_t L, uint32_t thre_mat, uint32_t thre_pat,
+                   Events &ev, uint32_t **d_cnt_out, std::string &err);
 // the same with the text in host memory: the bytes text[offsets[0] .. offsets[n_reads]) are uploaded
 int read_bins_host(Table &M, Table &P, int64_t n_reads, const char *text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t *out_mat, uint32_t *out_pat,
                    double *seconds, std::string &err);

@@ -238,6 +238,21 @@ class ReadBins:
         return isinstance(other, ReadBins) and self.mat.tobytes() == other.mat.tobytes() and self.pat.tobytes() == other.pat.tobytes()
 
 
+READ_TEXT_FORMATS = {"fastq": 0, "fasta": 1}
+
+
+class ReadText:
+    """one chunk of raw FASTQ / FASTA text parsed, packed and binned on the GPU (include/jasper_hip.h: jasper_read_text_bins): `used` =
+    the bytes whole records cover, `n_records`; `malformed` with `bad_record`, and then nothing else; otherwise `rec_start`
+    (np.int64[n + 1], the last = used), `head_end`, `lens` (np.int64[n]), `mat` / `pat` (np.uint32[n]) as ReadBins has them, `seq` (the
+    packed sequences, np.uint8, when asked for), `seconds` = device time of the binning kernels, `index_seconds` = of index + pack."""
+
+    def __init__(self, used, n_records, malformed, bad_record, seconds, index_seconds):
+        self.used, self.n_records, self.malformed, self.bad_record = used, n_records, malformed, bad_record
+        self.seconds, self.index_seconds = seconds, index_seconds
+        self.rec_start = self.head_end = self.lens = self.mat = self.pat = self.seq = None
+
+
 VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
 VARIANT_KINDS = {1: "het", 2: "error"}
 
@@ -1111,6 +1126,37 @@ class KmerTable:
         ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
         return KmerTable._read_bins_call(mat._L.jasper_read_bins_device if isinstance(mat, KmerTable) else None, mat, pat, C.c_void_p(ptr), offs, thre_mat, thre_pat,
                                          "read_bins_device")
+
+    @staticmethod
+    def read_bins_text(mat, pat, buf, eof, fmt, thre_mat, thre_pat, want_seq=False):
+        """the same from raw file text: buf (bytes or np.uint8) begins at a record's first byte, fmt is "fastq" or "fasta", eof says
+        whether buf ends the file.  The GPU finds the lines, verifies the records, packs the sequences and bins them -> ReadText; the
+        caller carries buf[used:] over to the next chunk.  A malformed chunk is no error: ReadText.malformed, nothing binned"""
+        import numpy as np
+        if fmt not in READ_TEXT_FORMATS:
+            raise ValueError("read_bins_text: fmt must be 'fastq' or 'fasta'")
+        if not isinstance(buf, bytes):
+            buf = np.ascontiguousarray(buf)
+            if buf.dtype != np.uint8 or buf.ndim != 1:
+                raise TypeError("read_bins_text: the buffer must be bytes or a one-dimensional np.uint8 array")
+        mh, ph = KmerTable._parent_handle(mat, "maternal", "read_bins_text"), KmerTable._parent_handle(pat, "paternal", "read_bins_text")
+        ptr = C.c_char_p(buf) if isinstance(buf, bytes) else C.c_void_p(buf.ctypes.data if buf.size else None)
+        used, n, bad, status, secs = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0), (C.c_double * 2)()
+        L = mat._L
+        check(L.jasper_read_text_bins(mh, ph, ptr, len(buf), 1 if eof else 0, READ_TEXT_FORMATS[fmt], _thre32(thre_mat), _thre32(thre_pat), C.byref(used), C.byref(n),
+                                      C.byref(status), C.byref(bad), secs))
+        r = ReadText(used.value, n.value, status.value != 0, bad.value, secs[1], secs[0])
+        if r.malformed:
+            return r
+        nr = r.n_records
+        r.rec_start, r.head_end, r.lens = np.zeros(nr + 1, dtype=np.int64), np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
+        r.mat, r.pat = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+        check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), None))
+        if want_seq:                                    # (its size is the sum of lens: a second fetch, for tests)
+            r.seq = np.zeros(int(r.lens.sum()), dtype=np.uint8)
+            check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), vp(r.seq) if r.seq.size else None))
+        return r
 
     # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
     def variant_scan(self, seqs, thre):

@@ -2,7 +2,7 @@
 
     python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
                                  [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
-                                 [--batch-bases N] [-o PREFIX] [--device D]
+                                 [--batch-bases N] [--reader host|device] [-o PREFIX] [--device D]
 
 An extension (the reference has no such tool), and the cure for what `--hapmers` only shows: a polisher that repairs toward the reads'
 solid k-mers can move a het site of a phased assembly onto the other haplotype, which hapmers.tsv lists as switches in its `after` row.
@@ -24,6 +24,13 @@ other byte has no k-mer).  The sequences go to the GPU packed back to back in ba
 batch holds at least one read), where KmerTable.read_bins counts per read the windows whose k-mer is a maternal marker (m) and those whose
 k-mer is a paternal one (p).  A malformed record ends the run with exit status 1 and a message that names the file and the record.  The
 tool's wall time is this reader's; the kernel's share is what JASPER_AMD_TIMING=1 prints.
+
+--reader device parses on the GPU instead: a file's bytes are read as above (open / gzip.open, DEVICE_CHUNK bytes at a time, the unused
+tail carried over) and go to HBM as they stand, where KmerTable.read_bins_text finds the lines, verifies the records, packs the sequences
+and bins them; only the per-record arrays come back.  Every output file is byte for byte the host reader's.  --batch-bases has no effect
+there (a batch is a chunk).  A chunk the GPU calls malformed is parsed once more by the host parser, which words the message.
+--write-reads then routes the second pass's bytes by the record starts the first pass has kept (8 bytes a record) instead of parsing
+again.  JASPER_TRIOBIN_CHUNK=<bytes> overrides DEVICE_CHUNK.  The default is host.
 
 The rule.  A template's m and p are its read's counts; with --paired they are the sums over its two mates.
 
@@ -62,15 +69,20 @@ from . import cli, extensions
 from .report import write_atomic
 
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
-         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--batch-bases N] [-o PREFIX] [--device D]")
+         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--batch-bases N (no effect with --reader device)] [--reader host|device] "
+         "[-o PREFIX] [--device D]")
 BINS = ("mat", "pat", "unknown")
 MAT, PAT, UNKNOWN = 0, 1, 2
 BATCH_BASES_DEFAULT = 256 << 20
 BATCH_BASES_MOST = 1 << 40          # (the kernel takes 2^43 text bytes per call)
 CHUNK = 16 << 20                    # file bytes parsed at a time
+DEVICE_CHUNK = 16 << 20             # ... with --reader device: file bytes uploaded and parsed at a time (JASPER_TRIOBIN_CHUNK overrides it)
+DEVICE_CHUNK_MOST = (1 << 30) - 1   # (a chunk and the tail carried into it stay below the kernels' 2^31 text bytes)
+READERS = ("host", "device")
 BOOL_FLAGS = ("--paired", "--per-read", "--write-reads")
 VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
-               "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases"}
+               "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases",
+               "--reader": "reader"}
 
 
 class Malformed(Exception):
@@ -262,19 +274,87 @@ def _share(a, b):
     return "%.2f %%" % (100.0 * a / b) if b else "NA"
 
 
-def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT):
+def device_chunk():
+    """file bytes per upload of the device reader: DEVICE_CHUNK, or what JASPER_TRIOBIN_CHUNK says"""
+    v = os.environ.get("JASPER_TRIOBIN_CHUNK")
+    if v is None:
+        return DEVICE_CHUNK
+    n = int(v) if v.isdigit() else 0
+    if not 1 <= n <= DEVICE_CHUNK_MOST:
+        cli.error_exit("JASPER_TRIOBIN_CHUNK must be a number of bytes from 1 to %d" % DEVICE_CHUNK_MOST)
+    return n
+
+
+class _DeviceReader:
+    """--reader device: a file's bytes go to the GPU as they stand, count_text(buf, eof, fmt) -> table.ReadText parses, packs and counts
+    them there.  chunks(path) yields what the host reader's chunks() yields, without the sequences; the counts come back in input order in
+    self.m / self.p as _Batcher has them.  With keep_starts, self.starts[path] = (the records' first byte, their absolute starts in the
+    decompressed file, its length): what the second pass of --write-reads routes by."""
+
+    def __init__(self, count_text, keep_starts):
+        self.count_text, self.keep_starts = count_text, keep_starts
+        self.m, self.p, self.seconds, self.starts = [], [], 0.0, {}
+
+    def chunks(self, path):
+        import numpy as np
+        size = device_chunk()
+        fmt, first, nrec, base, starts = None, b"", 0, 0, []
+        room, have = bytearray(size), 0                 # one buffer for every block: the tail carried over at its front, the file read in behind it
+        with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+            while True:
+                if have + size > len(room):             # (a tail as long as a block: a record longer than that)
+                    room = room[:have] + bytearray(size)
+                got = f.readinto(memoryview(room)[have:have + size])
+                eof = not got
+                n = have + got
+                if not n:
+                    break
+                if fmt is None:
+                    first = bytes(room[:1])
+                    if first not in (b"@", b">"):
+                        raise Malformed(path, 0, "the file begins with neither @ (FASTQ) nor > (FASTA)")
+                    fmt = "fastq" if first == b"@" else "fasta"
+                buf = np.frombuffer(room, dtype=np.uint8, count=n)
+                r = self.count_text(buf, eof, fmt)
+                if r.malformed:                         # the host parser words the message: the same (buf, eof) raises there
+                    (_fastq_chunk if fmt == "fastq" else _fasta_chunk)(buf, eof, path, nrec, False)
+                    raise RuntimeError("%s: the device reader calls record %d malformed and the host parser does not" % (path, nrec + r.bad_record))
+                self.seconds += r.seconds
+                if r.n_records:
+                    nrec += r.n_records
+                    self.m.append(r.mat)
+                    self.p.append(r.pat)
+                    if self.keep_starts:
+                        starts.append(r.rec_start[:-1] + base)
+                    yield Chunk(buf[:r.used], r.rec_start[:-1], r.rec_start[1:], r.head_end, None, r.lens)      # (looked at before the buffer is used again)
+                del buf
+                have = n - r.used
+                room[:have] = room[r.used:n]
+                base += r.used
+                if eof:
+                    break
+        if self.keep_starts:
+            self.starts[path] = (first, np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64), base + have)
+
+
+def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT, reader="host",
+              count_text=None):
     """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
-    cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds"""
+    cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds.  reader "device": the files'
+    bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called"""
     import numpy as np
     bat = _Batcher(batch_bases, count)
+    dev = _DeviceReader(count_text, write_reads) if reader == "device" else None
     nrec, lens, names = [], [], []
     try:
         for fi, path in enumerate(paths):
             fl, fn = [], []
-            for ch in chunks(path):
+            for ch in (dev.chunks(path) if dev else chunks(path)):
                 fl.append(ch.lens)
                 if per_read:
                     fn += names_of(ch)
+                if dev:
+                    continue
                 bat.add(ch.seq, ch.lens)
             lens.append(np.concatenate(fl) if fl else np.zeros(0, dtype=np.int64))
             nrec.append(len(lens[-1]))
@@ -284,6 +364,8 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
         bat.flush()
     except Malformed as e:
         cli.error_exit(str(e))
+    if dev:
+        bat.m, bat.p, bat.seconds = dev.m, dev.p, dev.seconds
     cuts = np.cumsum(nrec)[:-1]
     cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint32)      # noqa: E731
     ms, ps = np.split(cat(bat.m), cuts), np.split(cat(bat.p), cuts)
@@ -307,7 +389,9 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
     text += "".join("*\t%s\t%d\t%d\t%d\t%d\n" % ((BINS[b],) + tuple(int(v) for v in total[b])) for b in range(3))
     made = []
     try:
-        if write_reads:
+        if write_reads and dev:
+            _write_reads_by_starts(paths, prefix, bins, made, dev.starts)
+        elif write_reads:
             _write_reads(paths, prefix, bins, nrec, made)
         write_atomic(prefix + ".readbins.tsv", text)
         if per_read:
@@ -347,6 +431,45 @@ def _write_reads(paths, prefix, bins, nrec, made):
             except Malformed:
                 at = -1
             if at != nrec[fi]:
+                cli.error_exit("--write-reads: %s changed between the two passes" % path)
+        finally:
+            for f in files:
+                f.close()
+
+
+def _write_reads_by_starts(paths, prefix, bins, made, kept):
+    """the second pass of the device reader: nothing is parsed again, a block's bytes are routed by the record starts the first pass has
+    kept.  The file has changed when its decompressed length differs or a remembered start does not hold the records' first byte"""
+    import numpy as np
+    for fi, path in enumerate(paths):
+        outs = ["%s.%s.%s" % (prefix, b, out_basename(path)) for b in BINS]
+        made += outs
+        files = [open(fn + ".tmp", "wb") for fn in outs]
+        first, starts, length = kept[path]
+        try:
+            at = 0
+            with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+                while at >= 0:
+                    block = f.read(CHUNK)
+                    if not block:
+                        break
+                    buf = np.frombuffer(block, dtype=np.uint8)
+                    end = at + len(buf)
+                    if end > length:
+                        at = -1
+                        break
+                    i0 = int(np.searchsorted(starts, at, side="right")) - 1      # the record the block's first byte lies in (starts[0] == 0)
+                    i1 = int(np.searchsorted(starts, end, side="left"))          # records i0 .. i1 - 1 have bytes in the block
+                    begins = starts[i0:i1] - at
+                    begins = begins[begins >= 0]
+                    if not (buf[begins] == first[0]).all():
+                        at = -1
+                        break
+                    size = np.diff(np.concatenate(([0], starts[i0 + 1:i1] - at, [len(buf)])))
+                    for b in range(3):
+                        buf[np.repeat(bins[fi][i0:i1] == b, size)].tofile(files[b])
+                    at = end
+            if at != length:
                 cli.error_exit("--write-reads: %s changed between the two passes" % path)
         finally:
             for f in files:
@@ -403,6 +526,16 @@ def check_flags(a):
     return reads, k, device, hap, min_markers, batch_bases
 
 
+def check_reader(a):
+    """--reader, and with device the chunk size: refused before a parent is opened"""
+    reader = a["reader"] if a["reader"] is not None else "host"
+    if reader not in READERS:
+        cli.error_exit("--reader takes host or device; %s was given" % reader)
+    if reader == "device":
+        device_chunk()
+    return reader
+
+
 def check_totals(m_total, p_total):
     """a parent without a single hap-mer ends the run: the rule has nothing to weigh"""
     if m_total == 0 or p_total == 0:
@@ -413,6 +546,7 @@ def check_totals(m_total, p_total):
 def run(argv):
     from .table import KmerTable
     a = parse_args(argv)
+    reader = check_reader(a)
     reads, k, device, hap, min_markers, batch_bases = check_flags(a)
     prefix = a["prefix"] if a["prefix"] is not None else reads[0]
     mat, pat, tm, tp = extensions.open_parents(hap, k, device)
@@ -427,7 +561,16 @@ def run(argv):
             r = KmerTable.read_bins(mat, pat, (text, offs), tm, tp)
             return r.mat, r.pat, r.seconds
 
-        per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases)
+        index_seconds, text_bytes = [0.0], []
+
+        def count_text(buf, eof, fmt):
+            r = KmerTable.read_bins_text(mat, pat, buf, eof, fmt, tm, tp)
+            index_seconds[0] += r.index_seconds
+            text_bytes.append(r.used)
+            return r
+
+        per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
+                                     count_text=count_text)
     finally:
         mat.close()
         pat.close()
@@ -435,6 +578,9 @@ def run(argv):
     cli.log("Read bins: " + "; ".join("%s %d reads (%s), %d bases (%s)" % (BINS[b], per_bin[b][0], _share(per_bin[b][0], n), per_bin[b][1], _share(per_bin[b][1], bases))
                                       for b in range(3)) + " in %s.readbins.tsv" % prefix)
     extensions.device_line("[triobin] read_bins device seconds: %.6f; %s bases per second" % (seconds, "%.4g" % (bases / seconds) if seconds > 0 else "NA"))
+    if reader == "device":
+        extensions.device_line("[triobin] read_text index + pack device seconds: %.6f; %s text bytes per second" % (
+            index_seconds[0], "%.4g" % (sum(text_bytes) / index_seconds[0]) if index_seconds[0] > 0 else "NA"))
     return 0
 
 

@@ -1,7 +1,7 @@
 """The read binning kernel next to its two yardsticks, on bench.py's workload with reads (47 Mb synthetic genome, two synthetic parents
 0.1 % away, 30x of 150-base reads drawn from it, k = 37), and the tool's end-to-end time on the same reads.
 
-    python tools/prof_readbins.py trace|time|e2e       (run on the GPU box; tools/prof_readbins.sh puts `trace` under rocprofv3)
+    python tools/prof_readbins.py trace|time|e2e [--reader host|device]      (run on the GPU box; tools/prof_readbins.sh puts `trace` under rocprofv3)
 
 M and P = each parent's reads at 30x, counted (as tools/prof_hapmers.py makes them).  The batch = the first 256 Mi bases of the child's
 reads, packed back to back without separators: what one call of the tool sends.
@@ -12,7 +12,7 @@ trace: each of the three after a warm-up call of the same kind, in one process s
 time:  no profiler: the calls' own event seconds, five of (a) and (c) and three of (b) after a warm-up, and that (c) equals (b) read by read
 e2e:   the parents written as databases and ALL the child's reads as one FASTQ file, then `python -m jasper_amd.triobin` as a child
        process on them: its wall seconds, the kernel's summed device seconds (JASPER_AMD_TIMING=1), and the seconds the tool's reader
-       alone takes over the same file
+       alone takes over the same file.  `--reader R` is passed on to the tool (with device its index + pack seconds are reported too)
 summarize DIR: per kernel of a rocprofv3 --kernel-trace CSV under DIR the durations of its dispatches in order (the measured call's are
        the last ones)
 """
@@ -147,11 +147,13 @@ def e2e(torch, reads, nreads, m, p, tm, tp, head):
     assert n == nreads
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, "-m", "jasper_amd.triobin", "-r", paths["child.fq"], "--mat-jf", paths["mat.jf"], "--pat-jf", paths["pat.jf"], "--mat-threshold", str(tm),
-                        "--pat-threshold", str(tp), "-o", paths["out"]], env=dict(os.environ, PYTHONPATH=ROOT, JASPER_AMD_TIMING="1"), capture_output=True, text=True)
+                        "--pat-threshold", str(tp), "-o", paths["out"]] + sys.argv[2:], env=dict(os.environ, PYTHONPATH=ROOT, JASPER_AMD_TIMING="1"), capture_output=True, text=True)
     wall = time.perf_counter() - t0
     sys.stderr.write(r.stdout + r.stderr)
     dev_secs = re.search(r"read_bins device seconds: ([0-9.]+)", r.stderr)
-    head.update({"returncode": r.returncode, "tool_wall_seconds": wall, "reader_alone_seconds": reader, "kernel_device_seconds": float(dev_secs.group(1)) if dev_secs else None,
+    index_secs = re.search(r"read_text index \+ pack device seconds: ([0-9.]+)", r.stderr)
+    head.update({"tool_flags": sys.argv[2:], "index_pack_device_seconds": float(index_secs.group(1)) if index_secs else None,
+                 "returncode": r.returncode, "tool_wall_seconds": wall, "reader_alone_seconds": reader, "kernel_device_seconds": float(dev_secs.group(1)) if dev_secs else None,
                  "file_bytes": os.path.getsize(paths["child.fq"]), "table": open(paths["out"] + ".readbins.tsv").read() if r.returncode == 0 else None})
     print(json.dumps(head))
     for fn in list(paths.values()) + [paths["out"] + ".readbins.tsv"]:

@@ -1,13 +1,14 @@
 #!/bin/bash
 # run on the GPU box: one kernel trace that holds the read binning kernels and their two yardsticks (hapmer_scan_kernel without a child
 # over the same bytes as one contig, and over the same reads as separate sequences), each after a warm-up call; then the calls' own event
-# time with the profiler off.  With `e2e` as the second argument: the tool's end-to-end run on all the reads instead.
+# time with the profiler off.  With `e2e` as the second argument: the tool's end-to-end run on all the reads instead; what follows it
+# (`--reader device`) is passed on to the tool.
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=${1:-prof_readbins_out}      # where the traces and logs go (what is kept of a run is copied to profiles/, see its README)
 mkdir -p $OUT
 if [ "$2" = "e2e" ]; then
-    timeout -k 10 1000 python3 tools/prof_readbins.py e2e > $OUT/e2e.log 2> $OUT/e2e.err
+    timeout -k 10 1000 python3 tools/prof_readbins.py e2e "${@:3}" > $OUT/e2e.log 2> $OUT/e2e.err
     rc=$?
     tail -n 5 $OUT/e2e.err; tail -n 2 $OUT/e2e.log
     exit $rc
