@@ -466,6 +466,47 @@ int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text
 int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat,
                            uint8_t *out_seq /* may be NULL */);
 
+/* A gzip text session: ONE .gz read file inflated on the GPU (the device inflater of the counting path) whose text goes to the read-text
+ * path inside HBM.  The session belongs to `mat`: its device and stream, its workspace; no counting call may run on `mat` while a session
+ * is open, and a session is closed before its table.  The environment hooks of the device inflater (JASPER_INGEST_GZ_DEVICE_CHUNK,
+ * _SLAB_MB, _FALSE_STARTS) hold.  open is JASPER_ERR with a message when the file is not for the device inflater -- not a regular file, no
+ * valid gzip header, no device memory -- and the caller reads it the ordinary way.
+ * bins: one chunk.  Its text is the unused tail of the call before (n - used bytes, kept in a buffer of the session's) and up to `want`
+ * more inflated bytes; then everything is what the read-text call does with that text, eof = 1 when the inflater has ended, and the
+ * results are fetched with the read-text fetch.
+ *   format     in / out: 0 = decide from the text's first byte ('@' FASTQ, '>' FASTA), 1 = FASTQ, 2 = FASTA.  A first byte that is neither
+ *              gives status 2 (no format): nothing is parsed, format stays 0
+ *   status     0 clean, 1 malformed (as the read-text call has it; the text stays whole for the next call), 2 no format
+ *   device_seconds (may be NULL) three numbers, HIP events: [0], [1] as the read-text call has them, [2] this call's pull of inflated
+ *              text: events around it, so the inflater's kernels and copies and the host's stitching and waits between them
+ * Limits: the tail and want together stay below 2^31 bytes (more is JASPER_ERR before anything is inflated).  An inflater error (CRC or
+ * length, truncated or damaged data) is JASPER_ERR with a message that names the file, and every later call of the session fails too.
+ * copy: bytes [from, from + len) of the current bins call's text to host memory (a malformed chunk for the host parser; header lines).
+ * The text lies in mat's workspace: copy before any other read-text call on mat.  A session serves bins calls or route calls (below),
+ * not both: the other kind is JASPER_ERR.
+ * stats: the six numbers the last-inflate call reports, for this session. */
+typedef struct jasper_gz_text jasper_gz_text;
+int jasper_gz_text_open(jasper_table *mat, const char *path, jasper_gz_text **out);
+void jasper_gz_text_close(jasper_gz_text *h);
+int jasper_gz_text_bins(jasper_gz_text *h, jasper_table *mat, jasper_table *pat, int64_t want, int *format, uint32_t thre_mat, uint32_t thre_pat, int64_t *n, int *eof,
+                        int64_t *used, int64_t *n_records, int *status, int64_t *bad_record, double *device_seconds /* [3] */);
+int jasper_gz_text_copy(jasper_gz_text *h, int64_t from, int64_t len, uint8_t *dst /* host */);
+int jasper_gz_text_stats(jasper_gz_text *h, uint64_t stats[6]);
+
+/* Routing: a text of n bytes is cut into n_seg segments by bounds[n_seg + 1] (bounds[0] = 0, bounds[n_seg] = n, no value below the one
+ * before it; a segment may be empty), segment i has bin code bins[i] in 0..2.  out0 / out1 / out2 (host, room for n bytes each) get the
+ * segments of bin 0 / 1 / 2 back to back in input order, out_bytes[3] their byte totals: every text byte leaves exactly once.
+ * mismatches = the segments i >= check_from (0 or 1) that hold a byte and whose first byte is not `first`; the bytes are routed all the
+ * same.  device_seconds (may be NULL): the kernels' time, HIP events.  JASPER_ERR for bounds or bin codes that are not as above, n or
+ * n_seg of 2^31 or more, before any kernel runs.
+ * The session's route pulls the next `want` inflated bytes into HBM instead of taking a host text, and returns how many came in `got`;
+ * when got != bounds[n_seg] nothing is routed (JASPER_OK: the file is not the one the bounds were made for).  `t` is the session's table.
+ * device_seconds there: two numbers, [0] the kernels, [1] this call's pull, as the bins call times it. */
+int jasper_route_text(jasper_table *t, const uint8_t *text /* host */, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from,
+                      uint8_t *out0, uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *mismatches, double *device_seconds);
+int jasper_gz_text_route(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from,
+                         uint8_t *out0, uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *device_seconds /* [2] */);
+
 /* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
  * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
  * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.

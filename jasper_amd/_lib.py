@@ -238,6 +238,15 @@ SYMBOLS = {
     "jasper_read_text_bins": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "jasper_read_text_fetch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "jasper_gz_text_open": (C.c_int, [_P, C.c_char_p, C.POINTER(_P)]),
+    "jasper_gz_text_close": (None, [_P]),
+    "jasper_gz_text_bins": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "jasper_gz_text_copy": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "jasper_gz_text_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "jasper_route_text": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "jasper_gz_text_route": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_double)]),
     "jasper_variant_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_variant_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_varscan_num_seqs": (C.c_int, [_P]),

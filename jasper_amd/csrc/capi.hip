@@ -12,6 +12,8 @@
 #include "hapmers.hpp"
 #include "readbins.hpp"
 #include "readtext.hpp"
+#include "readroute.hpp"
+#include "readgz.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
 #include "compound.hpp"
@@ -931,6 +933,50 @@ int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text
 int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat, uint8_t *out_seq) {
     if (!mat) { g_err = "bad argument"; return JASPER_ERR; }
     return read_text_fetch(mat->t, n_records, rec_start, head_end, lens, out_mat, out_pat, out_seq, g_err) ? JASPER_ERR : JASPER_OK;
+}
+// ... from a .gz file inflated on the device (readgz.hip), and the second pass's routing (readroute.hip)
+struct jasper_gz_text {
+    GzText *g = nullptr;
+};
+int jasper_gz_text_open(jasper_table *mat, const char *path, jasper_gz_text **out) {
+    if (!mat || !path || !out) { g_err = "bad argument"; return JASPER_ERR; }
+    *out = nullptr;
+    GzText *g = gz_text_open(mat->t, path, g_err);
+    if (!g) return JASPER_ERR;
+    *out = new jasper_gz_text;
+    (*out)->g = g;
+    return JASPER_OK;
+}
+void jasper_gz_text_close(jasper_gz_text *h) {
+    if (!h) return;
+    delete h->g;
+    delete h;
+}
+int jasper_gz_text_bins(jasper_gz_text *h, jasper_table *mat, jasper_table *pat, int64_t want, int *format, uint32_t thre_mat, uint32_t thre_pat, int64_t *n, int *eof,
+                        int64_t *used, int64_t *n_records, int *status, int64_t *bad_record, double *device_seconds) {
+    if (!h || !mat || !pat) { g_err = "bad argument"; return JASPER_ERR; }
+    return gz_text_bins(*h->g, mat->t, pat->t, want, format, thre_mat, thre_pat, n, eof, used, n_records, status, bad_record, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_gz_text_copy(jasper_gz_text *h, int64_t from, int64_t len, uint8_t *dst) {
+    if (!h) { g_err = "bad argument"; return JASPER_ERR; }
+    return gz_text_copy(*h->g, from, len, dst, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_gz_text_stats(jasper_gz_text *h, uint64_t stats[6]) {
+    if (!h || !stats) { g_err = "bad argument"; return JASPER_ERR; }
+    for (int i = 0; i < GZS_N; ++i) stats[i] = h->g->stats[i];
+    return JASPER_OK;
+}
+int jasper_route_text(jasper_table *t, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
+                      uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *mismatches, double *device_seconds) {
+    if (!t) { g_err = "bad argument"; return JASPER_ERR; }
+    uint8_t *const out[3] = {out0, out1, out2};
+    return route_text_host(t->t, text, n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_gz_text_route(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
+                         uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *device_seconds) {
+    if (!h || !t) { g_err = "bad argument"; return JASPER_ERR; }
+    uint8_t *const out[3] = {out0, out1, out2};
+    return gz_text_route(*h->g, t->t, want, n_seg, bounds, bins, first, check_from, out, out_bytes, got, mismatches, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
 }
 
 // ---- variant scan (variants.hip) ----

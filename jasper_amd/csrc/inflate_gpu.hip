@@ -869,4 +869,32 @@ long DeviceGunzip::read(char *dst, size_t want) {
     return (long)got;
 }
 
+long DeviceGunzip::read_device(uint8_t *d_dst, size_t want) {
+    if (!err.empty()) return -1;
+    if (hipSetDevice(device_) != hipSuccess) { err = "hipSetDevice"; return -1; }
+    size_t got = 0;
+    while (got < want) {
+        if (dev_text_at_ < dev_text_n_) {
+            const size_t m = (size_t)std::min<uint64_t>(want - got, dev_text_n_ - dev_text_at_);
+            const hipError_t e = hipMemcpyAsync(d_dst + got, d_text_ + dev_text_at_, m, hipMemcpyDeviceToDevice, stream_);
+            if (e != hipSuccess) { err = std::string("inflate copy: ") + hipGetErrorString(e); return -1; }
+            dev_text_at_ += m;
+            got += m;
+            continue;
+        }
+        if (host_text_at_ < host_text_.size()) {
+            const size_t m = std::min(want - got, host_text_.size() - host_text_at_);
+            hipError_t e = hipMemcpyAsync(d_dst + got, host_text_.data() + host_text_at_, m, hipMemcpyHostToDevice, stream_);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream_);      // (host_text_ is pageable and is cleared by the next slab)
+            if (e != hipSuccess) { err = std::string("inflate copy: ") + hipGetErrorString(e); return -1; }
+            host_text_at_ += m;
+            got += m;
+            continue;
+        }
+        if (eof_) break;
+        if (!next_slab()) { if (err.empty()) err = "read error in " + path_; return -1; }      // (it waits for the stream: d_text_ is free to be written again)
+    }
+    return (long)got;
+}
+
 }  // namespace jk

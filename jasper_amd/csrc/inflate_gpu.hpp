@@ -50,6 +50,11 @@ class DeviceGunzip {
     // the contract of GzAhead::read: up to `want` bytes of text in order (copied device-to-host straight into dst), 0 at the
     // end, -1 on error (message in err).  Sets its device itself (it may be called from a read-ahead thread).
     long read(char *dst, size_t want);
+    // read's contract with the destination in HBM on the same device: a slab's device text is copied device-to-device on the stream, a
+    // gap the host has filled host-to-device.  The copies are ordered on the stream; what the host copy reads has left when this returns.
+    long read_device(uint8_t *d_dst, size_t want);
+    // nothing is left to hand out: the stream has ended and every byte of its text has been read
+    bool at_end() const { return eof_ && dev_text_at_ >= dev_text_n_ && host_text_at_ >= host_text_.size(); }
     std::string err;
 
   private:

@@ -275,8 +275,9 @@ const char *const RT_WHAT = "read text bins";
 
 }  // namespace
 
-int read_text_bins(Table &M, Table &P, const char *text, int64_t n, int eof, int format, uint32_t thre_mat, uint32_t thre_pat, int64_t *used, int64_t *n_records, int *status,
-                   int64_t *bad_record, double *seconds, std::string &err) {
+// what both entries refuse, and the state they start from
+int read_text_check(Table &M, Table &P, int64_t n, int format, uint32_t thre_mat, uint32_t thre_pat, int64_t *used, int64_t *n_records, int *status, int64_t *bad_record,
+                    double *seconds, std::string &err) {
     const std::string w(RT_WHAT);
     if (!used || !n_records || !status || !bad_record) { err = w + ": bad arguments"; return -1; }
     *used = *n_records = 0;
@@ -287,18 +288,36 @@ int read_text_bins(Table &M, Table &P, const char *text, int64_t n, int eof, int
     if (check_trio(RT_WHAT, M, P, nullptr, nullptr, thre_mat, thre_pat, 1, err)) return -1;
     if (n < 0 || (format != RT_FASTQ && format != RT_FASTA)) { err = w + ": bad arguments"; return -1; }
     if (n > RT_MAX_TEXT) { err = w + ": more than 2^31-1 text bytes in one call"; return -1; }      // (before the text is looked at)
-    if (n > 0 && !text) { err = w + ": null text"; return -1; }
+    return 0;
+}
+
+int read_text_bins(Table &M, Table &P, const char *text, int64_t n, int eof, int format, uint32_t thre_mat, uint32_t thre_pat, int64_t *used, int64_t *n_records, int *status,
+                   int64_t *bad_record, double *seconds, std::string &err) {
+    if (read_text_check(M, P, n, format, thre_mat, thre_pat, used, n_records, status, bad_record, seconds, err)) return -1;
+    if (n > 0 && !text) { err = std::string(RT_WHAT) + ": null text"; return -1; }
+    if (n > 0) {
+        HIPCHK(hipSetDevice(M.device));
+        uint8_t *d_text = (uint8_t *)M.workspace(Table::WS_READTEXT, (size_t)n + RT_PAD, err);
+        if (!d_text) return -1;
+        HIPCHK(hipMemcpyAsync(d_text, text, (size_t)n, hipMemcpyHostToDevice, M.stream));
+    }
+    return read_text_core(M, P, n, eof, format, n > 0 && text[n - 1] == '\n' ? 1 : 0, thre_mat, thre_pat, used, n_records, status, bad_record, seconds, err);
+}
+
+int read_text_core(Table &M, Table &P, int64_t n, int eof, int format, int last_is_lf, uint32_t thre_mat, uint32_t thre_pat, int64_t *used, int64_t *n_records, int *status,
+                   int64_t *bad_record, double *seconds, std::string &err) {
+    const std::string w(RT_WHAT);
+    if (n < 0 || n > RT_MAX_TEXT || (format != RT_FASTQ && format != RT_FASTA)) { err = w + ": bad arguments"; return -1; }      // (read_text_check is the caller's)
     auto nothing = [&]() { M.text_records = 0; M.text_seq_bytes = 0; M.text_used = 0; return 0; };
     if (n == 0) return nothing();
     HIPCHK(hipSetDevice(M.device));
     hipStream_t st = M.stream;
     const uint64_t un = (uint64_t)n, nblk = rt_blocks(un);
     const int W = Table::WS_READTEXT;
-    uint8_t *d_text = (uint8_t *)M.workspace(W, (size_t)un + RT_PAD, err);
+    uint8_t *d_text = (uint8_t *)M.workspace(W, (size_t)un + RT_PAD, err);      // (the caller's: large enough, so the same buffer)
     uint64_t *d_blk = (uint64_t *)M.workspace(W + 1, (size_t)(nblk + 1) * sizeof(uint64_t), err);
     unsigned long long *d_ctl = (unsigned long long *)M.workspace(W + 9, RTC_WORDS * sizeof(unsigned long long), err);
     if (!d_text || !d_blk || !d_ctl) return -1;
-    HIPCHK(hipMemcpyAsync(d_text, text, (size_t)un, hipMemcpyHostToDevice, st));
     Events ev_a, ev_b, ev_c;                            // index + pack is timed in three stretches: the host sizes buffers in between
     if (ev_a.create(err) || ev_b.create(err) || ev_c.create(err)) return -1;
     double index_seconds = 0;
@@ -312,9 +331,11 @@ int read_text_bins(Table &M, Table &P, const char *text, int64_t n, int eof, int
     HIPCHK(hipEventRecord(ev_a.e[1], st));
     uint64_t n_lf = 0;
     HIPCHK(hipMemcpyAsync(&n_lf, d_blk + nblk, sizeof n_lf, hipMemcpyDeviceToHost, st));
+    uint8_t last_byte = 0;
+    if (last_is_lf < 0) HIPCHK(hipMemcpyAsync(&last_byte, d_text + un - 1, 1, hipMemcpyDeviceToHost, st));
     HIPCHK(jk_stream_wait(st));
     if (ev_a.add_seconds(index_seconds, err)) return -1;
-    const TextLines T = text_lines(format, eof != 0, un, n_lf, text[un - 1] == '\n');
+    const TextLines T = text_lines(format, eof != 0, un, n_lf, last_is_lf < 0 ? last_byte == '\n' : last_is_lf != 0);
     if (T.ends_inside) {                                // (the host parser's first verdict, before any record is looked at)
         *status = RT_MALFORMED;
         *n_records = *bad_record = (int64_t)T.fastq_records;
@@ -404,6 +425,19 @@ int read_text_bins(Table &M, Table &P, const char *text, int64_t n, int eof, int
     M.text_records = n_rec;
     M.text_seq_bytes = L;
     M.text_used = (int64_t)tail[0];
+    return 0;
+}
+
+int rt_scan_words(hipStream_t st, const uint64_t *d_in, uint64_t n, uint64_t *d_blk, uint64_t *d_out, std::string &err) {
+    const uint64_t nb = rt_blocks(n);
+    if (nb) {
+        hipLaunchKernelGGL(rt_scan_reduce_kernel, dim3((unsigned)nb), dim3(RT_THREADS), 0, st, d_in, n, d_blk);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(rt_scan_tops_kernel, dim3(1), dim3(RT_SCAN_PASS), 0, st, d_blk, nb);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(rt_scan_apply_kernel, dim3((unsigned)rt_blocks(n + 1)), dim3(RT_THREADS), 0, st, d_in, n, d_blk, d_out);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

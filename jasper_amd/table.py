@@ -5,6 +5,7 @@ module `dna_jellyfish` (JF::swig/mer_file.i, JF::swig/mer_dna.i).  All compute h
 nothing here falls back to the CPU.
 """
 import ctypes as C
+import os
 
 from . import _lib
 from ._lib import FixRec, check
@@ -251,6 +252,112 @@ class ReadText:
         self.used, self.n_records, self.malformed, self.bad_record = used, n_records, malformed, bad_record
         self.seconds, self.index_seconds = seconds, index_seconds
         self.rec_start = self.head_end = self.lens = self.mat = self.pat = self.seq = None
+        self.no_format, self.inflate_seconds = False, 0.0      # (a gz session's: GzText.bins)
+
+
+GZ_TEXT_FORMATS = {None: 0, "fastq": 1, "fasta": 2}
+GZ_STATS = ("decoders", "accepted", "device_bytes", "host_bytes", "slabs", "members")
+
+
+class RoutedText:
+    """a block of text routed on the GPU (include/jasper_hip.h: jasper_route_text): `out` = three np.uint8 arrays, the bytes of bin 0, 1
+    and 2 in input order (views of the buffers handed in, or of fresh ones), `mismatches` = segments that do not begin with the expected
+    byte, `seconds` = device time of the kernels; from a gz session `got` = inflated bytes pulled (nothing is routed when that is not
+    bounds[-1]: `routed` False) and `inflate_seconds`."""
+
+    def __init__(self, out, mismatches, seconds, got=None, routed=True, inflate_seconds=0.0):
+        self.out, self.mismatches, self.seconds, self.got, self.routed, self.inflate_seconds = out, mismatches, seconds, got, routed, inflate_seconds
+
+
+def _route_args(bounds, bins, first, check_from, room, out):
+    import numpy as np
+    bounds = np.ascontiguousarray(bounds, dtype=np.int64)
+    bins = np.ascontiguousarray(bins, dtype=np.uint8)
+    if bounds.ndim != 1 or bins.ndim != 1 or len(bounds) != len(bins) + 1:
+        raise ValueError("route: bounds must hold one value more than bins")
+    if isinstance(first, (bytes, str)):
+        first = ord(first) if len(first) else 0         # (an empty file has no records and no first byte: nothing is compared)
+    if out is None:
+        out = [np.empty(max(room, 1), dtype=np.uint8) for _ in range(3)]
+    if len(out) != 3 or any(o.dtype != np.uint8 or o.ndim != 1 or not o.flags.c_contiguous or len(o) < room for o in out):
+        raise ValueError("route: out must be three contiguous np.uint8 arrays with room for the text")
+    return bounds, bins, int(first), int(check_from), out
+
+
+class GzText:
+    """a .gz read file inflated on the GPU, its text handed to the read-text path inside HBM (include/jasper_hip.h: jasper_gz_text_open).
+    Made by KmerTable.gz_text(path); a context manager.  `n` = bytes of the current call's text, `eof` = the inflater has ended."""
+
+    def __init__(self, table, path):
+        self._t, self._L, self.path = table, table._L, path
+        h = C.c_void_p()
+        check(self._L.jasper_gz_text_open(table._h, os.fsencode(path), C.byref(h)))
+        self._g = h
+        self.n, self.eof, self.fmt, self.inflate_seconds = 0, False, None, 0.0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._g is not None:
+            self._L.jasper_gz_text_close(self._g)
+            self._g = None
+
+    def _handle(self):
+        if self._g is None:
+            raise ValueError("gz_text: the session is closed")
+        return self._g
+
+    def bins(self, pat, want, fmt, thre_mat, thre_pat):
+        """one chunk: the tail the call before left unused, then up to `want` more inflated bytes -> ReadText (no_format: the first byte
+        is neither @ nor >).  fmt: None on the first call (the first byte decides; self.fmt says what), then "fastq" / "fasta" """
+        import numpy as np
+        if fmt not in GZ_TEXT_FORMATS:
+            raise ValueError("gz_text: fmt must be None, 'fastq' or 'fasta'")
+        ph = KmerTable._parent_handle(pat, "paternal", "gz_text")
+        used, nrec, bad, n = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        status, eof, f, secs = C.c_int(0), C.c_int(0), C.c_int(GZ_TEXT_FORMATS[fmt]), (C.c_double * 3)()
+        check(self._L.jasper_gz_text_bins(self._handle(), self._t._h, ph, int(want), C.byref(f), _thre32(thre_mat), _thre32(thre_pat), C.byref(n), C.byref(eof), C.byref(used),
+                                          C.byref(nrec), C.byref(status), C.byref(bad), secs))
+        self.n, self.eof, self.fmt = n.value, bool(eof.value), {0: None, 1: "fastq", 2: "fasta"}[f.value]
+        self.inflate_seconds += secs[2]
+        r = ReadText(used.value, nrec.value, status.value == 1, bad.value, secs[1], secs[0])
+        r.no_format, r.inflate_seconds = status.value == 2, secs[2]
+        if r.malformed or r.no_format:
+            return r
+        nr = r.n_records
+        r.rec_start, r.head_end, r.lens = np.zeros(nr + 1, dtype=np.int64), np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
+        r.mat, r.pat = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+        check(self._L.jasper_read_text_fetch(self._t._h, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), None))
+        return r
+
+    def text(self, start, length):
+        """bytes [start, start + length) of the current call's text -> np.uint8"""
+        import numpy as np
+        out = np.empty(int(length), dtype=np.uint8)
+        check(self._L.jasper_gz_text_copy(self._handle(), int(start), int(length), C.c_void_p(out.ctypes.data) if out.size else None))
+        return out
+
+    def stats(self):
+        """decoders, accepted, device_bytes, host_bytes, slabs, members: as KmerTable.last_inflate"""
+        st = (C.c_uint64 * 6)()
+        check(self._L.jasper_gz_text_stats(self._handle(), st))
+        return dict(zip(GZ_STATS, (int(v) for v in st)))
+
+    def route(self, want, bounds, bins, first, check_from=0, out=None):
+        """the next `want` inflated bytes routed as KmerTable.route_text routes a host text -> RoutedText with `got`"""
+        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, int(bounds[-1]) if len(bounds) else 0, out)
+        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+        nb, got, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(0), (C.c_double * 2)()
+        check(self._L.jasper_gz_text_route(self._handle(), self._t._h, int(want), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
+                                           vp(out[1]), vp(out[2]), nb, C.byref(got), C.byref(bad), secs))
+        self.inflate_seconds += secs[1]
+        routed = got.value == int(bounds[-1])
+        return RoutedText([o[:nb[b]] for b, o in enumerate(out)] if routed else None, bad.value, secs[0], got.value, routed, secs[1])
 
 
 VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
@@ -1157,6 +1264,25 @@ class KmerTable:
             r.seq = np.zeros(int(r.lens.sum()), dtype=np.uint8)
             check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), vp(r.seq) if r.seq.size else None))
         return r
+
+    def gz_text(self, path):
+        """a gzip text session on this table (the maternal one of the binning calls): the .gz file inflated on the GPU -> GzText.  Raises
+        when the file is not for the device inflater (no gzip header, not a regular file): the caller reads it the ordinary way"""
+        return GzText(self, path)
+
+    def route_text(self, text, bounds, bins, first, check_from=0, out=None):
+        """text (bytes or np.uint8) cut by bounds[n_seg + 1] into segments with bin codes bins[n_seg] (0..2) -> RoutedText: each bin's
+        segments back to back, and the segments i >= check_from that hold a byte and do not begin with `first`"""
+        import numpy as np
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text
+        if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
+            raise TypeError("route_text: the text must be bytes or a contiguous one-dimensional np.uint8 array")
+        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, len(buf), out)
+        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+        nb, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_double(0)
+        check(self._L.jasper_route_text(self._h, vp(buf) if buf.size else None, len(buf), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
+                                        vp(out[1]), vp(out[2]), nb, C.byref(bad), C.byref(secs)))
+        return RoutedText([o[:nb[b]] for b, o in enumerate(out)], bad.value, secs.value)
 
     # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
     def variant_scan(self, seqs, thre):

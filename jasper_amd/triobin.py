@@ -2,7 +2,7 @@
 
     python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
                                  [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
-                                 [--batch-bases N] [--reader host|device] [-o PREFIX] [--device D]
+                                 [--batch-bases N] [--reader host|device] [--gz host|device] [--route host|device] [-o PREFIX] [--device D]
 
 An extension (the reference has no such tool), and the cure for what `--hapmers` only shows: a polisher that repairs toward the reads'
 solid k-mers can move a het site of a phased assembly onto the other haplotype, which hapmers.tsv lists as switches in its `after` row.
@@ -31,6 +31,19 @@ and bins them; only the per-record arrays come back.  Every output file is byte 
 there (a batch is a chunk).  A chunk the GPU calls malformed is parsed once more by the host parser, which words the message.
 --write-reads then routes the second pass's bytes by the record starts the first pass has kept (8 bytes a record) instead of parsing
 again.  JASPER_TRIOBIN_CHUNK=<bytes> overrides DEVICE_CHUNK.  The default is host.
+
+--gz device (with --reader device) inflates a file whose name ends in .gz on the GPU as well: KmerTable.gz_text opens a session of the
+device inflater on the maternal table, and each chunk -- the tail carried over, then DEVICE_CHUNK more inflated bytes -- goes from the
+inflater to the parser inside HBM.  The text comes back only with --per-read (the names), and only as far as the records reach; a
+malformed chunk comes back whole for the host parser's message.  A file the device inflater refuses (no gzip header, not a regular file)
+is read through gzip.open, and JASPER_AMD_TIMING=1 says so.  A CRC or length error, a truncated or a damaged stream end the run with exit
+status 1 and a message that names the file.  Plain files go the way they go without the flag.  The default is host.
+
+--route device (with --reader device --write-reads) does the second pass's routing on the GPU: a block's record bounds and bin codes,
+computed from the kept starts as before, go to KmerTable.route_text with the block's bytes (a plain file, or a .gz one under --gz host)
+or to the session's route (a .gz file under --gz device: the bytes are inflated into HBM and never visit the host unrouted); three
+buffers come back and are written to the three files.  The file has changed between the passes when a block comes short, bytes are left
+over, or a record's first byte is no longer the records' first byte.  The default is host.
 
 The rule.  A template's m and p are its read's counts; with --paired they are the sums over its two mates.
 
@@ -70,7 +83,7 @@ from .report import write_atomic
 
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
          "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--batch-bases N (no effect with --reader device)] [--reader host|device] "
-         "[-o PREFIX] [--device D]")
+         "[--gz host|device (needs --reader device)] [--route host|device (needs --reader device --write-reads)] [-o PREFIX] [--device D]")
 BINS = ("mat", "pat", "unknown")
 MAT, PAT, UNKNOWN = 0, 1, 2
 BATCH_BASES_DEFAULT = 256 << 20
@@ -82,7 +95,7 @@ READERS = ("host", "device")
 BOOL_FLAGS = ("--paired", "--per-read", "--write-reads")
 VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
                "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases",
-               "--reader": "reader"}
+               "--reader": "reader", "--gz": "gz", "--route": "route"}
 
 
 class Malformed(Exception):
@@ -90,6 +103,13 @@ class Malformed(Exception):
 
     def __init__(self, path, record, what):
         Exception.__init__(self, "%s: record %d is malformed: %s" % (path, record, what))
+
+
+class Inflate(Exception):
+    """a .gz file the device inflater cannot read to its end: (file, what the inflater says)"""
+
+    def __init__(self, path, what):
+        Exception.__init__(self, "%s: the gzip stream cannot be inflated: %s" % (path, what))
 
 
 # what a file's reader hands on at a time: `buf` (np.uint8) holds whole records, record i is buf[rec_start[i]:rec_end[i]] and its header
@@ -289,13 +309,60 @@ class _DeviceReader:
     """--reader device: a file's bytes go to the GPU as they stand, count_text(buf, eof, fmt) -> table.ReadText parses, packs and counts
     them there.  chunks(path) yields what the host reader's chunks() yields, without the sequences; the counts come back in input order in
     self.m / self.p as _Batcher has them.  With keep_starts, self.starts[path] = (the records' first byte, their absolute starts in the
-    decompressed file, its length): what the second pass of --write-reads routes by."""
+    decompressed file, its length): what the second pass of --write-reads routes by.
+    --gz device: gz_open(path) -> a gzip text session (table.GzText with the parents bound: bins(want, fmt)) or an exception for a file
+    the device inflater refuses; a .gz file's chunks then come from the session, and the text is fetched only for the names (per_read)."""
 
-    def __init__(self, count_text, keep_starts):
-        self.count_text, self.keep_starts = count_text, keep_starts
+    def __init__(self, count_text, keep_starts, gz_open=None, per_read=False):
+        self.count_text, self.keep_starts, self.gz_open, self.per_read = count_text, keep_starts, gz_open, per_read
         self.m, self.p, self.seconds, self.starts = [], [], 0.0, {}
+        self.inflate_seconds, self.gz_stats = 0.0, []       # the sessions' summed pull seconds (HIP events around each pull), (path, stats) per session
 
     def chunks(self, path):
+        sess = open_session(self.gz_open, path)
+        return self._gz_chunks(path, sess) if sess is not None else self._host_chunks(path)
+
+    def _gz_chunks(self, path, sess):
+        import numpy as np
+        want = device_chunk()
+        fmt, first, nrec, base, have, starts = None, b"", 0, 0, 0, []
+        try:
+            while True:
+                try:
+                    r = sess.bins(want, fmt)
+                except RuntimeError as e:
+                    raise Inflate(path, str(e))
+                n, eof = sess.n, sess.eof
+                if not n:
+                    break
+                if r.no_format:
+                    raise Malformed(path, 0, "the file begins with neither @ (FASTQ) nor > (FASTA)")
+                if fmt is None:
+                    fmt = sess.fmt
+                    first = b"@" if fmt == "fastq" else b">"
+                if r.malformed:                         # the host parser words the message: the same (buf, eof) raises there
+                    (_fastq_chunk if fmt == "fastq" else _fasta_chunk)(sess.text(0, n), eof, path, nrec, False)
+                    raise RuntimeError("%s: the device reader calls record %d malformed and the host parser does not" % (path, nrec + r.bad_record))
+                self.seconds += r.seconds
+                if r.n_records:
+                    nrec += r.n_records
+                    self.m.append(r.mat)
+                    self.p.append(r.pat)
+                    if self.keep_starts:
+                        starts.append(r.rec_start[:-1] + base)
+                    yield Chunk(sess.text(0, r.used) if self.per_read else None, r.rec_start[:-1], r.rec_start[1:], r.head_end, None, r.lens)
+                have = n - r.used
+                base += r.used
+                if eof:
+                    break
+        finally:
+            self.inflate_seconds += sess.inflate_seconds
+            self.gz_stats.append((path, sess.stats()))
+            sess.close()
+        if self.keep_starts:
+            self.starts[path] = (first, np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64), base + have)
+
+    def _host_chunks(self, path):
         import numpy as np
         size = device_chunk()
         fmt, first, nrec, base, starts = None, b"", 0, 0, []
@@ -337,14 +404,43 @@ class _DeviceReader:
             self.starts[path] = (first, np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64), base + have)
 
 
+def open_session(gz_open, path):
+    """--gz device: the gzip text session of a .gz file, or None -- no gz_open, a plain file, or a file the device inflater refuses, which
+    is then read through gzip.open (JASPER_AMD_TIMING=1 says so)"""
+    if gz_open is None or not path.endswith(".gz"):
+        return None
+    try:
+        return gz_open(path)
+    except RuntimeError as e:
+        extensions.device_line("[triobin] gz %s: not for the device inflater, read through gzip.open (%s)" % (path, e))
+        return None
+
+
+def block_segments(starts, at, end):
+    """the second pass's block [at, end) of a file whose records begin at `starts` (starts[0] == 0, increasing) -> (i0, i1, bounds,
+    check_from): records i0 .. i1 - 1 have bytes in the block, bounds[i1 - i0 + 1] cut the block into their parts (bounds[0] = 0,
+    bounds[-1] = end - at), and check_from is 1 when the first part is the clipped rest of a record, which has no first byte to check"""
+    import numpy as np
+    i0 = int(np.searchsorted(starts, at, side="right")) - 1       # the record the block's first byte lies in
+    i1 = int(np.searchsorted(starts, end, side="left"))
+    bounds = np.empty(i1 - i0 + 1, dtype=np.int64)
+    bounds[0] = 0
+    bounds[1:-1] = starts[i0 + 1:i1] - at
+    bounds[-1] = end - at
+    return i0, i1, bounds, 0 if starts[i0] == at else 1
+
+
 def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT, reader="host",
-              count_text=None):
+              count_text=None, gz_open=None, route_text=None, timings=None):
     """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
     cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds.  reader "device": the files'
-    bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called"""
+    bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called.  gz_open: --gz device (_DeviceReader);
+    route_text: --route device, route_text(buf, bounds, bins, first, check_from, out) -> table.RoutedText.  timings (a dict) gets what
+    JASPER_AMD_TIMING=1 prints of the two"""
     import numpy as np
     bat = _Batcher(batch_bases, count)
-    dev = _DeviceReader(count_text, write_reads) if reader == "device" else None
+    dev = _DeviceReader(count_text, write_reads, gz_open, per_read) if reader == "device" else None
+    timings = {} if timings is None else timings
     nrec, lens, names = [], [], []
     try:
         for fi, path in enumerate(paths):
@@ -362,8 +458,11 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
             if paired and fi % 2 == 1 and nrec[fi] != nrec[fi - 1]:
                 cli.error_exit("--paired: %s has %d records and %s has %d; the files of a pair must hold the same templates" % (paths[fi - 1], nrec[fi - 1], path, nrec[fi]))
         bat.flush()
-    except Malformed as e:
+    except (Malformed, Inflate) as e:
         cli.error_exit(str(e))
+    finally:
+        if dev:
+            timings.update(inflate_seconds=dev.inflate_seconds, gz_stats=dev.gz_stats)
     if dev:
         bat.m, bat.p, bat.seconds = dev.m, dev.p, dev.seconds
     cuts = np.cumsum(nrec)[:-1]
@@ -390,7 +489,7 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
     made = []
     try:
         if write_reads and dev:
-            _write_reads_by_starts(paths, prefix, bins, made, dev.starts)
+            _write_reads_by_starts(paths, prefix, bins, made, dev.starts, route_text, gz_open, timings)
         elif write_reads:
             _write_reads(paths, prefix, bins, nrec, made)
         write_atomic(prefix + ".readbins.tsv", text)
@@ -437,43 +536,79 @@ def _write_reads(paths, prefix, bins, nrec, made):
                 f.close()
 
 
-def _write_reads_by_starts(paths, prefix, bins, made, kept):
+def _write_reads_by_starts(paths, prefix, bins, made, kept, route_text=None, gz_open=None, timings=None):
     """the second pass of the device reader: nothing is parsed again, a block's bytes are routed by the record starts the first pass has
-    kept.  The file has changed when its decompressed length differs or a remembered start does not hold the records' first byte"""
+    kept.  The file has changed when its decompressed length differs or a remembered start does not hold the records' first byte.
+    route_text (--route device) routes a block on the GPU instead of with three boolean masks; gz_open then inflates a .gz file there too"""
     import numpy as np
+    import time
+    t0 = time.perf_counter()
+    route_seconds, inflate_seconds, gz_stats = 0.0, 0.0, []
+    out = [np.empty(CHUNK, dtype=np.uint8) for _ in range(3)] if route_text else None
     for fi, path in enumerate(paths):
         outs = ["%s.%s.%s" % (prefix, b, out_basename(path)) for b in BINS]
         made += outs
         files = [open(fn + ".tmp", "wb") for fn in outs]
         first, starts, length = kept[path]
+        sess = open_session(gz_open, path) if route_text else None
         try:
             at = 0
-            with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
-                while at >= 0:
-                    block = f.read(CHUNK)
-                    if not block:
-                        break
-                    buf = np.frombuffer(block, dtype=np.uint8)
-                    end = at + len(buf)
-                    if end > length:
+            if sess is not None:
+                try:
+                    while 0 <= at < length:
+                        end = min(at + CHUNK, length)
+                        i0, i1, bounds, check_from = block_segments(starts, at, end)
+                        r = sess.route(end - at, bounds, bins[fi][i0:i1], first, check_from, out)
+                        route_seconds += r.seconds
+                        if not r.routed or r.mismatches:
+                            at = -1
+                            break
+                        for b in range(3):
+                            r.out[b].tofile(files[b])
+                        at = end
+                    if at == length and sess.route(1, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint8), first, 0, out).got:      # (bytes are left over)
                         at = -1
-                        break
-                    i0 = int(np.searchsorted(starts, at, side="right")) - 1      # the record the block's first byte lies in (starts[0] == 0)
-                    i1 = int(np.searchsorted(starts, end, side="left"))          # records i0 .. i1 - 1 have bytes in the block
-                    begins = starts[i0:i1] - at
-                    begins = begins[begins >= 0]
-                    if not (buf[begins] == first[0]).all():
-                        at = -1
-                        break
-                    size = np.diff(np.concatenate(([0], starts[i0 + 1:i1] - at, [len(buf)])))
-                    for b in range(3):
-                        buf[np.repeat(bins[fi][i0:i1] == b, size)].tofile(files[b])
-                    at = end
+                except RuntimeError as e:
+                    cli.error_exit(str(Inflate(path, str(e))))
+            else:
+                with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+                    while at >= 0:
+                        block = f.read(CHUNK)
+                        if not block:
+                            break
+                        buf = np.frombuffer(block, dtype=np.uint8)
+                        end = at + len(buf)
+                        if end > length:
+                            at = -1
+                            break
+                        i0, i1, bounds, check_from = block_segments(starts, at, end)
+                        if route_text:
+                            r = route_text(buf, bounds, bins[fi][i0:i1], first, check_from, out)
+                            route_seconds += r.seconds
+                            if r.mismatches:
+                                at = -1
+                                break
+                            for b in range(3):
+                                r.out[b].tofile(files[b])
+                        else:
+                            if not (buf[bounds[check_from:-1]] == first[0]).all():
+                                at = -1
+                                break
+                            size = np.diff(bounds)
+                            for b in range(3):
+                                buf[np.repeat(bins[fi][i0:i1] == b, size)].tofile(files[b])
+                        at = end
             if at != length:
                 cli.error_exit("--write-reads: %s changed between the two passes" % path)
         finally:
+            if sess is not None:
+                inflate_seconds += sess.inflate_seconds
+                gz_stats.append((path, sess.stats()))
+                sess.close()
             for f in files:
                 f.close()
+    if timings is not None:
+        timings.update(route_seconds=route_seconds, route_inflate_seconds=inflate_seconds, route_gz_stats=gz_stats, second_pass_wall=time.perf_counter() - t0)
 
 
 def parse_args(argv):
@@ -536,6 +671,21 @@ def check_reader(a):
     return reader
 
 
+def check_gz_route(a, reader):
+    """--gz and --route: refused before a parent is opened -> (gz, route)"""
+    gz = a["gz"] if a["gz"] is not None else "host"
+    route = a["route"] if a["route"] is not None else "host"
+    if gz not in READERS:
+        cli.error_exit("--gz takes host or device; %s was given" % gz)
+    if route not in READERS:
+        cli.error_exit("--route takes host or device; %s was given" % route)
+    if gz == "device" and reader != "device":
+        cli.error_exit("--gz device needs --reader device: the inflated text goes to the device reader inside the GPU's memory")
+    if route == "device" and not (reader == "device" and a["write_reads"]):
+        cli.error_exit("--route device needs --reader device --write-reads: it routes the second pass by the record starts the device reader keeps")
+    return gz, route
+
+
 def check_totals(m_total, p_total):
     """a parent without a single hap-mer ends the run: the rule has nothing to weigh"""
     if m_total == 0 or p_total == 0:
@@ -543,10 +693,45 @@ def check_totals(m_total, p_total):
             "parents have" if m_total == p_total else "mother has" if m_total == 0 else "father has"))
 
 
+class _Session:
+    """a table.GzText with the father's table and the thresholds bound: what _DeviceReader and the second pass drive.  note(r) sees every
+    chunk's ReadText (the run's sums of index + pack seconds and text bytes)"""
+
+    def __init__(self, g, pat, thre_mat, thre_pat, note):
+        self.g, self.pat, self.thre_mat, self.thre_pat, self.note = g, pat, thre_mat, thre_pat, note
+        self.text, self.stats, self.route, self.close = g.text, g.stats, g.route, g.close
+
+    n = property(lambda self: self.g.n)
+    eof = property(lambda self: self.g.eof)
+    fmt = property(lambda self: self.g.fmt)
+    inflate_seconds = property(lambda self: self.g.inflate_seconds)
+
+    def bins(self, want, fmt):
+        r = self.g.bins(self.pat, want, fmt, self.thre_mat, self.thre_pat)
+        self.note(r)
+        return r
+
+
+def timing_lines(t, gz, route):
+    """JASPER_AMD_TIMING=1: what --gz device and --route device add"""
+    stat = lambda st: " ".join("%s=%d" % kv for kv in st.items())      # noqa: E731
+    if gz == "device":
+        extensions.device_line("[triobin] gz inflate seconds by events: %.6f (first pass; the inflater's kernels and copies and the host's stitching between them)" % t.get("inflate_seconds", 0.0))
+        for path, st in t.get("gz_stats", []):
+            extensions.device_line("[triobin] gz stats %s: %s" % (path, stat(st)))
+    if "second_pass_wall" in t:
+        extensions.device_line("[triobin] second pass wall seconds: %.6f" % t["second_pass_wall"])
+    if route == "device" and "route_seconds" in t:
+        extensions.device_line("[triobin] route kernels device seconds: %.6f; gz inflate seconds by events: %.6f (second pass)" % (t["route_seconds"], t["route_inflate_seconds"]))
+        for path, st in t["route_gz_stats"]:
+            extensions.device_line("[triobin] gz stats %s (second pass): %s" % (path, stat(st)))
+
+
 def run(argv):
     from .table import KmerTable
     a = parse_args(argv)
     reader = check_reader(a)
+    gz, route = check_gz_route(a, reader)
     reads, k, device, hap, min_markers, batch_bases = check_flags(a)
     prefix = a["prefix"] if a["prefix"] is not None else reads[0]
     mat, pat, tm, tp = extensions.open_parents(hap, k, device)
@@ -569,8 +754,23 @@ def run(argv):
             text_bytes.append(r.used)
             return r
 
-        per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
-                                     count_text=count_text)
+        def noted(r):
+            index_seconds[0] += r.index_seconds
+            text_bytes.append(r.used)
+
+        def gz_open(path):
+            return _Session(mat.gz_text(path), pat, tm, tp, noted)
+
+        def route_text(buf, bounds, codes, first, check_from, out):
+            return mat.route_text(buf, bounds, codes, first, check_from, out)
+
+        timings = {}
+        try:
+            per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
+                                         count_text=count_text, gz_open=gz_open if gz == "device" else None, route_text=route_text if route == "device" else None,
+                                         timings=timings)
+        finally:
+            timing_lines(timings, gz, route)
     finally:
         mat.close()
         pat.close()

@@ -86,6 +86,8 @@ def main():
     head = {"mode": mode, "k": bench.K, "reads": nreads, "thr_mat": tm, "thr_pat": tp, "m_slots": m.info()["slots"], "m_distinct": m.info()["distinct"]}
     if mode == "e2e":
         return e2e(torch, reads, nreads, m, p, tm, tp, head)
+    if mode == "gz":
+        return gz_e2e(torch, reads, nreads, m, p, tm, tp, head)
     n = min(nreads, BATCH_BASES // rl)
     text = reads.view(-1, rl + 1)[:n, :rl].contiguous()      # the batch, packed: no separator bytes
     del reads
@@ -156,6 +158,137 @@ def e2e(torch, reads, nreads, m, p, tm, tp, head):
                  "returncode": r.returncode, "tool_wall_seconds": wall, "reader_alone_seconds": reader, "kernel_device_seconds": float(dev_secs.group(1)) if dev_secs else None,
                  "file_bytes": os.path.getsize(paths["child.fq"]), "table": open(paths["out"] + ".readbins.tsv").read() if r.returncode == 0 else None})
     print(json.dumps(head))
+    for fn in list(paths.values()) + [paths["out"] + ".readbins.tsv"]:
+        if os.path.exists(fn):
+            os.remove(fn)
+
+
+def _deflate_piece(args):
+    import zlib
+    data, last = args
+    co = zlib.compressobj(6, zlib.DEFLATED, -15)
+    return co.compress(data) + co.flush(zlib.Z_FINISH if last else zlib.Z_FULL_FLUSH)
+
+
+def write_gz(path, buf, procs=16):
+    """buf (np.uint8) as ONE gzip member at level 6; the pieces are deflated side by side and joined at full flushes, as pigz joins them"""
+    import struct
+    from multiprocessing.pool import ThreadPool         # (zlib releases the interpreter lock: threads deflate side by side, and nothing is forked beside the GPU runtime)
+    import zlib
+    step = -(-len(buf) // (4 * procs))
+    pieces = [(buf[i:i + step].tobytes(), i + step >= len(buf)) for i in range(0, len(buf), step)]
+    with ThreadPool(procs) as pool, open(path, "wb") as f:
+        f.write(b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03")
+        for part in pool.imap(_deflate_piece, pieces):
+            f.write(part)
+        f.write(struct.pack("<II", zlib.crc32(buf), len(buf) & 0xFFFFFFFF))
+
+
+def route_block(torch, m, text, rec_len, head):
+    """the route kernels on one 64 MiB block of the file's text: medians of five after a warm-up, next to a device-to-device copy of the
+    same bytes and to the three numpy mask gathers the host second pass does"""
+    import numpy as np
+    n = 64 << 20
+    buf = text[:n]
+    starts = np.arange(0, n, rec_len, dtype=np.int64)
+    bounds = np.append(starts, n)
+    codes = np.random.default_rng(5).integers(0, 3, len(starts)).astype(np.uint8)
+    out = [np.empty(n, dtype=np.uint8) for _ in range(3)]
+    secs = [m.route_text(buf, bounds, codes, b"@", 0, out).seconds for _ in range(6)][1:]
+    d = torch.frombuffer(bytearray(buf.tobytes()), dtype=torch.uint8).cuda()
+    e = torch.empty_like(d)
+    copies = []
+    for _ in range(6):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        e.copy_(d)
+        b.record()
+        torch.cuda.synchronize()
+        copies.append(a.elapsed_time(b) * 1e-3)
+    host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        size = np.diff(bounds)
+        parts = [buf[np.repeat(codes == b, size)] for b in range(3)]
+        host.append(time.perf_counter() - t0)
+    r = m.route_text(buf, bounds, codes, b"@", 0, out)
+    head["route_block"] = {"bytes": n, "segments": len(starts), "route_kernel_seconds": secs, "route_median": sorted(secs)[2], "d2d_copy_seconds": copies[1:],
+                           "d2d_median": sorted(copies[1:])[2], "numpy_mask_seconds": host, "equal_to_numpy": all(r.out[b].tobytes() == parts[b].tobytes() for b in range(3))}
+    del d, e
+
+
+def gz_e2e(torch, reads, nreads, m, p, tm, tp, head):
+    """the tool end to end on the workload as one level-6 .fastq.gz: --gz host / device without --write-reads, and the four --gz x --route
+    settings with it, two runs each, alternating, in the order run; then the route kernels on one block"""
+    import numpy as np
+    import bench
+    rl = bench.READ_LEN
+    d = os.environ.get("TMPDIR", "/tmp")
+    paths = {w: os.path.join(d, "prof_readbins_%s" % w) for w in ("mat.jf", "pat.jf", "child.fq.gz", "out")}
+    m.write_jf(paths["mat.jf"])
+    p.write_jf(paths["pat.jf"])
+    seq = reads.view(-1, rl + 1)[:, :rl].cpu().numpy()
+    del reads
+    torch.cuda.empty_cache()
+    rec = np.empty((nreads, 3 + rl + 3 + rl + 1), dtype=np.uint8)      # @r \n seq \n + \n qual \n
+    rec[:, 0:3] = np.frombuffer(b"@r\n", dtype=np.uint8)
+    rec[:, 3:3 + rl] = seq
+    rec[:, 3 + rl:6 + rl] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    rec[:, 6 + rl:6 + 2 * rl] = ord("I")
+    rec[:, -1] = 10
+    del seq
+    text = rec.reshape(-1)
+    route_block(torch, m, text, rec.shape[1], head)     # (in this process: if it faults, the process ends here and no child is ever started)
+    m.close()
+    p.close()
+    torch.cuda.empty_cache()
+    t0 = time.perf_counter()
+    write_gz(paths["child.fq.gz"], text)
+    head.update({"text_bytes": int(text.size), "gz_bytes": os.path.getsize(paths["child.fq.gz"]), "gz_write_seconds": time.perf_counter() - t0})
+    del rec, text
+    print(json.dumps(head), flush=True)
+    args = ["-r", paths["child.fq.gz"], "--mat-jf", paths["mat.jf"], "--pat-jf", paths["pat.jf"], "--mat-threshold", str(tm), "--pat-threshold", str(tp), "-o", paths["out"],
+            "--reader", "device"]
+    plain = [["--gz", "host"], ["--gz", "device"]]
+    written = [["--write-reads", "--gz", g, "--route", r] for g in ("host", "device") for r in ("host", "device")]
+    runs = [(ROOT, f) for f in ((plain + written) if "quick" in sys.argv[2:] else (plain + plain + written + written))]
+    parent = [a[len("parent="):] for a in sys.argv[2:] if a.startswith("parent=")]
+    if parent:                                          # a built copy of the parent commit's tree: its tool knows neither flag and does what host / host does
+        runs += [(os.path.abspath(parent[0]), ["--write-reads"]), (ROOT, ["--write-reads", "--gz", "host", "--route", "host"])]
+    sums = {}
+    # one child at a time, each under a time limit of its own; the first that fails, is killed by a signal or runs out of time ends the
+    # run -- nothing more is started on the GPU after it, and what was collected up to then is already written
+    for tree, flags in runs:
+        limit = 240 if "host" in flags[-3:] or flags == ["--write-reads"] else 150
+        t0 = time.perf_counter()
+        try:
+            r = subprocess.run([sys.executable, "-m", "jasper_amd.triobin"] + args + flags, env=dict(os.environ, PYTHONPATH=tree, JASPER_AMD_TIMING="1"), capture_output=True,
+                               text=True, timeout=limit, cwd=tree)
+            rc, err = r.returncode, r.stderr
+        except subprocess.TimeoutExpired as e:
+            rc, err = 124, (e.stderr or b"").decode(errors="replace") if isinstance(e.stderr, bytes) else (e.stderr or "")
+        wall = time.perf_counter() - t0
+        lines = [ln for ln in err.splitlines() if ln.startswith("[triobin]")]
+        digest = None
+        if rc == 0 and "--write-reads" in flags:
+            import hashlib
+            digest = {}
+            for b in ("mat", "pat", "unknown"):
+                fn = "%s.%s.prof_readbins_child.fq" % (paths["out"], b)
+                h = hashlib.sha256()
+                with open(fn, "rb") as f:
+                    for blk in iter(lambda: f.read(1 << 24), b""):
+                        h.update(blk)
+                digest[b] = h.hexdigest()[:16]
+                os.remove(fn)
+            sums.setdefault("read_files", digest)
+        table = open(paths["out"] + ".readbins.tsv").read() if rc == 0 else None
+        sums.setdefault("table", table)
+        print(json.dumps({"tree": "this commit" if tree == ROOT else "parent commit", "flags": flags, "returncode": rc, "time_limit": limit, "wall_seconds": wall, "lines": lines,
+                          "same_table": table == sums["table"], "same_read_files": digest == sums.get("read_files") if digest else None,
+                          "stderr_tail": err[-400:] if rc else None}), flush=True)
+        if rc != 0:
+            break
     for fn in list(paths.values()) + [paths["out"] + ".readbins.tsv"]:
         if os.path.exists(fn):
             os.remove(fn)
