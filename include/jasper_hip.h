@@ -507,6 +507,32 @@ int jasper_route_text(jasper_table *t, const uint8_t *text /* host */, int64_t n
 int jasper_gz_text_route(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from,
                          uint8_t *out0, uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *device_seconds /* [2] */);
 
+/* Compression: a text of n bytes (host) as BGZF members (SAM specification 4.1), made on the GPU.  The text is cut into blocks of 65280
+ * bytes, the last may be short; every block becomes one complete gzip member -- the 18-byte header 1f 8b 08 04 00000000 00 ff 06 00 42 43
+ * 02 00 <member bytes - 1 as u16>, one final deflate block, CRC-32 and ISIZE of the block's text -- of at most 65536 bytes, and the members
+ * lie back to back in `out` (host, room for out_cap bytes), *out_bytes of them.  n = 0 gives no member: the 28-byte empty member that ends a
+ * BGZF file is the file writer's, once per file.  Per block the cheapest in bytes of three encodings is written: a greedy LZ77 parse
+ * (matches of 3..258 bytes at distances up to 32768, found through a hash of three bytes and the byte before) under dynamic Huffman codes,
+ * the literals alone under a dynamic Huffman code, or a stored block; so a member never exceeds its text by more than 31 bytes and
+ * jasper_deflate_bound(n) = n + 31 * blocks always suffices for out_cap (-1 for n < 0).  Members that do not fit out_cap are JASPER_ERR,
+ * as is n of 2^31 or more.  The same text gives the same bytes in every call.
+ *   counters[6] (may be NULL): blocks, stored blocks, literal-only blocks, LZ blocks, and the LZ blocks' matches and matched bytes
+ *   device_seconds (may be NULL): the kernels' time, HIP events
+ * The two routing calls with the suffix _gz take what jasper_route_text / jasper_gz_text_route take and route as they do, but out0 / out1 /
+ * out2 (room for out_cap[b] bytes; jasper_deflate_bound(n) always suffices) get the BGZF members of each bin's bytes: the routed bytes stay
+ * in HBM, the compressor runs on the three ranges, only the members are copied down.  out_bytes[3] = the members' bytes, raw_bytes[3] = the
+ * routed bytes (what out_bytes is in the plain calls); a bin without a byte gets no member.  counters[6]: the three bins' sums.
+ * device_seconds: [0] the route kernels, [1] the compressor's kernels; from a session [0] the route kernels, [1] the pull, [2] the compressor. */
+int64_t jasper_deflate_bound(int64_t n);
+int jasper_deflate_bgzf(jasper_table *t, const uint8_t *text /* host */, int64_t n, uint8_t *out /* host */, int64_t out_cap, int64_t *out_bytes, uint64_t counters[6],
+                        double *device_seconds);
+int jasper_route_text_gz(jasper_table *t, const uint8_t *text /* host */, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from,
+                         uint8_t *out0, uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches,
+                         uint64_t counters[6], double *device_seconds /* [2] */);
+int jasper_gz_text_route_gz(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from,
+                            uint8_t *out0, uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got,
+                            int64_t *mismatches, uint64_t counters[6], double *device_seconds /* [3] */);
+
 /* Variant scan: WHERE on the sequences the reads hold a solid single-base alternative to the base the sequence has -- the second allele
  * of a diploid genome that a one-haplotype assembly cannot show, or a substitution the polisher has not made.  One resident table (whole,
  * wide, or attached owner-sharded) and a set of sequences, scanned densely on the GPU as jasper_kmer_report scans them.

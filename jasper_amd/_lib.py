@@ -247,6 +247,12 @@ SYMBOLS = {
     "jasper_route_text": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "jasper_gz_text_route": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_double)]),
+    "jasper_deflate_bound": (C.c_int64, [C.c_int64]),
+    "jasper_deflate_bgzf": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_route_text_gz": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_gz_text_route_gz": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_variant_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_variant_scan_device": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
     "jasper_varscan_num_seqs": (C.c_int, [_P]),

@@ -13,6 +13,7 @@
 #include "readbins.hpp"
 #include "readtext.hpp"
 #include "readroute.hpp"
+#include "deflate_gpu.hpp"
 #include "readgz.hpp"
 #include "variants.hpp"
 #include "indels.hpp"
@@ -977,6 +978,29 @@ int jasper_gz_text_route(jasper_gz_text *h, jasper_table *t, int64_t want, int64
     if (!h || !t) { g_err = "bad argument"; return JASPER_ERR; }
     uint8_t *const out[3] = {out0, out1, out2};
     return gz_text_route(*h->g, t->t, want, n_seg, bounds, bins, first, check_from, out, out_bytes, got, mismatches, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+// ... and the compressor (deflate_gpu.hip): a text as BGZF members, and the two routing calls with the three outputs compressed
+int64_t jasper_deflate_bound(int64_t n) { return n < 0 ? -1 : (int64_t)deflate_bound((uint64_t)n); }
+int jasper_deflate_bgzf(jasper_table *t, const uint8_t *text, int64_t n, uint8_t *out, int64_t out_cap, int64_t *out_bytes, uint64_t counters[6], double *device_seconds) {
+    if (!t) { g_err = "bad argument"; return JASPER_ERR; }
+    return deflate_host(t->t, text, n, out, out_cap, out_bytes, counters, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_route_text_gz(jasper_table *t, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
+                         uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t counters[6],
+                         double *device_seconds) {
+    if (!t) { g_err = "bad argument"; return JASPER_ERR; }
+    uint8_t *const out[3] = {out0, out1, out2};
+    return route_text_host_gz(t->t, text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, device_seconds, g_err) ? JASPER_ERR
+                                                                                                                                                                          : JASPER_OK;
+}
+int jasper_gz_text_route_gz(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
+                            uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches,
+                            uint64_t counters[6], double *device_seconds) {
+    if (!h || !t) { g_err = "bad argument"; return JASPER_ERR; }
+    uint8_t *const out[3] = {out0, out1, out2};
+    return gz_text_route_gz(*h->g, t->t, want, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, got, mismatches, counters, device_seconds, g_err)
+               ? JASPER_ERR
+               : JASPER_OK;
 }
 
 // ---- variant scan (variants.hip) ----

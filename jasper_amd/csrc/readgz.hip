@@ -1,6 +1,7 @@
 // readgz.hip -- the host stage of a gzip text session (readgz.hpp): no kernel of its own.  It moves text between the inflater's buffer,
 // the session's tail buffer and the slot the read-text or routing kernels read, always between distinct buffers, on the table's stream.
 #include "readgz.hpp"
+#include "deflate_plan.hpp"
 #include "scan_tile.hpp"
 
 namespace jk {
@@ -121,8 +122,11 @@ int gz_text_copy(GzText &G, int64_t from, int64_t len, uint8_t *dst, std::string
     return 0;
 }
 
-int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                  int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *seconds, std::string &err) {
+namespace {
+// what both route calls begin with: the arguments, the session's mode, the outputs' initial state, and the pull of the next `want`
+// inflated bytes into the routing path's text slot -> those bytes at *d_text, how many in *got, the pull's seconds in *pulled
+int route_pull(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, uint8_t **d_text,
+               double *pulled, std::string &err) {
     const std::string w(GZ_WHAT);
     if (!got || !out_bytes || !mismatches || !bounds || n_seg < 0 || want < 0) { err = w + ": bad arguments"; return -1; }
     if (&T != G.M) { err = w + ": the table is not the one the session was opened on"; return -1; }
@@ -130,20 +134,49 @@ int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_
     G.mode = 2;
     *got = 0;
     *mismatches = 0;
+    *pulled = 0;
     out_bytes[0] = out_bytes[1] = out_bytes[2] = 0;
-    if (seconds) seconds[0] = seconds[1] = 0;
     HIPCHK(hipSetDevice(T.device));
-    uint8_t *d_text = route_text_room(T, want, err);
-    if (!d_text) return -1;
+    *d_text = route_text_room(T, want, err);
+    if (!*d_text) return -1;
     Events ev;
     if (ev.create(err)) return -1;
-    const long g = pull(G, d_text, want, ev, err);
+    const long g = pull(G, *d_text, want, ev, err);
     if (g < 0) return -1;
     HIPCHK(jk_stream_wait(T.stream));
-    if (seconds && ev.add_seconds(seconds[1], err)) return -1;
+    if (ev.add_seconds(*pulled, err)) return -1;
     *got = g;
-    if (g != bounds[n_seg]) return 0;                   // (the file is not what the bounds were made for: nothing is routed)
-    return route_text_device(T, d_text, g, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err);
+    return 0;
+}
+}  // namespace
+
+int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                  int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *seconds, std::string &err) {
+    if (seconds) seconds[0] = seconds[1] = 0;
+    uint8_t *d_text = nullptr;
+    double pulled = 0;
+    if (route_pull(G, T, want, n_seg, bounds, out_bytes, got, mismatches, &d_text, &pulled, err)) return -1;
+    if (seconds) seconds[1] = pulled;
+    if (*got != bounds[n_seg]) return 0;                // (the file is not what the bounds were made for: nothing is routed)
+    return route_text_device(T, d_text, *got, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err);
+}
+
+int gz_text_route_gz(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
+    if (seconds) seconds[0] = seconds[1] = seconds[2] = 0;
+    if (counters)
+        for (int i = 0; i < DF_COUNTERS; ++i) counters[i] = 0;
+    if (!raw_bytes || !out_cap) { err = std::string(GZ_WHAT) + ": bad arguments"; return -1; }
+    raw_bytes[0] = raw_bytes[1] = raw_bytes[2] = 0;
+    uint8_t *d_text = nullptr;
+    double pulled = 0;
+    if (route_pull(G, T, want, n_seg, bounds, out_bytes, got, mismatches, &d_text, &pulled, err)) return -1;
+    if (seconds) seconds[1] = pulled;
+    if (*got != bounds[n_seg]) return 0;
+    double s2[2] = {0, 0};
+    const int rc = route_text_device_gz(T, d_text, *got, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, s2, err);
+    if (seconds) { seconds[0] = s2[0]; seconds[2] = s2[1]; }
+    return rc;
 }
 
 }  // namespace jk

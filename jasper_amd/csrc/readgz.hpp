@@ -40,5 +40,8 @@ int gz_text_copy(GzText &G, int64_t from, int64_t len, uint8_t *dst, std::string
 // seconds[2]: the route kernels, the pull (as above).  Refused on a session that has served a bins call, and bins on one that has routed
 int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
                   int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *seconds, std::string &err);
+// gz_text_route with the three outputs as BGZF members (route_text_device_gz): seconds[3] = the route kernels, the pull, the compressor's kernels
+int gz_text_route_gz(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
 
 }  // namespace jk

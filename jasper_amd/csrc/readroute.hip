@@ -13,6 +13,7 @@
 //                     begins where bin 0's total ends -- so the kernel reads the text once and writes n bytes once
 // The host stage waits once, for the three totals and the check's count; they say how much of the output buffer goes where.
 #include "readroute.hpp"
+#include "deflate_gpu.hpp"
 #include "readtext.hpp"
 #include "scan_tile.hpp"
 
@@ -101,12 +102,11 @@ int route_refuse(int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t 
     }
 }
 
-// the kernels and the copies out, for segments route_refuse has let pass
-int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                  int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {
+// the kernels, for segments route_refuse has let pass (n > 0): the routed bytes stay in HBM, bin b's tot[b] bytes behind those of the bins
+// before it from *d_routed on; the one wait of the path is here
+int route_core(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t **d_routed,
+               uint64_t tot[RR_BINS], int64_t *mismatches, double *seconds, std::string &err) {
     const std::string w(RR_WHAT);
-    if (n == 0) return 0;
-    if (!d_text || !out[0] || !out[1] || !out[2]) { err = w + ": bad arguments"; return -1; }
     HIPCHK(hipSetDevice(T.device));
     hipStream_t st = T.stream;
     const uint64_t un = (uint64_t)n, ns = (uint64_t)n_seg;
@@ -135,7 +135,7 @@ int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, con
     hipLaunchKernelGGL(rr_copy_kernel, dim3((unsigned)rt_blocks(un)), dim3(RT_THREADS), 0, st, d_text, un, d_bounds, d_bins, ns, d_pre, pw, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[1], st));
-    uint64_t tot[RR_BINS] = {0, 0, 0};
+    tot[0] = tot[1] = tot[2] = 0;
     unsigned long long bad = 0;
     for (int b = 0; b < RR_BINS; ++b) HIPCHK(hipMemcpyAsync(&tot[b], d_pre + b * pw + ns, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&bad, d_ctl + RRC_MISMATCH, sizeof bad, hipMemcpyDeviceToHost, st));
@@ -144,6 +144,21 @@ int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, con
     if (ev.add_seconds(s, err)) return -1;
     if (seconds) *seconds = s;
     if (tot[0] + tot[1] + tot[2] != un) { err = w + ": the scans left totals that are not the text's length"; return -1; }
+    *mismatches = (int64_t)bad;
+    *d_routed = d_out;
+    return 0;
+}
+
+// ... and the copies out
+int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                  int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {
+    if (n == 0) return 0;
+    if (!d_text || !out[0] || !out[1] || !out[2]) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
+    uint8_t *d_out = nullptr;
+    uint64_t tot[RR_BINS];
+    int64_t bad = 0;
+    if (route_core(T, d_text, n, n_seg, bounds, bins, first, check_from, &d_out, tot, &bad, seconds, err)) return -1;
+    hipStream_t st = T.stream;
     uint64_t at = 0;
     for (int b = 0; b < RR_BINS; ++b) {
         if (tot[b]) HIPCHK(hipMemcpyAsync(out[b], d_out + at, (size_t)tot[b], hipMemcpyDeviceToHost, st));
@@ -151,10 +166,61 @@ int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, con
         at += tot[b];
     }
     HIPCHK(jk_stream_wait(st));
-    *mismatches = (int64_t)bad;
+    *mismatches = bad;
+    return 0;
+}
+
+// ... or the compressor on each bin's range, and its members out
+int route_checked_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
+    if (n == 0) return 0;
+    if (!d_text || !out[0] || !out[1] || !out[2]) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
+    uint8_t *d_out = nullptr;
+    uint64_t tot[RR_BINS];
+    int64_t bad = 0;
+    if (route_core(T, d_text, n, n_seg, bounds, bins, first, check_from, &d_out, tot, &bad, seconds, err)) return -1;
+    uint64_t at = 0;
+    for (int b = 0; b < RR_BINS; ++b) {
+        if (deflate_device(T, d_out + at, (int64_t)tot[b], out[b], out_cap[b], &out_bytes[b], counters, seconds ? seconds + 1 : nullptr, err)) return -1;
+        raw_bytes[b] = (int64_t)tot[b];
+        at += tot[b];
+    }
+    *mismatches = bad;
+    return 0;
+}
+
+int route_refuse_gz(const int64_t *out_cap, int64_t raw_bytes[3], uint64_t *counters, double *seconds, std::string &err) {
+    if (!out_cap || !raw_bytes) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
+    raw_bytes[0] = raw_bytes[1] = raw_bytes[2] = 0;
+    if (counters)
+        for (int i = 0; i < DF_COUNTERS; ++i) counters[i] = 0;
+    if (seconds) seconds[1] = 0;                        // (route_refuse clears seconds[0])
     return 0;
 }
 }  // namespace
+
+int route_text_device_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                         const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
+    if (route_refuse_gz(out_cap, raw_bytes, counters, seconds, err)) return -1;
+    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
+    return route_checked_gz(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, seconds, err);
+}
+
+int route_text_host_gz(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                       const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
+    if (route_refuse_gz(out_cap, raw_bytes, counters, seconds, err)) return -1;
+    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
+    uint8_t *d_text = nullptr;
+    if (n > 0) {
+        if (!text) { err = std::string(RR_WHAT) + ": null text"; return -1; }
+        HIPCHK(hipSetDevice(T.device));
+        uint8_t *room = route_text_room(T, n, err);
+        if (!room) return -1;
+        d_text = room + ((uintptr_t)text & 15u);
+        HIPCHK(hipMemcpyAsync(d_text, text, (size_t)n, hipMemcpyHostToDevice, T.stream));
+    }
+    return route_checked_gz(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, seconds, err);
+}
 
 int route_text_device(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
                       int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {

@@ -19,6 +19,14 @@ int route_text_device(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg,
 // the same with the text in host memory: it is uploaded to WS_ROUTE + 0, at its host pointer's place within 16 bytes
 int route_text_host(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
                     int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err);
+// The same two, but out[b] (host, room for out_cap[b] bytes) gets bin b's bytes as BGZF members (deflate_gpu.hpp): the routed bytes stay in
+// HBM, the compressor runs on each bin's range and only the members are copied down.  out_bytes[b] = the members' bytes, raw_bytes[b] =
+// the routed bytes; counters[DF_COUNTERS] (may be null) = the three compressor calls' sums; seconds[2] (may be null) = the route kernels,
+// the compressor's kernels.  A bin without a byte gets no member.
+int route_text_device_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                         const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
+int route_text_host_gz(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
+                       const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
 // room for n text bytes in WS_ROUTE + 0 (what a caller that fills the text itself asks for first)
 uint8_t *route_text_room(Table &T, int64_t n, std::string &err);
 

@@ -263,14 +263,26 @@ class RoutedText:
     """a block of text routed on the GPU (include/jasper_hip.h: jasper_route_text): `out` = three np.uint8 arrays, the bytes of bin 0, 1
     and 2 in input order (views of the buffers handed in, or of fresh ones), `mismatches` = segments that do not begin with the expected
     byte, `seconds` = device time of the kernels; from a gz session `got` = inflated bytes pulled (nothing is routed when that is not
-    bounds[-1]: `routed` False) and `inflate_seconds`."""
+    bounds[-1]: `routed` False) and `inflate_seconds`.  With gz=True `out` holds each bin's bytes as BGZF members (jasper_route_text_gz),
+    `raw_bytes` = the routed bytes per bin, `deflate` = the compressor's counters (DEFLATE_COUNTERS), `deflate_seconds` its kernels' time."""
 
-    def __init__(self, out, mismatches, seconds, got=None, routed=True, inflate_seconds=0.0):
+    def __init__(self, out, mismatches, seconds, got=None, routed=True, inflate_seconds=0.0, raw_bytes=None, deflate=None, deflate_seconds=0.0):
         self.out, self.mismatches, self.seconds, self.got, self.routed, self.inflate_seconds = out, mismatches, seconds, got, routed, inflate_seconds
+        self.raw_bytes, self.deflate, self.deflate_seconds = raw_bytes, deflate, deflate_seconds
 
 
-def _route_args(bounds, bins, first, check_from, room, out):
+DEFLATE_COUNTERS = ("blocks", "stored", "literal_only", "lz", "matches", "matched_bytes")
+
+
+def deflate_bound(n):
+    """bytes that the BGZF members of n text bytes come to at the most (jasper_deflate_bound)"""
+    return int(_lib.lib().jasper_deflate_bound(int(n)))
+
+
+def _route_args(bounds, bins, first, check_from, room, out, gz=False):
     import numpy as np
+    if gz:
+        room = deflate_bound(room)
     bounds = np.ascontiguousarray(bounds, dtype=np.int64)
     bins = np.ascontiguousarray(bins, dtype=np.uint8)
     if bounds.ndim != 1 or bins.ndim != 1 or len(bounds) != len(bins) + 1:
@@ -348,11 +360,19 @@ class GzText:
         check(self._L.jasper_gz_text_stats(self._handle(), st))
         return dict(zip(GZ_STATS, (int(v) for v in st)))
 
-    def route(self, want, bounds, bins, first, check_from=0, out=None):
+    def route(self, want, bounds, bins, first, check_from=0, out=None, gz=False):
         """the next `want` inflated bytes routed as KmerTable.route_text routes a host text -> RoutedText with `got`"""
-        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, int(bounds[-1]) if len(bounds) else 0, out)
+        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, int(bounds[-1]) if len(bounds) else 0, out, gz)
         vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
-        nb, got, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(0), (C.c_double * 2)()
+        nb, got, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(0), (C.c_double * 3)()
+        if gz:
+            cap, raw, cnt = (C.c_int64 * 3)(*(len(o) for o in out)), (C.c_int64 * 3)(), (C.c_uint64 * 6)()
+            check(self._L.jasper_gz_text_route_gz(self._handle(), self._t._h, int(want), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
+                                                  vp(out[1]), vp(out[2]), cap, nb, raw, C.byref(got), C.byref(bad), cnt, secs))
+            self.inflate_seconds += secs[1]
+            routed = got.value == int(bounds[-1])
+            return RoutedText([o[:nb[b]] for b, o in enumerate(out)] if routed else None, bad.value, secs[0], got.value, routed, secs[1], [int(v) for v in raw],
+                              dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), secs[2])
         check(self._L.jasper_gz_text_route(self._handle(), self._t._h, int(want), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
                                            vp(out[1]), vp(out[2]), nb, C.byref(got), C.byref(bad), secs))
         self.inflate_seconds += secs[1]
@@ -1270,16 +1290,41 @@ class KmerTable:
         when the file is not for the device inflater (no gzip header, not a regular file): the caller reads it the ordinary way"""
         return GzText(self, path)
 
-    def route_text(self, text, bounds, bins, first, check_from=0, out=None):
+    def deflate_bgzf(self, text, out=None):
+        """text (bytes or np.uint8) -> (its BGZF members as np.uint8, one per 65280 bytes, without the empty member that ends a file;
+        the counters DEFLATE_COUNTERS as a dict; device seconds of the kernels).  out: a contiguous np.uint8 array of at least
+        deflate_bound(len(text)) bytes to write into (the result is a view of it)"""
+        import numpy as np
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text
+        if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
+            raise TypeError("deflate_bgzf: the text must be bytes or a contiguous one-dimensional np.uint8 array")
+        room = deflate_bound(len(buf))
+        if out is None:
+            out = np.empty(max(room, 1), dtype=np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous or len(out) < room:
+            raise ValueError("deflate_bgzf: out must be a contiguous np.uint8 array of at least deflate_bound(len(text)) bytes")
+        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+        nb, cnt, secs = C.c_int64(0), (C.c_uint64 * 6)(), C.c_double(0)
+        check(self._L.jasper_deflate_bgzf(self._h, vp(buf) if buf.size else None, len(buf), vp(out), len(out), C.byref(nb), cnt, C.byref(secs)))
+        return out[:nb.value], dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), secs.value
+
+    def route_text(self, text, bounds, bins, first, check_from=0, out=None, gz=False):
         """text (bytes or np.uint8) cut by bounds[n_seg + 1] into segments with bin codes bins[n_seg] (0..2) -> RoutedText: each bin's
-        segments back to back, and the segments i >= check_from that hold a byte and do not begin with `first`"""
+        segments back to back, and the segments i >= check_from that hold a byte and do not begin with `first`.  gz=True: each bin's
+        bytes come back as BGZF members, compressed on the GPU (out: room for deflate_bound(len(text)) bytes each)"""
         import numpy as np
         buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text
         if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
             raise TypeError("route_text: the text must be bytes or a contiguous one-dimensional np.uint8 array")
-        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, len(buf), out)
+        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, len(buf), out, gz)
         vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
         nb, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_double(0)
+        if gz:
+            cap, raw, cnt, secs2 = (C.c_int64 * 3)(*(len(o) for o in out)), (C.c_int64 * 3)(), (C.c_uint64 * 6)(), (C.c_double * 2)()
+            check(self._L.jasper_route_text_gz(self._h, vp(buf) if buf.size else None, len(buf), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from,
+                                               vp(out[0]), vp(out[1]), vp(out[2]), cap, nb, raw, C.byref(bad), cnt, secs2))
+            return RoutedText([o[:nb[b]] for b, o in enumerate(out)], bad.value, secs2[0], raw_bytes=[int(v) for v in raw],
+                              deflate=dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), deflate_seconds=secs2[1])
         check(self._L.jasper_route_text(self._h, vp(buf) if buf.size else None, len(buf), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
                                         vp(out[1]), vp(out[2]), nb, C.byref(bad), C.byref(secs)))
         return RoutedText([o[:nb[b]] for b, o in enumerate(out)], bad.value, secs.value)

@@ -2,7 +2,8 @@
 
     python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
                                  [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
-                                 [--batch-bases N] [--reader host|device] [--gz host|device] [--route host|device] [-o PREFIX] [--device D]
+                                 [--write-gz] [--deflate host|device] [--batch-bases N] [--reader host|device] [--gz host|device]
+                                 [--route host|device] [-o PREFIX] [--device D]
 
 An extension (the reference has no such tool), and the cure for what `--hapmers` only shows: a polisher that repairs toward the reads'
 solid k-mers can move a het site of a phased assembly onto the other haplotype, which hapmers.tsv lists as switches in its `after` row.
@@ -45,6 +46,15 @@ or to the session's route (a .gz file under --gz device: the bytes are inflated 
 buffers come back and are written to the three files.  The file has changed between the passes when a block comes short, bytes are left
 over, or a record's first byte is no longer the records' first byte.  The default is host.
 
+--write-gz (with --write-reads) writes every bin file compressed, as PREFIX.<bin>.<basename>.gz: BGZF (jasper_amd/bgzf.py), a series of
+independent gzip members of at most 65280 text bytes each and the 28-byte empty member at the end, which gzip -dc, Python's gzip, bgzip
+and this project's readers take -- the files go straight into jasper.sh -r.  A bin without a record gives a file of exactly that empty
+member.  Every write cuts its bytes into members on its own and carries no tail to the next, so the member boundaries follow the chunks
+(CHUNK, and JASPER_TRIOBIN_CHUNK in the first pass's reader); what is promised is the decompressed content, byte for byte the plain file.
+--deflate host (the default) compresses with zlib at level 1 on the host; --deflate device sends each write's bytes through
+KmerTable.deflate_bgzf (the GPU compressor: LZ77 and dynamic Huffman codes per member), with any --reader; under --route device the
+routed bytes are compressed where they lie in HBM (the _gz route calls) and only the members come back.
+
 The rule.  A template's m and p are its read's counts; with --paired they are the sums over its two mates.
 
     m + p < --min-markers (default 1, at least 1)    unknown
@@ -68,7 +78,8 @@ The files (each written as .tmp, then renamed; the read files renamed only when 
                                 that file's records of that bin, byte for byte as they stand in the decompressed input, in input order --
                                 the mates of a pair stay in step across R1 and R2, and the three files of an input hold each of its
                                 records exactly once.  Written by a second pass over the input with the bins in memory.  Two inputs with
-                                one base name end the run before anything is counted.  No .gz is written.
+                                one base name end the run before anything is counted.  With --write-gz the names end in .gz and the
+                                files are BGZF.
 
 PREFIX defaults to the first read file's name.  The log gives k, both thresholds and where they came from, M_total and P_total, then
 reads and bases per bin with their shares.  One GPU; parental tables that do not fit whole on it are an error.
@@ -78,12 +89,13 @@ import os
 import sys
 from collections import namedtuple
 
-from . import cli, extensions
+from . import bgzf, cli, extensions
 from .report import write_atomic
 
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
-         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--batch-bases N (no effect with --reader device)] [--reader host|device] "
-         "[--gz host|device (needs --reader device)] [--route host|device (needs --reader device --write-reads)] [-o PREFIX] [--device D]")
+         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--write-gz (needs --write-reads)] [--deflate host|device (needs --write-gz)] "
+         "[--batch-bases N (no effect with --reader device)] [--reader host|device] [--gz host|device (needs --reader device)] "
+         "[--route host|device (needs --reader device --write-reads)] [-o PREFIX] [--device D]")
 BINS = ("mat", "pat", "unknown")
 MAT, PAT, UNKNOWN = 0, 1, 2
 BATCH_BASES_DEFAULT = 256 << 20
@@ -92,10 +104,10 @@ CHUNK = 16 << 20                    # file bytes parsed at a time
 DEVICE_CHUNK = 16 << 20             # ... with --reader device: file bytes uploaded and parsed at a time (JASPER_TRIOBIN_CHUNK overrides it)
 DEVICE_CHUNK_MOST = (1 << 30) - 1   # (a chunk and the tail carried into it stay below the kernels' 2^31 text bytes)
 READERS = ("host", "device")
-BOOL_FLAGS = ("--paired", "--per-read", "--write-reads")
+BOOL_FLAGS = ("--paired", "--per-read", "--write-reads", "--write-gz")
 VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
                "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases",
-               "--reader": "reader", "--gz": "gz", "--route": "route"}
+               "--reader": "reader", "--gz": "gz", "--route": "route", "--deflate": "deflate"}
 
 
 class Malformed(Exception):
@@ -430,15 +442,81 @@ def block_segments(starts, at, end):
     return i0, i1, bounds, 0 if starts[i0] == at else 1
 
 
+class _Deflater:
+    """--deflate device: deflate(np.uint8 array) -> (its BGZF members, the compressor's counters, device seconds), KmerTable.deflate_bgzf.
+    An instance is what a bin file's writer compresses with, and it keeps the sums JASPER_AMD_TIMING=1 prints; note() adds what a _gz
+    route call has compressed"""
+
+    def __init__(self, deflate):
+        self.deflate, self.seconds, self.counters = deflate, 0.0, dict.fromkeys(("stored", "literal_only", "lz"), 0)
+
+    def note(self, counters, seconds):
+        self.seconds += seconds
+        for key in self.counters:
+            self.counters[key] += counters[key]
+
+    def __call__(self, arr):
+        out, counters, seconds = self.deflate(arr)
+        self.note(counters, seconds)
+        return out
+
+
+class _BinFiles:
+    """the three bin files of one input, as .tmp: plain, or BGZF with --write-gz (deflater: None for the host's zlib, a _Deflater for the
+    GPU).  write(b, arr) takes bytes of bin b; write_routed(r) what a route call returns -- bytes, or with gz members and their raw sizes"""
+
+    def __init__(self, prefix, path, made, write_gz=False, deflater=None, sums=None):
+        outs = ["%s.%s.%s%s" % (prefix, b, out_basename(path), ".gz" if write_gz else "") for b in BINS]
+        made += outs
+        self.sums, self.w = sums, []
+        try:
+            for fn in outs:
+                f = open(fn + ".tmp", "wb")
+                self.w.append(bgzf.BgzfWriter(f, deflater or bgzf.compress) if write_gz else bgzf.PlainWriter(f))
+        except BaseException:
+            self.close()
+            raise
+
+    def write(self, b, arr):
+        self.w[b].write(arr)
+
+    def write_routed(self, r):
+        for b in range(3):
+            if getattr(r, "raw_bytes", None) is None:
+                self.w[b].write(r.out[b])
+            else:
+                self.w[b].write_members(r.out[b], r.raw_bytes[b])
+
+    def close(self):
+        """every file is closed, whatever closing one of them raises (the end marker may not fit the disk): the first error leaves"""
+        writers, self.w, error = self.w, [], None
+        for w in writers:
+            try:
+                w.close()
+            except BaseException as e:      # noqa: B902  (re-raised below)
+                error = error or e
+                try:
+                    w.f.close()
+                except OSError:
+                    pass
+            if self.sums is not None:
+                self.sums["deflate_raw"] = self.sums.get("deflate_raw", 0) + w.raw
+                self.sums["deflate_written"] = self.sums.get("deflate_written", 0) + w.written
+        if error is not None:
+            raise error
+
+
 def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT, reader="host",
-              count_text=None, gz_open=None, route_text=None, timings=None):
+              count_text=None, gz_open=None, route_text=None, timings=None, write_gz=False, deflate=None):
     """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
     cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds.  reader "device": the files'
     bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called.  gz_open: --gz device (_DeviceReader);
     route_text: --route device, route_text(buf, bounds, bins, first, check_from, out) -> table.RoutedText.  timings (a dict) gets what
-    JASPER_AMD_TIMING=1 prints of the two"""
+    JASPER_AMD_TIMING=1 prints of the two.  write_gz: the bin files are BGZF; deflate (--deflate device): deflate(array) -> (members,
+    counters, seconds) compresses them, and with route_text the route calls are made with gz=True and return members"""
     import numpy as np
     bat = _Batcher(batch_bases, count)
+    deflater = _Deflater(deflate) if write_gz and deflate is not None else None
     dev = _DeviceReader(count_text, write_reads, gz_open, per_read) if reader == "device" else None
     timings = {} if timings is None else timings
     nrec, lens, names = [], [], []
@@ -487,11 +565,14 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
             text += "%s\t%s\t%d\t%d\t%d\t%d\n" % (path, BINS[b], row[0], row[1], row[2], row[3])
     text += "".join("*\t%s\t%d\t%d\t%d\t%d\n" % ((BINS[b],) + tuple(int(v) for v in total[b])) for b in range(3))
     made = []
+    opened = lambda path: _BinFiles(prefix, path, made, write_gz, deflater, timings if write_gz else None)      # noqa: E731
     try:
         if write_reads and dev:
-            _write_reads_by_starts(paths, prefix, bins, made, dev.starts, route_text, gz_open, timings)
+            _write_reads_by_starts(paths, opened, bins, dev.starts, route_text, gz_open, timings, deflater)
         elif write_reads:
-            _write_reads(paths, prefix, bins, nrec, made)
+            _write_reads(paths, opened, bins, nrec)
+        if deflater is not None:
+            timings.update(deflate_seconds=deflater.seconds, deflate_blocks=deflater.counters)
         write_atomic(prefix + ".readbins.tsv", text)
         if per_read:
             with open(prefix + ".readbins.reads.tsv.tmp", "w") as f:
@@ -509,13 +590,11 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
     return [(int(total[b][0]), int(total[b][1])) for b in range(3)], bat.seconds
 
 
-def _write_reads(paths, prefix, bins, nrec, made):
-    """the second pass: every input's records into its three .tmp files; `made` gets the names they are to have"""
+def _write_reads(paths, opened, bins, nrec):
+    """the second pass: every input's records into its three .tmp files (opened(path) -> _BinFiles, which notes the names they are to have)"""
     import numpy as np
     for fi, path in enumerate(paths):
-        outs = ["%s.%s.%s" % (prefix, b, out_basename(path)) for b in BINS]
-        made += outs
-        files = [open(fn + ".tmp", "wb") for fn in outs]
+        files = opened(path)
         try:
             at = 0
             try:
@@ -525,30 +604,36 @@ def _write_reads(paths, prefix, bins, nrec, made):
                         break
                     size = ch.rec_end - ch.rec_start
                     for b in range(3):
-                        ch.buf[np.repeat(bins[fi][at:at + n] == b, size)].tofile(files[b])
+                        files.write(b, ch.buf[np.repeat(bins[fi][at:at + n] == b, size)])
                     at += n
             except Malformed:
                 at = -1
             if at != nrec[fi]:
                 cli.error_exit("--write-reads: %s changed between the two passes" % path)
         finally:
-            for f in files:
-                f.close()
+            files.close()
 
 
-def _write_reads_by_starts(paths, prefix, bins, made, kept, route_text=None, gz_open=None, timings=None):
+def _write_reads_by_starts(paths, opened, bins, kept, route_text=None, gz_open=None, timings=None, deflater=None):
     """the second pass of the device reader: nothing is parsed again, a block's bytes are routed by the record starts the first pass has
     kept.  The file has changed when its decompressed length differs or a remembered start does not hold the records' first byte.
-    route_text (--route device) routes a block on the GPU instead of with three boolean masks; gz_open then inflates a .gz file there too"""
+    route_text (--route device) routes a block on the GPU instead of with three boolean masks; gz_open then inflates a .gz file there too;
+    deflater (--write-gz --deflate device) then has the route calls compress the three outputs there as well (gz=True)"""
     import numpy as np
     import time
     t0 = time.perf_counter()
     route_seconds, inflate_seconds, gz_stats = 0.0, 0.0, []
-    out = [np.empty(CHUNK, dtype=np.uint8) for _ in range(3)] if route_text else None
+    gz = {"gz": True} if route_text and deflater is not None else {}
+    room = CHUNK + (31 * (-(-CHUNK // bgzf.BLOCK)) if gz else 0)        # (a member adds at most 31 bytes to its text)
+    out = [np.empty(room, dtype=np.uint8) for _ in range(3)] if route_text else None
+
+    def routed(r):
+        if gz:
+            deflater.note(r.deflate, r.deflate_seconds)
+        files.write_routed(r)
+
     for fi, path in enumerate(paths):
-        outs = ["%s.%s.%s" % (prefix, b, out_basename(path)) for b in BINS]
-        made += outs
-        files = [open(fn + ".tmp", "wb") for fn in outs]
+        files = opened(path)
         first, starts, length = kept[path]
         sess = open_session(gz_open, path) if route_text else None
         try:
@@ -558,13 +643,12 @@ def _write_reads_by_starts(paths, prefix, bins, made, kept, route_text=None, gz_
                     while 0 <= at < length:
                         end = min(at + CHUNK, length)
                         i0, i1, bounds, check_from = block_segments(starts, at, end)
-                        r = sess.route(end - at, bounds, bins[fi][i0:i1], first, check_from, out)
+                        r = sess.route(end - at, bounds, bins[fi][i0:i1], first, check_from, out, **gz)
                         route_seconds += r.seconds
                         if not r.routed or r.mismatches:
                             at = -1
                             break
-                        for b in range(3):
-                            r.out[b].tofile(files[b])
+                        routed(r)
                         at = end
                     if at == length and sess.route(1, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint8), first, 0, out).got:      # (bytes are left over)
                         at = -1
@@ -583,20 +667,19 @@ def _write_reads_by_starts(paths, prefix, bins, made, kept, route_text=None, gz_
                             break
                         i0, i1, bounds, check_from = block_segments(starts, at, end)
                         if route_text:
-                            r = route_text(buf, bounds, bins[fi][i0:i1], first, check_from, out)
+                            r = route_text(buf, bounds, bins[fi][i0:i1], first, check_from, out, **gz)
                             route_seconds += r.seconds
                             if r.mismatches:
                                 at = -1
                                 break
-                            for b in range(3):
-                                r.out[b].tofile(files[b])
+                            routed(r)
                         else:
                             if not (buf[bounds[check_from:-1]] == first[0]).all():
                                 at = -1
                                 break
                             size = np.diff(bounds)
                             for b in range(3):
-                                buf[np.repeat(bins[fi][i0:i1] == b, size)].tofile(files[b])
+                                files.write(b, buf[np.repeat(bins[fi][i0:i1] == b, size)])
                         at = end
             if at != length:
                 cli.error_exit("--write-reads: %s changed between the two passes" % path)
@@ -605,15 +688,14 @@ def _write_reads_by_starts(paths, prefix, bins, made, kept, route_text=None, gz_
                 inflate_seconds += sess.inflate_seconds
                 gz_stats.append((path, sess.stats()))
                 sess.close()
-            for f in files:
-                f.close()
+            files.close()
     if timings is not None:
         timings.update(route_seconds=route_seconds, route_inflate_seconds=inflate_seconds, route_gz_stats=gz_stats, second_pass_wall=time.perf_counter() - t0)
 
 
 def parse_args(argv):
     o = dict.fromkeys(set(VALUE_FLAGS.values()))
-    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False)
+    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False, write_gz=False)
     i = 0
     while i < len(argv):
         key = argv[i]
@@ -686,6 +768,18 @@ def check_gz_route(a, reader):
     return gz, route
 
 
+def check_write_gz(a):
+    """--write-gz and --deflate: refused before a parent is opened -> (write_gz, deflate)"""
+    deflate = a["deflate"] if a["deflate"] is not None else "host"
+    if deflate not in READERS:
+        cli.error_exit("--deflate takes host or device; %s was given" % deflate)
+    if a["write_gz"] and not a["write_reads"]:
+        cli.error_exit("--write-gz needs --write-reads: it is the bin files that are written compressed")
+    if a["deflate"] is not None and not a["write_gz"]:
+        cli.error_exit("--deflate %s needs --write-gz: it says where the bin files are compressed" % deflate)
+    return a["write_gz"], deflate
+
+
 def check_totals(m_total, p_total):
     """a parent without a single hap-mer ends the run: the rule has nothing to weigh"""
     if m_total == 0 or p_total == 0:
@@ -712,8 +806,8 @@ class _Session:
         return r
 
 
-def timing_lines(t, gz, route):
-    """JASPER_AMD_TIMING=1: what --gz device and --route device add"""
+def timing_lines(t, gz, route, deflate=None):
+    """JASPER_AMD_TIMING=1: what --gz device, --route device and --write-gz add"""
     stat = lambda st: " ".join("%s=%d" % kv for kv in st.items())      # noqa: E731
     if gz == "device":
         extensions.device_line("[triobin] gz inflate seconds by events: %.6f (first pass; the inflater's kernels and copies and the host's stitching between them)" % t.get("inflate_seconds", 0.0))
@@ -725,6 +819,11 @@ def timing_lines(t, gz, route):
         extensions.device_line("[triobin] route kernels device seconds: %.6f; gz inflate seconds by events: %.6f (second pass)" % (t["route_seconds"], t["route_inflate_seconds"]))
         for path, st in t["route_gz_stats"]:
             extensions.device_line("[triobin] gz stats %s (second pass): %s" % (path, stat(st)))
+    if deflate is not None and "deflate_raw" in t:
+        c = t.get("deflate_blocks", {})
+        extensions.device_line("[triobin] deflate %s: kernels device seconds %s; %d raw bytes, %d compressed bytes; blocks stored %s, literal-only %s, LZ %s" % (
+            deflate, "%.6f" % t["deflate_seconds"] if "deflate_seconds" in t else "NA", t["deflate_raw"], t["deflate_written"], c.get("stored", "NA"),
+            c.get("literal_only", "NA"), c.get("lz", "NA")))
 
 
 def run(argv):
@@ -732,6 +831,7 @@ def run(argv):
     a = parse_args(argv)
     reader = check_reader(a)
     gz, route = check_gz_route(a, reader)
+    write_gz, deflate = check_write_gz(a)
     reads, k, device, hap, min_markers, batch_bases = check_flags(a)
     prefix = a["prefix"] if a["prefix"] is not None else reads[0]
     mat, pat, tm, tp = extensions.open_parents(hap, k, device)
@@ -761,16 +861,16 @@ def run(argv):
         def gz_open(path):
             return _Session(mat.gz_text(path), pat, tm, tp, noted)
 
-        def route_text(buf, bounds, codes, first, check_from, out):
-            return mat.route_text(buf, bounds, codes, first, check_from, out)
+        def route_text(buf, bounds, codes, first, check_from, out, gz=False):
+            return mat.route_text(buf, bounds, codes, first, check_from, out, gz=gz)
 
         timings = {}
         try:
             per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
                                          count_text=count_text, gz_open=gz_open if gz == "device" else None, route_text=route_text if route == "device" else None,
-                                         timings=timings)
+                                         timings=timings, write_gz=write_gz, deflate=mat.deflate_bgzf if write_gz and deflate == "device" else None)
         finally:
-            timing_lines(timings, gz, route)
+            timing_lines(timings, gz, route, deflate if write_gz else None)
     finally:
         mat.close()
         pat.close()

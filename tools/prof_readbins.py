@@ -88,6 +88,8 @@ def main():
         return e2e(torch, reads, nreads, m, p, tm, tp, head)
     if mode == "gz":
         return gz_e2e(torch, reads, nreads, m, p, tm, tp, head)
+    if mode == "wgz":
+        return wgz_e2e(torch, reads, nreads, m, p, tm, tp, head)
     n = min(nreads, BATCH_BASES // rl)
     text = reads.view(-1, rl + 1)[:n, :rl].contiguous()      # the batch, packed: no separator bytes
     del reads
@@ -290,6 +292,131 @@ def gz_e2e(torch, reads, nreads, m, p, tm, tp, head):
         if rc != 0:
             break
     for fn in list(paths.values()) + [paths["out"] + ".readbins.tsv"]:
+        if os.path.exists(fn):
+            os.remove(fn)
+
+
+def deflate_block(torch, m, text, head):
+    """the compressor on 64 MiB of the file's text: five timed calls after a warm-up (HIP events), next to a device-to-device copy of the
+    same bytes; its size next to the host compressor's (zlib level 1, the same blocking, one core, timed) and zlib level 6 over the block"""
+    import zlib
+    import numpy as np
+    from jasper_amd import bgzf
+    n = 64 << 20
+    buf = text[:n]
+    out = np.empty(n + 31 * (-(-n // bgzf.BLOCK)), dtype=np.uint8)
+    got = [m.deflate_bgzf(buf, out=out) for _ in range(6)]
+    secs = [g[2] for g in got[1:]]
+    members = got[-1][0]
+    d = torch.frombuffer(bytearray(buf.tobytes()), dtype=torch.uint8).cuda()
+    e = torch.empty_like(d)
+    copies = []
+    for _ in range(6):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        e.copy_(d)
+        b.record()
+        torch.cuda.synchronize()
+        copies.append(a.elapsed_time(b) * 1e-3)
+    del d, e
+    t0 = time.perf_counter()
+    host = bgzf.compress(buf)
+    host_secs = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    six = len(zlib.compress(buf, 6))
+    six_secs = time.perf_counter() - t0
+    import gzip
+    head["deflate_block"] = {"bytes": n, "deflate_kernel_seconds": secs, "deflate_median": sorted(secs)[2], "d2d_copy_seconds": copies[1:], "d2d_median": sorted(copies[1:])[2],
+                             "counters": got[-1][1], "device_bytes": int(len(members)), "host_level1_bgzf_bytes": len(host), "host_level1_bgzf_seconds": host_secs,
+                             "zlib_level6_bytes": six, "zlib_level6_seconds": six_secs, "inflates_to_the_text": gzip.decompress(members.tobytes()) == buf.tobytes()}
+
+
+def wgz_e2e(torch, reads, nreads, m, p, tm, tp, head):
+    """`--write-gz` end to end on the workload as one level-6 .fastq.gz, every device flag on: --deflate device twice; the plain run (what
+    the parent commit writes) and `gzip -1` of its three files on one core, which is what a user does without the flag; --deflate host.
+    Every .gz file's text is held to the plain run's by SHA-256 (gzip -dc).  Then nothing else is started."""
+    import hashlib
+    import numpy as np
+    import bench
+    rl = bench.READ_LEN
+    d = os.environ.get("TMPDIR", "/tmp")
+    paths = {w: os.path.join(d, "prof_readbins_%s" % w) for w in ("mat.jf", "pat.jf", "child.fq.gz", "out")}
+    m.write_jf(paths["mat.jf"])
+    p.write_jf(paths["pat.jf"])
+    seq = reads.view(-1, rl + 1)[:, :rl].cpu().numpy()
+    del reads
+    torch.cuda.empty_cache()
+    rec = np.empty((nreads, 3 + rl + 3 + rl + 1), dtype=np.uint8)      # @r \n seq \n + \n qual \n
+    rec[:, 0:3] = np.frombuffer(b"@r\n", dtype=np.uint8)
+    rec[:, 3:3 + rl] = seq
+    rec[:, 3 + rl:6 + rl] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    rec[:, 6 + rl:6 + 2 * rl] = ord("I")
+    rec[:, -1] = 10
+    del seq
+    text = rec.reshape(-1)
+    deflate_block(torch, m, text, head)                 # (in this process: if it faults, the process ends here and no child is ever started)
+    m.close()
+    p.close()
+    torch.cuda.empty_cache()
+    write_gz(paths["child.fq.gz"], text)
+    head.update({"text_bytes": int(text.size), "gz_bytes": os.path.getsize(paths["child.fq.gz"])})
+    del rec, text
+    print(json.dumps(head), flush=True)
+    args = ["-r", paths["child.fq.gz"], "--mat-jf", paths["mat.jf"], "--pat-jf", paths["pat.jf"], "--mat-threshold", str(tm), "--pat-threshold", str(tp), "-o", paths["out"],
+            "--reader", "device", "--gz", "device", "--route", "device", "--write-reads"]
+    dev = ["--write-gz", "--deflate", "device"]
+    runs = [dev, dev, [], ["--write-gz", "--deflate", "host"]]
+    names = ["%s.%s.prof_readbins_child.fq" % (paths["out"], b) for b in ("mat", "pat", "unknown")]
+
+    def sha(cmd):
+        h = hashlib.sha256()
+        with subprocess.Popen(cmd, stdout=subprocess.PIPE) as pr:
+            for blk in iter(lambda: pr.stdout.read(1 << 24), b""):
+                h.update(blk)
+        return h.hexdigest()[:16] if pr.returncode == 0 else None
+
+    want = None
+    for i, flags in enumerate(runs):
+        t0 = time.perf_counter()
+        try:
+            r = subprocess.run([sys.executable, "-m", "jasper_amd.triobin"] + args + flags, env=dict(os.environ, PYTHONPATH=ROOT, JASPER_AMD_TIMING="1"), capture_output=True,
+                               text=True, timeout=400, cwd=ROOT)
+            rc, err = r.returncode, r.stderr
+        except subprocess.TimeoutExpired:
+            rc, err = 124, ""
+        wall = time.perf_counter() - t0
+        line = {"flags": flags, "returncode": rc, "wall_seconds": wall, "lines": [ln for ln in err.splitlines() if ln.startswith("[triobin]")], "stderr_tail": err[-400:] if rc else None}
+        if rc == 0 and not flags:                       # the plain files: their digests, then what a user does with them today
+            want = [sha(["cat", fn]) for fn in names]
+            line["plain_bytes"] = [os.path.getsize(fn) for fn in names]
+            t0 = time.perf_counter()
+            sizes = []
+            for fn in names:
+                with open(fn + ".1.gz", "wb") as f:
+                    subprocess.check_call(["gzip", "-1", "-c", fn], stdout=f)
+                sizes.append(os.path.getsize(fn + ".1.gz"))
+                os.remove(fn + ".1.gz")
+            line.update({"gzip_1_one_core_seconds": time.perf_counter() - t0, "gzip_1_bytes": sizes})
+            t0 = time.perf_counter()
+            with open(names[0], "rb") as f:
+                sample = f.read(256 << 20)
+            pr = subprocess.run(["gzip", "-6", "-c"], input=sample, stdout=subprocess.PIPE)
+            line.update({"gzip_6_sample_bytes": len(sample), "gzip_6_sample_out": len(pr.stdout), "gzip_6_sample_seconds": time.perf_counter() - t0})
+            del sample, pr
+        elif rc == 0:
+            line["gz_bytes"] = [os.path.getsize(fn + ".gz") for fn in names]
+            if i != 0:                                  # (the first device run's files are checked after the plain run has given the digests)
+                line["same_text_as_plain"] = [sha(["gzip", "-dc", fn + ".gz"]) for fn in names] == want if want else None
+        if i == 0 and rc == 0:
+            keep = [fn + ".gz.first" for fn in names]
+            for fn, k in zip(names, keep):
+                os.replace(fn + ".gz", k)
+        print(json.dumps(line), flush=True)
+        if rc != 0:
+            break
+    else:
+        print(json.dumps({"first_device_run_same_text_as_plain": [sha(["gzip", "-dc", fn + ".gz.first"]) for fn in names] == want}), flush=True)
+    for fn in list(paths.values()) + [paths["out"] + ".readbins.tsv"] + names + [fn + ".gz" for fn in names] + [fn + ".gz.first" for fn in names]:
         if os.path.exists(fn):
             os.remove(fn)
 
