@@ -354,6 +354,64 @@ double jasper_copyrep_seconds(const jasper_copyrep *r);                         
 int jasper_copyrep_retried(const jasper_copyrep *r);
 void jasper_copyrep_free(jasper_copyrep *r);
 
+/* Pair spectrum: both haplotypes of a diploid assembly against the reads.  Three resident tables of the same k on the same device --
+ * `reads` (R), `assembly` (A1) and `alt` (A2, the other haplotype), the latter two counted as jasper_table_spectrum's A is -- joined on the
+ * GPU.  No key crosses to the host.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart (the diploid mode of a k-mer evaluation).  The
+ * result is a matrix P[4][10002] of unsigned 64-bit cells, row-major:
+ *   row j     = (count in A1 >= 1 ? 1 : 0) | (count in A2 >= 1 ? 2 : 0): 0 = reads only, 1 = asm only, 2 = alt only, 3 = shared
+ *   column c  = min(min(count in R, 2^32-1), 10001), the binning of jasper_histogram: 0 = not in the reads
+ *   P[j][c], c >= 1   distinct keys of R with that (j, c)
+ *   P[j][0], j >= 1   distinct keys of A1 u A2 that R does not have, each counted once
+ *   P[0][0]           0
+ * A slot whose count is 0 is no key, in any of the tables.  With S1 = the spectrum of (R, A1) and S2 = that of (R, A2), for every c:
+ * P[1][c] + P[3][c] = sum over m >= 1 of S1[m][c], P[2][c] + P[3][c] = the same of S2, and for c >= 1 the sum over j of P[j][c] is R's
+ * histogram bin c.  Copy numbers are not kept (jasper_table_spectrum has them per assembly).
+ * Any table may be narrow or wide; all three must be whole tables (an attached owner-sharded R is refused here, unlike
+ * jasper_table_spectrum's).  No table is modified.  A different k, different devices, an attached table, or a handle given twice is
+ * JASPER_ERR, each with its own message.
+ * out_cells: 4 * 10002 words in host memory; device_seconds (may be NULL): device time of the three sweeps, HIP events. */
+int jasper_table_spectrum_pair(jasper_table *reads, jasper_table *assembly, jasper_table *alt, uint64_t *out_cells /* 4 * 10002, row-major */,
+                               double *device_seconds);
+
+/* Pair scan: WHERE on one haplotype's sequences the k-mers lie that the other haplotype does not hold.  Two resident tables of the same
+ * k on the same device -- `reads` (R) and `other` (O, the OTHER haplotype's sequences counted into a table of its own), both whole
+ * tables and different handles (otherwise JASPER_ERR as for jasper_table_spectrum_pair) -- and a set of sequences of THIS haplotype,
+ * scanned densely on the GPU as jasper_kmer_report scans them, every window looked up in both tables.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  For a sequence of n bytes and the tables' k:
+ *   window i (0 <= i <= n-k)  valid          iff all its k bytes are ACGTacgt (case folded)
+ *                             c              R's count of its canonical k-mer, clamped to 2^32-1
+ *                             b              O's count of it
+ *                             unreliable     valid and c < thre; absent: valid and c == 0 (jasper_kmer_report's rules)
+ *                             private_solid  (class 1) valid, b == 0 and c >= thre: the haplotypes differ here and the reads hold this
+ *                                            haplotype's allele (a SNP between the haplotypes gives a run of k windows on each)
+ *                             private_weak   (class 2) valid, b == 0 and c < thre: an error only this haplotype has
+ *                             class 0        otherwise; an unreliable window that is not private is an unsupported k-mer both
+ *                                            haplotypes hold.  With thre == 0 nothing is unreliable and nothing is weak
+ *   per sequence              six counters: windows, valid, unreliable, absent, private_solid, private_weak; the first four are
+ *                             jasper_kmer_report's for the same sequences and threshold
+ *   run                       a maximal range of consecutive windows of one sequence with the same non-zero class (a solid window
+ *                             directly followed by a weak one gives two runs that touch): first window, windows, the sum of c over
+ *                             them, sequence, class
+ * Sequences shorter than k (empty ones too) are legal and give zeros.  Runs are ordered by (seq, start).  Neither table is modified and
+ * the result is the same on every call.  The library sizes its run buffer by itself and repeats the scan once when there were more runs
+ * than it had room for (jasper_pairscan_retried).  Tiles are those of the report (jasper_report_tile_windows()).
+ *   jasper_pair_scan           sequences in host memory
+ *   jasper_pairscan_counts     out6 = windows, valid, unreliable, absent, private_solid, private_weak of one sequence
+ *   jasper_pairscan_runs       the run list (owned by the result)
+ *   jasper_pairscan_seconds    device time of the scan's kernels (HIP events) */
+typedef struct jasper_pairscan jasper_pairscan;
+typedef struct jasper_pair_run { int64_t start; uint64_t n_kmers; uint64_t sum_reads; uint32_t seq; uint32_t kind; } jasper_pair_run;
+int jasper_pair_scan(jasper_table *reads, jasper_table *other, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_pairscan **out);
+int jasper_pairscan_num_seqs(const jasper_pairscan *r);
+int jasper_pairscan_counts(const jasper_pairscan *r, int seq, uint64_t out6[6]);   /* windows, valid, unreliable, absent, private_solid, private_weak */
+int jasper_pairscan_runs(const jasper_pairscan *r, const jasper_pair_run **runs, uint64_t *n);
+double jasper_pairscan_seconds(const jasper_pairscan *r);                          /* device time, HIP events */
+int jasper_pairscan_retried(const jasper_pairscan *r);
+void jasper_pairscan_free(jasper_pairscan *r);
+
 /* Trio hap-mer scan and census: WHERE on the sequences the k-mers lie that only one parent's reads hold, and how many of them an assembly
  * has.  The tables, all of the same k on the same device and all different handles:
  *   mat (M), pat (P)  the mother's and the father's reads, whole tables

@@ -39,6 +39,13 @@ class CopyRun(C.Structure):
 assert C.sizeof(CopyRun) == 40
 
 
+class PairRun(C.Structure):
+    _fields_ = [("start", C.c_int64), ("n_kmers", C.c_uint64), ("sum_reads", C.c_uint64), ("seq", C.c_uint32), ("kind", C.c_uint32)]
+
+
+assert C.sizeof(PairRun) == 32
+
+
 class DupRun(C.Structure):
     _fields_ = [("start", C.c_int64), ("mate_start", C.c_int64), ("n_kmers", C.c_uint64), ("sum_reads", C.c_uint64), ("n_deficit", C.c_uint64),
                 ("seq", C.c_uint32), ("mate_seq", C.c_uint32), ("strand", C.c_uint32), ("pad", C.c_uint32)]
@@ -216,6 +223,14 @@ SYMBOLS = {
     "jasper_copyrep_seconds": (C.c_double, [_P]),
     "jasper_copyrep_retried": (C.c_int, [_P]),
     "jasper_copyrep_free": (None, [_P]),
+    "jasper_table_spectrum_pair": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_pair_scan": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(_P)]),
+    "jasper_pairscan_num_seqs": (C.c_int, [_P]),
+    "jasper_pairscan_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "jasper_pairscan_runs": (C.c_int, [_P, C.POINTER(C.POINTER(PairRun)), C.POINTER(C.c_uint64)]),
+    "jasper_pairscan_seconds": (C.c_double, [_P]),
+    "jasper_pairscan_retried": (C.c_int, [_P]),
+    "jasper_pairscan_free": (None, [_P]),
     "jasper_dup_map": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "jasper_dup_map_device": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "jasper_dupmap_num_seqs": (C.c_int, [_P]),

@@ -9,6 +9,7 @@
 #include "report.hpp"
 #include "spectra.hpp"
 #include "copies.hpp"
+#include "diploid.hpp"
 #include "hapmers.hpp"
 #include "readbins.hpp"
 #include "readtext.hpp"
@@ -59,6 +60,9 @@ static_assert(sizeof(jasper_fixrec) == sizeof(FixRec), "public and device record
 
 struct jasper_copyrep {
     CopyOut r;
+};
+struct jasper_pairscan {
+    PairOut r;
 };
 struct jasper_dupmap {
     DupOut r;
@@ -860,6 +864,25 @@ int jasper_copyrep_runs(const jasper_copyrep *r, const jasper_copy_run **runs, u
 double jasper_copyrep_seconds(const jasper_copyrep *r) { return r ? r->r.seconds : 0.0; }
 int jasper_copyrep_retried(const jasper_copyrep *r) { return r ? r->r.retried : 0; }
 void jasper_copyrep_free(jasper_copyrep *r) { delete r; }
+
+// ---- pair spectrum and pair scan of a diploid assembly (diploid.hip) ----
+static_assert(offsetof(jasper_pair_run, sum_reads) == offsetof(PairRun, sum_reads) && offsetof(jasper_pair_run, seq) == offsetof(PairRun, seq) &&
+                  offsetof(jasper_pair_run, kind) == offsetof(PairRun, kind),
+              "public and device run layouts must match");
+int jasper_table_spectrum_pair(jasper_table *reads, jasper_table *assembly, jasper_table *alt, uint64_t *out_cells, double *device_seconds) {
+    if (!reads || !assembly || !alt || !out_cells) { g_err = "bad argument"; return JASPER_ERR; }
+    return table_spectrum_pair(reads->t, assembly->t, alt->t, out_cells, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+}
+int jasper_pair_scan(jasper_table *reads, jasper_table *other, int n_seqs, const char *const *seqs, const int64_t *lens, uint32_t thre, jasper_pairscan **out) {
+    return scan_call(host_args(n_seqs, seqs, lens), reads && other, n_seqs, out,
+                     [&](jasper_pairscan &r) { return pair_scan_host(reads->t, other->t, n_seqs, seqs, lens, thre, r.r, g_err); });
+}
+int jasper_pairscan_num_seqs(const jasper_pairscan *r) { return r ? (int)(r->r.counts.size() / 6) : 0; }
+int jasper_pairscan_counts(const jasper_pairscan *r, int seq, uint64_t out6[6]) { return counts_out<6>(r ? &r->r.counts : nullptr, seq, out6); }
+int jasper_pairscan_runs(const jasper_pairscan *r, const jasper_pair_run **runs, uint64_t *n) { return records_out(r ? &r->r.runs : nullptr, runs, n); }
+double jasper_pairscan_seconds(const jasper_pairscan *r) { return r ? r->r.seconds : 0.0; }
+int jasper_pairscan_retried(const jasper_pairscan *r) { return r ? r->r.retried : 0; }
+void jasper_pairscan_free(jasper_pairscan *r) { delete r; }
 
 // ---- duplication map (dups.hip) ----
 static_assert(offsetof(jasper_dup_run, mate_start) == offsetof(DupRun, mate_start) && offsetof(jasper_dup_run, n_deficit) == offsetof(DupRun, n_deficit) &&

@@ -15,7 +15,6 @@
 // of them before any is resolved (table_get_prefetched): a sweep is otherwise one dependent HBM round trip per key.  One flush per
 // workgroup: 64-bit global adds of the non-zero bins; integer sums, so the result does not depend on the order.
 #include "spectra.hpp"
-#include <algorithm>
 #include <vector>
 
 namespace jk {
@@ -28,36 +27,6 @@ namespace jk {
             return -1;                                                                \
         }                                                                             \
     } while (0)
-
-// SP_BATCH slots of the swept table per thread and trip: slot, hash and count of those that hold a key, and the home slot of each key
-// in the other table O (loads issued together).  `slots` = the swept slot array (S.slots, or one shard of an attached S).
-struct SpBatch {
-    u128 h[SP_BATCH];
-    unsigned long long cnt[SP_BATCH];    // count in the swept table (0: no key)
-    ulonglong2 ent[SP_BATCH];            // the key's home slot in the other table
-};
-__device__ __forceinline__ void sp_load(const TableDev &S, const unsigned long long *__restrict__ slots, const TableDev &O, uint64_t base, uint64_t stride,
-                                        uint64_t nslots, SpBatch &b) {
-    ulonglong2 e[SP_BATCH];
-#pragma unroll
-    for (int u = 0; u < SP_BATCH; ++u) {
-        const uint64_t i = base + (uint64_t)u * stride;
-        e[u] = make_ulonglong2(0ull, 0ull);
-        if (i < nslots) e[u] = *reinterpret_cast<const ulonglong2 *>(slots + 2 * i);   // tag + count, one 16-B load
-    }
-#pragma unroll
-    for (int u = 0; u < SP_BATCH; ++u) {
-        const uint64_t i = base + (uint64_t)u * stride;
-        const bool key = e[u].x != 0ull && e[u].y != 0ull;      // (a slot whose count is 0 is no key: histo_kernel's rule)
-        b.cnt[u] = key ? e[u].y : 0ull;
-        b.h[u] = mk(0, 0);
-        b.ent[u] = make_ulonglong2(0ull, 0ull);
-        if (key) {
-            b.h[u] = slot_hash(S, i, e[u].x);
-            b.ent[u] = *reinterpret_cast<const ulonglong2 *>(read_slots(O, b.h[u]) + 2 * home_of(b.h[u], O.B, O.s));
-        }
-    }
-}
 
 __global__ __launch_bounds__(SP_THREADS) void spectra_reads_kernel(TableDev R, const unsigned long long *__restrict__ slots, TableDev A,
                                                                    unsigned long long *__restrict__ out) {
@@ -81,8 +50,7 @@ __global__ __launch_bounds__(SP_THREADS) void spectra_reads_kernel(TableDev R, c
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < SP_ROWS * SP_LDS_COLS; i += SP_THREADS)
-        if (bins[i]) atomicAdd(&out[(size_t)(i / SP_LDS_COLS) * SP_COLS + (i % SP_LDS_COLS)], (unsigned long long)bins[i]);
+    sp_flush<SP_ROWS>(bins, out);
 }
 
 __global__ __launch_bounds__(SP_THREADS) void spectra_asm_kernel(TableDev A, TableDev R, unsigned long long *__restrict__ out) {
@@ -131,13 +99,6 @@ struct Events {
     hipEvent_t e[3] = {nullptr, nullptr, nullptr};
     ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
-// workgroups of a sweep: fills the chip (256 CUs x 8), the rest is grid-stride; a workgroup's 32-bit LDS bins hold what it sweeps
-unsigned sweep_grid(uint64_t nslots) {
-    uint64_t b = (nslots + (uint64_t)SP_THREADS * SP_BATCH - 1) / ((uint64_t)SP_THREADS * SP_BATCH);
-    b = std::min<uint64_t>(std::max<uint64_t>(b, 1), 256 * 8);
-    while (nslots / b >= 0xFFFFFFFFull) b *= 2;
-    return (unsigned)b;
-}
 }  // namespace
 
 int table_spectrum(Table &R, Table &A, uint64_t *out, double *seconds, std::string &err) {

@@ -5,6 +5,9 @@ through the reads' table while it is in HBM, none of which has a counterpart in 
     its scan           of one text: scan_* / run_repair / Run.asm_scans
     its files and log  *_files, from a list of scanned stages [(stage, Text, result)]
 
+kmerqc's --alt (the other haplotype of a diploid assembly: alt_flag, diploid_scans, diploid_files) is the evaluator's alone and is not in
+the flag tables: the driver does not take it.
+
 The list of stages is before / after (the input assembly and the polished FASTA) for the driver and asm for kmerqc.  A file is
 PREFIX.<stem>[.<stage>].<ext>, the stage only when there are two (Run.name); a log line is "X: before polishing A; after polishing B"
 for two stages and "X: A in PREFIX.file" for one (stages_log), A and B being the writer module's stage_log_text.  What a run shares --
@@ -328,9 +331,10 @@ class Run:
         from . import copies
         return copies_peak(given, copies.histogram_from_rows(self.histo()), self.thresh)
 
-    def asm_scans(self, stage, hapmers=None):
-        """the stage's text counted into a table of its own -- ONCE, it serves --spectra, --copies, --dups and, for kmerqc, --hapmers
-        (hapmers(text, asm) -> hapmers_scan's three) -- and closed before anything else is counted: {extension: (stage, Text, result)}"""
+    def asm_scans(self, stage, hooks=None):
+        """the stage's text counted into a table of its own -- ONCE, it serves --spectra, --copies, --dups and, for kmerqc, what `hooks`
+        names: {extension: work(text, asm) -> its result} in the order they are to run (--hapmers: hapmers_scan's three; --alt:
+        diploid_scans' three) -- and closed before anything else is counted: {extension: (stage, Text, result)}"""
         o, f, text, out = self.o, self.f, self.text(stage), {}
         asm = assembly_table(self.table, text.contigs)
         try:
@@ -340,8 +344,8 @@ class Run:
                 out["copies"] = (stage, text, self.table.copy_report(asm, text.seqs, self.thresh, f["peak"]))
             if o.dups:
                 out["dups"] = (stage, text, self.table.dup_map(asm, text.seqs, self.thresh, f["dups_peak"]))
-            if hapmers is not None:
-                out["hapmers"] = (stage, text, hapmers(text, asm))
+            for what, work in (hooks or {}).items():
+                out[what] = (stage, text, work(text, asm))
         finally:
             asm.close()
         return out
@@ -691,6 +695,49 @@ def hapmers_files(run, done):
     stages_log(run, "Hap-mer scan (thresholds mat %d pat %d child %d)" % (tm, tp, run.thresh), [hapmers.stage_log_text(st, cen) for _, _, (st, cen, _) in done],
                run.name("hapmers", "bed"))
     device_line("[hapmers] scan device seconds: %s; census device seconds: %s" % (per_stage(done, "%.6f", lambda r: r[2].seconds), per_stage(done, "%.6f", lambda r: r[1].seconds)))
+
+
+def alt_flag(alt, asm):
+    """kmerqc's --alt as given (None or a path), checked before anything is counted; exits on a file that does not exist, is empty or is
+    the -a file itself"""
+    if alt is None:
+        return
+    if not _cli()._nonempty(alt):
+        error_exit("--alt: %s does not exist or is empty. Please supply the other haplotype's fasta file." % alt)
+    if os.path.samefile(alt, asm):
+        error_exit("--alt: %s is the -a assembly itself; give the OTHER haplotype's fasta file" % alt)
+
+
+def diploid_scans(run, text, asm, alt_text):
+    """--alt (kmerqc): the other haplotype's contigs counted into a table of their own beside `asm` (the -a assembly's, which the caller
+    has and keeps), the three tables joined (KmerTable.spectrum_pair) and each haplotype's contigs scanned against the reads' table and
+    the OTHER haplotype's (KmerTable.pair_scan) -> (PairSpectrum, PairScan of asm, PairScan of alt)"""
+    table = run.table
+    alt = assembly_table(table, alt_text.contigs)
+    try:
+        return table.spectrum_pair(asm, alt), table.pair_scan(alt, text.seqs, run.thresh), table.pair_scan(asm, alt_text.seqs, run.thresh)
+    finally:
+        alt.close()
+
+
+def diploid_files(run, text, alt_text, res):
+    """--alt (kmerqc): `PREFIX.spectra_asm.tsv`, `PREFIX.diploid.completeness.tsv`, `PREFIX.diploid.tsv` and
+    `PREFIX.private.{asm,alt}.bed` (jasper_amd/diploid.py) and three log lines.  res: diploid_scans' three."""
+    from . import diploid
+    k = run.k
+    pair, scan_asm, scan_alt = res
+    rows = diploid.completeness_rows(pair, run.thresh)
+    diploid.write_atomic(run.name("spectra_asm", "tsv"), diploid.spectra_asm_text(pair))
+    diploid.write_atomic(run.name("diploid.completeness", "tsv"), diploid.completeness_text(k, rows))
+    diploid.write_atomic(run.name("diploid", "tsv"), diploid.diploid_tsv_text(k, [("asm", text.names, text.lengths, scan_asm.counts),
+                                                                                  ("alt", alt_text.names, alt_text.lengths, scan_alt.counts)]))
+    diploid.write_atomic(run.name("private.asm", "bed"), diploid.bed_text(k, text.names, scan_asm.runs))
+    diploid.write_atomic(run.name("private.alt", "bed"), diploid.bed_text(k, alt_text.names, scan_alt.runs))
+    log("Diploid %s" % diploid.completeness_log_text(rows))
+    log("Diploid %s" % diploid.qv_log_text(k, scan_asm.counts, scan_alt.counts))
+    log("Diploid %s in %s and %s" % (diploid.private_log_text(scan_asm.counts, scan_asm.runs, scan_alt.counts, scan_alt.runs), run.name("private.asm", "bed"),
+                                     run.name("private.alt", "bed")))
+    device_line("[diploid] device seconds: join %.6f scan asm %.6f scan alt %.6f" % (pair.seconds, scan_asm.seconds, scan_alt.seconds))
 
 
 def repair_files(run, text, rp):

@@ -1,6 +1,6 @@
 """Stand-alone k-mer evaluator: the dense k-mer report of an assembly against reads or an existing Jellyfish database.
 
-    python -m jasper_amd.kmerqc -a asm.fa (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
+    python -m jasper_amd.kmerqc -a asm.fa [--alt hap2.fa] (-r 'R1.fq R2.fq' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra]
                                 [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants]
                                 [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]]
                                 [--compound [--compound-max-len N]] [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs]]
@@ -91,6 +91,20 @@ threshold defaults to what that parent's histogram gives; the child's is the run
     PREFIX.phased_blocks.bed         one line per phase block (--phase-short-range, default 20000; --phase-max-switches, default 100)
     PREFIX.hapmer_completeness.tsv   two rows (mat, pat): hap-mers, how many the assembly holds, completeness, occurrences
 
+With --alt hap2.fa the -a assembly is ONE haplotype of a diploid assembly and hap2.fa the other: its contigs are counted into a table of
+their own as well, the three tables are joined (KmerTable.spectrum_pair) and each haplotype's contigs are scanned against the reads'
+table and the OTHER haplotype's (KmerTable.pair_scan; the -a assembly's table is the one --spectra, --copies, --dups and --hapmers
+use, counted once).  Every other flag keeps describing the -a assembly alone, and its files are what they are without --alt.  Five
+more files and three log lines (jasper_amd/diploid.py); the driver has no such flag:
+
+    PREFIX.spectra_asm.tsv           distinct k-mers by class (reads_only, asm_only, alt_only, shared) and count in the reads
+    PREFIX.diploid.completeness.tsv  three rows (asm, alt, both): the share of the reads' solid k-mers the set holds, k-mers not in the reads
+    PREFIX.diploid.tsv               per contig of each haplotype, then `asm *`, `alt *`, `both *`: the report's counters and QV, private_solid
+                                     (the haplotypes differ, the reads hold this allele), private_weak (an error only this haplotype
+                                     has), shared_unreliable, private_fraction
+    PREFIX.private.asm.bed           one line per run of private windows of the -a contigs: contig start end solid|weak n_kmers mean_reads
+    PREFIX.private.alt.bed           the same for the --alt contigs
+
 PREFIX defaults to the assembly's file name.  Nothing is polished and no other file is written.
 
 The flags, the scans, the files and the log lines are the driver's, described once for both in jasper_amd/extensions.py; here the list
@@ -102,13 +116,13 @@ import sys
 from . import cli, extensions, polisher
 from .table import KmerTable
 
-USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
+USAGE = "Usage: python -m jasper_amd.kmerqc -a asm.fa [--alt hap2.fa] (-r 'reads...' | -j db.jf) [-k 37] [--threshold N] [-o PREFIX] [--device D] [--spectra] [--copies [--peak N] [--copies-min-run N]] [--dups [--peak N] [--dups-min-run N]] [--variants] [--indels [--indel-max-len N] [--indel-mixed] [--het-clusters [--het-cluster-max-len N]]] [--compound [--compound-max-len N]] [--gaps [--gap-max-len N] [--gap-max-trim N] [--gap-long-runs]] [--hapmers (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [--mat-threshold N] [--pat-threshold N] [--phase-short-range D] [--phase-max-switches S]]"
 NOT_HERE = ("--report", "--repair", "--repair-rounds", "--gaps-fill")      # of the extension flags: the report is always written, nothing is repaired, no assembly is written
 
 
 def parse_args(argv):
-    o = dict(extensions.flag_defaults(), asm=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0)
-    keys = {"-a": "asm", "--assembly": "asm", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
+    o = dict(extensions.flag_defaults(), asm=None, alt=None, reads=None, jf=None, k="37", threshold=None, prefix=None, device=0)
+    keys = {"-a": "asm", "--assembly": "asm", "--alt": "alt", "-r": "reads", "--reads": "reads", "-j": "jf", "--jf": "jf", "-k": "k", "--kmer": "k",
             "--threshold": "threshold", "-o": "prefix", "--device": "device"}
     keys.update((f, a) for f, a in extensions.VALUE_FLAGS.items() if f not in NOT_HERE)
     keys["--copies-min-run"] = "min_run"        # (the name it has always had in this result; run() hands it on as copies_min_run)
@@ -147,6 +161,7 @@ def run(argv):
     o = type("KmerqcOptions", (), dict(a, copies_min_run=a["min_run"]))
     f = extensions.check_flags(o, k, a["jf"], given)
     hap = f["hap"]
+    extensions.alt_flag(a["alt"], a["asm"])
     if a["jf"] is not None:
         try:
             table = KmerTable.from_jf(a["jf"], device=device)
@@ -169,6 +184,7 @@ def run(argv):
     run = extensions.Run(table, prefix, {"asm": a["asm"]}, o, f, hap, table.histo_rows, given)
     run.derive_peaks()
     text = run.text("asm")
+    alt_text = extensions.Text(a["alt"]) if a["alt"] is not None else None
     # every scan first, then the table goes, then the files
     if o.compound:
         cscan = extensions.scan_compound(table, text.contigs, given, f["compound_max_len"])[2]      # (its dense scan is the report's)
@@ -182,9 +198,13 @@ def run(argv):
             cli.error_exit("--hapmers needs a threshold of at least 1; the histogram gave %d: give --threshold" % given)
         return extensions.with_parents(run, lambda parents: extensions.hapmers_scan(run, text, parents, asm))
 
-    own = {}
-    if o.spectra or o.copies or o.dups or hap is not None:
-        own = run.asm_scans("asm", trio if hap is not None else None)          # the assembly's table: counted once, it serves all of them
+    own, hooks = {}, {}
+    if hap is not None:
+        hooks["hapmers"] = trio
+    if alt_text is not None:
+        hooks["diploid"] = lambda text, asm: extensions.diploid_scans(run, text, asm, alt_text)
+    if o.spectra or o.copies or o.dups or hooks:
+        own = run.asm_scans("asm", hooks)          # the assembly's table: counted once, it serves all of them
     iscan = extensions.scan_indels(table, text.contigs, given, f["indel_max_len"], o.indel_mixed, f["clusters"])[2] if o.indels else None
     vscan = extensions.scan_variants(table, text.contigs, given)[2] if o.variants and iscan is None else None
     table.close()
@@ -206,6 +226,8 @@ def run(argv):
         extensions.gaps_files(run, [("asm", text, gscan)])
     if o.dups:
         extensions.dups_files(run, [own["dups"]])
+    if alt_text is not None:
+        extensions.diploid_files(run, text, alt_text, own["diploid"][2])      # after everything else: the other files and log lines are what they are without --alt
     return 0
 
 

@@ -162,6 +162,44 @@ class CopyReport:
         return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"]), int(r["sum_asm"])) for r in self.runs]
 
 
+class PairSpectrum:
+    """pair spectrum of a read table and the tables of both haplotypes of a diploid assembly (include/jasper_hip.h:
+    jasper_table_spectrum_pair): `cells` = numpy uint64 array (4, 10002), cells[j][c] = distinct k-mers with j = (in asm ? 1 : 0) |
+    (in alt ? 2 : 0) and min(count in the reads, 10001) = c (column 0: not in the reads), `seconds` = device time of the three
+    sweeps.  The numbers derived from it and the files: jasper_amd/diploid.py."""
+
+    def __init__(self, cells, seconds):
+        self.cells = cells
+        self.seconds = seconds
+
+    def __eq__(self, other):
+        return isinstance(other, PairSpectrum) and self.cells.shape == other.cells.shape and bool((self.cells == other.cells).all())
+
+
+PAIRRUN_DTYPE = [("start", "<i8"), ("n_kmers", "<u8"), ("sum_reads", "<u8"), ("seq", "<u4"), ("kind", "<u4")]
+PAIR_KINDS = {1: "solid", 2: "weak"}
+
+
+class PairScan:
+    """scan of one haplotype's sequences against the reads' table and the other haplotype's (include/jasper_hip.h:
+    jasper_pair_scan): `counts[i]` = (windows, valid, unreliable, absent, private_solid, private_weak) of sequence i, `runs` = numpy
+    structured array (PAIRRUN_DTYPE) of the maximal runs of one class (kind 1 = private and solid, 2 = private and weak) ordered
+    by (seq, start), `seconds` = device time of the kernels.  The files made from it: jasper_amd/diploid.py."""
+
+    def __init__(self, counts, runs, seconds, retried):
+        self.counts = counts
+        self.runs = runs
+        self.seconds = seconds
+        self.retried = retried
+
+    def __eq__(self, other):
+        return isinstance(other, PairScan) and self.counts == other.counts and self.runs.tobytes() == other.runs.tobytes()
+
+    def run_tuples(self):
+        """[(seq, start, n_kmers, kind, sum_reads)]"""
+        return [(int(r["seq"]), int(r["start"]), int(r["n_kmers"]), int(r["kind"]), int(r["sum_reads"])) for r in self.runs]
+
+
 DUPRUN_DTYPE = [("start", "<i8"), ("mate_start", "<i8"), ("n_kmers", "<u8"), ("sum_reads", "<u8"), ("n_deficit", "<u8"), ("seq", "<u4"), ("mate_seq", "<u4"),
                 ("strand", "<u4"), ("pad", "<u4")]
 
@@ -1097,6 +1135,37 @@ class KmerTable:
         finally:
             if res:
                 self._L.jasper_copyrep_free(res)
+
+    # ---- both haplotypes of a diploid assembly (an extension: no counterpart in the reference) ------------
+    def spectrum_pair(self, asm_table, alt_table):
+        """this table as the reads' counts joined on the GPU with `asm_table` and `alt_table` (whole KmerTables of the same k on the
+        same device, one haplotype's assembly counted into each) -> PairSpectrum; no table is modified"""
+        import numpy as np
+        for t, name in ((asm_table, "assembly"), (alt_table, "alt assembly")):
+            if not isinstance(t, KmerTable) or not t._h:
+                raise TypeError("spectrum_pair: the %s must be an open KmerTable" % name)
+        cells = np.zeros((4, 10002), dtype=np.uint64)
+        secs = C.c_double(0)
+        check(self._L.jasper_table_spectrum_pair(self._h, asm_table._h, alt_table._h, cells.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(secs)))
+        return PairSpectrum(cells, secs.value)
+
+    def pair_scan(self, other_table, seqs, thre):
+        """this table as the reads' counts, `other_table` the OTHER haplotype's (a whole KmerTable of the same k on the same device),
+        `seqs` the sequences of THIS haplotype: per-sequence counters and the runs of windows the other haplotype does not hold,
+        solid (the reads hold them `thre` times or more) or weak -> PairScan; neither table is modified"""
+        if not isinstance(other_table, KmerTable) or not other_table._h:
+            raise TypeError("pair_scan: the other haplotype must be an open KmerTable")
+        n, cs, lens = _seq_args(seqs)
+        res = C.c_void_p()
+        rc = self._L.jasper_pair_scan(self._h, other_table._h, n, cs, lens, int(thre), C.byref(res))
+        try:
+            check(rc)
+            counts = _counts(self._L.jasper_pairscan_num_seqs, self._L.jasper_pairscan_counts, res, 6)
+            runs = _records(self._L.jasper_pairscan_runs, res, _lib.PairRun, PAIRRUN_DTYPE)
+            return PairScan(counts, runs, self._L.jasper_pairscan_seconds(res), bool(self._L.jasper_pairscan_retried(res)))
+        finally:
+            if res:
+                self._L.jasper_pairscan_free(res)
 
     # ---- duplication map (an extension: no counterpart in the reference) ----------------------------------
     def dup_map(self, assembly_table, seqs, thre, peak):
