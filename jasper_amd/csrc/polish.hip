@@ -1153,109 +1153,161 @@ __global__ __launch_bounds__(64, 2) void seg_walk_kernel(TableDev T, SegDev *seg
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SC_THREADS = 256, SC_GROUP = 16, SC_TILE = SC_THREADS * SC_GROUP, SC_HALO = 4;
 
-// copy each segment's text range out of its chunk into the segment's gap buffer (text right of the gap)
-__global__ __launch_bounds__(256) void seg_init_kernel(SegDev *segs, int n_segs, const uint8_t *const *chunk_text) {
+// ---- the kernels around the walk take their work as a flat list of (segment, 4 KiB piece): segments run from a few hundred bytes
+// to a whole clean cell, and "blocks per segment" left a pass waiting for the blocks of its longest one.  The host knows every
+// segment's pass-start lengths (make_pieces); what a walk added or removed falls to the segment's last piece.
+__device__ __forceinline__ void piece_range(const SegPiece P, int64_t n, int64_t &q_lo, int64_t &q_hi) {
+    q_lo = (int64_t)(P.piece & ~SEG_PIECE_LAST) * SEG_PIECE;
+    q_hi = (P.piece & SEG_PIECE_LAST) ? n : q_lo + SEG_PIECE;
+    if (q_hi > n) q_hi = n;
+}
+
+// copy each segment's text range out of its chunk into the segment's gap buffer (text right of the gap); and preset what the walk
+// behind it and the next pass expect, instead of fills on the stream: the arrive slots (with the two guard slots), the walk's ticket,
+// the candidate count (fetched by now) and the changed-text flags (read by now; the stitch sets them again)
+__global__ __launch_bounds__(256) void seg_init_kernel(const SegDev *__restrict__ segs, const SegPiece *__restrict__ work, int n_work,
+                                                       const uint8_t *const *__restrict__ chunk_text, PassPreset Z) {
     struct __attribute__((packed, aligned(1))) V16 { uint32_t w[4]; };
-    for (int s = blockIdx.y; s < n_segs; s += gridDim.y) {
-        const SegDev S = segs[s];
-        const uint8_t *src = chunk_text[S.chunk] + S.seg_lo;
-        uint8_t *dst = S.buf + S.glen;
-        const int64_t nblk = (S.len0 + 15) >> 4;
-        for (int64_t blk = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; blk < nblk; blk += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t q0 = blk << 4;
-            if (q0 + 16 <= S.len0) *reinterpret_cast<V16 *>(dst + q0) = *reinterpret_cast<const V16 *>(src + q0);
-            else for (int64_t q = q0; q < S.len0; ++q) dst[q] = src[q];
+    const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gn = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = gt; i < Z.n_arrive; i += gn) Z.arrive[i] = ARRIVE_PENDING;
+    for (int64_t i = gt; i < Z.n_flag16; i += gn) reinterpret_cast<uint4 *>(Z.flags)[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (gt == 0) {
+        *Z.ticket = 0u;
+        if (Z.cand_count) *Z.cand_count = 0u;
+    }
+    for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const SegPiece P = work[w];
+        const SegDev *__restrict__ S = segs + P.seg;
+        const int64_t len0 = S->len0;
+        const uint8_t *src = chunk_text[S->chunk] + S->seg_lo;
+        uint8_t *dst = S->buf + S->glen;
+        int64_t q_lo, q_hi;
+        piece_range(P, len0, q_lo, q_hi);
+        for (int64_t q0 = q_lo + (int64_t)threadIdx.x * 16; q0 < q_hi; q0 += (int64_t)blockDim.x * 16) {
+            if (q0 + 16 <= len0) *reinterpret_cast<V16 *>(dst + q0) = *reinterpret_cast<const V16 *>(src + q0);
+            else for (int64_t q = q0; q < len0; ++q) dst[q] = src[q];
         }
     }
 }
 
-// write each segment's owned part of the polished text into the chunk's new text.  With cls_out it also carries the
+// After a pass's walks, one launch (seg_finish_kernel): blocks 0 .. n_work - 1 stitch, the blocks behind them gather.
+//
+// Stitch: write each segment's owned part of the polished text into the chunk's new text.  With cls_out it also carries the
 // position classes over: a new position is traced back through the segment's edits (newest first); if it lands in or
-// next to replaced text its 64-position tile is flagged for the rescan, otherwise its old class is copied.
+// next to replaced text its 64-position tile is flagged for the rescan, otherwise its old class is copied.  (Flags are only ever
+// SET here -- a tile may belong to two segments; seg_init_kernel cleared them.)
+//
+// Gather: pack the fix records (and aux bytes) of all segments of a pass into compact arrays, turning segment-local
+// coordinates into chunk coordinates: index += idx_base, seqno += seq_base, aux_off += aux_base.  One wave per segment.  With `sum`
+// (the device's bookkeeping) rec_off / aux_off count from the chunk's first record and the records of the chunks before it are
+// added here; without (the host's) they are offsets into the pass's arrays already.
 constexpr uint32_t STITCH_MAX_EDITS = 32;   // beyond this the whole segment is flagged (always safe: flagged = recomputed)
-__global__ __launch_bounds__(256) void seg_stitch_kernel(const SegDev *segs, int n_segs, uint8_t *const *chunk_out, uint8_t *const *cls_out,
-                                                         uint8_t *const *flags) {
+__global__ __launch_bounds__(256) void seg_finish_kernel(const SegDev *__restrict__ segs, int n_segs, const SegPiece *__restrict__ work, int n_work,
+                                                         uint8_t *const *__restrict__ chunk_out, uint8_t *const *__restrict__ cls_out,
+                                                         uint8_t *const *__restrict__ flags, const int64_t *__restrict__ idx_base,
+                                                         const uint32_t *__restrict__ seq_base, const uint32_t *__restrict__ rec_off,
+                                                         const uint32_t *__restrict__ aux_off, const ChunkSummary *__restrict__ sum, FixRec *out_recs,
+                                                         uint8_t *out_aux) {
     struct __attribute__((packed, aligned(1))) V16 { uint32_t w[4]; };
-    for (int s = blockIdx.y; s < n_segs; s += gridDim.y) {
-        const SegDev S = segs[s];
-        uint8_t *dst = chunk_out[S.chunk] + S.out_off;
-        uint8_t *cdst = cls_out ? cls_out[S.chunk] + S.out_off : nullptr;
-        uint8_t *fl = cls_out ? flags[S.chunk] : nullptr;
-        const int64_t n = S.own_hi - S.own_lo;
-        const bool all_dirty = S.nedit > STITCH_MAX_EDITS;
-        const int64_t nblk = (n + 15) >> 4;
-        for (int64_t blk = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; blk < nblk; blk += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t q0 = blk << 4;
-            const int64_t p0 = S.own_lo + q0;
-            const bool full = q0 + 16 <= n;
-            bool text_done = false, cls_done = !cdst;
-            if (full && (p0 + 16 <= S.gs || p0 >= S.gs)) {                 // sixteen text bytes on one side of the gap
-                *reinterpret_cast<V16 *>(dst + q0) = *reinterpret_cast<const V16 *>(S.buf + (p0 < S.gs ? p0 : p0 + S.glen));
-                text_done = true;
+    __shared__ EditRec s_edits[STITCH_MAX_EDITS];
+    if ((int)blockIdx.x >= n_work) {
+        const int lane = threadIdx.x & 63;
+        const int s = ((int)blockIdx.x - n_work) * 4 + (threadIdx.x >> 6);
+        if (s >= n_segs) return;
+        const SegDev *__restrict__ S = segs + s;
+        const uint32_t nrec = S->nrec, naux = S->naux;
+        if (!(nrec | naux)) return;
+        uint32_t rb = rec_off[s], ab = aux_off[s];
+        if (sum) {
+            const int c = (int)S->chunk;
+            uint32_t r = 0, a = 0;
+            for (int q = lane; q < c; q += 64) { r += sum[q].nrec; a += sum[q].naux; }
+            for (int o = 32; o > 0; o >>= 1) { r += __shfl_xor(r, o); a += __shfl_xor(a, o); }
+            rb += r; ab += a;
+        }
+        const FixRec *recs = S->recs;
+        const uint8_t *aux = S->aux;
+        const int64_t ib = idx_base[s];
+        const uint32_t sb = seq_base[s];
+        for (uint32_t r = lane; r < nrec; r += 64) {
+            FixRec f = recs[r];
+            f.index += ib;
+            f.seqno += sb;
+            if (f.kind == 'x') f.aux_off += ab;
+            out_recs[rb + r] = f;
+        }
+        for (uint32_t q = lane; q < naux; q += 64) out_aux[ab + q] = aux[q];
+        return;
+    }
+    const SegPiece P = work[blockIdx.x];
+    const SegDev *__restrict__ S = segs + P.seg;
+    const uint32_t chunk = S->chunk, nedit = S->nedit;
+    const int64_t own_lo = S->own_lo, out_off = S->out_off, gs = S->gs, glen = S->glen, seg_lo = S->seg_lo, cls_n = S->cls_n;
+    const int64_t n = S->own_hi - own_lo;
+    const uint8_t *buf = S->buf, *cls = S->cls;
+    uint8_t *dst = chunk_out[chunk] + out_off;
+    uint8_t *cdst = cls_out ? cls_out[chunk] + out_off : nullptr;
+    uint8_t *fl = cls_out ? flags[chunk] : nullptr;
+    const bool all_dirty = nedit > STITCH_MAX_EDITS;
+    const int ne = (cdst && !all_dirty) ? (int)nedit : 0;
+    if ((int)threadIdx.x < ne) s_edits[threadIdx.x] = S->edits[threadIdx.x];
+    __syncthreads();
+    int64_t q_lo, q_hi;
+    piece_range(P, n, q_lo, q_hi);
+    for (int64_t q0 = q_lo + (int64_t)threadIdx.x * 16; q0 < q_hi; q0 += (int64_t)blockDim.x * 16) {
+        const int64_t p0 = own_lo + q0;
+        const bool full = q0 + 16 <= n;
+        bool text_done = false, cls_done = !cdst;
+        if (full && (p0 + 16 <= gs || p0 >= gs)) {                 // sixteen text bytes on one side of the gap
+            *reinterpret_cast<V16 *>(dst + q0) = *reinterpret_cast<const V16 *>(buf + (p0 < gs ? p0 : p0 + glen));
+            text_done = true;
+        }
+        if (full && cdst && !all_dirty) {
+            // sixteen classes with one common shift: trace the block's two ends through the edits together; as long as
+            // both lie on the same side of every edit (and outside its one-position margin) so does everything between
+            int64_t lA = p0, lB = p0 + 15;
+            bool uniform = true;
+            for (int e = ne - 1; e >= 0; --e) {
+                const EditRec E = s_edits[e];
+                if (lA > E.a + E.plen) { const int64_t d = (int64_t)E.plen - E.oldlen; lA -= d; lB -= d; }
+                else if (lB < E.a - 1) { }
+                else { uniform = false; break; }
             }
-            if (full && cdst && !all_dirty) {
-                // sixteen classes with one common shift: trace the block's two ends through the edits together; as long as
-                // both lie on the same side of every edit (and outside its one-position margin) so does everything between
-                int64_t lA = p0, lB = p0 + 15;
-                bool uniform = true;
-                for (int e = (int)S.nedit - 1; e >= 0; --e) {
-                    const EditRec E = S.edits[e];
-                    if (lA > E.a + E.plen) { const int64_t d = (int64_t)E.plen - E.oldlen; lA -= d; lB -= d; }
-                    else if (lB < E.a - 1) { }
-                    else { uniform = false; break; }
-                }
-                if (uniform && S.seg_lo + lB < S.cls_n) {
-                    *reinterpret_cast<V16 *>(cdst + q0) = *reinterpret_cast<const V16 *>(S.cls + S.seg_lo + lA);
-                    cls_done = true;
-                }
+            if (uniform && seg_lo + lB < cls_n) {
+                *reinterpret_cast<V16 *>(cdst + q0) = *reinterpret_cast<const V16 *>(cls + seg_lo + lA);
+                cls_done = true;
             }
-            if (text_done && cls_done) continue;
-            const int64_t qe = q0 + 16 < n ? q0 + 16 : n;
-            for (int64_t q = q0; q < qe; ++q) {
-                const int64_t p = S.own_lo + q;
-                if (!text_done) dst[q] = S.buf[p < S.gs ? p : p + S.glen];
-                if (cls_done) continue;
-                int64_t l = p;
-                bool dirty = all_dirty;
-                if (!dirty)
-                    for (int e = (int)S.nedit - 1; e >= 0; --e) {
-                        const EditRec E = S.edits[e];
-                        if (l > E.a + E.plen) l -= (int64_t)E.plen - E.oldlen;
-                        else if (l >= E.a - 1) { dirty = true; break; }
-                    }
-                if (dirty) {
-                    fl[(S.out_off + q) >> 6] = 1;
-                    cdst[q] = PC_OTHER;
-                } else {
-                    const int64_t old = S.seg_lo + l;
-                    cdst[q] = old < S.cls_n ? S.cls[old] : (uint8_t)PC_OTHER;
+        }
+        if (text_done && cls_done) continue;
+        const int64_t qe = q0 + 16 < n ? q0 + 16 : n;
+        for (int64_t q = q0; q < qe; ++q) {
+            const int64_t p = own_lo + q;
+            if (!text_done) dst[q] = buf[p < gs ? p : p + glen];
+            if (cls_done) continue;
+            int64_t l = p;
+            bool dirty = all_dirty;
+            if (!dirty)
+                for (int e = ne - 1; e >= 0; --e) {
+                    const EditRec E = s_edits[e];
+                    if (l > E.a + E.plen) l -= (int64_t)E.plen - E.oldlen;
+                    else if (l >= E.a - 1) { dirty = true; break; }
                 }
+            if (dirty) {
+                fl[(out_off + q) >> 6] = 1;
+                cdst[q] = PC_OTHER;
+            } else {
+                const int64_t old = seg_lo + l;
+                cdst[q] = old < cls_n ? cls[old] : (uint8_t)PC_OTHER;
             }
         }
     }
-}
-
-// pack the fix records (and aux bytes) of all segments of a pass into compact arrays, turning segment-local
-// coordinates into chunk coordinates: index += idx_base, seqno += seq_base, aux_off += aux_base
-__global__ __launch_bounds__(64) void seg_gather_kernel(const SegDev *segs, int n_segs, const int64_t *idx_base, const uint32_t *seq_base,
-                                                        const uint32_t *rec_off, const uint32_t *aux_off, FixRec *out_recs, uint8_t *out_aux) {
-    const int s = blockIdx.x;
-    if (s >= n_segs) return;
-    const SegDev S = segs[s];
-    for (uint32_t r = threadIdx.x; r < S.nrec; r += blockDim.x) {
-        FixRec f = S.recs[r];
-        f.index += idx_base[s];
-        f.seqno += seq_base[s];
-        if (f.kind == 'x') f.aux_off += aux_off[s];
-        out_recs[rec_off[s] + r] = f;
-    }
-    for (uint32_t q = threadIdx.x; q < S.naux; q += blockDim.x) out_aux[aux_off[s] + q] = S.aux[q];
 }
 
 // ---- after the walks: what the host's bookkeeping loop did, on the device -----------------------------------------------
 // One wave per chunk record, 64 of its segments at a time (running sums by wave prefix scans); then lane 0 of block 0's last
-// arriver would have to scan the chunks -- instead every wave adds up the chunks BEFORE its own (n_chunks is small: the chunk
-// records of one polish call), which needs the other chunks' totals only: phase 1 writes them, a second launch adds the bases.
+// arriver would have to scan the chunks -- instead rec_off / aux_off stay relative to the chunk's first record, and the one consumer
+// (the gather of seg_finish_kernel) adds up the ChunkSummary totals of the chunks BEFORE its own (n_chunks is small: the chunk
+// records of one polish call).
 __device__ __forceinline__ long long wave_scan_incl64(long long v) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -1291,7 +1343,7 @@ __global__ __launch_bounds__(64) void seg_summary_kernel(SegDev *segs, const int
             S.out_off = newlen + i_own - own;
             idx_base[s] = seg_lo + shift + i_d - d;
             seq_base[s] = (uint32_t)(seqc + i_rec - nrec);
-            rec_off[s] = (uint32_t)(recc + i_rec - nrec);          // (relative to the chunk: seg_offsets_kernel adds the chunks before it)
+            rec_off[s] = (uint32_t)(recc + i_rec - nrec);          // (relative to the chunk: the gather adds the chunks before it)
             aux_off[s] = (uint32_t)(auxc + i_aux - naux);
         }
         newlen += __shfl(i_own, 63); shift += __shfl(i_d, 63);
@@ -1309,17 +1361,6 @@ __global__ __launch_bounds__(64) void seg_summary_kernel(SegDev *segs, const int
         out[c] = R;
     }
 }
-// rec_off / aux_off of a chunk's segments become offsets into the pass's record / aux arrays: plus the totals of the chunks before
-__global__ __launch_bounds__(64) void seg_offsets_kernel(const int32_t *first_seg, int n_chunks, uint32_t *rec_off, uint32_t *aux_off, const ChunkSummary *sum) {
-    const int c = blockIdx.x;
-    if (c >= n_chunks || c == 0) return;
-    const int lane = threadIdx.x;
-    unsigned long long rb = 0, ab = 0;
-    for (int q = lane; q < c; q += 64) { rb += sum[q].nrec; ab += sum[q].naux; }
-    for (int o = 32; o > 0; o >>= 1) { rb += __shfl_xor(rb, o); ab += __shfl_xor(ab, o); }
-    for (int s = first_seg[c] + lane; s < first_seg[c + 1]; s += 64) { rec_off[s] += (uint32_t)rb; aux_off[s] += (uint32_t)ab; }
-}
-
 // ---- batched variants: blockIdx.y walks the chunks of the batch ---------------------------------------------------
 // Pass 0: count AND class of every window in one kernel.  A block takes the windows that END at origin .. origin + 4095, origin =
 // tile * SC_STRIDE - 64: thread t rolls through its 16 of them as before (hash four, four home-slot loads in flight, resolve), the
@@ -1424,7 +1465,8 @@ __global__ __launch_bounds__(SC_THREADS) void scan_classify_batch_kernel(const S
     }
 }
 
-__global__ __launch_bounds__(256) void find_sync_batch_kernel(const ScanChunk *__restrict__ chunks, int n_chunks, int k) {
+// (bx of gx: the block's place among the blocks of find_cuts_batch_kernel that look for sync points)
+__device__ __forceinline__ void find_sync_blocks(const ScanChunk *__restrict__ chunks, int n_chunks, int k, int bx, int gx) {
     struct __attribute__((packed, aligned(1))) V16 { uint32_t w[4]; };
     const int64_t W = 4ll * k;
     for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
@@ -1436,7 +1478,7 @@ __global__ __launch_bounds__(256) void find_sync_batch_kernel(const ScanChunk *_
         // sixteen positions per thread: a candidate is a BAD position whose left neighbour is CLEAN -- rare, so most
         // blocks are rejected after one 16-B load
         const int64_t nblk = (nwin + 15) >> 4;
-        for (int64_t blk = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; blk < nblk; blk += (int64_t)gridDim.x * blockDim.x) {
+        for (int64_t blk = bx * (int64_t)blockDim.x + threadIdx.x; blk < nblk; blk += (int64_t)gx * blockDim.x) {
             const int64_t p0 = blk << 4;
             uint32_t w[4];
             if (p0 + 16 <= nwin) {
@@ -1561,12 +1603,13 @@ __global__ __launch_bounds__(256) void rescan_batch_kernel(const ScanChunk *__re
 // clean-zone boundaries: per CLEAN_CELL positions of a chunk, a position p (searched from the middle of the cell) whose
 // window starts [p-4k, p+k) are all CLEAN.  No event can happen there whatever stride phase the walk arrives with, so
 // a chunk may be cut at p if the segment to the right takes its start position from the one to the left (SegDev::chain_in).
-__global__ __launch_bounds__(64) void find_clean_batch_kernel(const ScanChunk *__restrict__ chunks, int n_chunks, int k) {
-    const int lane = threadIdx.x;
+// (one wave per cell: wx of gw = the wave's place among the waves of find_cuts_batch_kernel that look for clean zones)
+__device__ __forceinline__ void find_clean_waves(const ScanChunk *__restrict__ chunks, int n_chunks, int k, int wx, int gw) {
+    const int lane = threadIdx.x & 63;
     for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
         const ScanChunk C = chunks[ci];
         const int64_t nwin = C.len - k + 1;
-        for (uint32_t g = blockIdx.x; g < C.n_cells; g += gridDim.x) {
+        for (uint32_t g = (uint32_t)wx; g < C.n_cells; g += (uint32_t)gw) {
             int64_t p0 = (int64_t)g * CLEAN_CELL + CLEAN_CELL / 2;
             const int64_t cell_end = (int64_t)(g + 1) * CLEAN_CELL;
             int64_t cand = -1;
@@ -1587,10 +1630,17 @@ __global__ __launch_bounds__(64) void find_clean_batch_kernel(const ScanChunk *_
     }
 }
 
-static void launch_find_clean(const ScanChunk *d_chunks, int n_chunks, int k, hipStream_t stream) {
-    const int gy = n_chunks < 1024 ? n_chunks : 1024;
-    const int gx = std::max(1, 8192 / gy);
-    hipLaunchKernelGGL(find_clean_batch_kernel, dim3(gx, gy), dim3(64), 0, stream, d_chunks, n_chunks, k);
+// Both searches read the classes the scan in front of them wrote and nothing of each other: one launch, the first sync_gx blocks
+// of a row look for sync points, the rest -- four waves each -- for clean zones.  (Not inside the scan: a candidate's 4k
+// neighbourhood crosses its blocks.)
+__global__ __launch_bounds__(256) void find_cuts_batch_kernel(const ScanChunk *__restrict__ chunks, int n_chunks, int k, int sync_gx) {
+    if ((int)blockIdx.x < sync_gx) find_sync_blocks(chunks, n_chunks, k, (int)blockIdx.x, sync_gx);
+    else find_clean_waves(chunks, n_chunks, k, ((int)blockIdx.x - sync_gx) * 4 + (int)(threadIdx.x >> 6), ((int)gridDim.x - sync_gx) * 4);
+}
+
+static void launch_find_cuts(const ScanChunk *d_chunks, int n_chunks, int k, int gx, int gy, hipStream_t stream) {
+    const int clean_gx = (std::max(1, 8192 / gy) + 3) / 4;
+    hipLaunchKernelGGL(find_cuts_batch_kernel, dim3(gx + clean_gx, gy), dim3(256), 0, stream, d_chunks, n_chunks, k, gx);
 }
 
 void launch_rescan_batch(const TableDev &T, const ScanChunk *d_chunks, int n_chunks, int k, uint32_t solid, hipStream_t stream) {
@@ -1598,8 +1648,7 @@ void launch_rescan_batch(const TableDev &T, const ScanChunk *d_chunks, int n_chu
     const int gy = n_chunks < 1024 ? n_chunks : 1024;
     const int gx = std::max(1, 4096 / gy);
     hipLaunchKernelGGL(rescan_batch_kernel, dim3(gx, gy), dim3(256), 0, stream, d_chunks, n_chunks, T, solid);
-    hipLaunchKernelGGL(find_sync_batch_kernel, dim3(gx, gy), dim3(256), 0, stream, d_chunks, n_chunks, k);
-    launch_find_clean(d_chunks, n_chunks, k, stream);
+    launch_find_cuts(d_chunks, n_chunks, k, gx, gy, stream);
 }
 
 void launch_scan_batch(const TableDev &T, const ScanChunk *d_chunks, int n_chunks, int k, uint32_t solid, hipStream_t stream) {
@@ -1607,8 +1656,7 @@ void launch_scan_batch(const TableDev &T, const ScanChunk *d_chunks, int n_chunk
     const int gy = n_chunks < 1024 ? n_chunks : 1024;
     const int gx = std::max(1, 4096 / gy);
     hipLaunchKernelGGL(scan_classify_batch_kernel, dim3(gx, gy), dim3(SC_THREADS), 0, stream, d_chunks, n_chunks, T, solid);
-    hipLaunchKernelGGL(find_sync_batch_kernel, dim3(gx, gy), dim3(256), 0, stream, d_chunks, n_chunks, k);
-    launch_find_clean(d_chunks, n_chunks, k, stream);
+    launch_find_cuts(d_chunks, n_chunks, k, gx, gy, stream);
 }
 
 // chunk texts <-> one packed buffer (text of chunk c at pack + offs[c]): a batch of very many small records crosses PCIe in one
@@ -1628,35 +1676,28 @@ void launch_copy_chunks(uint8_t *const *d_chunk_ptr, uint8_t *d_pack, const int6
     hipLaunchKernelGGL(copy_chunks_kernel, dim3((unsigned)std::min(n, 256 * 16)), dim3(256), 0, stream, d_chunk_ptr, d_pack, d_offs, n, to_chunks ? 1 : 0);
 }
 
-void launch_seg_init(SegDev *d_segs, int n_segs, const uint8_t *const *d_chunk_text, hipStream_t stream) {
-    if (n_segs <= 0) return;
-    dim3 grid(n_segs >= 512 ? 4 : 64, n_segs < 4096 ? n_segs : 4096);
-    hipLaunchKernelGGL(seg_init_kernel, grid, dim3(256), 0, stream, d_segs, n_segs, d_chunk_text);
+void launch_seg_init(const SegDev *d_segs, const SegPiece *d_work, int n_work, const uint8_t *const *d_chunk_text, const PassPreset &preset,
+                     hipStream_t stream) {
+    if (n_work <= 0) return;
+    hipLaunchKernelGGL(seg_init_kernel, dim3(n_work), dim3(256), 0, stream, d_segs, d_work, n_work, d_chunk_text, preset);
 }
 void launch_seg_walk(const TableDev &T, SegDev *d_segs, int n_segs, PolishParams pp, int pass, ScratchPool pool, unsigned int *d_ticket,
                      hipStream_t stream) {
     if (n_segs <= 0) return;
-    (void)hipMemsetAsync(d_ticket, 0, sizeof(unsigned int), stream);
     hipLaunchKernelGGL(seg_walk_kernel, dim3(n_segs), dim3(64), 0, stream, T, d_segs, n_segs, pp, pass, pool, d_ticket);
 }
 void launch_seg_summary(SegDev *d_segs, int n_segs, const int32_t *d_first_seg, int n_chunks, int64_t *idx_base, uint32_t *seq_base, uint32_t *rec_off,
                         uint32_t *aux_off, ChunkSummary *d_out, hipStream_t stream) {
     if (n_segs <= 0 || n_chunks <= 0) return;
     hipLaunchKernelGGL(seg_summary_kernel, dim3(n_chunks), dim3(64), 0, stream, d_segs, d_first_seg, n_chunks, idx_base, seq_base, rec_off, aux_off, d_out);
-    hipLaunchKernelGGL(seg_offsets_kernel, dim3(n_chunks), dim3(64), 0, stream, d_first_seg, n_chunks, rec_off, aux_off, d_out);
 }
-void launch_seg_gather(const SegDev *d_segs, int n_segs, const int64_t *idx_base, const uint32_t *seq_base, const uint32_t *rec_off,
-                       const uint32_t *aux_off, FixRec *out_recs, uint8_t *out_aux, hipStream_t stream) {
-    if (n_segs <= 0) return;
-    hipLaunchKernelGGL(seg_gather_kernel, dim3(n_segs), dim3(64), 0, stream, d_segs, n_segs, idx_base, seq_base, rec_off, aux_off, out_recs, out_aux);
-}
-void launch_seg_stitch(const SegDev *d_segs, int n_segs, uint8_t *const *d_chunk_out, uint8_t *const *d_cls_out, uint8_t *const *d_flags,
-                       hipStream_t stream) {
-    if (n_segs <= 0) return;
-    // (blocks per segment: measured 116 / 158 / 434 us with 2 / 4 / 16 for the 3 800 segments of a 47 Mb batch's pass 0, 45 / 40 with 2 / 4
-    //  for the 700 of its later passes)
-    dim3 grid(n_segs >= 2048 ? 2 : n_segs >= 512 ? 4 : 64, n_segs < 4096 ? n_segs : 4096);
-    hipLaunchKernelGGL(seg_stitch_kernel, grid, dim3(256), 0, stream, d_segs, n_segs, d_chunk_out, d_cls_out, d_flags);
+void launch_seg_finish(const SegDev *d_segs, int n_segs, const SegPiece *d_work, int n_work, uint8_t *const *d_chunk_out, uint8_t *const *d_cls_out,
+                       uint8_t *const *d_flags, const int64_t *idx_base, const uint32_t *seq_base, const uint32_t *rec_off, const uint32_t *aux_off,
+                       const ChunkSummary *d_sum, FixRec *out_recs, uint8_t *out_aux, hipStream_t stream) {
+    if (n_segs <= 0 || n_work <= 0) return;
+    const int gather_blocks = out_recs ? (n_segs + 3) / 4 : 0;
+    hipLaunchKernelGGL(seg_finish_kernel, dim3(n_work + gather_blocks), dim3(256), 0, stream, d_segs, n_segs, d_work, n_work, d_chunk_out, d_cls_out, d_flags,
+                       idx_base, seq_base, rec_off, aux_off, d_sum, out_recs, out_aux);
 }
 
 }  // namespace jk

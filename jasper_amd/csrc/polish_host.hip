@@ -97,21 +97,29 @@ struct PolishLane {
     int ws_base = 0, pin_base = 0, ws_next = 0;
     DevBuf b_textA, b_textB, b_pack, b_cls, b_clsB, b_flags, b_segedit, b_cells, b_arrive, b_ptrA, b_segs, b_segtext, b_segrec, b_segaux, b_pool, b_locks, b_scan, b_ticket;
     DevBuf b_first, b_sum, b_idx, b_seq, b_ro, b_ao;     // the bookkeeping after a pass's walks happens on the device (seg_summary_kernel)
+                                                         // (b_first: not read any more, the first-segment table lies in b_segs; its slot keeps the numbering)
     DevBuf b_iooffs;
-    static constexpr size_t PIN_RECS = 1u << 18, PIN_AUX = 8u << 20;      // records / aux bytes of ALL passes that travel without a host wait
+    static constexpr size_t PIN_OUT = (size_t)(1u << 18) * sizeof(FixRec) + (8u << 20);   // records + aux bytes of ALL passes that travel without a host wait
+    // The segment table goes up as ONE block, [first-segment table | segments | pieces], from pinned slot 0 into b_segs: table_p and
+    // b_segs.p are its start, the segments (segs_p, d_segs) lie first_bytes behind it and the pieces (polish.hpp: make_pieces) follow the last segment
+    uint8_t *table_p = nullptr;
+    size_t first_bytes = 0;
     SegDev *segs_p = nullptr;
     int32_t *first_p = nullptr;
+    SegDev *d_segs = nullptr;
+    SegPiece *d_work = nullptr;       // the pieces of the table on the device
+    size_t n_work = 0;
+    std::vector<SegPiece> work_h;     // the rare path's pieces
     ChunkSummary *sum_p = nullptr;
     int64_t *cand_p = nullptr;        // [count (2 words) | cells | first candidates]
-    FixRec *recs_p = nullptr;
-    uint8_t *aux_p = nullptr;
+    uint8_t *out_p = nullptr;         // per pass [records | aux bytes], as they lie on the device
     ScanChunk *sc_p = nullptr;
     uint8_t *io_stage = nullptr;
     bool packed_io = false;
     int64_t total_len = 0;
     std::vector<int64_t> io_offs;
-    size_t pin_recs_used = 0, pin_aux_used = 0;
-    struct PinnedPass { size_t rec_at, nrec, aux_at, naux, r0, pass_i; };      // what a pass left in the pinned record buffers: copied out after the last pass
+    size_t pin_out_used = 0;
+    struct PinnedPass { size_t at, nrec, naux, r0, pass_i; };      // what a pass left in the pinned record buffer: copied out after the last pass
     std::vector<PinnedPass> pinned_passes;
 
     // ---- pointer tables (one upload): [0] the text the next pass READS per chunk, [1] where it WRITES, [2] the third arena's
@@ -178,8 +186,7 @@ struct PolishLane {
             STEP(host_bookkeeping(segs, n_chunks, pass, passes, books, pc, R, err));
         }
         STEP(account_chunks(len.data(), L, pc, pass, passes, R, err));
-        STEP(gather());
-        return stitch_and_swap();
+        return finish_pass();
     }
 
     // ---------------- before the passes ----------------
@@ -220,12 +227,14 @@ struct PolishLane {
 
     // workspace, scratch pool, pinned memory
     int allocate() {
+        first_bytes = al256(((size_t)n_chunks + 1) * 4);
+        const size_t table_bytes = first_bytes + (size_t)L.max_segs * sizeof(SegDev) + max_pieces((size_t)L.max_segs, L.text_bytes) * sizeof(SegPiece);
         if (!ws(b_textA, L.text_bytes) || !ws(b_textB, L.text_bytes) ||
             !ws(b_cls, L.pos_items) || !ws(b_clsB, L.pos_items) || !ws(b_flags, L.flag_items) ||
             !ws(b_segedit, L.seg_rec_bound * sizeof(EditRec)) || !ws(b_cells, (2 + L.cell_items + L.cand_items) * 8) ||      // [count | clean-zone cells | sync-point candidates]: one copy brings the first two and the candidates' head
             !ws(b_arrive, ((size_t)L.max_segs + 4) * 8) ||
             !ws(b_ptrA, (size_t)6 * n_chunks * sizeof(void *)) ||
-            !ws(b_segs, (size_t)L.max_segs * sizeof(SegDev)) || !ws(b_segtext, L.seg_text_bound) ||
+            !ws(b_segs, table_bytes) || !ws(b_segtext, L.seg_text_bound) ||
             !ws(b_segrec, L.seg_rec_bound * sizeof(FixRec)) || !ws(b_segaux, L.seg_aux_bound))
             return -2;
         pool.nslots = 256;
@@ -242,14 +251,15 @@ struct PolishLane {
         if (!ws(b_first, ((size_t)n_chunks + 1) * 4) || !ws(b_sum, (size_t)n_chunks * sizeof(ChunkSummary)) || !ws(b_idx, (size_t)L.max_segs * 8) ||
             !ws(b_seq, (size_t)L.max_segs * 4) || !ws(b_ro, (size_t)L.max_segs * 4) || !ws(b_ao, (size_t)L.max_segs * 4)) return -2;
         // pinned host memory for everything that crosses PCIe inside the pass loop (kept with the table)
-        segs_p = pin<SegDev>(0, (size_t)L.max_segs * sizeof(SegDev));
-        first_p = pin<int32_t>(1, ((size_t)n_chunks + 1) * 4);
+        table_p = pin<uint8_t>(0, table_bytes);                                 // (slot 1 held the first-segment table: it travels with the segments now)
         sum_p = pin<ChunkSummary>(2, (size_t)n_chunks * sizeof(ChunkSummary));
         cand_p = pin<int64_t>(3, (std::min<size_t>(L.cand_items, 32768) + L.cell_items + 8) * 8);
-        recs_p = pin<FixRec>(4, PIN_RECS * sizeof(FixRec));
-        aux_p = pin<uint8_t>(5, PIN_AUX);
+        out_p = pin<uint8_t>(4, PIN_OUT);                                       // (slot 5 held the aux bytes: they travel behind their records now)
         sc_p = pin<ScanChunk>(6, sizeof(ScanChunk) * (size_t)n_chunks);
-        if (!segs_p || !first_p || !sum_p || !cand_p || !recs_p || !aux_p || !sc_p) return -2;
+        if (!table_p || !sum_p || !cand_p || !out_p || !sc_p) return -2;
+        first_p = reinterpret_cast<int32_t *>(table_p);
+        segs_p = reinterpret_cast<SegDev *>(table_p + first_bytes);
+        d_segs = reinterpret_cast<SegDev *>(b_segs.as<uint8_t>() + first_bytes);
         // very many small records in host memory: their texts cross PCIe packed, one transfer each way (a transfer per record costs
         // ~10 us: 100 000 contigs of a fragmented assembly took 2.8 s for 70 ms of kernels)
         for (int c = 0; c < n_chunks; ++c) total_len += len[c];
@@ -286,6 +296,7 @@ struct PolishLane {
     // pointer tables and the texts to the device
     int upload() {
         HIPCHK(hipMemsetAsync(pool.locks, 0, pool.nslots * 4, st));
+        HIPCHK(hipMemsetAsync(d_count, 0, 4, st));             // pass 0's candidate count; every pass's seg_init zeroes it for the next
         clsIn = b_cls.as<uint8_t>();
         clsOut = b_clsB.as<uint8_t>();
         tables.resize((size_t)6 * n_chunks);
@@ -328,7 +339,6 @@ struct PolishLane {
     // ---- 1. position classes + sync-point candidates: a dense scan in pass 0; afterwards the stitch has carried the
     //         classes of untouched windows over and only the tiles next to changed text are recomputed
     int scan() {
-        HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
         for (int c = 0; c < n_chunks; ++c) {
             ScanChunk &S = sc[c];
             S.text = hIn[c];
@@ -387,24 +397,35 @@ struct PolishLane {
         if (!nsv) return 0;
         const bool fine = opt.debug && opt.debug_level >= 2;   // (waits between the steps: their times, not the pass's)
         double tf[5] = {fine ? now_ms() : 0, 0, 0, 0, 0};
-        if (hipMemcpyAsync(b_segs.p, sv, nsv * sizeof(SegDev), hipMemcpyHostToDevice, st) != hipSuccess) { err = "polish: H2D segs"; return -1; }
-        if (summary && hipMemcpyAsync(b_first.p, first_p, ((size_t)n_chunks + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess) { err = "polish: H2D first"; return -1; }
+        d_work = reinterpret_cast<SegPiece *>(d_segs + nsv);
+        if (sv == segs_p) {                      // the pass's own table: first-segment table, segments and pieces in one copy
+            n_work = make_pieces(sv, nsv, reinterpret_cast<SegPiece *>(sv + nsv));
+            if (hipMemcpyAsync(b_segs.p, table_p, first_bytes + nsv * sizeof(SegDev) + n_work * sizeof(SegPiece), hipMemcpyHostToDevice, st) != hipSuccess) { err = "polish: H2D segs"; return -1; }
+        } else {                                 // a redo's table (every copy of the rare path is waited for before its source changes)
+            work_h.resize(max_pieces(nsv, L.text_bytes));
+            n_work = make_pieces(sv, nsv, work_h.data());
+            if (hipMemcpyAsync(d_segs, sv, nsv * sizeof(SegDev), hipMemcpyHostToDevice, st) != hipSuccess) { err = "polish: H2D segs"; return -1; }
+            if (hipMemcpyAsync(d_work, work_h.data(), n_work * sizeof(SegPiece), hipMemcpyHostToDevice, st) != hipSuccess) { err = "polish: H2D pieces"; return -1; }
+        }
         if (fine) { (void)jk_stream_wait(st); tf[1] = now_ms(); }
-        launch_seg_init(b_segs.as<SegDev>(), (int)nsv, (const uint8_t *const *)dIn, st);
-        if (hipMemsetAsync(b_arrive.p, 0x80, (nsv + 2) * 8, st) != hipSuccess) { err = "polish: memset"; return -1; }   // ARRIVE_PENDING
+        // (no fills: seg_init presets the arrive slots -- ARRIVE_PENDING, the guard slots in front of and behind the segments' too --
+        //  the ticket, the next pass's candidate count and the flags the stitch is going to set)
+        const PassPreset preset{b_arrive.as<long long>(), (int64_t)nsv + 2, b_ticket.as<unsigned int>(), reinterpret_cast<unsigned int *>(d_count),
+                                b_flags.as<uint8_t>(), (int64_t)(L.flag_items / 16)};
+        launch_seg_init(d_segs, d_work, (int)n_work, (const uint8_t *const *)dIn, preset, st);
         if (fine) { (void)jk_stream_wait(st); tf[2] = now_ms(); }
-        launch_seg_walk(T.d, b_segs.as<SegDev>(), (int)nsv, pp, pass, pool, b_ticket.as<unsigned int>(), st);
+        launch_seg_walk(T.d, d_segs, (int)nsv, pp, pass, pool, b_ticket.as<unsigned int>(), st);
         if (hipGetLastError() != hipSuccess) { err = "polish: kernel launch failed"; return -1; }
         if (fine) { (void)jk_stream_wait(st); tf[3] = now_ms(); }
         if (summary) {
-            launch_seg_summary(b_segs.as<SegDev>(), (int)nsv, b_first.as<int32_t>(), n_chunks, b_idx.as<int64_t>(), b_seq.as<uint32_t>(), b_ro.as<uint32_t>(),
+            launch_seg_summary(d_segs, (int)nsv, b_segs.as<int32_t>(), n_chunks, b_idx.as<int64_t>(), b_seq.as<uint32_t>(), b_ro.as<uint32_t>(),
                                b_ao.as<uint32_t>(), b_sum.as<ChunkSummary>(), st);
             if (hipMemcpyAsync(sum_p, b_sum.p, (size_t)n_chunks * sizeof(ChunkSummary), hipMemcpyDeviceToHost, st) != hipSuccess) { err = "polish: D2H summary"; return -1; }
-        } else if (hipMemcpyAsync(sv, b_segs.p, nsv * sizeof(SegDev), hipMemcpyDeviceToHost, st) != hipSuccess) { err = "polish: D2H segs"; return -1; }
+        } else if (hipMemcpyAsync(sv, d_segs, nsv * sizeof(SegDev), hipMemcpyDeviceToHost, st) != hipSuccess) { err = "polish: D2H segs"; return -1; }
         if (jk_stream_wait(st) != hipSuccess) { err = "polish: kernel execution failed"; return -1; }
         if (fine) {
             tf[4] = now_ms();
-            fprintf(stderr, "[polish]     %zu segments x %zu B: H2D %.3f ms, init + memset %.3f ms, walk %.3f ms, %s %.3f ms\n", nsv, sizeof(SegDev), tf[1] - tf[0], tf[2] - tf[1],
+            fprintf(stderr, "[polish]     %zu segments x %zu B: H2D %.3f ms, init %.3f ms, walk %.3f ms, %s %.3f ms\n", nsv, sizeof(SegDev), tf[1] - tf[0], tf[2] - tf[1],
                     tf[3] - tf[2], summary ? "summary + D2H" : "D2H", tf[4] - tf[3]);
         }
         return 0;
@@ -413,7 +434,7 @@ struct PolishLane {
     // the rare path wants the whole table
     int fetch_table() {
         segs.resize(ns);
-        HIPCHK(hipMemcpyAsync(segs.data(), b_segs.p, ns * sizeof(SegDev), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(segs.data(), d_segs, ns * sizeof(SegDev), hipMemcpyDeviceToHost, st));
         HIPCHK(jk_stream_wait(st));
         R.n_segments += segs.size();
         return 0;
@@ -473,50 +494,49 @@ struct PolishLane {
         fprintf(stderr, "[polish]   segments by walk time: <0.1ms %d, <0.3 %d, <1 %d, <2 %d, <4 %d, <8 %d, <16 %d, more %d\n", hb[0], hb[1], hb[2], hb[3], hb[4], hb[5], hb[6], hb[7]);
     }
 
-    // ---- 5. gather records / aux
-    int gather() {
+    // ---- 5. gather records / aux and stitch the new text: one launch; and the arenas change their roles
+    int finish_pass() {
         rec_pass_begin.push_back(R.recs.size());
         aux_pass.emplace_back();
-        if (!ordinary) {                            // the host's bookkeeping goes up: the segment table and the four coordinate bases
-            HIPCHK(hipMemcpyAsync(b_segs.p, segs.data(), ns * sizeof(SegDev), hipMemcpyHostToDevice, st));
+        if (!ordinary) {                            // the host's bookkeeping goes up: the segment table, its pieces and the four coordinate bases
+            work_h.resize(max_pieces(ns, L.text_bytes));
+            n_work = make_pieces(segs.data(), ns, work_h.data());
+            d_work = reinterpret_cast<SegPiece *>(d_segs + ns);
+            HIPCHK(hipMemcpyAsync(d_segs, segs.data(), ns * sizeof(SegDev), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_work, work_h.data(), n_work * sizeof(SegPiece), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(b_idx.p, books.idx_base.data(), ns * 8, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(b_seq.p, books.seq_base.data(), ns * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(b_ro.p, books.rec_off.data(), ns * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(b_ao.p, books.aux_off.data(), ns * 4, hipMemcpyHostToDevice, st));
         }
-        if (!pc.nrec) return 0;
-        DevBuf d_recs, d_aux;
-        const int ws_save = ws_next;          // the same two workspace slots every pass
-        if (!ws(d_recs, pc.nrec * sizeof(FixRec)) || !ws(d_aux, pc.naux)) return -2;
-        ws_next = ws_save;
-        launch_seg_gather(b_segs.as<SegDev>(), (int)ns, b_idx.as<int64_t>(), b_seq.as<uint32_t>(), b_ro.as<uint32_t>(), b_ao.as<uint32_t>(), d_recs.as<FixRec>(),
-                          d_aux.as<uint8_t>(), st);
-        HIPCHK(hipGetLastError());
-        const size_t r0 = R.recs.size();
-        R.recs.resize(r0 + pc.nrec);
-        aux_pass.back().resize(pc.naux);
-        if (pin_recs_used + pc.nrec <= PIN_RECS && pin_aux_used + pc.naux <= PIN_AUX) {
-            // through pinned memory, without waiting: the stream orders the copy before the next pass's gather reuses d_recs
-            HIPCHK(hipMemcpyAsync(recs_p + pin_recs_used, d_recs.p, pc.nrec * sizeof(FixRec), hipMemcpyDeviceToHost, st));
-            if (pc.naux) HIPCHK(hipMemcpyAsync(aux_p + pin_aux_used, d_aux.p, pc.naux, hipMemcpyDeviceToHost, st));
-            pinned_passes.push_back(PinnedPass{pin_recs_used, pc.nrec, pin_aux_used, pc.naux, r0, aux_pass.size() - 1});
-            pin_recs_used += pc.nrec;
-            pin_aux_used += pc.naux;
-        } else {
-            HIPCHK(hipMemcpyAsync(&R.recs[r0], d_recs.p, pc.nrec * sizeof(FixRec), hipMemcpyDeviceToHost, st));
-            if (pc.naux) HIPCHK(hipMemcpyAsync(aux_pass.back().data(), d_aux.p, pc.naux, hipMemcpyDeviceToHost, st));
-            HIPCHK(jk_stream_wait(st));
+        // the pass's records and, behind them, its aux bytes: one device buffer (the same workspace slot every pass), one copy
+        DevBuf d_out;
+        const size_t rec_bytes = pc.nrec * sizeof(FixRec), out_bytes = rec_bytes + pc.naux;
+        if (pc.nrec) {
+            const int ws_save = ws_next;
+            if (!ws(d_out, out_bytes)) return -2;
+            ws_next = ws_save;
         }
-        return 0;
-    }
-
-    // ... stitch the new text, and the arenas change their roles
-    int stitch_and_swap() {
         const bool carry = pass < passes;           // another pass follows: carry the classes over, flag changed text
-        if (carry) HIPCHK(hipMemsetAsync(b_flags.p, 0, L.flag_items, st));
-        launch_seg_stitch(b_segs.as<SegDev>(), (int)ns, (uint8_t *const *)dOut, carry ? (uint8_t *const *)ptrClsOut : nullptr,
-                          carry ? (uint8_t *const *)ptrFlags : nullptr, st);
+        launch_seg_finish(d_segs, (int)ns, d_work, (int)n_work, (uint8_t *const *)dOut, carry ? (uint8_t *const *)ptrClsOut : nullptr,
+                          carry ? (uint8_t *const *)ptrFlags : nullptr, b_idx.as<int64_t>(), b_seq.as<uint32_t>(), b_ro.as<uint32_t>(), b_ao.as<uint32_t>(),
+                          ordinary ? b_sum.as<ChunkSummary>() : nullptr, d_out.as<FixRec>(), d_out.as<uint8_t>() + rec_bytes, st);
         HIPCHK(hipGetLastError());
+        if (pc.nrec) {
+            const size_t r0 = R.recs.size();
+            R.recs.resize(r0 + pc.nrec);
+            aux_pass.back().resize(pc.naux);
+            if (pin_out_used + out_bytes <= PIN_OUT) {
+                // through pinned memory, without waiting: the stream orders the copy before the next pass's gather reuses d_out
+                HIPCHK(hipMemcpyAsync(out_p + pin_out_used, d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+                pinned_passes.push_back(PinnedPass{pin_out_used, pc.nrec, pc.naux, r0, aux_pass.size() - 1});
+                pin_out_used += (out_bytes + 31) & ~(size_t)31;
+            } else {
+                HIPCHK(hipMemcpyAsync(&R.recs[r0], d_out.p, rec_bytes, hipMemcpyDeviceToHost, st));
+                if (pc.naux) HIPCHK(hipMemcpyAsync(aux_pass.back().data(), d_out.as<uint8_t>() + rec_bytes, pc.naux, hipMemcpyDeviceToHost, st));
+                HIPCHK(jk_stream_wait(st));
+            }
+        }
         for (int c = 0; c < n_chunks; ++c) len[c] = pc.newlen[c];
         // A precaution.  The host's own bookkeeping went up from ordinary host memory (segs and the four vectors of books): an
         // asynchronous copy may read its source when the stream gets to it, not when it is issued, so the vectors must not change or
@@ -566,8 +586,8 @@ struct PolishLane {
         HIPCHK(hipEventElapsedTime(&ms, ev0.e, ev1.e));
         R.seconds = ms * 1e-3;
         for (const PinnedPass &P : pinned_passes) {                                             // what travelled through pinned memory
-            memcpy(&R.recs[P.r0], recs_p + P.rec_at, P.nrec * sizeof(FixRec));
-            if (P.naux) memcpy(aux_pass[P.pass_i].data(), aux_p + P.aux_at, P.naux);
+            memcpy(&R.recs[P.r0], out_p + P.at, P.nrec * sizeof(FixRec));
+            if (P.naux) memcpy(aux_pass[P.pass_i].data(), out_p + P.at + P.nrec * sizeof(FixRec), P.naux);
         }
         regroup_and_sort(R, rec_pass_begin, aux_pass);
         return 0;

@@ -62,7 +62,7 @@ out["counting_pipeline"] = {"steps_profiled": steps, "hbm_bytes_per_step": tot_k
                                     "corrected figure 2 x FETCH_SIZE + WRITE_SIZE (gfx950 tallies 128-B read requests at 64 B)"}
 # the polishing kernels, per polish CALL: a table polishes in several lanes from its second call on, so no kernel's dispatch count is
 # the number of calls; the profiled process says how many it made (bench.py: warm-up + timed steps + the untimed host-buffer calls)
-pk = ("scan_classify_batch", "find_sync_batch", "find_clean_batch", "seg_init", "seg_walk", "seg_summary", "seg_gather", "seg_stitch", "rescan_batch")
+pk = ("scan_classify_batch", "find_cuts_batch", "seg_init", "seg_walk", "seg_summary", "seg_finish", "rescan_batch")
 calls = steps + 3
 try:
     calls = int(json.loads(open(os.path.join(src, "trace_run.json")).read().strip().splitlines()[-1])["polish_calls_in_process"])

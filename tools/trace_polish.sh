@@ -1,5 +1,6 @@
 #!/bin/bash
 # GPU box: kernel trace of one steady-state polish call (all lanes), one line per dispatch with its queue; usage: tools/trace_polish.sh <dir under gpurun_out> [env ...]
+# (copies that the tracer reports as copies come in a column of their own, behind the queues)
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-trace_polish}; shift
@@ -13,6 +14,10 @@ out = sys.argv[1]
 rows = []
 for f in glob.glob(out + "/kt/**/*kernel_trace.csv", recursive=True):
     rows += list(csv.DictReader(open(f)))
+for f in glob.glob(out + "/kt/**/*memory_copy_trace.csv", recursive=True):      # copies: rows without a queue, named by their direction
+    for r in csv.DictReader(open(f)):
+        if r.get("Start_Timestamp") and r.get("End_Timestamp"):
+            rows.append(dict(Kernel_Name="copy " + (r.get("Direction") or r.get("Kind") or ""), Queue_Id="copies", Start_Timestamp=r["Start_Timestamp"], End_Timestamp=r["End_Timestamp"]))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"] for r in rows]
 starts = [i for i, n in enumerate(names) if "scan_classify" in n]
