@@ -467,6 +467,26 @@ void jasper_hapscan_free(jasper_hapscan *r);
 int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *child, jasper_table *assembly, uint32_t thre_mat, uint32_t thre_pat, uint32_t thre_child,
                          uint64_t out6[6] /* mat: hapmers, found, occurrences; then pat */, double *device_seconds);
 
+/* A join of tables as a table: the census's set H, kept instead of counted.  src (S), absent (A) and dst are whole tables of the same k
+ * on the same device, all handles different; solid (R) may be NULL and may be an attached owner-sharded table; thre_src and thre_solid
+ * are each at least 1; dst holds no key.  Anything else -- a different k, different devices, the same handle twice, an attached S, A or
+ * dst, a threshold of 0, a dst with keys -- is JASPER_ERR with a message that names the cause, before any table is touched.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.
+ *
+ * Selected = the distinct keys x of S with S[x] >= thre_src (the 64-bit count), A[x] == 0 and (R NULL or min(R[x], 2^32-1) >=
+ * thre_solid).  After the call dst holds exactly the selected keys, each with its 64-bit count S[x]; S, A and R are not modified.  With
+ * thre_src = the parent's threshold this is H_mat of jasper_hapmer_census(S, A, R, ...): `selected` equals its `hapmers`.
+ *   out4 = candidates   keys of S with S[x] >= thre_src
+ *          in_absent    candidates dropped because A holds them
+ *          not_solid    candidates A does not hold, dropped because R holds them fewer than thre_solid times (0 when solid is NULL)
+ *          selected     candidates - in_absent - not_solid = the keys of dst
+ * S is swept in pieces of at most 2^24 slots (JASPER_SELECT_PIECE=<slots>, 1 .. 2^24, overrides it: a test hook); a piece's keys reach
+ * dst through the import that jasper_table_import_device is, so dst grows as any table does, and JASPER_ERR_CAPACITY is that import's.
+ * device_seconds (may be NULL): device time of the select sweeps, HIP events; the imports are not in it. */
+int jasper_table_select(jasper_table *dst, jasper_table *src, jasper_table *absent, jasper_table *solid /* may be NULL */, uint32_t thre_src, uint32_t thre_solid,
+                        uint64_t out4[4] /* candidates, in_absent, not_solid, selected */, double *device_seconds);
+
 /* Trio read binning: per READ of the child, how many of its windows hold a k-mer that only the mother's reads have and how many hold one
  * that only the father's have -- what TrioCanu-style binning sorts the child's reads by.  The tables are the scan's mat (M) and pat (P)
  * above: whole tables of the same k on the same device, different handles; thre_mat and thre_pat are each at least 1.  No table is

@@ -11,6 +11,7 @@
 #include "copies.hpp"
 #include "diploid.hpp"
 #include "hapmers.hpp"
+#include "select.hpp"
 #include "readbins.hpp"
 #include "readtext.hpp"
 #include "readroute.hpp"
@@ -935,6 +936,14 @@ int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *chi
     return hapmer_census(mat->t, pat->t, child ? &child->t : nullptr, assembly ? &assembly->t : nullptr, thre_mat, thre_pat, thre_child, out6, device_seconds, g_err)
                ? JASPER_ERR
                : JASPER_OK;
+}
+
+// ---- a join of tables as a table (select.hip) ----
+int jasper_table_select(jasper_table *dst, jasper_table *src, jasper_table *absent, jasper_table *solid, uint32_t thre_src, uint32_t thre_solid, uint64_t out4[4],
+                        double *device_seconds) {
+    if (!dst || !src || !absent || !out4) { g_err = "bad argument"; return JASPER_ERR; }
+    const int rc = table_select(dst->t, src->t, absent->t, solid ? &solid->t : nullptr, thre_src, thre_solid, out4, device_seconds, g_err);
+    return rc == 0 ? JASPER_OK : rc == -2 ? JASPER_ERR_CAPACITY : JASPER_ERR;
 }
 
 // ---- trio read binning (readbins.hip) ----

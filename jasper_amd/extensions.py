@@ -384,9 +384,14 @@ def stages_log(run, title, texts, file, one=""):
 def assembly_table(table, contigs):
     """the contigs [(name token, sequence)] counted into a second table of their own (sized from their length; the sequences
     joined by a separator byte, so no k-mer spans two contigs) on `table`'s device -> KmerTable, the caller closes it"""
+    return contigs_table(table.k, table.device, contigs)
+
+
+def contigs_table(k, device, contigs):
+    """assembly_table for a caller that has no reads' table yet: the contigs counted with this k on this device"""
     from .table import KmerTable
     seqs = [s for _, s in contigs]
-    asm = KmerTable(table.k, min_slots=max(1 << 16, int(1.25 * sum(len(s) for s in seqs))), device=table.device)
+    asm = KmerTable(k, min_slots=max(1 << 16, int(1.25 * sum(len(s) for s in seqs))), device=device)
     try:
         asm.count_bases("N".join(seqs))
     except BaseException:

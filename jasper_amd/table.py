@@ -1262,6 +1262,31 @@ class KmerTable:
         v = [int(x) for x in out]
         return HapmerCensus(tuple(v[:3]), tuple(v[3:]), secs.value)
 
+    # ---- a join of tables as a table (an extension: the census's set, kept instead of counted) ------------------
+    SELECT_SLOTS_LEAST, SELECT_SLOTS_MOST = 1 << 16, 1 << 26
+
+    @staticmethod
+    def select(src, absent, solid=None, thre_src=1, thre_solid=1):
+        """the keys of `src` with a count of at least thre_src that `absent` does not hold and (with `solid`) that `solid` holds at least
+        thre_solid times, with their counts in src, as a NEW table on src's device (include/jasper_hip.h: jasper_table_select) ->
+        (KmerTable, stats); stats = dict of candidates, in_absent, not_solid, selected and seconds (device time of the select sweeps).
+        The caller closes the table.  It starts at 1/16 of src's distinct keys in slots, at least 2^16 and at most 2^26, grows as any
+        table does while the pieces are imported, and is cut to a load of at most 0.5 at the end."""
+        sh, ah = KmerTable._parent_handle(src, "source", "select"), KmerTable._parent_handle(absent, "absent", "select")
+        rh = KmerTable._parent_handle(solid, "solid", "select") if solid is not None else None
+        slots = min(max(src.info()["distinct"] // 16, KmerTable.SELECT_SLOTS_LEAST), KmerTable.SELECT_SLOTS_MOST)
+        dst = KmerTable(src.k, min_slots=slots, device=src.device)
+        try:
+            out = (C.c_uint64 * 4)()
+            secs = C.c_double(0)
+            check(src._L.jasper_table_select(dst._h, sh, ah, rh, _thre32(thre_src), _thre32(thre_solid), out, C.byref(secs)))
+            dst.fit()
+        except BaseException:
+            dst.close()
+            raise
+        v = [int(x) for x in out]
+        return dst, dict(candidates=v[0], in_absent=v[1], not_solid=v[2], selected=v[3], seconds=secs.value)
+
     # ---- trio read binning (an extension: the hap-mer scan's probes over a packed batch of reads) ----------
     @staticmethod
     def _packed_reads(reads):

@@ -3,7 +3,9 @@
     python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
                                  [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
                                  [--write-gz] [--deflate host|device] [--batch-bases N] [--reader host|device] [--gz host|device]
-                                 [--route host|device] [-o PREFIX] [--device D]
+                                 [--route host|device] [--marker-tables] [-o PREFIX] [--device D]
+    python -m jasper_amd.triobin -r 'reads...' --hap1 hap1.fa --hap2 hap2.fa [--markers solid|all] [--child-threshold N] [--child-jf db.jf]
+                                 [every flag above but the parents' six]
 
 An extension (the reference has no such tool), and the cure for what `--hapmers` only shows: a polisher that repairs toward the reads'
 solid k-mers can move a het site of a phased assembly onto the other haplotype, which hapmers.tsv lists as switches in its `after` row.
@@ -18,6 +20,27 @@ The parents.  The mother's and the father's reads are counted into two whole tab
 one parent -- count >= that parent's threshold, --mat-threshold / --pat-threshold or what its histogram gives -- and has count 0 in the
 other.  M_total and P_total are how many of them each parent has (KmerTable.hapmer_census_parents); when either is 0 the run ends with
 exit status 1.  All of this is extensions.open_parents, with the messages of `--hapmers`.
+
+--marker-tables.  After the parents are opened and given thresholds, the two hap-mer sets are MATERIALISED as tables of their own
+(KmerTable.select: the mother's keys with count >= her threshold that the father does not hold, and the mirror), the parental tables
+are closed -- tens of GB on a human trio, for two small tables -- M_total and P_total are the selects' counts, and the reads are binned
+against the two marker tables with thresholds 1.  Every output file and both log lines are byte for byte what the run without the flag
+writes; JASPER_AMD_TIMING=1 adds one line with both selects' device seconds and their four counters.
+
+Two haplotype assemblies instead of parents (--hap1 hap1.fa --hap2 hap2.fa; the parents' six options are refused beside them).  Both
+FASTA files are read as kmerqc reads -a and --alt and counted into tables (extensions.assembly_table).  A marker of hap1 is a k-mer hap1
+holds and hap2 does not and -- with --markers solid, the default -- that the READS hold at least --child-threshold times: an assembly
+ERROR is private to its haplotype too (kmerqc --alt calls it private_weak), and as a marker it would inflate that haplotype's total and
+skew the rule toward the cleaner one.  For that the reads are counted first (as kmerqc counts -r), or --child-jf db.jf is loaded (its
+header decides k); the threshold is --child-threshold or what the solid-k-mer rule derives from the histogram, and a histogram that
+gives none ends the run with exit status 1 and a message that asks for the flag.  --markers all takes every private k-mer and counts
+nothing.  Two selects make the marker tables (M' = select(hap1, hap2, reads, 1, threshold), P' its mirror), the three source tables are
+closed, M_total and P_total are the selected counts, and everything below runs on (M', P', 1, 1) -- every reader, --gz, --route and
+--deflate combination.  The bins are hap1, hap2 and unknown in the file names, in both tables (columns hap1_markers, hap2_markers; hap1,
+hap2) and in the log, whose first line gives k, the marker mode, the threshold and where it came from, both totals and each haplotype's
+private k-mers before the solid filter.  A side without a single marker ends the run with exit status 1.  --marker-tables is accepted
+and changes nothing: this mode always works that way.  With --markers solid the reads are read twice (once counted, once binned) unless
+--child-jf is given.
 
 The reads.  The child's files are read on the host: FASTQ in four-line records or FASTA with one or more sequence lines, line ends LF or
 CRLF, plain or .gz.  A read's sequence is its sequence lines without line ends, bytes as they stand (lower case counts as upper case, any
@@ -95,19 +118,25 @@ from .report import write_atomic
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
          "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--write-gz (needs --write-reads)] [--deflate host|device (needs --write-gz)] "
          "[--batch-bases N (no effect with --reader device)] [--reader host|device] [--gz host|device (needs --reader device)] "
-         "[--route host|device (needs --reader device --write-reads)] [-o PREFIX] [--device D]")
+         "[--route host|device (needs --reader device --write-reads)] [--marker-tables] [-o PREFIX] [--device D]\n"
+         "       python -m jasper_amd.triobin -r 'reads...' --hap1 hap1.fa --hap2 hap2.fa [--markers solid|all] [--child-threshold N (with solid)] "
+         "[--child-jf db.jf (with solid)] [every other option but the parents']")
 BINS = ("mat", "pat", "unknown")
+HAP_BINS = ("hap1", "hap2", "unknown")        # assembly mode: the same three roles under the haplotypes' names
 MAT, PAT, UNKNOWN = 0, 1, 2
+MARKERS = ("solid", "all")
 BATCH_BASES_DEFAULT = 256 << 20
 BATCH_BASES_MOST = 1 << 40          # (the kernel takes 2^43 text bytes per call)
 CHUNK = 16 << 20                    # file bytes parsed at a time
 DEVICE_CHUNK = 16 << 20             # ... with --reader device: file bytes uploaded and parsed at a time (JASPER_TRIOBIN_CHUNK overrides it)
 DEVICE_CHUNK_MOST = (1 << 30) - 1   # (a chunk and the tail carried into it stay below the kernels' 2^31 text bytes)
 READERS = ("host", "device")
-BOOL_FLAGS = ("--paired", "--per-read", "--write-reads", "--write-gz")
+BOOL_FLAGS = ("--paired", "--per-read", "--write-reads", "--write-gz", "--marker-tables")
 VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
                "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases",
-               "--reader": "reader", "--gz": "gz", "--route": "route", "--deflate": "deflate"}
+               "--reader": "reader", "--gz": "gz", "--route": "route", "--deflate": "deflate", "--hap1": "hap1", "--hap2": "hap2", "--markers": "markers",
+               "--child-threshold": "child_threshold", "--child-jf": "child_jf"}
+PARENT_FLAGS = ("--mat", "--mat-jf", "--pat", "--pat-jf", "--mat-threshold", "--pat-threshold")
 
 
 class Malformed(Exception):
@@ -465,8 +494,8 @@ class _BinFiles:
     """the three bin files of one input, as .tmp: plain, or BGZF with --write-gz (deflater: None for the host's zlib, a _Deflater for the
     GPU).  write(b, arr) takes bytes of bin b; write_routed(r) what a route call returns -- bytes, or with gz members and their raw sizes"""
 
-    def __init__(self, prefix, path, made, write_gz=False, deflater=None, sums=None):
-        outs = ["%s.%s.%s%s" % (prefix, b, out_basename(path), ".gz" if write_gz else "") for b in BINS]
+    def __init__(self, prefix, path, made, write_gz=False, deflater=None, sums=None, names=BINS):
+        outs = ["%s.%s.%s%s" % (prefix, b, out_basename(path), ".gz" if write_gz else "") for b in names]
         made += outs
         self.sums, self.w = sums, []
         try:
@@ -507,19 +536,21 @@ class _BinFiles:
 
 
 def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT, reader="host",
-              count_text=None, gz_open=None, route_text=None, timings=None, write_gz=False, deflate=None):
+              count_text=None, gz_open=None, route_text=None, timings=None, write_gz=False, deflate=None, names=BINS):
     """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
     cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds.  reader "device": the files'
     bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called.  gz_open: --gz device (_DeviceReader);
     route_text: --route device, route_text(buf, bounds, bins, first, check_from, out) -> table.RoutedText.  timings (a dict) gets what
     JASPER_AMD_TIMING=1 prints of the two.  write_gz: the bin files are BGZF; deflate (--deflate device): deflate(array) -> (members,
-    counters, seconds) compresses them, and with route_text the route calls are made with gz=True and return members"""
+    counters, seconds) compresses them, and with route_text the route calls are made with gz=True and return members.  names: what the
+    three bins are called in the file names, in both tables and, the first two, in the marker and per-read columns (HAP_BINS in assembly
+    mode)"""
     import numpy as np
     bat = _Batcher(batch_bases, count)
     deflater = _Deflater(deflate) if write_gz and deflate is not None else None
     dev = _DeviceReader(count_text, write_reads, gz_open, per_read) if reader == "device" else None
     timings = {} if timings is None else timings
-    nrec, lens, names = [], [], []
+    nrec, lens, rnames = [], [], []
     try:
         for fi, path in enumerate(paths):
             fl, fn = [], []
@@ -532,7 +563,7 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
                 bat.add(ch.seq, ch.lens)
             lens.append(np.concatenate(fl) if fl else np.zeros(0, dtype=np.int64))
             nrec.append(len(lens[-1]))
-            names.append(fn)
+            rnames.append(fn)
             if paired and fi % 2 == 1 and nrec[fi] != nrec[fi - 1]:
                 cli.error_exit("--paired: %s has %d records and %s has %d; the files of a pair must hold the same templates" % (paths[fi - 1], nrec[fi - 1], path, nrec[fi]))
         bat.flush()
@@ -555,17 +586,17 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
         else:
             bins.append(bin_codes(ms[fi], ps[fi], m_total, p_total, min_markers))
     # the table
-    text = "#file\tbin\treads\tbases\tmat_markers\tpat_markers\n"
+    text = "#file\tbin\treads\tbases\t%s_markers\t%s_markers\n" % names[:2]
     total = np.zeros((3, 4), dtype=object)
     for fi, path in enumerate(paths):
         for b in range(3):
             sel = bins[fi] == b
             row = [int(sel.sum()), int(lens[fi][sel].sum()), int(ms[fi][sel].sum(dtype=np.uint64)), int(ps[fi][sel].sum(dtype=np.uint64))]
             total[b] += row
-            text += "%s\t%s\t%d\t%d\t%d\t%d\n" % (path, BINS[b], row[0], row[1], row[2], row[3])
-    text += "".join("*\t%s\t%d\t%d\t%d\t%d\n" % ((BINS[b],) + tuple(int(v) for v in total[b])) for b in range(3))
+            text += "%s\t%s\t%d\t%d\t%d\t%d\n" % (path, names[b], row[0], row[1], row[2], row[3])
+    text += "".join("*\t%s\t%d\t%d\t%d\t%d\n" % ((names[b],) + tuple(int(v) for v in total[b])) for b in range(3))
     made = []
-    opened = lambda path: _BinFiles(prefix, path, made, write_gz, deflater, timings if write_gz else None)      # noqa: E731
+    opened = lambda path: _BinFiles(prefix, path, made, write_gz, deflater, timings if write_gz else None, names)      # noqa: E731
     try:
         if write_reads and dev:
             _write_reads_by_starts(paths, opened, bins, dev.starts, route_text, gz_open, timings, deflater)
@@ -577,9 +608,9 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
         if per_read:
             with open(prefix + ".readbins.reads.tsv.tmp", "w") as f:
                 made.append(prefix + ".readbins.reads.tsv")
-                f.write("#file\trecord\tname\tlength\tmat\tpat\tbin\n")
+                f.write("#file\trecord\tname\tlength\t%s\t%s\tbin\n" % names[:2])
                 for fi, path in enumerate(paths):
-                    f.writelines("%s\t%d\t%s\t%d\t%d\t%d\t%s\n" % (path, i, names[fi][i], lens[fi][i], ms[fi][i], ps[fi][i], BINS[bins[fi][i]]) for i in range(nrec[fi]))
+                    f.writelines("%s\t%d\t%s\t%d\t%d\t%d\t%s\n" % (path, i, rnames[fi][i], lens[fi][i], ms[fi][i], ps[fi][i], names[bins[fi][i]]) for i in range(nrec[fi]))
         for fn in made:
             os.replace(fn + ".tmp", fn)
         made = []
@@ -695,7 +726,7 @@ def _write_reads_by_starts(paths, opened, bins, kept, route_text=None, gz_open=N
 
 def parse_args(argv):
     o = dict.fromkeys(set(VALUE_FLAGS.values()))
-    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False, write_gz=False)
+    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False, write_gz=False, marker_tables=False)
     i = 0
     while i < len(argv):
         key = argv[i]
@@ -714,8 +745,42 @@ def parse_args(argv):
     return o
 
 
+def check_haps(a):
+    """assembly mode's flags, refused before anything is opened -> None (trio mode) or dict(hap1, hap2, markers, thre_child (None: from the
+    histogram; not used with markers all), child_jf)"""
+    on = a["hap1"] is not None or a["hap2"] is not None
+    if not on:
+        for flag in ("--markers", "--child-threshold", "--child-jf"):
+            if a[VALUE_FLAGS[flag]] is not None:
+                cli.error_exit("%s is an option of binning by two haplotype assemblies: give --hap1 and --hap2 as well" % flag)
+        return None
+    for flag, other in (("--hap1", "--hap2"), ("--hap2", "--hap1")):
+        if a[VALUE_FLAGS[other]] is None:
+            cli.error_exit("%s needs %s: the reads are binned by the two haplotypes of one assembly" % (flag, other))
+    for flag in PARENT_FLAGS:
+        if a[VALUE_FLAGS[flag]] is not None:
+            cli.error_exit("%s cannot be given with --hap1 / --hap2: the markers come either from the parents' reads or from the two haplotype assemblies" % flag)
+    for flag in ("--hap1", "--hap2"):
+        if not cli._nonempty(a[VALUE_FLAGS[flag]]):
+            cli.error_exit("%s: %s does not exist or is empty. Please supply that haplotype's fasta file." % (flag, a[VALUE_FLAGS[flag]]))
+    if os.path.samefile(a["hap1"], a["hap2"]):
+        cli.error_exit("--hap2: %s is the --hap1 assembly itself; give the OTHER haplotype's fasta file" % a["hap2"])
+    markers = a["markers"] if a["markers"] is not None else "solid"
+    if markers not in MARKERS:
+        cli.error_exit("--markers takes solid or all; %s was given" % markers)
+    if markers == "all":
+        for flag in ("--child-jf", "--child-threshold"):
+            if a[VALUE_FLAGS[flag]] is not None:
+                cli.error_exit("%s has no use with --markers all: only --markers solid looks at the child's k-mers" % flag)
+    thre = extensions._range_flag("--child-threshold", a["child_threshold"], None, 1, 0xFFFFFFFF)
+    if a["child_jf"] is not None and not cli._nonempty(a["child_jf"]):
+        cli.error_exit("--child-jf: %s does not exist or is empty" % a["child_jf"])
+    return dict(hap1=a["hap1"], hap2=a["hap2"], markers=markers, thre_child=thre, child_jf=a["child_jf"])
+
+
 def check_flags(a):
-    """everything that can be refused before a parent is opened -> (read files, k, device, the parents' flags, min_markers, batch_bases)"""
+    """everything that can be refused before a parent is opened -> (read files, k, device, the parents' flags (assembly mode: check_haps'
+    dict), min_markers, batch_bases)"""
     if a["reads"] is None:
         cli.error_exit("No reads given. Please supply the child's read files with -r, separated by space and wrapped in one pair of quotation marks.")
     opts = cli.Options()
@@ -727,11 +792,18 @@ def check_flags(a):
     device = extensions._range_flag("--device", a["device"], 0, 0, 1023)
     min_markers = extensions._range_flag("--min-markers", a["min_markers"], 1, 1, 1 << 33)
     batch_bases = extensions._range_flag("--batch-bases", a["batch_bases"], BATCH_BASES_DEFAULT, 1, BATCH_BASES_MOST)
-    o = type("TriobinOptions", (), dict(a, hapmers=True, phase_short_range=None, phase_max_switches=None))
-    first_jf = a["mat_jf"] if a["mat_jf"] is not None else a["pat_jf"]
-    hap = extensions.hapmer_flags(o, k, first_jf)       # (a database's header decides k; both parents must have it)
-    if first_jf is not None:
-        k = extensions.jf_k(first_jf)
+    hap = check_haps(a)
+    if hap is not None:
+        if hap["child_jf"] is not None:                 # (a database's header decides k)
+            k = extensions.jf_k(hap["child_jf"])
+            if k is None:
+                cli.error_exit("--child-jf: " + cli._jf_failed(hap["child_jf"]))
+    else:
+        o = type("TriobinOptions", (), dict(a, hapmers=True, phase_short_range=None, phase_max_switches=None))
+        first_jf = a["mat_jf"] if a["mat_jf"] is not None else a["pat_jf"]
+        hap = extensions.hapmer_flags(o, k, first_jf)       # (a database's header decides k; both parents must have it)
+        if first_jf is not None:
+            k = extensions.jf_k(first_jf)
     if a["paired"] and len(reads) % 2:
         cli.error_exit("--paired takes the read files as R1 R2 [R1 R2 ...]; %d files were given" % len(reads))
     if a["write_reads"]:
@@ -826,6 +898,119 @@ def timing_lines(t, gz, route, deflate=None):
             c.get("literal_only", "NA"), c.get("lz", "NA")))
 
 
+def haps_totals_check(m_total, p_total):
+    """check_totals for two haplotype assemblies: a side without a single marker ends the run"""
+    if m_total == 0 or p_total == 0:
+        cli.error_exit("%s no marker k-mers: nothing tells the two haplotypes' reads apart." % (
+            "The haplotypes have" if m_total == p_total else "hap1 has" if m_total == 0 else "hap2 has"))
+
+
+def marker_tables(first, second, solid, thre_first, thre_second, thre_solid):
+    """the two marker sets as tables (KmerTable.select): the keys of `first` (count >= thre_first) that `second` does not hold and,
+    with `solid`, that it holds at least thre_solid times, and the mirror -> (M', P', the two selects' stats); the caller closes them"""
+    from .table import KmerTable
+    m, sm = KmerTable.select(first, second, solid, thre_first, thre_solid)
+    try:
+        p, sp = KmerTable.select(second, first, solid, thre_second, thre_solid)
+    except BaseException:
+        m.close()
+        raise
+    return m, p, sm, sp
+
+
+def select_line(names, stats):
+    """JASPER_AMD_TIMING=1: both selects' device seconds and their four counters"""
+    extensions.device_line("[triobin] select device seconds: " + "; ".join(
+        "%s %.6f (candidates %d, in_absent %d, not_solid %d, selected %d)" % (n, st["seconds"], st["candidates"], st["in_absent"], st["not_solid"], st["selected"])
+        for n, st in zip(names, stats)))
+
+
+def child_table(hap, reads, k, device):
+    """--markers solid: the child's reads counted into a table (as kmerqc counts -r), or --child-jf loaded, and the threshold --
+    --child-threshold, or what the solid-k-mer rule derives from the histogram -> (KmerTable, threshold, where it came from)"""
+    from . import polisher
+    from .table import KmerTable
+    try:
+        if hap["child_jf"] is not None:
+            t = KmerTable.from_jf(hap["child_jf"], device=device)
+        else:
+            size = sum(os.stat(fn).st_size for fn in reads) // 10
+            t = KmerTable(k, min_slots=max(1 << 20, int(1.25 * size)), device=device)
+            try:
+                t.count_files(reads)
+            except BaseException:
+                t.close()
+                raise
+    except Exception as e:      # noqa: BLE001
+        cli.error_exit("--markers solid: the child's table could not be made on GPU %d: %s" % (device, e))
+    if hap["thre_child"] is not None:
+        return t, hap["thre_child"], "given"
+    txt, status = polisher.threshold_from_histo_rows(t.histo_rows())
+    if status != 0 or not txt.split() or int(txt.split()[0]) < 1:
+        t.close()
+        cli.error_exit("The child's reads' k-mer histogram gives no threshold. Please give one with --child-threshold.")
+    return t, int(txt.split()[0]), "from the histogram"
+
+
+def open_haps(hap, reads, k, device):
+    """assembly mode: both assemblies counted (as kmerqc counts -a and --alt), with --markers solid the child's table beside them, the
+    two selects, the three source tables closed -> (M', P', M_total, P_total); the caller closes M' and P'.  Writes the mode's log line."""
+    tables = []
+    try:
+        for fn in (hap["hap1"], hap["hap2"]):
+            tables.append(extensions.contigs_table(k, device, extensions.Text(fn).contigs))
+        thre, origin = 1, None
+        if hap["markers"] == "solid":
+            child, thre, origin = child_table(hap, reads, k, device)
+            tables.append(child)
+        m, p, sm, sp = marker_tables(tables[0], tables[1], tables[2] if len(tables) > 2 else None, 1, 1, thre)
+    finally:
+        for t in tables:
+            t.close()
+    try:                                                # (the marker tables are this function's until it returns them)
+        cli.log("Haplotype read binning with k = %d: markers %s, %s; %d hap1 and %d hap2 markers, of %d and %d k-mers private to hap1 and to hap2" % (
+            k, hap["markers"], "child threshold %d (%s)" % (thre, origin) if origin else "no child threshold", sm["selected"], sp["selected"],
+            sm["candidates"] - sm["in_absent"], sp["candidates"] - sp["in_absent"]))
+        select_line(HAP_BINS, (sm, sp))
+    except BaseException:
+        m.close()
+        p.close()
+        raise
+    return m, p, sm["selected"], sp["selected"]
+
+
+def open_trio(hap, k, device, as_tables):
+    """trio mode: the parents opened, their hap-mers counted, the first log line -> (mat, pat, thre_mat, thre_pat, M_total, P_total); the
+    caller closes the tables.  as_tables (--marker-tables): the two hap-mer sets become tables of their own (marker_tables), the parents
+    are closed, the totals are the selects', and what comes back is (M', P', 1, 1, ...): the same counts per read from far smaller tables"""
+    from .table import KmerTable
+    mat, pat, tm, tp = extensions.open_parents(hap, k, device)
+    line = "Trio read binning with k = %%d: maternal threshold %%d (%s), paternal threshold %%d (%s); %%d maternal and %%d paternal hap-mers" % (
+        "given" if hap["thre_mat"] is not None else "from the histogram", "given" if hap["thre_pat"] is not None else "from the histogram")
+    if not as_tables:
+        try:
+            census = KmerTable.hapmer_census_parents(mat, pat, None, tm, tp)
+            cli.log(line % (k, tm, tp, census.mat[0], census.pat[0]))
+        except BaseException:
+            mat.close()
+            pat.close()
+            raise
+        return mat, pat, tm, tp, census.mat[0], census.pat[0]
+    try:
+        m, p, sm, sp = marker_tables(mat, pat, None, tm, tp, 1)
+    finally:
+        mat.close()
+        pat.close()
+    try:                                                # (from here on the marker tables are this function's until it returns them)
+        cli.log(line % (k, tm, tp, sm["selected"], sp["selected"]))
+        select_line(BINS, (sm, sp))
+    except BaseException:
+        m.close()
+        p.close()
+        raise
+    return m, p, 1, 1, sm["selected"], sp["selected"]
+
+
 def run(argv):
     from .table import KmerTable
     a = parse_args(argv)
@@ -834,13 +1019,15 @@ def run(argv):
     write_gz, deflate = check_write_gz(a)
     reads, k, device, hap, min_markers, batch_bases = check_flags(a)
     prefix = a["prefix"] if a["prefix"] is not None else reads[0]
-    mat, pat, tm, tp = extensions.open_parents(hap, k, device)
+    by_haps = "hap1" in hap
+    names = HAP_BINS if by_haps else BINS
+    if by_haps:
+        mat, pat, m_total, p_total = open_haps(hap, reads, k, device)
+        tm = tp = 1
+    else:
+        mat, pat, tm, tp, m_total, p_total = open_trio(hap, k, device, a["marker_tables"])
     try:
-        census = KmerTable.hapmer_census_parents(mat, pat, None, tm, tp)
-        m_total, p_total = census.mat[0], census.pat[0]
-        cli.log("Trio read binning with k = %d: maternal threshold %d (%s), paternal threshold %d (%s); %d maternal and %d paternal hap-mers" % (
-            k, tm, "given" if hap["thre_mat"] is not None else "from the histogram", tp, "given" if hap["thre_pat"] is not None else "from the histogram", m_total, p_total))
-        check_totals(m_total, p_total)
+        (haps_totals_check if by_haps else check_totals)(m_total, p_total)
 
         def count(text, offs):
             r = KmerTable.read_bins(mat, pat, (text, offs), tm, tp)
@@ -868,14 +1055,14 @@ def run(argv):
         try:
             per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
                                          count_text=count_text, gz_open=gz_open if gz == "device" else None, route_text=route_text if route == "device" else None,
-                                         timings=timings, write_gz=write_gz, deflate=mat.deflate_bgzf if write_gz and deflate == "device" else None)
+                                         timings=timings, write_gz=write_gz, deflate=mat.deflate_bgzf if write_gz and deflate == "device" else None, names=names)
         finally:
             timing_lines(timings, gz, route, deflate if write_gz else None)
     finally:
         mat.close()
         pat.close()
     n, bases = sum(r for r, _ in per_bin), sum(b for _, b in per_bin)
-    cli.log("Read bins: " + "; ".join("%s %d reads (%s), %d bases (%s)" % (BINS[b], per_bin[b][0], _share(per_bin[b][0], n), per_bin[b][1], _share(per_bin[b][1], bases))
+    cli.log("Read bins: " + "; ".join("%s %d reads (%s), %d bases (%s)" % (names[b], per_bin[b][0], _share(per_bin[b][0], n), per_bin[b][1], _share(per_bin[b][1], bases))
                                       for b in range(3)) + " in %s.readbins.tsv" % prefix)
     extensions.device_line("[triobin] read_bins device seconds: %.6f; %s bases per second" % (seconds, "%.4g" % (bases / seconds) if seconds > 0 else "NA"))
     if reader == "device":
