@@ -999,17 +999,28 @@ int jasper_gz_text_stats(jasper_gz_text *h, uint64_t stats[6]) {
     for (int i = 0; i < GZS_N; ++i) stats[i] = h->g->stats[i];
     return JASPER_OK;
 }
+// The four routing calls fill RouteJob / RouteOut and give RouteSeconds its places in device_seconds: the one place where a position in
+// that array has a meaning (include/jasper_hip.h).  The two host-text calls read the array first, since a refusal of the arguments leaves
+// the caller's numbers as they were; a session's route zeroes them before anything else.
 int jasper_route_text(jasper_table *t, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
                       uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *mismatches, double *device_seconds) {
     if (!t) { g_err = "bad argument"; return JASPER_ERR; }
     uint8_t *const out[3] = {out0, out1, out2};
-    return route_text_host(t->t, text, n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+    double *const ds = device_seconds;
+    RouteSeconds S = {ds ? ds[0] : 0, 0, 0};
+    const int rc = route_text(t->t, text, false, n, RouteJob{n_seg, bounds, bins, first, check_from}, RouteOut{out, nullptr, out_bytes, nullptr, mismatches, nullptr}, S, g_err);
+    if (ds) ds[0] = S.route;
+    return rc ? JASPER_ERR : JASPER_OK;
 }
 int jasper_gz_text_route(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
                          uint8_t *out1, uint8_t *out2, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *device_seconds) {
     if (!h || !t) { g_err = "bad argument"; return JASPER_ERR; }
     uint8_t *const out[3] = {out0, out1, out2};
-    return gz_text_route(*h->g, t->t, want, n_seg, bounds, bins, first, check_from, out, out_bytes, got, mismatches, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
+    double *const ds = device_seconds;
+    RouteSeconds S = {0, 0, 0};
+    const int rc = gz_text_route(*h->g, t->t, want, RouteJob{n_seg, bounds, bins, first, check_from}, RouteOut{out, nullptr, out_bytes, nullptr, mismatches, nullptr}, got, S, g_err);
+    if (ds) { ds[0] = S.route; ds[1] = S.pull; }
+    return rc ? JASPER_ERR : JASPER_OK;
 }
 // ... and the compressor (deflate_gpu.hip): a text as BGZF members, and the two routing calls with the three outputs compressed
 int64_t jasper_deflate_bound(int64_t n) { return n < 0 ? -1 : (int64_t)deflate_bound((uint64_t)n); }
@@ -1017,22 +1028,35 @@ int jasper_deflate_bgzf(jasper_table *t, const uint8_t *text, int64_t n, uint8_t
     if (!t) { g_err = "bad argument"; return JASPER_ERR; }
     return deflate_host(t->t, text, n, out, out_cap, out_bytes, counters, device_seconds, g_err) ? JASPER_ERR : JASPER_OK;
 }
+// (a null out_cap is refused here, in the words the call had for it: to route_text and gz_text_route it means plain outputs)
 int jasper_route_text_gz(jasper_table *t, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
                          uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t counters[6],
                          double *device_seconds) {
     if (!t) { g_err = "bad argument"; return JASPER_ERR; }
+    if (!out_cap) { g_err = "route text: bad arguments"; return JASPER_ERR; }
     uint8_t *const out[3] = {out0, out1, out2};
-    return route_text_host_gz(t->t, text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, device_seconds, g_err) ? JASPER_ERR
-                                                                                                                                                                          : JASPER_OK;
+    double *const ds = device_seconds;
+    RouteSeconds S = {ds ? ds[0] : 0, 0, ds ? ds[1] : 0};
+    const int rc = route_text(t->t, text, false, n, RouteJob{n_seg, bounds, bins, first, check_from}, RouteOut{out, out_cap, out_bytes, raw_bytes, mismatches, counters}, S, g_err);
+    if (ds) { ds[0] = S.route; ds[1] = S.deflate; }
+    return rc ? JASPER_ERR : JASPER_OK;
 }
 int jasper_gz_text_route_gz(jasper_gz_text *h, jasper_table *t, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *out0,
                             uint8_t *out1, uint8_t *out2, const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches,
                             uint64_t counters[6], double *device_seconds) {
     if (!h || !t) { g_err = "bad argument"; return JASPER_ERR; }
     uint8_t *const out[3] = {out0, out1, out2};
-    return gz_text_route_gz(*h->g, t->t, want, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, got, mismatches, counters, device_seconds, g_err)
-               ? JASPER_ERR
-               : JASPER_OK;
+    double *const ds = device_seconds;
+    RouteSeconds S = {0, 0, 0};
+    int rc = -1;
+    if (out_cap) {
+        rc = gz_text_route(*h->g, t->t, want, RouteJob{n_seg, bounds, bins, first, check_from}, RouteOut{out, out_cap, out_bytes, raw_bytes, mismatches, counters}, got, S, g_err);
+    } else {
+        if (counters) std::fill(counters, counters + DF_COUNTERS, (uint64_t)0);
+        g_err = "gz text: bad arguments";
+    }
+    if (ds) { ds[0] = S.route; ds[1] = S.pull; ds[2] = S.deflate; }
+    return rc ? JASPER_ERR : JASPER_OK;
 }
 
 // ---- variant scan (variants.hip) ----

@@ -122,61 +122,36 @@ int gz_text_copy(GzText &G, int64_t from, int64_t len, uint8_t *dst, std::string
     return 0;
 }
 
-namespace {
-// what both route calls begin with: the arguments, the session's mode, the outputs' initial state, and the pull of the next `want`
-// inflated bytes into the routing path's text slot -> those bytes at *d_text, how many in *got, the pull's seconds in *pulled
-int route_pull(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, int64_t out_bytes[3], int64_t *got, int64_t *mismatches, uint8_t **d_text,
-               double *pulled, std::string &err) {
+// the arguments, the session's mode, the outputs' initial state, the pull of the next `want` inflated bytes into the routing path's text
+// slot, and route_text on them where they are
+int gz_text_route(GzText &G, Table &T, int64_t want, const RouteJob &J, const RouteOut &O, int64_t *got, RouteSeconds &S, std::string &err) {
     const std::string w(GZ_WHAT);
-    if (!got || !out_bytes || !mismatches || !bounds || n_seg < 0 || want < 0) { err = w + ": bad arguments"; return -1; }
+    S = RouteSeconds{0, 0, 0};
+    if (O.out_cap) {
+        if (O.counters)
+            for (int i = 0; i < DF_COUNTERS; ++i) O.counters[i] = 0;
+        if (!O.raw_bytes) { err = w + ": bad arguments"; return -1; }
+        O.raw_bytes[0] = O.raw_bytes[1] = O.raw_bytes[2] = 0;
+    }
+    if (!got || !O.out_bytes || !O.mismatches || !J.bounds || J.n_seg < 0 || want < 0) { err = w + ": bad arguments"; return -1; }
     if (&T != G.M) { err = w + ": the table is not the one the session was opened on"; return -1; }
     if (G.mode == 1) { err = w + ": the session has served bins calls; a pass over the file is bins calls or route calls, not both"; return -1; }
     G.mode = 2;
     *got = 0;
-    *mismatches = 0;
-    *pulled = 0;
-    out_bytes[0] = out_bytes[1] = out_bytes[2] = 0;
+    *O.mismatches = 0;
+    O.out_bytes[0] = O.out_bytes[1] = O.out_bytes[2] = 0;
     HIPCHK(hipSetDevice(T.device));
-    *d_text = route_text_room(T, want, err);
-    if (!*d_text) return -1;
+    uint8_t *d_text = route_text_room(T, want, err);
+    if (!d_text) return -1;
     Events ev;
     if (ev.create(err)) return -1;
-    const long g = pull(G, *d_text, want, ev, err);
+    const long g = pull(G, d_text, want, ev, err);
     if (g < 0) return -1;
     HIPCHK(jk_stream_wait(T.stream));
-    if (ev.add_seconds(*pulled, err)) return -1;
+    if (ev.add_seconds(S.pull, err)) return -1;
     *got = g;
-    return 0;
-}
-}  // namespace
-
-int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                  int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *seconds, std::string &err) {
-    if (seconds) seconds[0] = seconds[1] = 0;
-    uint8_t *d_text = nullptr;
-    double pulled = 0;
-    if (route_pull(G, T, want, n_seg, bounds, out_bytes, got, mismatches, &d_text, &pulled, err)) return -1;
-    if (seconds) seconds[1] = pulled;
-    if (*got != bounds[n_seg]) return 0;                // (the file is not what the bounds were made for: nothing is routed)
-    return route_text_device(T, d_text, *got, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err);
-}
-
-int gz_text_route_gz(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
-    if (seconds) seconds[0] = seconds[1] = seconds[2] = 0;
-    if (counters)
-        for (int i = 0; i < DF_COUNTERS; ++i) counters[i] = 0;
-    if (!raw_bytes || !out_cap) { err = std::string(GZ_WHAT) + ": bad arguments"; return -1; }
-    raw_bytes[0] = raw_bytes[1] = raw_bytes[2] = 0;
-    uint8_t *d_text = nullptr;
-    double pulled = 0;
-    if (route_pull(G, T, want, n_seg, bounds, out_bytes, got, mismatches, &d_text, &pulled, err)) return -1;
-    if (seconds) seconds[1] = pulled;
-    if (*got != bounds[n_seg]) return 0;
-    double s2[2] = {0, 0};
-    const int rc = route_text_device_gz(T, d_text, *got, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, s2, err);
-    if (seconds) { seconds[0] = s2[0]; seconds[2] = s2[1]; }
-    return rc;
+    if (*got != J.bounds[J.n_seg]) return 0;            // (the file is not what the bounds were made for: nothing is routed)
+    return route_text(T, d_text, true, *got, J, O, S, err);
 }
 
 }  // namespace jk

@@ -37,11 +37,9 @@ GzText *gz_text_open(Table &M, const char *path, std::string &err);
 int gz_text_bins(GzText &G, Table &M, Table &P, int64_t want, int *format, uint32_t thre_mat, uint32_t thre_pat, int64_t *n, int *eof, int64_t *used, int64_t *n_records,
                  int *status, int64_t *bad_record, double *seconds, std::string &err);
 int gz_text_copy(GzText &G, int64_t from, int64_t len, uint8_t *dst, std::string &err);
-// seconds[2]: the route kernels, the pull (as above).  Refused on a session that has served a bins call, and bins on one that has routed
-int gz_text_route(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                  int64_t out_bytes[3], int64_t *got, int64_t *mismatches, double *seconds, std::string &err);
-// gz_text_route with the three outputs as BGZF members (route_text_device_gz): seconds[3] = the route kernels, the pull, the compressor's kernels
-int gz_text_route_gz(GzText &G, Table &T, int64_t want, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *got, int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
+// The next `want` inflated bytes pulled into the routing path's text slot, *got of them, and routed there by route_text (readroute.hpp: the
+// outputs plain or as BGZF members) when *got is what the bounds end with; otherwise nothing is routed.  S is zeroed first; S.pull is timed
+// as above.  Refused on a session that has served a bins call, and bins on one that has routed
+int gz_text_route(GzText &G, Table &T, int64_t want, const RouteJob &J, const RouteOut &O, int64_t *got, RouteSeconds &S, std::string &err);
 
 }  // namespace jk

@@ -11,7 +11,9 @@
 //                     leave in one 16-byte store (global stores need no alignment on gfx950), the others byte by byte.  A 100 kb record
 //                     is spread over many workgroups this way.  The three outputs lie back to back in one buffer of n bytes -- bin 1
 //                     begins where bin 0's total ends -- so the kernel reads the text once and writes n bytes once
-// The host stage waits once, for the three totals and the check's count; they say how much of the output buffer goes where.
+// The host stage is route_text: what is refused (route_refuse), the upload of a host text, the kernels (route_core) and what leaves the GPU
+// (route_finish: the three ranges, or their BGZF members).  It waits once, for the three totals and the check's count; they say how much
+// of the output buffer goes where.
 #include "readroute.hpp"
 #include "deflate_gpu.hpp"
 #include "readtext.hpp"
@@ -86,15 +88,22 @@ uint8_t *route_text_room(Table &T, int64_t n, std::string &err) {
 }
 
 namespace {
-// what every entry refuses before anything is queued, and the outputs' initial state: the arguments, then route_check's verdict in words
-int route_refuse(int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3], int64_t out_bytes[3],
-                 int64_t *mismatches, double *seconds, std::string &err) {
+// what is refused before anything is queued, and the outputs' initial state: the compressed outputs' arguments, the others, then
+// route_check's verdict in words
+int route_refuse(int64_t n, const RouteJob &J, const RouteOut &O, RouteSeconds &S, std::string &err) {
     const std::string w(RR_WHAT);
-    if (!out_bytes || !mismatches || !out || (check_from != 0 && check_from != 1) || first < 0 || first > 255) { err = w + ": bad arguments"; return -1; }
-    out_bytes[0] = out_bytes[1] = out_bytes[2] = 0;
-    *mismatches = 0;
-    if (seconds) *seconds = 0;
-    switch (route_check(n, n_seg, bounds, bins)) {
+    if (O.out_cap) {
+        if (!O.raw_bytes) { err = w + ": bad arguments"; return -1; }
+        O.raw_bytes[0] = O.raw_bytes[1] = O.raw_bytes[2] = 0;
+        if (O.counters)
+            for (int i = 0; i < DF_COUNTERS; ++i) O.counters[i] = 0;
+        S.deflate = 0;
+    }
+    if (!O.out_bytes || !O.mismatches || !O.out || (J.check_from != 0 && J.check_from != 1) || J.first < 0 || J.first > 255) { err = w + ": bad arguments"; return -1; }
+    O.out_bytes[0] = O.out_bytes[1] = O.out_bytes[2] = 0;
+    *O.mismatches = 0;
+    S.route = 0;
+    switch (route_check(n, J.n_seg, J.bounds, J.bins)) {
     case RR_TOO_LARGE: err = w + ": more than 2^31-1 text bytes or segments in one call"; return -1;
     case RR_BAD_BOUNDS: err = w + ": bounds must begin with 0, end with n and never decrease"; return -1;
     case RR_BAD_BIN: err = w + ": a bin code is not 0, 1 or 2"; return -1;
@@ -149,98 +158,46 @@ int route_core(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const 
     return 0;
 }
 
-// ... and the copies out
-int route_checked(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                  int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {
-    if (n == 0) return 0;
-    if (!d_text || !out[0] || !out[1] || !out[2]) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
-    uint8_t *d_out = nullptr;
-    uint64_t tot[RR_BINS];
-    int64_t bad = 0;
-    if (route_core(T, d_text, n, n_seg, bounds, bins, first, check_from, &d_out, tot, &bad, seconds, err)) return -1;
+// what leaves the GPU: the three ranges as they are, or the compressor on each of them and its members
+int route_finish(Table &T, const uint8_t *d_routed, const uint64_t tot[RR_BINS], const RouteOut &O, RouteSeconds &S, std::string &err) {
     hipStream_t st = T.stream;
     uint64_t at = 0;
     for (int b = 0; b < RR_BINS; ++b) {
-        if (tot[b]) HIPCHK(hipMemcpyAsync(out[b], d_out + at, (size_t)tot[b], hipMemcpyDeviceToHost, st));
-        out_bytes[b] = (int64_t)tot[b];
+        if (O.out_cap) {
+            if (deflate_device(T, d_routed + at, (int64_t)tot[b], O.out[b], O.out_cap[b], &O.out_bytes[b], O.counters, &S.deflate, err)) return -1;
+            O.raw_bytes[b] = (int64_t)tot[b];
+        } else {
+            if (tot[b]) HIPCHK(hipMemcpyAsync(O.out[b], d_routed + at, (size_t)tot[b], hipMemcpyDeviceToHost, st));
+            O.out_bytes[b] = (int64_t)tot[b];
+        }
         at += tot[b];
     }
-    HIPCHK(jk_stream_wait(st));
-    *mismatches = bad;
-    return 0;
-}
-
-// ... or the compressor on each bin's range, and its members out
-int route_checked_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                     const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
-    if (n == 0) return 0;
-    if (!d_text || !out[0] || !out[1] || !out[2]) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
-    uint8_t *d_out = nullptr;
-    uint64_t tot[RR_BINS];
-    int64_t bad = 0;
-    if (route_core(T, d_text, n, n_seg, bounds, bins, first, check_from, &d_out, tot, &bad, seconds, err)) return -1;
-    uint64_t at = 0;
-    for (int b = 0; b < RR_BINS; ++b) {
-        if (deflate_device(T, d_out + at, (int64_t)tot[b], out[b], out_cap[b], &out_bytes[b], counters, seconds ? seconds + 1 : nullptr, err)) return -1;
-        raw_bytes[b] = (int64_t)tot[b];
-        at += tot[b];
-    }
-    *mismatches = bad;
-    return 0;
-}
-
-int route_refuse_gz(const int64_t *out_cap, int64_t raw_bytes[3], uint64_t *counters, double *seconds, std::string &err) {
-    if (!out_cap || !raw_bytes) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
-    raw_bytes[0] = raw_bytes[1] = raw_bytes[2] = 0;
-    if (counters)
-        for (int i = 0; i < DF_COUNTERS; ++i) counters[i] = 0;
-    if (seconds) seconds[1] = 0;                        // (route_refuse clears seconds[0])
+    if (!O.out_cap) HIPCHK(jk_stream_wait(st));         // (the compressor has waited for its members)
     return 0;
 }
 }  // namespace
 
-int route_text_device_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                         const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
-    if (route_refuse_gz(out_cap, raw_bytes, counters, seconds, err)) return -1;
-    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
-    return route_checked_gz(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, seconds, err);
-}
-
-int route_text_host_gz(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                       const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err) {
-    if (route_refuse_gz(out_cap, raw_bytes, counters, seconds, err)) return -1;
-    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
-    uint8_t *d_text = nullptr;
-    if (n > 0) {
+int route_text(Table &T, const uint8_t *text, bool on_device, int64_t n, const RouteJob &J, const RouteOut &O, RouteSeconds &S, std::string &err) {
+    if (route_refuse(n, J, O, S, err)) return -1;
+    const uint8_t *d_text = on_device ? text : nullptr;
+    if (!on_device && n > 0) {
         if (!text) { err = std::string(RR_WHAT) + ": null text"; return -1; }
         HIPCHK(hipSetDevice(T.device));
         uint8_t *room = route_text_room(T, n, err);
         if (!room) return -1;
-        d_text = room + ((uintptr_t)text & 15u);
-        HIPCHK(hipMemcpyAsync(d_text, text, (size_t)n, hipMemcpyHostToDevice, T.stream));
+        uint8_t *up = room + ((uintptr_t)text & 15u);   // (the kernels take any alignment; the tests reach every one through the host pointer)
+        HIPCHK(hipMemcpyAsync(up, text, (size_t)n, hipMemcpyHostToDevice, T.stream));
+        d_text = up;
     }
-    return route_checked_gz(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_cap, out_bytes, raw_bytes, mismatches, counters, seconds, err);
-}
-
-int route_text_device(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                      int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {
-    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
-    return route_checked(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err);
-}
-
-int route_text_host(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                    int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err) {
-    if (route_refuse(n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err)) return -1;
-    uint8_t *d_text = nullptr;
-    if (n > 0) {
-        if (!text) { err = std::string(RR_WHAT) + ": null text"; return -1; }
-        HIPCHK(hipSetDevice(T.device));
-        uint8_t *room = route_text_room(T, n, err);
-        if (!room) return -1;
-        d_text = room + ((uintptr_t)text & 15u);        // (the kernels take any alignment; the tests reach every one through the host pointer)
-        HIPCHK(hipMemcpyAsync(d_text, text, (size_t)n, hipMemcpyHostToDevice, T.stream));
-    }
-    return route_checked(T, d_text, n, n_seg, bounds, bins, first, check_from, out, out_bytes, mismatches, seconds, err);
+    if (n == 0) return 0;
+    if (!d_text || !O.out[0] || !O.out[1] || !O.out[2]) { err = std::string(RR_WHAT) + ": bad arguments"; return -1; }
+    uint8_t *d_out = nullptr;
+    uint64_t tot[RR_BINS];
+    int64_t bad = 0;
+    if (route_core(T, d_text, n, J.n_seg, J.bounds, J.bins, J.first, J.check_from, &d_out, tot, &bad, &S.route, err)) return -1;
+    if (route_finish(T, d_out, tot, O, S, err)) return -1;
+    *O.mismatches = bad;
+    return 0;
 }
 
 }  // namespace jk

@@ -11,22 +11,37 @@
 
 namespace jk {
 
-// Route the n bytes at d_text (any alignment; T's device) on T's stream.  out[b] (host, room for n bytes each) gets bin b's bytes,
-// out_bytes[b] how many.  mismatches = the segments i >= check_from that hold a byte and whose first byte is not `first`.  seconds
-// (may be null) = device time of the kernels (HIP events).  Buffers: T's workspace slots WS_ROUTE + 1 ..; d_text may lie in WS_ROUTE + 0.
-int route_text_device(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                      int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err);
-// the same with the text in host memory: it is uploaded to WS_ROUTE + 0, at its host pointer's place within 16 bytes
-int route_text_host(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                    int64_t out_bytes[3], int64_t *mismatches, double *seconds, std::string &err);
-// The same two, but out[b] (host, room for out_cap[b] bytes) gets bin b's bytes as BGZF members (deflate_gpu.hpp): the routed bytes stay in
-// HBM, the compressor runs on each bin's range and only the members are copied down.  out_bytes[b] = the members' bytes, raw_bytes[b] =
-// the routed bytes; counters[DF_COUNTERS] (may be null) = the three compressor calls' sums; seconds[2] (may be null) = the route kernels,
-// the compressor's kernels.  A bin without a byte gets no member.
-int route_text_device_gz(Table &T, const uint8_t *d_text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                         const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
-int route_text_host_gz(Table &T, const uint8_t *text, int64_t n, int64_t n_seg, const int64_t *bounds, const uint8_t *bins, int first, int check_from, uint8_t *const out[3],
-                       const int64_t out_cap[3], int64_t out_bytes[3], int64_t raw_bytes[3], int64_t *mismatches, uint64_t *counters, double *seconds, std::string &err);
+// how a text is cut and what is checked: mismatches = the segments i >= check_from that hold a byte and whose first byte is not `first`
+struct RouteJob {
+    int64_t n_seg;
+    const int64_t *bounds;
+    const uint8_t *bins;
+    int first;
+    int check_from;
+};
+// Where the three bins go (all host memory).  out_cap == nullptr: plain bytes -- out[b] (room for n bytes each) gets bin b's bytes,
+// out_bytes[b] how many; raw_bytes and counters are not looked at.  Otherwise BGZF members (deflate_gpu.hpp): the routed bytes stay in
+// HBM, the compressor runs on each bin's range and only the members are copied down to out[b] (room for out_cap[b] bytes); out_bytes[b] =
+// the members' bytes, raw_bytes[b] = the routed bytes, counters[DF_COUNTERS] (may be null) = the three compressor calls' sums.  A bin
+// without a byte gets no member.
+struct RouteOut {
+    uint8_t *const *out;
+    const int64_t *out_cap;
+    int64_t *out_bytes;
+    int64_t *raw_bytes;
+    int64_t *mismatches;
+    uint64_t *counters;
+};
+// device time by HIP events: the route kernels, a session's pull of inflated text (readgz.hpp), the compressor's kernels.  A call zeroes
+// the ones it can fill once it has accepted the arguments they belong to
+struct RouteSeconds {
+    double route, pull, deflate;
+};
+
+// Route the n bytes at `text` (any alignment) on T's stream.  on_device: the text lies on T's device (it may lie in WS_ROUTE + 0);
+// otherwise it is host memory and is uploaded to WS_ROUTE + 0, at its host pointer's place within 16 bytes.  Buffers: T's workspace slots
+// WS_ROUTE + 1 ..
+int route_text(Table &T, const uint8_t *text, bool on_device, int64_t n, const RouteJob &J, const RouteOut &O, RouteSeconds &S, std::string &err);
 // room for n text bytes in WS_ROUTE + 0 (what a caller that fills the text itself asks for first)
 uint8_t *route_text_room(Table &T, int64_t n, std::string &err);
 

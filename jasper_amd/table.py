@@ -317,7 +317,9 @@ def deflate_bound(n):
     return int(_lib.lib().jasper_deflate_bound(int(n)))
 
 
-def _route_args(bounds, bins, first, check_from, room, out, gz=False):
+def _route_call(L, th, session, buf, n, room, bounds, bins, first, check_from, out, gz):
+    """what KmerTable.route_text (session None: buf = the text, n its length) and GzText.route (buf None, n = want) share: the arguments
+    made ready, the one of the four C calls that matches -- a session's or not, BGZF members or not -- and its RoutedText"""
     import numpy as np
     if gz:
         room = deflate_bound(room)
@@ -331,7 +333,34 @@ def _route_args(bounds, bins, first, check_from, room, out, gz=False):
         out = [np.empty(max(room, 1), dtype=np.uint8) for _ in range(3)]
     if len(out) != 3 or any(o.dtype != np.uint8 or o.ndim != 1 or not o.flags.c_contiguous or len(o) < room for o in out):
         raise ValueError("route: out must be three contiguous np.uint8 arrays with room for the text")
-    return bounds, bins, int(first), int(check_from), out
+    vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+    nb, raw, cnt, got, bad, secs = (C.c_int64 * 3)(), (C.c_int64 * 3)(), (C.c_uint64 * 6)(), C.c_int64(0), C.c_int64(0), (C.c_double * 3)()
+    src = (th, vp(buf) if buf.size else None, n) if session is None else (session._handle(), th, n)
+    job = (len(bins), vp(bounds), vp(bins) if len(bins) else None, int(first), int(check_from), vp(out[0]), vp(out[1]), vp(out[2]))
+    outs = ((C.c_int64 * 3)(*(len(o) for o in out)), nb, raw) if gz else (nb,)
+    rest = (() if session is None else (C.byref(got),)) + (C.byref(bad),) + ((cnt,) if gz else ()) + (secs,)
+    check(getattr(L, ("jasper_route_text" if session is None else "jasper_gz_text_route") + ("_gz" if gz else ""))(*src, *job, *outs, *rest))
+    # device_seconds: the kernels, then a session's pull, then the compressor (include/jasper_hip.h)
+    pull, deflate = (0.0, secs[1]) if session is None else (secs[1], secs[2])
+    routed = session is None or got.value == int(bounds[-1])
+    r = RoutedText([o[:nb[b]] for b, o in enumerate(out)] if routed else None, bad.value, secs[0], None if session is None else got.value, routed, pull)
+    if gz:
+        r.raw_bytes, r.deflate, r.deflate_seconds = [int(v) for v in raw], dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), deflate
+    return r
+
+
+def _fetch_records(L, mh, r, want_seq=False):
+    """the per-record arrays of the clean ReadText r, from the maternal table's workspace (jasper_read_text_fetch) -> r"""
+    import numpy as np
+    nr = r.n_records
+    r.rec_start, r.head_end, r.lens = np.zeros(nr + 1, dtype=np.int64), np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
+    r.mat, r.pat = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32)
+    vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+    check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), None))
+    if want_seq:                                    # (its size is the sum of lens: a second fetch, for tests)
+        r.seq = np.zeros(int(r.lens.sum()), dtype=np.uint8)
+        check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), vp(r.seq) if r.seq.size else None))
+    return r
 
 
 class GzText:
@@ -364,7 +393,6 @@ class GzText:
     def bins(self, pat, want, fmt, thre_mat, thre_pat):
         """one chunk: the tail the call before left unused, then up to `want` more inflated bytes -> ReadText (no_format: the first byte
         is neither @ nor >).  fmt: None on the first call (the first byte decides; self.fmt says what), then "fastq" / "fasta" """
-        import numpy as np
         if fmt not in GZ_TEXT_FORMATS:
             raise ValueError("gz_text: fmt must be None, 'fastq' or 'fasta'")
         ph = KmerTable._parent_handle(pat, "paternal", "gz_text")
@@ -378,12 +406,7 @@ class GzText:
         r.no_format, r.inflate_seconds = status.value == 2, secs[2]
         if r.malformed or r.no_format:
             return r
-        nr = r.n_records
-        r.rec_start, r.head_end, r.lens = np.zeros(nr + 1, dtype=np.int64), np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
-        r.mat, r.pat = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32)
-        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
-        check(self._L.jasper_read_text_fetch(self._t._h, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), None))
-        return r
+        return _fetch_records(self._L, self._t._h, r)
 
     def text(self, start, length):
         """bytes [start, start + length) of the current call's text -> np.uint8"""
@@ -400,22 +423,9 @@ class GzText:
 
     def route(self, want, bounds, bins, first, check_from=0, out=None, gz=False):
         """the next `want` inflated bytes routed as KmerTable.route_text routes a host text -> RoutedText with `got`"""
-        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, int(bounds[-1]) if len(bounds) else 0, out, gz)
-        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
-        nb, got, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(0), (C.c_double * 3)()
-        if gz:
-            cap, raw, cnt = (C.c_int64 * 3)(*(len(o) for o in out)), (C.c_int64 * 3)(), (C.c_uint64 * 6)()
-            check(self._L.jasper_gz_text_route_gz(self._handle(), self._t._h, int(want), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
-                                                  vp(out[1]), vp(out[2]), cap, nb, raw, C.byref(got), C.byref(bad), cnt, secs))
-            self.inflate_seconds += secs[1]
-            routed = got.value == int(bounds[-1])
-            return RoutedText([o[:nb[b]] for b, o in enumerate(out)] if routed else None, bad.value, secs[0], got.value, routed, secs[1], [int(v) for v in raw],
-                              dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), secs[2])
-        check(self._L.jasper_gz_text_route(self._handle(), self._t._h, int(want), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
-                                           vp(out[1]), vp(out[2]), nb, C.byref(got), C.byref(bad), secs))
-        self.inflate_seconds += secs[1]
-        routed = got.value == int(bounds[-1])
-        return RoutedText([o[:nb[b]] for b, o in enumerate(out)] if routed else None, bad.value, secs[0], got.value, routed, secs[1])
+        r = _route_call(self._L, self._t._h, self, None, int(want), int(bounds[-1]) if len(bounds) else 0, bounds, bins, first, check_from, out, gz)
+        self.inflate_seconds += r.inflate_seconds
+        return r
 
 
 VARIANT_DTYPE = [("pos", "<i8"), ("seq", "<u4"), ("ref_min", "<u4"), ("alt_min", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"), ("pad", "u1")]
@@ -1369,15 +1379,7 @@ class KmerTable:
         r = ReadText(used.value, n.value, status.value != 0, bad.value, secs[1], secs[0])
         if r.malformed:
             return r
-        nr = r.n_records
-        r.rec_start, r.head_end, r.lens = np.zeros(nr + 1, dtype=np.int64), np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
-        r.mat, r.pat = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32)
-        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
-        check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), None))
-        if want_seq:                                    # (its size is the sum of lens: a second fetch, for tests)
-            r.seq = np.zeros(int(r.lens.sum()), dtype=np.uint8)
-            check(L.jasper_read_text_fetch(mh, nr, vp(r.rec_start), vp(r.head_end), vp(r.lens), vp(r.mat), vp(r.pat), vp(r.seq) if r.seq.size else None))
-        return r
+        return _fetch_records(L, mh, r, want_seq)
 
     def gz_text(self, path):
         """a gzip text session on this table (the maternal one of the binning calls): the .gz file inflated on the GPU -> GzText.  Raises
@@ -1410,18 +1412,7 @@ class KmerTable:
         buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else text
         if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
             raise TypeError("route_text: the text must be bytes or a contiguous one-dimensional np.uint8 array")
-        bounds, bins, first, check_from, out = _route_args(bounds, bins, first, check_from, len(buf), out, gz)
-        vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
-        nb, bad, secs = (C.c_int64 * 3)(), C.c_int64(0), C.c_double(0)
-        if gz:
-            cap, raw, cnt, secs2 = (C.c_int64 * 3)(*(len(o) for o in out)), (C.c_int64 * 3)(), (C.c_uint64 * 6)(), (C.c_double * 2)()
-            check(self._L.jasper_route_text_gz(self._h, vp(buf) if buf.size else None, len(buf), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from,
-                                               vp(out[0]), vp(out[1]), vp(out[2]), cap, nb, raw, C.byref(bad), cnt, secs2))
-            return RoutedText([o[:nb[b]] for b, o in enumerate(out)], bad.value, secs2[0], raw_bytes=[int(v) for v in raw],
-                              deflate=dict(zip(DEFLATE_COUNTERS, (int(v) for v in cnt))), deflate_seconds=secs2[1])
-        check(self._L.jasper_route_text(self._h, vp(buf) if buf.size else None, len(buf), len(bins), vp(bounds), vp(bins) if len(bins) else None, first, check_from, vp(out[0]),
-                                        vp(out[1]), vp(out[2]), nb, C.byref(bad), C.byref(secs)))
-        return RoutedText([o[:nb[b]] for b, o in enumerate(out)], bad.value, secs.value)
+        return _route_call(self._L, self._h, None, buf, len(buf), len(buf), bounds, bins, first, check_from, out, gz)
 
     # ---- variant scan (an extension: the reference acts on such sites inside its walk and reports nothing) --
     def variant_scan(self, seqs, thre):

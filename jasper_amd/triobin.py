@@ -114,6 +114,7 @@ from collections import namedtuple
 
 from . import bgzf, cli, extensions
 from .report import write_atomic
+from .table import GzText, KmerTable, RoutedText
 
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
          "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--write-gz (needs --write-reads)] [--deflate host|device (needs --write-gz)] "
@@ -346,13 +347,45 @@ def device_chunk():
     return n
 
 
+class _HostText:
+    """a file read on the host, behind what _DeviceReader uses of a gzip text session: bins(want, fmt) reads up to `want` bytes more into
+    ONE buffer for every chunk -- the tail the chunk before left unused at its front, the file read in behind it -- and has
+    count_text(buf, eof, fmt) bin them -> table.ReadText (None: no text, or a first byte that is no format's); then n = the text's bytes,
+    eof, fmt; text(start, length) = a view of the text, good until the next bins()"""
+
+    def __init__(self, path, count_text):
+        self.count_text, self.room, self.n, self.used, self.eof, self.fmt = count_text, bytearray(), 0, 0, False, None
+        self.f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+        self.close = self.f.close
+
+    def bins(self, want, fmt):
+        have = self.n - self.used
+        self.room[:have] = self.room[self.used:self.n]
+        if have + want > len(self.room):                # (at first; then for a tail as long as a block: a record longer than that)
+            self.room = self.room[:have] + bytearray(want)
+        got = self.f.readinto(memoryview(self.room)[have:have + want])
+        self.n, self.used, self.eof = have + got, 0, not got
+        if self.n and fmt is None:
+            self.fmt = {b"@": "fastq", b">": "fasta"}.get(bytes(self.room[:1]))
+        if not self.n or self.fmt is None:
+            return None
+        r = self.count_text(self.text(0, self.n), self.eof, self.fmt)
+        self.used = r.used
+        return r
+
+    def text(self, start, length):
+        import numpy as np
+        return np.frombuffer(self.room, dtype=np.uint8, count=length, offset=start)
+
+
 class _DeviceReader:
     """--reader device: a file's bytes go to the GPU as they stand, count_text(buf, eof, fmt) -> table.ReadText parses, packs and counts
     them there.  chunks(path) yields what the host reader's chunks() yields, without the sequences; the counts come back in input order in
     self.m / self.p as _Batcher has them.  With keep_starts, self.starts[path] = (the records' first byte, their absolute starts in the
     decompressed file, its length): what the second pass of --write-reads routes by.
     --gz device: gz_open(path) -> a gzip text session (table.GzText with the parents bound: bins(want, fmt)) or an exception for a file
-    the device inflater refuses; a .gz file's chunks then come from the session, and the text is fetched only for the names (per_read)."""
+    the device inflater refuses; a .gz file's chunks then come from the session instead of a _HostText, and the text, which stays in HBM,
+    is fetched only for the names (per_read) and for a malformed chunk."""
 
     def __init__(self, count_text, keep_starts, gz_open=None, per_read=False):
         self.count_text, self.keep_starts, self.gz_open, self.per_read = count_text, keep_starts, gz_open, per_read
@@ -360,29 +393,29 @@ class _DeviceReader:
         self.inflate_seconds, self.gz_stats = 0.0, []       # the sessions' summed pull seconds (HIP events around each pull), (path, stats) per session
 
     def chunks(self, path):
-        sess = open_session(self.gz_open, path)
-        return self._gz_chunks(path, sess) if sess is not None else self._host_chunks(path)
-
-    def _gz_chunks(self, path, sess):
         import numpy as np
+        sess = open_session(self.gz_open, path)
+        src = sess if sess is not None else _HostText(path, self.count_text)
         want = device_chunk()
         fmt, first, nrec, base, have, starts = None, b"", 0, 0, 0, []
         try:
             while True:
                 try:
-                    r = sess.bins(want, fmt)
+                    r = src.bins(want, fmt)
                 except RuntimeError as e:
+                    if sess is None:
+                        raise
                     raise Inflate(path, str(e))
-                n, eof = sess.n, sess.eof
+                n, eof = src.n, src.eof
                 if not n:
                     break
-                if r.no_format:
+                if src.fmt is None:                     # (the host's first byte, or the session's no_format)
                     raise Malformed(path, 0, "the file begins with neither @ (FASTQ) nor > (FASTA)")
                 if fmt is None:
-                    fmt = sess.fmt
+                    fmt = src.fmt
                     first = b"@" if fmt == "fastq" else b">"
                 if r.malformed:                         # the host parser words the message: the same (buf, eof) raises there
-                    (_fastq_chunk if fmt == "fastq" else _fasta_chunk)(sess.text(0, n), eof, path, nrec, False)
+                    (_fastq_chunk if fmt == "fastq" else _fasta_chunk)(src.text(0, n), eof, path, nrec, False)
                     raise RuntimeError("%s: the device reader calls record %d malformed and the host parser does not" % (path, nrec + r.bad_record))
                 self.seconds += r.seconds
                 if r.n_records:
@@ -391,56 +424,17 @@ class _DeviceReader:
                     self.p.append(r.pat)
                     if self.keep_starts:
                         starts.append(r.rec_start[:-1] + base)
-                    yield Chunk(sess.text(0, r.used) if self.per_read else None, r.rec_start[:-1], r.rec_start[1:], r.head_end, None, r.lens)
+                    # (the host's text is a view of its buffer: looked at before the buffer is used again)
+                    yield Chunk(src.text(0, r.used) if sess is None or self.per_read else None, r.rec_start[:-1], r.rec_start[1:], r.head_end, None, r.lens)
                 have = n - r.used
                 base += r.used
                 if eof:
                     break
         finally:
-            self.inflate_seconds += sess.inflate_seconds
-            self.gz_stats.append((path, sess.stats()))
-            sess.close()
-        if self.keep_starts:
-            self.starts[path] = (first, np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64), base + have)
-
-    def _host_chunks(self, path):
-        import numpy as np
-        size = device_chunk()
-        fmt, first, nrec, base, starts = None, b"", 0, 0, []
-        room, have = bytearray(size), 0                 # one buffer for every block: the tail carried over at its front, the file read in behind it
-        with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
-            while True:
-                if have + size > len(room):             # (a tail as long as a block: a record longer than that)
-                    room = room[:have] + bytearray(size)
-                got = f.readinto(memoryview(room)[have:have + size])
-                eof = not got
-                n = have + got
-                if not n:
-                    break
-                if fmt is None:
-                    first = bytes(room[:1])
-                    if first not in (b"@", b">"):
-                        raise Malformed(path, 0, "the file begins with neither @ (FASTQ) nor > (FASTA)")
-                    fmt = "fastq" if first == b"@" else "fasta"
-                buf = np.frombuffer(room, dtype=np.uint8, count=n)
-                r = self.count_text(buf, eof, fmt)
-                if r.malformed:                         # the host parser words the message: the same (buf, eof) raises there
-                    (_fastq_chunk if fmt == "fastq" else _fasta_chunk)(buf, eof, path, nrec, False)
-                    raise RuntimeError("%s: the device reader calls record %d malformed and the host parser does not" % (path, nrec + r.bad_record))
-                self.seconds += r.seconds
-                if r.n_records:
-                    nrec += r.n_records
-                    self.m.append(r.mat)
-                    self.p.append(r.pat)
-                    if self.keep_starts:
-                        starts.append(r.rec_start[:-1] + base)
-                    yield Chunk(buf[:r.used], r.rec_start[:-1], r.rec_start[1:], r.head_end, None, r.lens)      # (looked at before the buffer is used again)
-                del buf
-                have = n - r.used
-                room[:have] = room[r.used:n]
-                base += r.used
-                if eof:
-                    break
+            if sess is not None:
+                self.inflate_seconds += sess.inflate_seconds
+                self.gz_stats.append((path, sess.stats()))
+            src.close()
         if self.keep_starts:
             self.starts[path] = (first, np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64), base + have)
 
@@ -645,6 +639,33 @@ def _write_reads(paths, opened, bins, nrec):
             files.close()
 
 
+def _route_by_masks(buf, bounds, codes, first, check_from, out):
+    """what route_text computes, on the host: three boolean masks, and the count of starts that do not hold the records' first byte"""
+    import numpy as np
+    size = np.diff(bounds)
+    return RoutedText([buf[np.repeat(codes == b, size)] for b in range(3)], int((buf[bounds[check_from:-1]] != first[0]).sum()), 0.0)
+
+
+class _FileBlocks:
+    """a file read on the host, behind what the second pass uses of a gzip text session: route(want, bounds, codes, first, check_from, out)
+    reads the next `want` bytes (`got` of them) and, when they are the bytes the bounds were made for (`routed`), has route_text route
+    them -- KmerTable.route_text (--route device) or _route_by_masks"""
+
+    def __init__(self, path, route_text):
+        self.route_text = route_text
+        self.f = gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
+        self.close = self.f.close
+
+    def route(self, want, bounds, codes, first, check_from, out, **gz):
+        import numpy as np
+        buf = np.frombuffer(self.f.read(want), dtype=np.uint8)
+        if not len(buf) or len(buf) != bounds[-1]:
+            return RoutedText(None, 0, 0.0, len(buf), False)
+        r = self.route_text(buf, bounds, codes, first, check_from, out, **gz)
+        r.got, r.routed = len(buf), True
+        return r
+
+
 def _write_reads_by_starts(paths, opened, bins, kept, route_text=None, gz_open=None, timings=None, deflater=None):
     """the second pass of the device reader: nothing is parsed again, a block's bytes are routed by the record starts the first pass has
     kept.  The file has changed when its decompressed length differs or a remembered start does not hold the records' first byte.
@@ -657,68 +678,42 @@ def _write_reads_by_starts(paths, opened, bins, kept, route_text=None, gz_open=N
     gz = {"gz": True} if route_text and deflater is not None else {}
     room = CHUNK + (31 * (-(-CHUNK // bgzf.BLOCK)) if gz else 0)        # (a member adds at most 31 bytes to its text)
     out = [np.empty(room, dtype=np.uint8) for _ in range(3)] if route_text else None
-
-    def routed(r):
-        if gz:
-            deflater.note(r.deflate, r.deflate_seconds)
-        files.write_routed(r)
-
     for fi, path in enumerate(paths):
         files = opened(path)
         first, starts, length = kept[path]
         sess = open_session(gz_open, path) if route_text else None
+        src = sess
         try:
+            if sess is None:
+                src = _FileBlocks(path, route_text or _route_by_masks)
             at = 0
-            if sess is not None:
-                try:
-                    while 0 <= at < length:
-                        end = min(at + CHUNK, length)
-                        i0, i1, bounds, check_from = block_segments(starts, at, end)
-                        r = sess.route(end - at, bounds, bins[fi][i0:i1], first, check_from, out, **gz)
-                        route_seconds += r.seconds
-                        if not r.routed or r.mismatches:
-                            at = -1
-                            break
-                        routed(r)
-                        at = end
-                    if at == length and sess.route(1, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint8), first, 0, out).got:      # (bytes are left over)
+            try:
+                while 0 <= at < length:
+                    end = min(at + CHUNK, length)
+                    i0, i1, bounds, check_from = block_segments(starts, at, end)
+                    r = src.route(end - at, bounds, bins[fi][i0:i1], first, check_from, out, **gz)
+                    route_seconds += r.seconds
+                    if not r.routed or r.mismatches:    # (a block that came short; a start that does not hold the records' first byte)
                         at = -1
-                except RuntimeError as e:
-                    cli.error_exit(str(Inflate(path, str(e))))
-            else:
-                with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
-                    while at >= 0:
-                        block = f.read(CHUNK)
-                        if not block:
-                            break
-                        buf = np.frombuffer(block, dtype=np.uint8)
-                        end = at + len(buf)
-                        if end > length:
-                            at = -1
-                            break
-                        i0, i1, bounds, check_from = block_segments(starts, at, end)
-                        if route_text:
-                            r = route_text(buf, bounds, bins[fi][i0:i1], first, check_from, out, **gz)
-                            route_seconds += r.seconds
-                            if r.mismatches:
-                                at = -1
-                                break
-                            routed(r)
-                        else:
-                            if not (buf[bounds[check_from:-1]] == first[0]).all():
-                                at = -1
-                                break
-                            size = np.diff(bounds)
-                            for b in range(3):
-                                files.write(b, buf[np.repeat(bins[fi][i0:i1] == b, size)])
-                        at = end
+                        break
+                    if gz:
+                        deflater.note(r.deflate, r.deflate_seconds)
+                    files.write_routed(r)
+                    at = end
+                if at == length and src.route(1, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint8), first, 0, out).got:      # (bytes are left over)
+                    at = -1
+            except RuntimeError as e:
+                if sess is None:
+                    raise
+                cli.error_exit(str(Inflate(path, str(e))))
             if at != length:
                 cli.error_exit("--write-reads: %s changed between the two passes" % path)
         finally:
             if sess is not None:
                 inflate_seconds += sess.inflate_seconds
                 gz_stats.append((path, sess.stats()))
-                sess.close()
+            if src is not None:
+                src.close()
             files.close()
     if timings is not None:
         timings.update(route_seconds=route_seconds, route_inflate_seconds=inflate_seconds, route_gz_stats=gz_stats, second_pass_wall=time.perf_counter() - t0)
@@ -815,11 +810,17 @@ def check_flags(a):
     return reads, k, device, hap, min_markers, batch_bases
 
 
+def _host_or_device(a, flag):
+    """the value of a flag that takes host or device: host when it is not given"""
+    v = a[VALUE_FLAGS[flag]] if a[VALUE_FLAGS[flag]] is not None else "host"
+    if v not in READERS:
+        cli.error_exit("%s takes host or device; %s was given" % (flag, v))
+    return v
+
+
 def check_reader(a):
     """--reader, and with device the chunk size: refused before a parent is opened"""
-    reader = a["reader"] if a["reader"] is not None else "host"
-    if reader not in READERS:
-        cli.error_exit("--reader takes host or device; %s was given" % reader)
+    reader = _host_or_device(a, "--reader")
     if reader == "device":
         device_chunk()
     return reader
@@ -827,12 +828,7 @@ def check_reader(a):
 
 def check_gz_route(a, reader):
     """--gz and --route: refused before a parent is opened -> (gz, route)"""
-    gz = a["gz"] if a["gz"] is not None else "host"
-    route = a["route"] if a["route"] is not None else "host"
-    if gz not in READERS:
-        cli.error_exit("--gz takes host or device; %s was given" % gz)
-    if route not in READERS:
-        cli.error_exit("--route takes host or device; %s was given" % route)
+    gz, route = _host_or_device(a, "--gz"), _host_or_device(a, "--route")
     if gz == "device" and reader != "device":
         cli.error_exit("--gz device needs --reader device: the inflated text goes to the device reader inside the GPU's memory")
     if route == "device" and not (reader == "device" and a["write_reads"]):
@@ -842,9 +838,7 @@ def check_gz_route(a, reader):
 
 def check_write_gz(a):
     """--write-gz and --deflate: refused before a parent is opened -> (write_gz, deflate)"""
-    deflate = a["deflate"] if a["deflate"] is not None else "host"
-    if deflate not in READERS:
-        cli.error_exit("--deflate takes host or device; %s was given" % deflate)
+    deflate = _host_or_device(a, "--deflate")
     if a["write_gz"] and not a["write_reads"]:
         cli.error_exit("--write-gz needs --write-reads: it is the bin files that are written compressed")
     if a["deflate"] is not None and not a["write_gz"]:
@@ -859,23 +853,46 @@ def check_totals(m_total, p_total):
             "parents have" if m_total == p_total else "mother has" if m_total == 0 else "father has"))
 
 
-class _Session:
-    """a table.GzText with the father's table and the thresholds bound: what _DeviceReader and the second pass drive.  note(r) sees every
-    chunk's ReadText (the run's sums of index + pack seconds and text bytes)"""
+class _Tables:
+    """the two tables and their thresholds, bound into what bin_files calls: count, count_text, gz_open, route_text, deflate.  Every
+    chunk's ReadText passes note(): index_seconds and text_bytes are the run's sums of index + pack seconds and of the bytes records cover"""
 
-    def __init__(self, g, pat, thre_mat, thre_pat, note):
-        self.g, self.pat, self.thre_mat, self.thre_pat, self.note = g, pat, thre_mat, thre_pat, note
-        self.text, self.stats, self.route, self.close = g.text, g.stats, g.route, g.close
+    def __init__(self, mat, pat, thre_mat, thre_pat):
+        self.mat, self.pat, self.thre_mat, self.thre_pat = mat, pat, thre_mat, thre_pat
+        self.index_seconds, self.text_bytes = 0.0, 0
 
-    n = property(lambda self: self.g.n)
-    eof = property(lambda self: self.g.eof)
-    fmt = property(lambda self: self.g.fmt)
-    inflate_seconds = property(lambda self: self.g.inflate_seconds)
+    def note(self, r):
+        self.index_seconds += r.index_seconds
+        self.text_bytes += r.used
+        return r
+
+    def count(self, text, offs):
+        r = KmerTable.read_bins(self.mat, self.pat, (text, offs), self.thre_mat, self.thre_pat)
+        return r.mat, r.pat, r.seconds
+
+    def count_text(self, buf, eof, fmt):
+        return self.note(KmerTable.read_bins_text(self.mat, self.pat, buf, eof, fmt, self.thre_mat, self.thre_pat))
+
+    def gz_open(self, path):
+        return _Session(self, path)
+
+    def route_text(self, buf, bounds, codes, first, check_from, out, gz=False):
+        return self.mat.route_text(buf, bounds, codes, first, check_from, out, gz=gz)
+
+    def deflate(self, arr):
+        return self.mat.deflate_bgzf(arr)
+
+
+class _Session(GzText):
+    """a table.GzText on the maternal table with the father's table and the thresholds bound: bins(want, fmt), what _DeviceReader drives"""
+
+    def __init__(self, tables, path):
+        GzText.__init__(self, tables.mat, path)
+        self.tables = tables
 
     def bins(self, want, fmt):
-        r = self.g.bins(self.pat, want, fmt, self.thre_mat, self.thre_pat)
-        self.note(r)
-        return r
+        t = self.tables
+        return t.note(GzText.bins(self, t.pat, want, fmt, t.thre_mat, t.thre_pat))
 
 
 def timing_lines(t, gz, route, deflate=None):
@@ -1012,7 +1029,6 @@ def open_trio(hap, k, device, as_tables):
 
 
 def run(argv):
-    from .table import KmerTable
     a = parse_args(argv)
     reader = check_reader(a)
     gz, route = check_gz_route(a, reader)
@@ -1028,34 +1044,11 @@ def run(argv):
         mat, pat, tm, tp, m_total, p_total = open_trio(hap, k, device, a["marker_tables"])
     try:
         (haps_totals_check if by_haps else check_totals)(m_total, p_total)
-
-        def count(text, offs):
-            r = KmerTable.read_bins(mat, pat, (text, offs), tm, tp)
-            return r.mat, r.pat, r.seconds
-
-        index_seconds, text_bytes = [0.0], []
-
-        def count_text(buf, eof, fmt):
-            r = KmerTable.read_bins_text(mat, pat, buf, eof, fmt, tm, tp)
-            index_seconds[0] += r.index_seconds
-            text_bytes.append(r.used)
-            return r
-
-        def noted(r):
-            index_seconds[0] += r.index_seconds
-            text_bytes.append(r.used)
-
-        def gz_open(path):
-            return _Session(mat.gz_text(path), pat, tm, tp, noted)
-
-        def route_text(buf, bounds, codes, first, check_from, out, gz=False):
-            return mat.route_text(buf, bounds, codes, first, check_from, out, gz=gz)
-
-        timings = {}
+        t, timings = _Tables(mat, pat, tm, tp), {}
         try:
-            per_bin, seconds = bin_files(reads, prefix, count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
-                                         count_text=count_text, gz_open=gz_open if gz == "device" else None, route_text=route_text if route == "device" else None,
-                                         timings=timings, write_gz=write_gz, deflate=mat.deflate_bgzf if write_gz and deflate == "device" else None, names=names)
+            per_bin, seconds = bin_files(reads, prefix, t.count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
+                                         count_text=t.count_text, gz_open=t.gz_open if gz == "device" else None, route_text=t.route_text if route == "device" else None,
+                                         timings=timings, write_gz=write_gz, deflate=t.deflate if write_gz and deflate == "device" else None, names=names)
         finally:
             timing_lines(timings, gz, route, deflate if write_gz else None)
     finally:
@@ -1067,7 +1060,7 @@ def run(argv):
     extensions.device_line("[triobin] read_bins device seconds: %.6f; %s bases per second" % (seconds, "%.4g" % (bases / seconds) if seconds > 0 else "NA"))
     if reader == "device":
         extensions.device_line("[triobin] read_text index + pack device seconds: %.6f; %s text bytes per second" % (
-            index_seconds[0], "%.4g" % (sum(text_bytes) / index_seconds[0]) if index_seconds[0] > 0 else "NA"))
+            t.index_seconds, "%.4g" % (t.text_bytes / t.index_seconds) if t.index_seconds > 0 else "NA"))
     return 0
 
 
