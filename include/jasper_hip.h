@@ -487,6 +487,27 @@ int jasper_hapmer_census(jasper_table *mat, jasper_table *pat, jasper_table *chi
 int jasper_table_select(jasper_table *dst, jasper_table *src, jasper_table *absent, jasper_table *solid /* may be NULL */, uint32_t thre_src, uint32_t thre_solid,
                         uint64_t out4[4] /* candidates, in_absent, not_solid, selected */, double *device_seconds);
 
+/* The counting sibling of the select: dst = src - minus as a table.  src (S), minus (M) and dst are whole tables of the same k on the same
+ * device, all handles different, narrow or wide, of any sizes; dst holds no key.  Anything else is JASPER_ERR with a message that names
+ * the cause, before any table is touched.
+ *
+ * What it replaces: nothing -- this is an EXTENSION, the reference has no counterpart.  Counting is additive: where M counts a part of the
+ * sequences S counts, dst counts the rest, key by key and exactly (jasper_count_binned: all reads - the other bin = own bin + unknown).
+ *
+ * For every distinct key x of S, with the full 64-bit counts S[x] and M[x] (0 for a key M lacks -- not the 32-bit clamp of the lookups):
+ * dst[x] = S[x] - M[x] where that is above 0, otherwise x is not in dst.  S and M are not modified.
+ *   out5 = swept      the keys of S
+ *          matched    those M holds
+ *          dropped    those with M[x] == S[x]
+ *          underflow  those with M[x] > S[x]: left out of dst
+ *          kept       swept - dropped - underflow = the keys of dst
+ * dst's occurrences (jasper_table_info) are the sum of its counts: the k-mer occurrences of the sequences S counts and M does not.
+ * M is a sub-multiset of S iff underflow == 0 and matched == the distinct keys of M; the call returns the table either way.
+ * S is swept in pieces of at most 2^24 slots (JASPER_SUBTRACT_PIECE=<slots>, 1 .. 2^24, overrides it: a test hook); a piece's keys reach
+ * dst through the select's import.  device_seconds (may be NULL): device time of the subtract sweeps, HIP events; the imports are not in it. */
+int jasper_table_subtract(jasper_table *dst, jasper_table *src, jasper_table *minus, uint64_t out5[5] /* swept, matched, dropped, underflow, kept */,
+                          double *device_seconds);
+
 /* Trio read binning: per READ of the child, how many of its windows hold a k-mer that only the mother's reads have and how many hold one
  * that only the father's have -- what TrioCanu-style binning sorts the child's reads by.  The tables are the scan's mat (M) and pat (P)
  * above: whole tables of the same k on the same device, different handles; thre_mat and thre_pat are each at least 1.  No table is
@@ -543,6 +564,34 @@ int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text
                           int64_t *used, int64_t *n_records, int *status, int64_t *bad_record, double *device_seconds /* [2] */);
 int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat,
                            uint8_t *out_seq /* may be NULL */);
+
+/* The reads of chosen BINS of a packed batch counted into tables of their own, while the batch is in HBM.  An EXTENSION like the binning:
+ * that says which bin a read belongs to, this makes the k-mer table of "the reads of bins {..}".
+ *
+ * Input.  n_reads reads packed back to back as jasper_read_bins takes them (offsets: a host array of n_reads+1 entries), and codes, a host
+ * array of one bin code 0 .. 2 per read.  n_sinks (1 .. 3) SINKS: sink s is the table sinks[s] and masks[s], a value 1 .. 7 with bit b
+ * set iff the sink takes the reads of code b.  The sinks are whole tables of one k on one device, all handles different.
+ * Output.  Every sink's table has been added the canonical k-mers of the reads whose code is in its mask, exactly as
+ * jasper_count_bases_device counts a stream of those reads, in input order, each followed by one non-base byte: no k-mer spans two reads,
+ * a read shorter than k (empty ones too) gives none.  The stream is gathered on the GPU in pieces of whole reads of at most 2^28 bytes
+ * (JASPER_BINCOUNT_PIECE=<bytes> overrides it: a test hook); a longer read is a piece of its own.  A sink's kernels run on its stream.
+ *   out           3 numbers per sink: the reads, the bases and the k-mer occurrences gathered into it
+ *   seconds       (may be NULL) 2 numbers per sink: device time of the gather kernel alone (HIP events), wall time of the counting calls
+ *   jasper_count_binned         the text in host memory (text[offsets[0] .. offsets[n_reads]) is uploaded)
+ *   jasper_count_binned_device  the text in HBM on the sinks' device, at any alignment, complete when the call is made
+ *   jasper_read_text_count      the packed sequences and offsets that the last jasper_read_text_bins / jasper_gz_text_bins call left in
+ *                               mat's workspace: no sequence visits the host.  n_records must be what that call returned; pat (may be
+ *                               NULL) is that call's other table, and neither may be a sink
+ * n_reads == 0 is legal and counts nothing.  JASPER_ERR with a message that names the cause: a sink of another k or on another device,
+ * an attached (owner-sharded) sink, one table in two sinks, a sink that is mat or pat, a code above 2, a mask of 0 or above 7, offsets
+ * that decrease or start below 0, an n_records that is not the binning call's, input beyond jasper_read_bins' limits.
+ * JASPER_ERR_CAPACITY is the counting call's. */
+int jasper_count_binned(int n_sinks, jasper_table *const *sinks, const uint32_t *masks, int64_t n_reads, const char *text /* host */, const int64_t *offsets,
+                        const uint8_t *codes, uint64_t *out /* [3 * n_sinks] */, double *seconds /* [2 * n_sinks] */);
+int jasper_count_binned_device(int n_sinks, jasper_table *const *sinks, const uint32_t *masks, int64_t n_reads, const void *d_text, const int64_t *offsets /* host */,
+                               const uint8_t *codes, uint64_t *out, double *seconds);
+int jasper_read_text_count(jasper_table *mat, jasper_table *pat /* may be NULL */, int64_t n_records, const uint8_t *codes, int n_sinks, jasper_table *const *sinks,
+                           const uint32_t *masks, uint64_t *out, double *seconds);
 
 /* A gzip text session: ONE .gz read file inflated on the GPU (the device inflater of the counting path) whose text goes to the read-text
  * path inside HBM.  The session belongs to `mat`: its device and stream, its workspace; no counting call may run on `mat` while a session

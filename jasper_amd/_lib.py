@@ -249,6 +249,10 @@ SYMBOLS = {
     "jasper_hapscan_free": (None, [_P]),
     "jasper_hapmer_census": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_table_select": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_table_subtract": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_count_binned": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(C.c_uint32), C.c_int64, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_count_binned_device": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(C.c_uint32), C.c_int64, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "jasper_read_text_count": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.POINTER(_P), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "jasper_read_bins": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(C.c_double)]),
     "jasper_read_bins_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(C.c_double)]),
     "jasper_read_text_bins": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int),

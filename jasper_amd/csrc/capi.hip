@@ -12,6 +12,7 @@
 #include "diploid.hpp"
 #include "hapmers.hpp"
 #include "select.hpp"
+#include "bincount.hpp"
 #include "readbins.hpp"
 #include "readtext.hpp"
 #include "readroute.hpp"
@@ -946,6 +947,12 @@ int jasper_table_select(jasper_table *dst, jasper_table *src, jasper_table *abse
     return rc == 0 ? JASPER_OK : rc == -2 ? JASPER_ERR_CAPACITY : JASPER_ERR;
 }
 
+int jasper_table_subtract(jasper_table *dst, jasper_table *src, jasper_table *minus, uint64_t out5[5], double *device_seconds) {
+    if (!dst || !src || !minus || !out5) { g_err = "bad argument"; return JASPER_ERR; }
+    const int rc = table_subtract(dst->t, src->t, minus->t, out5, device_seconds, g_err);
+    return rc == 0 ? JASPER_OK : rc == -2 ? JASPER_ERR_CAPACITY : JASPER_ERR;
+}
+
 // ---- trio read binning (readbins.hip) ----
 int jasper_read_bins(jasper_table *mat, jasper_table *pat, int64_t n_reads, const char *text, const int64_t *offsets, uint32_t thre_mat, uint32_t thre_pat, uint32_t *out_mat,
                      uint32_t *out_pat, double *device_seconds) {
@@ -966,6 +973,42 @@ int jasper_read_text_bins(jasper_table *mat, jasper_table *pat, const char *text
 int jasper_read_text_fetch(jasper_table *mat, int64_t n_records, int64_t *rec_start, int64_t *head_end, int64_t *lens, uint32_t *out_mat, uint32_t *out_pat, uint8_t *out_seq) {
     if (!mat) { g_err = "bad argument"; return JASPER_ERR; }
     return read_text_fetch(mat->t, n_records, rec_start, head_end, lens, out_mat, out_pat, out_seq, g_err) ? JASPER_ERR : JASPER_OK;
+}
+// ... and the reads of chosen bins counted into tables of their own (bincount.hip)
+namespace {
+// the handles of a call's sinks as tables: false for a count outside 1 .. 3 or a null handle
+bool sink_tables(int n_sinks, jasper_table *const *sinks, const uint32_t *masks, uint64_t *out, double *seconds, Table *tables[BC_SINKS], BinSinks &S) {
+    if (n_sinks < 1 || n_sinks > BC_SINKS || !sinks || !masks || !out) { g_err = "count binned: bad arguments (1 to 3 sinks)"; return false; }
+    for (int i = 0; i < n_sinks; ++i) {
+        if (!sinks[i]) { g_err = "count binned: bad arguments (a sink without a table)"; return false; }
+        tables[i] = &sinks[i]->t;
+    }
+    S = BinSinks{n_sinks, tables, masks, out, seconds};
+    return true;
+}
+int binned_rc(int rc) { return rc == 0 ? JASPER_OK : rc == -2 ? JASPER_ERR_CAPACITY : JASPER_ERR; }
+}  // namespace
+int jasper_count_binned(int n_sinks, jasper_table *const *sinks, const uint32_t *masks, int64_t n_reads, const char *text, const int64_t *offsets, const uint8_t *codes,
+                        uint64_t *out, double *seconds) {
+    Table *tables[BC_SINKS];
+    BinSinks S;
+    if (!sink_tables(n_sinks, sinks, masks, out, seconds, tables, S)) return JASPER_ERR;
+    return binned_rc(count_binned_host(S, n_reads, text, offsets, codes, g_err));
+}
+int jasper_count_binned_device(int n_sinks, jasper_table *const *sinks, const uint32_t *masks, int64_t n_reads, const void *d_text, const int64_t *offsets, const uint8_t *codes,
+                               uint64_t *out, double *seconds) {
+    Table *tables[BC_SINKS];
+    BinSinks S;
+    if (!sink_tables(n_sinks, sinks, masks, out, seconds, tables, S)) return JASPER_ERR;
+    return binned_rc(count_binned_device(S, n_reads, (const uint8_t *)d_text, offsets, codes, nullptr, 0, g_err));
+}
+int jasper_read_text_count(jasper_table *mat, jasper_table *pat, int64_t n_records, const uint8_t *codes, int n_sinks, jasper_table *const *sinks, const uint32_t *masks,
+                           uint64_t *out, double *seconds) {
+    if (!mat) { g_err = "bad argument"; return JASPER_ERR; }
+    Table *tables[BC_SINKS];
+    BinSinks S;
+    if (!sink_tables(n_sinks, sinks, masks, out, seconds, tables, S)) return JASPER_ERR;
+    return binned_rc(read_text_count(mat->t, pat ? &pat->t : nullptr, n_records, codes, S, g_err));
 }
 // ... from a .gz file inflated on the device (readgz.hip), and the second pass's routing (readroute.hip)
 struct jasper_gz_text {

@@ -364,7 +364,8 @@ struct Table {
                          WS_DEFLATE = WS_ROUTE + 8,                                      // the compressor's text, member slots, match records, sizes, scans, output and counters (deflate_gpu.hip)
                          WS_DIPLOID = WS_DEFLATE + 8,                                    // the pair spectrum's matrix, then the pair scan's buffers (diploid.hip)
                          WS_SELECT = WS_DIPLOID + 9,                                     // the select's entry buffer of one piece and its control words (select.hip)
-                         WS_SLOTS = WS_SELECT + 2;
+                         WS_BINCOUNT = WS_SELECT + 2,                                    // a host text, a sink's two lists and the gathered piece (bincount.hip)
+                         WS_SLOTS = WS_BINCOUNT + 4;
     // what the last read-text call left in this table's workspace for its fetch (readtext.hip); -1: nothing (any binning call since)
     int64_t text_records = -1, text_seq_bytes = 0, text_used = 0;
     WsBuf ws[WS_SLOTS];   // 0..WS_POLISH_MAX-1: polisher (polish_host.hip, in allocation order); WS_COUNT..+3: partitioned counting

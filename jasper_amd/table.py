@@ -1297,6 +1297,95 @@ class KmerTable:
         v = [int(x) for x in out]
         return dst, dict(candidates=v[0], in_absent=v[1], not_solid=v[2], selected=v[3], seconds=secs.value)
 
+    @staticmethod
+    def subtract(src, minus):
+        """src - minus as a NEW table on src's device (include/jasper_hip.h: jasper_table_subtract): the keys of `src` whose 64-bit count
+        exceeds their count in `minus`, each with the difference -> (KmerTable, stats); stats = dict of swept, matched, dropped,
+        underflow, kept, missing (= the distinct keys of minus - matched) and seconds (device time of the sweeps).  underflow or missing
+        above 0: minus is no sub-multiset of src; the table comes back all the same and the caller decides.  Neither source is
+        modified; the caller closes the table.  It is sized for src's distinct keys and cut to a load of at most 0.5 at the end."""
+        sh, mh = KmerTable._parent_handle(src, "source", "subtract"), KmerTable._parent_handle(minus, "minus", "subtract")
+        dst = KmerTable(src.k, min_slots=max(2 * src.info()["distinct"], KmerTable.SELECT_SLOTS_LEAST), device=src.device)
+        try:
+            out = (C.c_uint64 * 5)()
+            secs = C.c_double(0)
+            check(src._L.jasper_table_subtract(dst._h, sh, mh, out, C.byref(secs)))
+            dst.fit()
+        except BaseException:
+            dst.close()
+            raise
+        v = [int(x) for x in out]
+        return dst, dict(swept=v[0], matched=v[1], dropped=v[2], underflow=v[3], kept=v[4], missing=minus.info()["distinct"] - v[1], seconds=secs.value)
+
+    # ---- the reads of chosen bins counted into tables of their own (an extension: what triobin --write-jf is made of) ----
+    @staticmethod
+    def _sink_args(sinks, what):
+        """sinks: pairs (KmerTable, bins) with bins the bin codes the table takes (an iterable of 0 .. 2) or their mask as an int ->
+        (n, handles, masks, out, seconds) for the C call"""
+        sinks = list(sinks)
+        handles = (C.c_void_p * max(len(sinks), 1))(*(KmerTable._parent_handle(t, "sink", what).value for t, _ in sinks))
+        masks = (C.c_uint32 * max(len(sinks), 1))()
+        for i, (_, bins) in enumerate(sinks):
+            m = int(bins) if isinstance(bins, int) else sum(1 << int(b) for b in set(bins))
+            if not 0 <= m <= 0xFFFFFFFF:
+                raise ValueError("%s: a sink's bins must be codes 0 .. 2 or their mask" % what)
+            masks[i] = m
+        return len(sinks), handles, masks, (C.c_uint64 * (3 * max(len(sinks), 1)))(), (C.c_double * (2 * max(len(sinks), 1)))()
+
+    @staticmethod
+    def _sink_stats(n, out, secs):
+        return [dict(reads=int(out[3 * i]), bases=int(out[3 * i + 1]), occurrences=int(out[3 * i + 2]), gather_seconds=secs[2 * i], count_seconds=secs[2 * i + 1])
+                for i in range(n)]
+
+    @staticmethod
+    def _codes(codes, n, what):
+        import numpy as np
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        if codes.ndim != 1 or len(codes) != n:
+            raise ValueError("%s: codes must hold one bin code per read" % what)
+        return codes
+
+    @staticmethod
+    def count_binned(reads, codes, sinks):
+        """the reads of chosen bins counted into tables (include/jasper_hip.h: jasper_count_binned).  reads: as read_bins takes them;
+        codes: one bin code 0 .. 2 per read; sinks: up to three pairs (KmerTable, bins) -- the table is added the canonical k-mers of
+        the reads whose code is in bins (an iterable of codes, or their mask), no k-mer spanning two reads -> a dict per sink: reads,
+        bases, occurrences gathered, gather_seconds (device time of the gather kernel), count_seconds (wall time of the counting)"""
+        import numpy as np
+        buf, offs = KmerTable._packed_reads(reads)
+        codes = KmerTable._codes(codes, len(offs) - 1, "count_binned")
+        ptr = C.c_char_p(buf) if isinstance(buf, bytes) else C.c_void_p(buf.ctypes.data if buf.size else None)
+        n, handles, masks, out, secs = KmerTable._sink_args(sinks, "count_binned")
+        check(_lib.lib().jasper_count_binned(n, handles, masks, len(offs) - 1, ptr, C.c_void_p(offs.ctypes.data), C.c_void_p(codes.ctypes.data) if len(codes) else None,
+                                             out, secs))
+        return KmerTable._sink_stats(n, out, secs)
+
+    @staticmethod
+    def count_binned_device(d_text, offsets, codes, sinks):
+        """the same for reads already in HBM on the sinks' device: d_text is a device pointer (int) or an object with .data_ptr() holding
+        the reads back to back, complete when the call is made; offsets the n+1 boundaries (host)"""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or len(offs) < 1:
+            raise ValueError("count_binned_device: offsets must hold n+1 boundaries")
+        codes = KmerTable._codes(codes, len(offs) - 1, "count_binned_device")
+        ptr = d_text.data_ptr() if hasattr(d_text, "data_ptr") else int(d_text)
+        n, handles, masks, out, secs = KmerTable._sink_args(sinks, "count_binned_device")
+        check(_lib.lib().jasper_count_binned_device(n, handles, masks, len(offs) - 1, C.c_void_p(ptr), C.c_void_p(offs.ctypes.data),
+                                                    C.c_void_p(codes.ctypes.data) if len(codes) else None, out, secs))
+        return KmerTable._sink_stats(n, out, secs)
+
+    @staticmethod
+    def count_binned_workspace(mat, pat, n_records, codes, sinks):
+        """the same for the packed sequences the last read_bins_text / GzText.bins call on (mat, pat) left in mat's workspace (--reader
+        device: no sequence visits the host).  n_records is what that call returned; pat may be None; neither may be a sink"""
+        mh = KmerTable._parent_handle(mat, "maternal", "count_binned_workspace")
+        ph = KmerTable._parent_handle(pat, "paternal", "count_binned_workspace") if pat is not None else None
+        codes = KmerTable._codes(codes, int(n_records), "count_binned_workspace")
+        n, handles, masks, out, secs = KmerTable._sink_args(sinks, "count_binned_workspace")
+        check(mat._L.jasper_read_text_count(mh, ph, int(n_records), C.c_void_p(codes.ctypes.data) if len(codes) else None, n, handles, masks, out, secs))
+        return KmerTable._sink_stats(n, out, secs)
+
     # ---- trio read binning (an extension: the hap-mer scan's probes over a packed batch of reads) ----------
     @staticmethod
     def _packed_reads(reads):

@@ -2,7 +2,7 @@
 
     python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf)
                                  [-k 37] [--mat-threshold N] [--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads]
-                                 [--write-gz] [--deflate host|device] [--batch-bases N] [--reader host|device] [--gz host|device]
+                                 [--write-jf] [--write-gz] [--deflate host|device] [--batch-bases N] [--reader host|device] [--gz host|device]
                                  [--route host|device] [--marker-tables] [-o PREFIX] [--device D]
     python -m jasper_amd.triobin -r 'reads...' --hap1 hap1.fa --hap2 hap2.fa [--markers solid|all] [--child-threshold N] [--child-jf db.jf]
                                  [every flag above but the parents' six]
@@ -78,6 +78,27 @@ member.  Every write cuts its bytes into members on its own and carries no tail 
 KmerTable.deflate_bgzf (the GPU compressor: LZ77 and dynamic Huffman codes per member), with any --reader; under --route device the
 routed bytes are compressed where they lie in HBM (the _gz route calls) and only the members come back.
 
+--write-jf writes what the polisher reads, not what it would have to count again: PREFIX.<first>.jf and PREFIX.<second>.jf (mat / pat, or
+hap1 / hap2), Jellyfish databases of the canonical k-mers of the reads binned <that bin> or unknown -- the sequences as --per-read
+measures them -- which go straight into jasper.sh -j:
+
+    python -m jasper_amd.triobin -r 'reads.fq' --hap1 hap1.fa --hap2 hap2.fa --write-jf -o dip
+    jasper.sh -a hap1.fa -j dip.hap1.jf ...
+    jasper.sh -a hap2.fa -j dip.hap2.jf ...
+
+Counting is additive, so count(own bin + unknown) = count(all reads) - count(other bin), key by key in 64-bit counts.  Once the bins
+are known a second pass goes over the inputs with the reader the first pass used (chunks, or the device reader and its gz sessions)
+and counts each bin's reads where the batch lies in HBM (KmerTable.count_binned, count_binned_workspace) into T1 (the first bin) and
+T2 (the second); the unknown reads, most of a real genome's, are never counted on their own.  The reads' table R is the child's table
+of --markers solid, kept open instead of closed (counted, or --child-jf), and otherwise a third sink of the same pass that takes every
+read.  Then first.jf = R - T2 (KmerTable.subtract) is written and closed before second.jf = R - T1 is made: the peak is R and one
+result.  The header's command line is `count -C -m K -o <file name>` and the read files as given.  A record count that differs from the
+first pass's ends the run (FILE changed between the two passes); so does a subtraction that meets a k-mer the reads' table holds less
+often than a bin's reads do, which only a --child-jf that is not these reads' database can cause.  Either way no .jf is left.  The log
+gets one more line -- per database its bins, reads, bases, distinct k-mers and occurrences -- and JASPER_AMD_TIMING=1 one with the
+gather kernels' seconds and bytes, the counting seconds, both subtracts' seconds and counters and the pass's wall time.  Works with or
+without --write-reads, in both modes, with every --reader, --gz and --paired combination.
+
 The rule.  A template's m and p are its read's counts; with --paired they are the sums over its two mates.
 
     m + p < --min-markers (default 1, at least 1)    unknown
@@ -97,6 +118,7 @@ The files (each written as .tmp, then renamed; the read files renamed only when 
                                 columns sum m and p of the bin's reads, each read's own counts, not its template's
     PREFIX.readbins.reads.tsv   with --per-read: #file record name length mat pat bin, one line per read in input order; record is 0-based
                                 within its file, name the first token of the header line without @ / >
+    PREFIX.<bin>.jf             with --write-jf, for the first two bins: the k-mer database of that bin's and the unknown bin's reads
     PREFIX.<bin>.<basename>     with --write-reads: for each of the three bins and each input file (its base name without a final .gz)
                                 that file's records of that bin, byte for byte as they stand in the decompressed input, in input order --
                                 the mates of a pair stay in step across R1 and R2, and the three files of an input hold each of its
@@ -117,7 +139,7 @@ from .report import write_atomic
 from .table import GzText, KmerTable, RoutedText
 
 USAGE = ("Usage: python -m jasper_amd.triobin -r 'child reads...' (--mat 'files' | --mat-jf db.jf) (--pat 'files' | --pat-jf db.jf) [-k 37] [--mat-threshold N] "
-         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--write-gz (needs --write-reads)] [--deflate host|device (needs --write-gz)] "
+         "[--pat-threshold N] [--min-markers N] [--paired] [--per-read] [--write-reads] [--write-jf] [--write-gz (needs --write-reads)] [--deflate host|device (needs --write-gz)] "
          "[--batch-bases N (no effect with --reader device)] [--reader host|device] [--gz host|device (needs --reader device)] "
          "[--route host|device (needs --reader device --write-reads)] [--marker-tables] [-o PREFIX] [--device D]\n"
          "       python -m jasper_amd.triobin -r 'reads...' --hap1 hap1.fa --hap2 hap2.fa [--markers solid|all] [--child-threshold N (with solid)] "
@@ -132,7 +154,7 @@ CHUNK = 16 << 20                    # file bytes parsed at a time
 DEVICE_CHUNK = 16 << 20             # ... with --reader device: file bytes uploaded and parsed at a time (JASPER_TRIOBIN_CHUNK overrides it)
 DEVICE_CHUNK_MOST = (1 << 30) - 1   # (a chunk and the tail carried into it stay below the kernels' 2^31 text bytes)
 READERS = ("host", "device")
-BOOL_FLAGS = ("--paired", "--per-read", "--write-reads", "--write-gz", "--marker-tables")
+BOOL_FLAGS = ("--paired", "--per-read", "--write-reads", "--write-gz", "--marker-tables", "--write-jf")
 VALUE_FLAGS = {"-r": "reads", "--reads": "reads", "-k": "k", "--kmer": "k", "-o": "prefix", "--device": "device", "--mat": "mat", "--mat-jf": "mat_jf", "--pat": "pat",
                "--pat-jf": "pat_jf", "--mat-threshold": "mat_threshold", "--pat-threshold": "pat_threshold", "--min-markers": "min_markers", "--batch-bases": "batch_bases",
                "--reader": "reader", "--gz": "gz", "--route": "route", "--deflate": "deflate", "--hap1": "hap1", "--hap2": "hap2", "--markers": "markers",
@@ -530,7 +552,7 @@ class _BinFiles:
 
 
 def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=False, per_read=False, write_reads=False, batch_bases=BATCH_BASES_DEFAULT, reader="host",
-              count_text=None, gz_open=None, route_text=None, timings=None, write_gz=False, deflate=None, names=BINS):
+              count_text=None, gz_open=None, route_text=None, timings=None, write_gz=False, deflate=None, names=BINS, write_jf=None):
     """everything after the parents: read, count (count(text, offsets) -> (m, p, seconds)), bin, write.  Errors leave through
     cli.error_exit before any output file exists; -> (reads, bases) per bin and the counter's summed seconds.  reader "device": the files'
     bytes are parsed and counted by count_text (_DeviceReader) and `count` is not called.  gz_open: --gz device (_DeviceReader);
@@ -538,7 +560,8 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
     JASPER_AMD_TIMING=1 prints of the two.  write_gz: the bin files are BGZF; deflate (--deflate device): deflate(array) -> (members,
     counters, seconds) compresses them, and with route_text the route calls are made with gz=True and return members.  names: what the
     three bins are called in the file names, in both tables and, the first two, in the marker and per-read columns (HAP_BINS in assembly
-    mode)"""
+    mode).  write_jf (--write-jf): write_jf(bins, nrec, made) is called once the bins are known, writes its databases as .tmp and adds
+    their names to `made`, the list of what is renamed when the run has succeeded (a _WriteJf)"""
     import numpy as np
     bat = _Batcher(batch_bases, count)
     deflater = _Deflater(deflate) if write_gz and deflate is not None else None
@@ -598,6 +621,8 @@ def bin_files(paths, prefix, count, m_total, p_total, min_markers=1, paired=Fals
             _write_reads(paths, opened, bins, nrec)
         if deflater is not None:
             timings.update(deflate_seconds=deflater.seconds, deflate_blocks=deflater.counters)
+        if write_jf is not None:
+            write_jf(bins, nrec, made)
         write_atomic(prefix + ".readbins.tsv", text)
         if per_read:
             with open(prefix + ".readbins.reads.tsv.tmp", "w") as f:
@@ -719,9 +744,110 @@ def _write_reads_by_starts(paths, opened, bins, kept, route_text=None, gz_open=N
         timings.update(route_seconds=route_seconds, route_inflate_seconds=inflate_seconds, route_gz_stats=gz_stats, second_pass_wall=time.perf_counter() - t0)
 
 
+class _WriteJf:
+    """--write-jf: once the bins are known, a second pass over the inputs counts the reads of the first bin into T1 and those of the
+    second into T2 (and, where the reads' table R is not at hand, all of them into R), then first.jf = R - T2 is written and closed
+    and second.jf = R - T1 after it.  tables: the run's _Tables (the device reader parses and packs on its maternal table, whose
+    workspace the counting reads); reads_table: R kept from the markers (assembly mode, --markers solid), or None.  An instance is
+    bin_files' write_jf; afterwards `databases` holds per file (name, bins, distinct, occurrences) and `timing` what
+    JASPER_AMD_TIMING=1 prints"""
+
+    def __init__(self, tables, reads_table, k, device, prefix, names, paths, reader, gz_open):
+        self.tables, self.reads_table, self.k, self.device, self.prefix, self.names = tables, reads_table, k, device, prefix, names
+        self.paths, self.reader, self.gz_open = paths, reader, gz_open
+        self.databases, self.timing = [], {}
+
+    def count_pass(self, bins, nrec, sinks):
+        """every input once more, with the first pass's reader: a chunk's sequences and its reads' codes go to the sinks -> the sums of
+        the sinks' stats.  A record count that is not the first pass's ends the run"""
+        import numpy as np
+        sums = [dict(reads=0, bases=0, occurrences=0, gather_seconds=0.0, count_seconds=0.0) for _ in sinks]
+        t = self.tables
+        dev = _DeviceReader(t.count_text, False, self.gz_open, False) if self.reader == "device" else None
+        for fi, path in enumerate(self.paths):
+            at = 0
+            try:
+                for ch in (dev.chunks(path) if dev else chunks(path)):
+                    n = len(ch.lens)
+                    if at + n > nrec[fi]:
+                        at = -1
+                        break
+                    codes = bins[fi][at:at + n]
+                    if dev:                             # (the chunk's packed sequences are what the maternal table's workspace holds now)
+                        stats = KmerTable.count_binned_workspace(t.mat, t.pat, n, codes, sinks)
+                    else:
+                        offs = np.zeros(n + 1, dtype=np.int64)
+                        np.cumsum(ch.lens, out=offs[1:])
+                        stats = KmerTable.count_binned((ch.seq, offs), codes, sinks)
+                    for total, st in zip(sums, stats):
+                        for key in total:
+                            total[key] += st[key]
+                    at += n
+            except (Malformed, Inflate):
+                at = -1
+            if at != nrec[fi]:
+                cli.error_exit("--write-jf: %s changed between the two passes" % path)
+        return sums
+
+    def __call__(self, bins, nrec, made):
+        import time
+        t0 = time.perf_counter()
+        opened = []
+        table = lambda: opened.append(KmerTable(self.k, min_slots=1 << 20, device=self.device)) or opened[-1]      # noqa: E731
+        try:
+            first, second = table(), table()
+            sinks = [(first, (MAT,)), (second, (PAT,))]
+            reads = self.reads_table
+            if reads is None:
+                reads = table()
+                sinks.append((reads, (MAT, PAT, UNKNOWN)))
+            sums = self.count_pass(bins, nrec, sinks)
+            subtracts = []
+            for own, minus in ((MAT, second), (PAT, first)):
+                fn = "%s.%s.jf" % (self.prefix, self.names[own])
+                dst, st = KmerTable.subtract(reads, minus)
+                try:
+                    subtracts.append(st)
+                    if st["underflow"] or st["missing"]:
+                        cli.error_exit("--write-jf: the reads' k-mer table holds %d k-mers of the %s reads less often than those reads do and lacks %d of them: "
+                                       "--child-jf is not the database of these reads" % (st["underflow"], self.names[1 - own], st["missing"]))
+                    made.append(fn)
+                    dst.write_jf(fn + ".tmp", ["count", "-C", "-m", str(self.k), "-o", fn] + list(self.paths))
+                    info = dst.info()
+                    self.databases.append((fn, (self.names[own], self.names[UNKNOWN]), info["distinct"], info["occurrences"]))
+                finally:
+                    dst.close()
+        finally:
+            for t in opened:
+                t.close()
+        self.timing = dict(sums=sums, subtracts=subtracts, wall=time.perf_counter() - t0)
+
+    def log(self, per_bin):
+        """the log's line after `Read bins:`, and JASPER_AMD_TIMING=1's"""
+        cli.log("K-mer databases: " + "; ".join("%s of the %s and %s reads: %d reads, %d bases, %d distinct k-mers, %d occurrences" % (
+            fn, b[0], b[1], per_bin[i][0] + per_bin[UNKNOWN][0], per_bin[i][1] + per_bin[UNKNOWN][1], distinct, occ) for i, (fn, b, distinct, occ) in enumerate(self.databases)))
+        if self.timing:
+            sums, subs = self.timing["sums"], self.timing["subtracts"]
+            extensions.device_line("[triobin] write-jf: gather kernels device seconds %.6f for %d bytes; counting seconds %.6f; subtract device seconds %s; pass wall seconds %.6f" % (
+                sum(s["gather_seconds"] for s in sums), sum(s["bases"] + s["reads"] for s in sums), sum(s["count_seconds"] for s in sums),
+                "; ".join("%s %.6f (swept %d, matched %d, dropped %d, underflow %d, kept %d)" % (
+                    self.names[i], st["seconds"], st["swept"], st["matched"], st["dropped"], st["underflow"], st["kept"]) for i, st in enumerate(subs)),
+                self.timing["wall"]))
+
+
+def check_write_jf(a, hap, prefix, names):
+    """--write-jf: refused before anything is opened -- a database it would write is the one --child-jf reads"""
+    if not a["write_jf"]:
+        return
+    child = hap.get("child_jf")
+    for fn in ("%s.%s.jf" % (prefix, b) for b in names[:2]):
+        if child is not None and os.path.abspath(fn) == os.path.abspath(child):
+            cli.error_exit("--write-jf: %s would be written over the --child-jf database; give another prefix with -o" % fn)
+
+
 def parse_args(argv):
     o = dict.fromkeys(set(VALUE_FLAGS.values()))
-    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False, write_gz=False, marker_tables=False)
+    o.update(k="37", device="0", paired=False, per_read=False, write_reads=False, write_gz=False, marker_tables=False, write_jf=False)
     i = 0
     while i < len(argv):
         key = argv[i]
@@ -969,10 +1095,12 @@ def child_table(hap, reads, k, device):
     return t, int(txt.split()[0]), "from the histogram"
 
 
-def open_haps(hap, reads, k, device):
+def open_haps(hap, reads, k, device, keep_child=False):
     """assembly mode: both assemblies counted (as kmerqc counts -a and --alt), with --markers solid the child's table beside them, the
-    two selects, the three source tables closed -> (M', P', M_total, P_total); the caller closes M' and P'.  Writes the mode's log line."""
-    tables = []
+    two selects, the three source tables closed -> (M', P', M_total, P_total, None); the caller closes M' and P'.  keep_child
+    (--write-jf): the child's table of --markers solid is not closed but returned in the None's place, and is the caller's to close.
+    Writes the mode's log line."""
+    tables, child, done = [], None, False
     try:
         for fn in (hap["hap1"], hap["hap2"]):
             tables.append(extensions.contigs_table(k, device, extensions.Text(fn).contigs))
@@ -981,10 +1109,14 @@ def open_haps(hap, reads, k, device):
             child, thre, origin = child_table(hap, reads, k, device)
             tables.append(child)
         m, p, sm, sp = marker_tables(tables[0], tables[1], tables[2] if len(tables) > 2 else None, 1, 1, thre)
+        done = True
     finally:
         for t in tables:
-            t.close()
-    try:                                                # (the marker tables are this function's until it returns them)
+            if not (done and keep_child and t is child):
+                t.close()
+    if not keep_child:
+        child = None
+    try:                                                # (the marker tables, and a kept child's, are this function's until it returns them)
         cli.log("Haplotype read binning with k = %d: markers %s, %s; %d hap1 and %d hap2 markers, of %d and %d k-mers private to hap1 and to hap2" % (
             k, hap["markers"], "child threshold %d (%s)" % (thre, origin) if origin else "no child threshold", sm["selected"], sp["selected"],
             sm["candidates"] - sm["in_absent"], sp["candidates"] - sp["in_absent"]))
@@ -992,8 +1124,10 @@ def open_haps(hap, reads, k, device):
     except BaseException:
         m.close()
         p.close()
+        if child is not None:
+            child.close()
         raise
-    return m, p, sm["selected"], sp["selected"]
+    return m, p, sm["selected"], sp["selected"], child
 
 
 def open_trio(hap, k, device, as_tables):
@@ -1037,26 +1171,33 @@ def run(argv):
     prefix = a["prefix"] if a["prefix"] is not None else reads[0]
     by_haps = "hap1" in hap
     names = HAP_BINS if by_haps else BINS
+    check_write_jf(a, hap, prefix, names)
+    reads_table = None
     if by_haps:
-        mat, pat, m_total, p_total = open_haps(hap, reads, k, device)
+        mat, pat, m_total, p_total, reads_table = open_haps(hap, reads, k, device, keep_child=a["write_jf"])
         tm = tp = 1
     else:
         mat, pat, tm, tp, m_total, p_total = open_trio(hap, k, device, a["marker_tables"])
     try:
         (haps_totals_check if by_haps else check_totals)(m_total, p_total)
         t, timings = _Tables(mat, pat, tm, tp), {}
+        jf = _WriteJf(t, reads_table, k, device, prefix, names, reads, reader, t.gz_open if gz == "device" else None) if a["write_jf"] else None
         try:
             per_bin, seconds = bin_files(reads, prefix, t.count, m_total, p_total, min_markers, a["paired"], a["per_read"], a["write_reads"], batch_bases, reader=reader,
                                          count_text=t.count_text, gz_open=t.gz_open if gz == "device" else None, route_text=t.route_text if route == "device" else None,
-                                         timings=timings, write_gz=write_gz, deflate=t.deflate if write_gz and deflate == "device" else None, names=names)
+                                         timings=timings, write_gz=write_gz, deflate=t.deflate if write_gz and deflate == "device" else None, names=names, write_jf=jf)
         finally:
             timing_lines(timings, gz, route, deflate if write_gz else None)
     finally:
         mat.close()
         pat.close()
+        if reads_table is not None:
+            reads_table.close()
     n, bases = sum(r for r, _ in per_bin), sum(b for _, b in per_bin)
     cli.log("Read bins: " + "; ".join("%s %d reads (%s), %d bases (%s)" % (names[b], per_bin[b][0], _share(per_bin[b][0], n), per_bin[b][1], _share(per_bin[b][1], bases))
                                       for b in range(3)) + " in %s.readbins.tsv" % prefix)
+    if jf is not None:
+        jf.log(per_bin)
     extensions.device_line("[triobin] read_bins device seconds: %.6f; %s bases per second" % (seconds, "%.4g" % (bases / seconds) if seconds > 0 else "NA"))
     if reader == "device":
         extensions.device_line("[triobin] read_text index + pack device seconds: %.6f; %s text bytes per second" % (
